@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X polyphase resampling engine.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c5] [--dump-outputs DIR]
 
 Workload `headline` (BASELINE.json metric "Msamples/s in (Float32, 147//160, 24*147 taps)"): FIRRational
 147//160, 3528 windowed-sinc x Kaiser(7.8562) taps (README.md:172-179 recipe), Float32 taps and
@@ -319,6 +319,46 @@ def traffic_for(bytes_per_launch):
     return None, None
 
 
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all files of one run together stay under this
+
+
+def output_sample(y, max_bytes, seed):
+    """What a caller of the timed path receives, as host arrays small enough to store: `y` (channels x outputs on the device,
+    float32 or complex64) whole when it fits in max_bytes, else every channel at a fixed set of output columns -- the first
+    quarter of the column budget from the start, a quarter from the end, and between them one column drawn with `seed` from
+    each of the remaining equal strata.  Complex outputs become float32 with a trailing (re, im) axis.
+    Returns (values, columns as float64); the two together take at most max_bytes."""
+    import numpy as np
+    torch = sys.modules["torch"]
+    nch, n_out = y.shape
+    k = min(n_out, max(1, max_bytes // (nch * y.element_size() + 8)))
+    if k == n_out:
+        cols = np.arange(n_out, dtype=np.int64)
+    else:
+        head = tail = k // 4
+        m, span = k - head - tail, n_out - head - tail
+        edges = head + (np.arange(m + 1, dtype=np.int64) * span) // m
+        mid = edges[:-1] + np.random.default_rng(seed).integers(0, edges[1:] - edges[:-1])
+        cols = np.concatenate([np.arange(head), mid, np.arange(n_out - tail, n_out)]).astype(np.int64)
+    vals = y.index_select(1, torch.from_numpy(cols).to(y.device))
+    if vals.is_complex():
+        vals = torch.view_as_real(vals)
+    return vals.cpu().numpy(), cols.astype(np.float64)
+
+
+def dump_outputs(dirname, arrays):
+    """Write name -> array as dirname/<name>.npy (float32 / float64 only)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def dump_name(base, world, rank):
+    return base if world == 1 else f"{base}_rank{rank}"
+
+
 _BC = None
 
 
@@ -397,6 +437,9 @@ def run_headline(args, R):
     n_launch, kern_ms = filt.timing_read()
     filt.set_timing(False)
     assert produced == n_out_total, (produced, n_out_total)
+    if args.dump_outputs:            # the last timed step's outputs, before the passes below write into y again
+        vals, cols = output_sample(y, DUMP_MAX_BYTES // 2 // world, seed=0x4D52D000 + rank)
+        dump_outputs(args.dump_outputs, {dump_name("y", world, rank): vals, dump_name("y_columns", world, rank): cols})
 
     # The same batch streamed in 1e6-sample chunks (100 filt! calls per pass), reported next to the timed workload,
     # never as `value`.  Outputs are bit-identical to the single call (chunked == unchunked is a tested invariant).
@@ -568,6 +611,9 @@ def run_c5(args, R):
     n_launch, kern_ms = sh.filter.timing_read() if sh.filter is not None else (0, 0.0)
     if sh.filter is not None:
         sh.filter.set_timing(False)
+        if args.dump_outputs:
+            vals, cols = output_sample(y, DUMP_MAX_BYTES // 4 // world, seed=0xC500D000 + rank)
+            dump_outputs(args.dump_outputs, {dump_name("c5_y", world, rank): vals, dump_name("c5_y_columns", world, rank): cols})
 
     # the final gather, timed on its own: to rank 0, and as an all-gather (every rank ends with all 4096 channels)
     gather = {}
@@ -755,7 +801,12 @@ def main():
     ap.add_argument("--no-c5", action="store_true", help="multi-GPU headline: skip the config-5 pass appended as `c5`")
     ap.add_argument("--c5-channels", type=int, default=0, help="multi-GPU headline: channels in all of the appended config-5 pass (default 4096)")
     ap.add_argument("--c5-samples", type=int, default=0, help="... and its samples per channel (default 1e6)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one (a fixed sample of them when they are larger than "
+                         "the budget, with the sampled output columns) as DIR/<name>.npy, 64 MB at most in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "RANK" not in os.environ and args.gpus > 1:
         # started directly, not by torch.distributed.run: become the launcher (no GPU call in this process)
