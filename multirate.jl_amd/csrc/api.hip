@@ -95,20 +95,11 @@ size_t y_elt(const mrhip_filter *f) { return dtype_size(f->ty); }
 // what Julia's promotion does on every multiply (Real*Real / Real*Complex methods).
 // The vector sits between two runs of kTapPad zero elements: fir_stream_rt_kernel reads whole blocks of taps around the
 // ends of a window (it discards what the out-of-window ones produce) without a clamp per tap.
-constexpr size_t kDecimTabBytes = 4 * 64 * sizeof(float);
-// decim_lane_kernel (kernels_decim_lane.hip) reads the taps of a FIRDecimator 1//4 x 128 Float32 taps as four doubled, age-ordered columns:
-// they sit behind the tap vector's second pad.  NULL: not that shape.
-const float *decim_tab(const mrhip_filter *f)
-{
-    if (f->kind != MRHIP_FIR_DECIMATOR || f->M != 4 || f->hLen != 128 || f->th != MRHIP_F32 || f->r_f64 || !f->d_taps_alloc) return nullptr;
-    return reinterpret_cast<const float *>(static_cast<const unsigned char *>(f->d_taps_alloc) + 128 * sizeof(float) + 2 * static_cast<size_t>(mrhip::kTapPad) * sizeof(float));
-}
-
 int upload_taps(mrhip_filter *f, const std::vector<unsigned char> &src, void **dptr, void **alloc)
 {
     const size_t n = src.size() / dtype_scalar_size(f->th);
     const size_t pad = static_cast<size_t>(mrhip::kTapPad) * r_size(f);
-    const size_t bytes = std::max<size_t>(n * r_size(f), 16) + 2 * pad + kDecimTabBytes;   // (+ decim_lane_kernel's tap columns: decim_tab)
+    const size_t bytes = std::max<size_t>(n * r_size(f), 16) + 2 * pad;
     MRHIP_CHECK_HIP(hipMalloc(alloc, bytes));
     MRHIP_CHECK_HIP(hipMemset(*alloc, 0, bytes));
     *dptr = static_cast<unsigned char *>(*alloc) + pad;
@@ -295,11 +286,6 @@ hipError_t launch_opair_blocks(mrhip_filter *f, const TypeKey &tk, bool fused, c
 }  // namespace
 // kernels_interp_lane.hip: FIRInterpolator 4//1, 32 taps per phase, ComplexF32: a lane per channel (plans and launches; false: not its call)
 bool try_launch_interp_lane(const TypeKey &tk, bool fused, const PolyArgs &a, unsigned *counters, hipStream_t s, const char **kname, int num_cus, hipError_t *err);
-// (kernels_decim_lane.hip: FIRDecimator 1//4 x 128 taps, ComplexF32, long calls -- a lane per channel, the 32 outputs in flight in registers)
-void decim_lane_table(const float *taps_oldest_first, float *tab);
-bool try_launch_decim_lane(const TypeKey &tk, bool fused, const PolyArgs &a, const float *tab, unsigned *counters, hipStream_t s, const char **kname, int num_cus, hipError_t *err);
-// (kernels_arb_window.hip: FIRArbitrary, Float64, 32 taps per phase, long calls -- a lane per channel, the window in registers)
-bool try_launch_arb_window(const TypeKey &tk, bool fused, const ArbArgs &a, double rate, unsigned *counters, hipStream_t s, const char **kname, int num_cus, hipError_t *err);
 namespace {
 
 // Kernel selection for the rational family.  Tuned kernels are tried first; the universal
@@ -311,8 +297,6 @@ hipError_t launch_poly(const mrhip_filter *f, const TypeKey &tk, bool fused, con
     *rec_written = false;             // the pair kernels and the universal kernel file the call's end state in the device record
     if (!f->force_generic) {
         if (a.L == 1) {
-            hipError_t ed = hipSuccess;           // (shiftin! and the record are the caller's: did_shiftin / rec_written stay false)
-            if (try_launch_decim_lane(tk, fused, a, decim_tab(f), counters, s, kname, f->num_cus, &ed)) return ed;
             PairArgs spa;
             dim3 sblock;
             size_t slds = 0;
@@ -426,11 +410,6 @@ int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int6
         taps2pfb(h, hLen, th, L, f->h_taps.data());
     }
     int rc = upload_taps(f, f->h_taps, &f->d_taps, &f->d_taps_alloc);
-    if (!rc && decim_tab(f)) {
-        float tab[4 * 64];
-        mrhip::decim_lane_table(reinterpret_cast<const float *>(f->h_taps.data()), tab);
-        if (hipMemcpy(const_cast<float *>(decim_tab(f)), tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) rc = fail(MRHIP_ERR_HIP, "hipMemcpy failed");
-    }
     if (!rc) rc = alloc_common(f);
     if (rc) { mrhip_destroy(f); return rc; }
     *out = f;
@@ -1185,6 +1164,11 @@ static int filt_device_one(mrhip_filter *f, const void *x, int64_t x_len, int64_
         //  from the call record, cnt is its upper bound)
         const void *sched_dn = nullptr, *sched_dacc = nullptr;      // set by the branch that filled them, before its launch_range
         const int *sched_spans = nullptr;
+        // (a small call -- at most MRHIP_ARB_SMALL_MAX (150 000) outputs x channels -- runs faster on the universal kernel, one lane per output and
+        //  nothing to set up: 1 ch x 1e5 samples 6.7 against 8.6 us, the crossover at 1 ch x 3e5 / 2 ch x 1.5e5; profiles/r05/experiments.md O)
+        auto small_call = [&](int64_t n_out) { return n_out * f->nch <= static_cast<int64_t>(MRHIP_ENV_INT("MRHIP_ARB_SMALL_MAX", 150000)); };
+        // the FIRArbitrary dispatch below tries arb_lane_kernel on a call of n_out outputs (if the kernel takes its shape: arb_lane_eligible)
+        auto lane_ok = [&](int64_t n_out) { return !f->force_generic && !small_call(n_out) && MRHIP_ENV_INT("MRHIP_PIPE_DYNAMIC", 1) != 0; };
         // whole_call: the range is the call (not a piece of a long one): the kernels that can (arb_pipe_kernel, farrow_wave_kernel) then write the
         // next call's history themselves (ShiftFold) -- inside a capture straight into the slot the replay reads, which takes x_len >= H
         auto launch_range = [&](int64_t k0, int64_t cnt, const int32_t *n_host, const DevCall *dyn, bool whole_call = false) -> int {
@@ -1234,25 +1218,14 @@ static int filt_device_one(mrhip_filter *f, const void *x, int64_t x_len, int64_
             if (int rc = timing_mark(f, stream)) return rc;
             ArbTileArgs ta;
             size_t lds = 0;
-            // (a small call -- at most MRHIP_ARB_SMALL_MAX (150 000) outputs x channels -- runs faster on the universal kernel, one lane per output and
-            //  nothing to set up: 1 ch x 1e5 samples 6.7 against 8.6 us, the crossover at 1 ch x 3e5 / 2 ch x 1.5e5; profiles/r05/experiments.md O)
-            const bool small_call = cnt * f->nch <= static_cast<int64_t>(MRHIP_ENV_INT("MRHIP_ARB_SMALL_MAX", 150000));
             ArbLaneArgs la;
-            const bool lane_ok = !f->force_generic && !small_call && MRHIP_ENV_INT("MRHIP_PIPE_DYNAMIC", 1) != 0;
-            hipError_t ew = hipSuccess;
-            if (lane_ok && sf.hist_new) a.fold = sf;            // (every kernel below folds shiftin! into its last workgroup)
-            if (lane_ok && try_launch_arb_window(tk, fused, a, f->rate, f->d_counters, stream, &f->last_kernel, f->num_cus, &ew)) {
-                // (a long call of config 4's shape: one wave per stretch, the window in registers -- kernels_arb_window.hip)
-                if (sf.hist_new) { did_shiftin = true; hist_in_place = in_place; }
-                MRHIP_CHECK_HIP(ew);
-            }
-            else if (lane_ok && plan_arb_lane(tk, a, f->rate, &la, &lds)) {
+            if (lane_ok(cnt) && plan_arb_lane(tk, a, f->rate, &la, &lds)) {
                 // (64 channels or more, Float64, a rate >= 1: a lane per channel, the taps in scalar registers -- kernels_arb_lane.hip)
                 la.counters = f->d_counters;
                 if (sf.hist_new) { a.fold = sf; did_shiftin = true; hist_in_place = in_place; }
                 MRHIP_CHECK_HIP(launch_arb_lane(fused, a, la, lds, stream, &f->last_kernel, f->num_cus));
             }
-            else if (!f->force_generic && !small_call && plan_arb_tiled(tk, a, n_host, sched_spans, f->num_cus, &ta, &lds)) {
+            else if (!f->force_generic && !small_call(cnt) && plan_arb_tiled(tk, a, n_host, sched_spans, f->num_cus, &ta, &lds)) {
                 // the pipe kernel's tiles are handed out from a counter of the filter (its launches are stream-ordered: one at a
                 // time); MRHIP_PIPE_DYNAMIC=0: every workgroup takes every gridDim-th tile
                 ta.counters = MRHIP_ENV_INT("MRHIP_PIPE_DYNAMIC", 1) != 0 ? f->d_counters : nullptr;
@@ -1291,8 +1264,10 @@ static int filt_device_one(mrhip_filter *f, const void *x, int64_t x_len, int64_
             //  cannot run BESIDE it: its tables / chain workgroups either wait for the kernel's end anyway or, when the race at the start lets
             //  them in, both run much longer -- config 4 on a continuing stream read 3.9 or 4.5-5.1 ms per call.  Behind it, on the caller's
             //  stream: 3.93 + 0.2 ms, every call.  profiles/r06/experiments.md I; MRHIP_SCHED_BESIDE_LANE=1: as before)
-            const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && tk.x_f64 && tk.r_f64 && !tk.complex_x && (f->T == 32 || f->T == 16) && f->rate >= 1.0 &&
-                                    f->nch >= 48 && MRHIP_ENV_INT("MRHIP_ARB_LANE", 1) != 0 && MRHIP_ENV_INT("MRHIP_SCHED_BESIDE_LANE", 0) == 0;
+            //  (the call launches est outputs: launch_range below)
+            const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && lane_ok(est) &&
+                                    arb_lane_eligible(tk, static_cast<int>(f->T), static_cast<int>(f->H), f->nch, f->rate, x_len, x_stride, y_stride) &&
+                                    MRHIP_ENV_INT("MRHIP_SCHED_BESIDE_LANE", 0) == 0;
             const bool inline_sched = est <= MRHIP_ENV_INT("MRHIP_SCHED_INLINE_MAX", 65536) || lane_shape;
             hipStream_t ss = capturing || !f->s_sched || x_from || inline_sched ? stream : f->s_sched;
             // a chained call's schedule ran on the CALLER's stream (it reads the previous stage's call record there) and wrote the record,

@@ -457,18 +457,24 @@ hipError_t launch_lane_t(bool fused, const ArbArgs &a, const ArbLaneArgs &la, si
 
 }  // namespace
 
-// Eligible: Float64 taps and real Float64 samples, tapsPerPhi in {16, 24, 32}, a rate >= 1 (consecutive outputs then start 0 or 1
-// samples apart and 16 outputs need at most 16 new samples), enough channels to fill most of a wave's lanes, and the tiles'
-// hand-out counters (the filter's).
-bool plan_arb_lane(const TypeKey &tk, const ArbArgs &a, double rate, ArbLaneArgs *out, size_t *lds)
+// Eligible: Float64 taps and real Float64 samples, tapsPerPhi in {16, 32}, a rate >= 1 (consecutive outputs then start 0 or 1
+// samples apart and 16 outputs need at most 16 new samples) and enough channels to fill most of a wave's lanes.
+// (api.hip also asks this before the call's phase schedule, to run it behind this kernel rather than beside it.)
+bool arb_lane_eligible(const TypeKey &tk, int T, int H, int64_t nch, double rate, int64_t x_len, int64_t x_stride, int64_t y_stride)
 {
     if (MRHIP_ENV_INT("MRHIP_ARB_LANE", 1) == 0) return false;
     if (!tk.x_f64 || !tk.r_f64 || tk.complex_x) return false;     // (the tap banks are kept in the arithmetic type: Float64)
-    if (a.T != 32 && a.T != 16) return false;
-    if (!(rate >= 1.0) || a.n_out < 1 || a.H > kLaneMirror || a.x_len < 64) return false;
-    if (static_cast<double>(a.x_stride) * 8.0 * 8.0 >= 4294967296.0 || static_cast<double>(a.y_stride) * 8.0 * 8.0 >= 4294967296.0) return false;   // (the 32-bit lane offsets of staging and stores span 8 rows)
+    if (T != 32 && T != 16) return false;
+    if (!(rate >= 1.0) || H > kLaneMirror || x_len < 64) return false;
+    if (static_cast<double>(x_stride) * 8.0 * 8.0 >= 4294967296.0 || static_cast<double>(y_stride) * 8.0 * 8.0 >= 4294967296.0) return false;   // (the 32-bit lane offsets of staging and stores span 8 rows)
     const int min_ch = MRHIP_ENV_INT("MRHIP_LANE_MIN_CH", 48);
-    if (a.nch < min_ch || (a.nch % 64 != 0 && a.nch % 64 < min_ch)) return false;          // (a last group with few channels wastes its lanes)
+    return nch >= min_ch && (nch % 64 == 0 || nch % 64 >= min_ch);                    // (a last group with few channels wastes its lanes)
+}
+
+// The launch of an eligible call with at least one output; the tiles' hand-out counters are the filter's.
+bool plan_arb_lane(const TypeKey &tk, const ArbArgs &a, double rate, ArbLaneArgs *out, size_t *lds)
+{
+    if (a.n_out < 1 || !arb_lane_eligible(tk, a.T, a.H, a.nch, rate, a.x_len, a.x_stride, a.y_stride)) return false;
     ArbLaneArgs la{};
     la.ring = lane_ring(a.T);
     la.pitch8 = lane_pitch8(a.T);

@@ -593,6 +593,7 @@ struct ArbLaneArgs {
     int y16;                 // 16-byte stores into y are aligned
     unsigned *counters;      // [0] stretches handed out beyond the first grid-full, [64] workgroups through (zero between launches)
 };
+bool arb_lane_eligible(const TypeKey &tk, int T, int H, int64_t nch, double rate, int64_t x_len, int64_t x_stride, int64_t y_stride);
 bool plan_arb_lane(const TypeKey &tk, const ArbArgs &a, double rate, ArbLaneArgs *out, size_t *lds);
 hipError_t launch_arb_lane(bool fused, const ArbArgs &a, const ArbLaneArgs &la, size_t lds, hipStream_t s, const char **kname, int num_cus);
 hipError_t launch_arb_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,

@@ -1485,14 +1485,11 @@ def test_phase_stationary_kernel_first_call_after_an_upload(pkg, O, torch_cuda, 
         assert_bit_equal(y[nch - 1], fo.filt(x[nch - 1]), f"{L}//{M} vs oracle")
 
 
-def test_decim_lane_kernel_behind_its_switch(pkg, O, torch_cuda, monkeypatch):
-    """decim_lane_kernel (kernels_decim_lane.hip: FIRDecimator 1//4 x 128 taps, ComplexF32, a lane per channel in TRANSPOSED form -- the 32
-    outputs whose windows contain a sample are in flight in registers, every accumulator started from -0.0 or, where the reference's loop
-    does, from +0.0) is NOT the default -- on config 3b it measures slower than fir_stream_kernel (profiles/r06/experiments.md J) -- but
-    stays in the library behind MRHIP_DECIM_LANE: outputs, end state and history bit for bit those of fir_stream_kernel, of the universal
-    kernel and (STRICT) of the oracle: full, several and partial channel groups, every inputDeficit a call can start with (chunks of
-    4 k + 1, + 2, + 3 samples), calls too short for the kernel, -0.0 / +-Inf / NaN samples and an all-negative-zero stretch (the sign of a zero
-    sum is where "-0.0 start" and "first product initialises" could differ)."""
+def test_fir_stream_kernel_decimator_1_4_128_edge_values(pkg, O, torch_cuda, monkeypatch):
+    """fir_stream_kernel on config 3b's shape (FIRDecimator 1//4 x 128 taps, ComplexF32): outputs, end state and history bit for bit
+    those of the universal kernel and (STRICT) of the oracle: 64 / 256 / 50 / 113 channels, every inputDeficit a call can start with
+    (chunks of 4 k + 1, + 2, + 3 samples), calls shorter than a stretch, -0.0 / +-Inf / NaN samples and an all-negative-zero stretch (the
+    sign of a zero sum is where "-0.0 start" and "first product initialises" could differ)."""
     torch = torch_cuda
     rng = np.random.default_rng(909)
     for nch, n in ((64, 30_000), (256, 9_000), (50, 9_000), (113, 9_000)):
@@ -1506,7 +1503,7 @@ def test_decim_lane_kernel_behind_its_switch(pkg, O, torch_cuda, monkeypatch):
         sizes = [3_001, 1, 17, 64, 65, 2, 3, 1_002, n - 5_158 - 1_003, 1_003]
         for numerics in (pkg.NUMERICS_STRICT, pkg.NUMERICS_FUSED):
             got = {}
-            for mode, env in (("lane", {"MRHIP_DECIM_LANE": "2"}), ("stream", {}), ("generic", {"MRHIP_FORCE_GENERIC": "1"})):
+            for mode, env in (("stream", {}), ("generic", {"MRHIP_FORCE_GENERIC": "1"})):
                 for k, v in env.items():
                     monkeypatch.setenv(k, v)
                 f = pkg.FIRFilter(h, Fraction(1, 4), numerics=numerics)
@@ -1520,15 +1517,14 @@ def test_decim_lane_kernel_behind_its_switch(pkg, O, torch_cuda, monkeypatch):
                 for k in env:
                     monkeypatch.delenv(k)
             tag = f"nch={nch} numerics={numerics}"
-            assert "decim_lane_kernel" in got["lane"][1] and "decim_lane_kernel" not in got["stream"][1], (tag, got["lane"][1], got["stream"][1])
-            assert_bit_equal(got["lane"][0], got["generic"][0], "lane vs universal " + tag)
-            assert_bit_equal(got["lane"][0], got["stream"][0], "lane vs streaming kernel " + tag)
-            assert got["lane"][2] == got["generic"][2], tag
-            assert_bit_equal(got["lane"][3], got["generic"][3], "history " + tag)
+            assert "fir_stream_kernel" in got["stream"][1], (tag, got["stream"][1])
+            assert_bit_equal(got["stream"][0], got["generic"][0], "streaming kernel vs universal " + tag)
+            assert got["stream"][2] == got["generic"][2], tag
+            assert_bit_equal(got["stream"][3], got["generic"][3], "history " + tag)
             if numerics == pkg.NUMERICS_STRICT:
                 for c in (0, 3, 4, nch - 1):
                     fo = O.FIRFilter(h, Fraction(1, 4), tx=np.complex64)
-                    assert_bit_equal(got["lane"][0][c], np.concatenate(_run_chunks(fo, x[c], sizes)), f"lane vs oracle ch {c} " + tag)
+                    assert_bit_equal(got["stream"][0][c], np.concatenate(_run_chunks(fo, x[c], sizes)), f"streaming kernel vs oracle ch {c} " + tag)
 
 
 def test_arb_lane_kernel_float64_lane_per_channel(pkg, O, torch_cuda, monkeypatch):
@@ -1579,12 +1575,10 @@ def test_arb_lane_kernel_float64_lane_per_channel(pkg, O, torch_cuda, monkeypatc
         f.close()
 
 
-def test_arb_window_kernel_behind_its_switch(pkg, O, torch_cuda, monkeypatch):
-    """arb_window_kernel (kernels_arb_window.hip: FIRArbitrary, Float64, 32 taps per phase, one wave per stretch with the window in
-    registers) is NOT the default -- on config 4 it measures slower than arb_lane_kernel (profiles/r06/experiments.md G) -- but stays in the
-    library behind MRHIP_ARB_WINDOW: outputs, end state and history bit for bit those of arb_lane_kernel, of the universal kernel and
-    (STRICT) of the oracle: full, several and partial channel groups, rates whose consecutive windows coincide (10.3) or never do (1.0),
-    chunkings with a one-sample and a 17-sample call, -0.0 / +-Inf / NaN samples."""
+def test_arb_lane_kernel_float64_32_taps_edge_values(pkg, O, torch_cuda, monkeypatch):
+    """arb_lane_kernel with Float64 taps and 32 taps per phase (config 4's shape): outputs, end state and history bit for bit those of
+    the universal kernel and (STRICT) of the oracle: full, several and partial channel groups, rates whose consecutive windows coincide
+    (10.3) or never do (1.0), chunkings with a one-sample and a 17-sample call, -0.0 / +-Inf / NaN samples."""
     torch = torch_cuda
     rng = np.random.default_rng(808)
     monkeypatch.setenv("MRHIP_ARB_SMALL_MAX", "0")
@@ -1597,7 +1591,7 @@ def test_arb_window_kernel_behind_its_switch(pkg, O, torch_cuda, monkeypatch):
         sizes = [5_000, 1, 17, n - 5_018 - 3_003, 3_003]
         for numerics in (pkg.NUMERICS_STRICT, pkg.NUMERICS_FUSED):
             got = {}
-            for mode, env in (("window", {"MRHIP_ARB_WINDOW": "2"}), ("lane", {}), ("generic", {"MRHIP_FORCE_GENERIC": "1"})):
+            for mode, env in (("lane", {}), ("generic", {"MRHIP_FORCE_GENERIC": "1"})):
                 for k, v in env.items():
                     monkeypatch.setenv(k, v)
                 f = pkg.FIRFilter(h, float(rate), nphi, numerics=numerics)
@@ -1608,15 +1602,14 @@ def test_arb_window_kernel_behind_its_switch(pkg, O, torch_cuda, monkeypatch):
                 for k in env:
                     monkeypatch.delenv(k)
             tag = f"Nphi={nphi} nch={nch} rate={rate:.4f} numerics={numerics}"
-            assert got["window"][1] == "arb_window_kernel" and got["lane"][1] == "arb_lane_kernel" and got["generic"][1] == "arb_generic_kernel", (tag, got["window"][1], got["lane"][1])
-            assert_bit_equal(got["window"][0], got["generic"][0], "window vs universal " + tag)
-            assert_bit_equal(got["window"][0], got["lane"][0], "window vs lane " + tag)
-            assert got["window"][2] == got["generic"][2], tag
-            assert_bit_equal(got["window"][3], got["generic"][3], "history " + tag)
+            assert got["lane"][1] == "arb_lane_kernel" and got["generic"][1] == "arb_generic_kernel", (tag, got["lane"][1], got["generic"][1])
+            assert_bit_equal(got["lane"][0], got["generic"][0], "lane vs universal " + tag)
+            assert got["lane"][2] == got["generic"][2], tag
+            assert_bit_equal(got["lane"][3], got["generic"][3], "history " + tag)
             if numerics == pkg.NUMERICS_STRICT:
                 for c in (0, 2, nch - 1):
                     fo = O.FIRFilter(h, float(rate), nphi, tx=np.float64)
-                    assert_bit_equal(got["window"][0][c], np.concatenate(_run_chunks(fo, x[c], sizes)), f"window vs oracle ch {c} " + tag)
+                    assert_bit_equal(got["lane"][0][c], np.concatenate(_run_chunks(fo, x[c], sizes)), f"lane vs oracle ch {c} " + tag)
 
 
 def test_large_L_runs_on_the_output_pair_kernel_in_period_blocks(pkg, O, torch_cuda, monkeypatch):
