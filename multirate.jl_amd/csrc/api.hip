@@ -264,7 +264,7 @@ hipError_t launch_opair_blocks(mrhip_filter *f, const TypeKey &tk, bool fused, c
         m.u0 = u0b; m.d0 = a.d0; m.phi_end = a.phi_end; m.d_end = a.d_end;
         m.steps_per_channel = static_cast<unsigned>(std::max<long long>(spc, 1));
         m.total_steps = static_cast<unsigned>(spc * a.nch);
-        m.spc_magic = spc <= 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+        m.spc_magic = step_magic(spc);
         m.nch = b == 0 ? a.nch : 0;                                                      // (shiftin! and the record: once per call)
         m.P_blk = static_cast<int>(Pb);
         m.q0 = static_cast<int>((u0b / a.L) & ~1LL);                                    // even: the lanes' run starts keep their parity
@@ -603,7 +603,7 @@ void mrhip_destroy(mrhip_filter *f)
 // The host's state written into the device record, in stream order behind whatever the filter enqueued last (the stream of
 // its last call; when that stream no longer exists -- torch side streams come and go -- behind the whole device, on the
 // filter's own stream).
-// the filter's schedule stream behind a chained call's schedule, which ran on the caller's stream (filt_device_one)
+// the filter's schedule stream behind a chained call's schedule, which ran on the caller's stream (arb_call_device_sched)
 // The schedule stream behind what ran on a caller's stream (chain_pending / chain_stream): the event is recorded NOW -- it then covers at least
 // what it has to -- and not by every small call (one host call each: profiles/r05/experiments.md O).  A stream that no longer exists has
 // nothing pending the device could still be running for long: the device is waited for instead.
@@ -670,12 +670,33 @@ int64_t mrhip_outputlength(const mrhip_filter *f, int64_t n)
     return -1;
 }
 
+// FIRArbitrary / FIRFarrow: the host's stream state as the phase recurrence takes it, and back (Filters.jl:731-735)
+static ArbState arb_state(const mrhip_filter *f) { return ArbState{f->phiAcc, f->phiIdx, f->alpha, f->xIdx, f->inputDeficit}; }
+static void arb_state_commit(mrhip_filter *f, const ArbState &st)
+{
+    f->phiAcc = st.acc; f->phiIdx = st.phiIdx; f->alpha = st.alpha; f->xIdx = st.xIdx;
+    f->inputDeficit = st.inputDeficit;
+}
+
+// Upper bound of the output count of x_len samples from the current state (the reference's outputlength estimate,
+// Filters.jl:375-381, + 2 for the rounding of its Float64 recurrence)
+static int64_t arb_estimate(const mrhip_filter *f, int64_t x_len)
+{
+    return x_len >= f->inputDeficit ? static_cast<int64_t>(std::ceil(static_cast<double>(x_len - f->inputDeficit + 1) * f->rate)) + 2 : 0;
+}
+
+// samples per FIRArbitrary / FIRFarrow launch: at most 2^24 schedule entries, at least 4096 samples
+static int64_t arb_launch_step(const mrhip_filter *f)
+{
+    return std::max<int64_t>(4096, static_cast<int64_t>(static_cast<double>(1LL << 24) / f->rate));
+}
+
 // FIRArbitrary: evaluate (or reuse) the phase schedule for a call of x_len samples from the current state
 static int64_t arb_schedule(mrhip_filter *f, int64_t x_len, ArbState *end_state)
 {
     if (!(f->sched_cached && f->sched_xlen == x_len && f->sched_acc0 == f->phiAcc && f->sched_deficit0 == f->inputDeficit)) {
         if (f->sched_in_flight) { (void)hipEventSynchronize(f->sched_copied); f->sched_in_flight = false; }
-        ArbState st{f->phiAcc, f->phiIdx, f->alpha, f->xIdx, f->inputDeficit};
+        ArbState st = arb_state(f);
         f->sched_acc0 = f->phiAcc; f->sched_deficit0 = f->inputDeficit; f->sched_xlen = x_len;
         f->sched_count = run_arbitrary_schedule(st, f->delta, f->Nphi, x_len, &f->sched_n, &f->sched_acc, f->mod_form);
         f->sched_end = st;
@@ -709,11 +730,11 @@ int64_t mrhip_advance_state(mrhip_filter *f, int64_t n)
         // its first sample this way, sharding.py); short ones, and rates the device evaluation does not cover, keep the loop.
         total = 0;
         int64_t left = n;
-        const int64_t step = std::max<int64_t>(4096, static_cast<int64_t>(static_cast<double>(1LL << 24) / f->rate));
+        const int64_t step = arb_launch_step(f);
         while (left > 0) {
             const int64_t len = std::min(left, step);
-            const int64_t est = len >= f->inputDeficit ? static_cast<int64_t>(std::ceil(static_cast<double>(len - f->inputDeficit + 1) * f->rate)) + 2 : 0;
-            ArbState st{f->phiAcc, f->phiIdx, f->alpha, f->xIdx, f->inputDeficit};
+            const int64_t est = arb_estimate(f, len);
+            ArbState st = arb_state(f);
             int64_t got = 0;
             if (sched_wants_device(f, est) && f->s_sched) {
                 SchedOut so{};
@@ -727,15 +748,13 @@ int64_t mrhip_advance_state(mrhip_filter *f, int64_t n)
                     if (!relaunch) break;
                 }
                 got = so.count; st = so.end;
-                f->sched_drift = so.drift; f->sched_ksteps = so.ksteps;
-                if (so.periodic || f->per_valid) f->per_pos = so.per_pos_end;
+                sched_commit(f, so);
                 f->memo_valid = false;                      // (the entries in the buffer belong to a call that was never made)
             } else {
                 got = run_arbitrary_schedule(st, f->delta, f->Nphi, len, nullptr, nullptr, f->mod_form);    // (count only: no entries kept)
                 sched_forget(f);
             }
-            f->phiAcc = st.acc; f->phiIdx = st.phiIdx; f->alpha = st.alpha; f->xIdx = st.xIdx;   // Filters.jl:731-735
-            f->inputDeficit = st.inputDeficit;
+            arb_state_commit(f, st);
             total += got;
             left -= len;
         }
@@ -1096,6 +1115,491 @@ static hipError_t launch_poly_dyn(mrhip_filter *f, const TypeKey &tk, bool fused
     return launch_poly_generic(tk, fused, a, s, kname);
 }
 
+// One filt! launch as filt_device_one took it in, and what every path of it reads.
+struct CallArgs {
+    const void *x;
+    int64_t x_len, x_stride;
+    void *y;
+    int64_t y_capacity, y_stride;
+    int64_t *n_written;
+    hipStream_t stream;
+    bool continuation;                 // (filt_device_one)
+    bool capturing, dev_planned;       // dev_planned: planned on the device (an asynchronous or captured call)
+    long long *count_dev;
+    const DevCall *x_from;             // a chained call: the previous stage's call record
+    TypeKey tk;
+    bool fused;
+    int64_t bound;                     // output_bound(f, x_len)
+    int hist_next;                     // the history slot this call writes
+};
+
+// What the path of a call leaves for finish_call.
+struct CallOut {
+    int64_t n_out = 0;                 // -1: only the device knows the count (a call planned there)
+    bool did_shiftin = false;          // a filter kernel wrote the call-end history (no launch of shiftin_kernel)
+    bool hist_in_place = false;        // ... inside a capture, straight into the slot the replay reads (ShiftFold)
+    bool rec_current = false;          // the device record has (or will have, in stream order) this call's end state
+    bool sched_inline = false;         // FIRArbitrary / FIRFarrow: this call's schedule ran on the caller's stream although the filter has a schedule stream
+};
+
+// ---- the rational family --------------------------------------------------------------------------------------------------
+// The launch arguments of a rational-family call, all but the output count, the call-start state and the record.  `continuation`:
+// see filt_device_one.
+static PolyArgs poly_call_args(const mrhip_filter *f, const void *x, void *y, int64_t x_stride, int64_t y_stride, int64_t x_len, bool continuation)
+{
+    PolyArgs a{};
+    a.x = x; a.y = y; a.hist = f->d_hist[f->hist_cur]; a.hist_new = f->d_hist[hist_other(f)]; a.taps = f->d_taps;
+    a.x_stride = x_stride; a.y_stride = y_stride; a.x_len = x_len;
+    a.zero_start_below = continuation ? 0
+                       : f->kind == MRHIP_FIR_STANDARD ? f->hLen + 1
+                       : f->kind == MRHIP_FIR_DECIMATOR ? f->hLen : 0;
+    a.L = static_cast<int>(f->L); a.M = static_cast<int>(f->M);
+    a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H);
+    a.nch = static_cast<int>(f->nch);
+    return a;
+}
+
+// A rational-family call planned on the device: the plan kernel in front of the filter kernel takes count and call-start state from the record.
+static int poly_call_device(mrhip_filter *f, const CallArgs &c, CallOut &out)
+{
+    PolyArgs a = poly_call_args(f, c.x, c.y, c.x_stride, c.y_stride, c.x_len, c.continuation);
+    a.n_out = std::max<int64_t>(c.bound, 1);                          // upper bounds: the plan kernel leaves the call's own values in the call record
+    a.u0 = 0; a.d0 = 1;
+    a.rec = f->d_rec; a.dyn = f->d_call;
+    if (int rc = timing_mark(f, c.stream)) return rc;
+    {
+        const hipError_t e = launch_poly_dyn(f, c.tk, c.fused, a, c.x_len, c.y_capacity, c.count_dev, c.stream, &f->last_kernel, &out.did_shiftin, c.x_from);
+        if (e == hipErrorNotSupported && c.x_from)
+            return fail(MRHIP_ERR_UNSUPPORTED, "a chained call (input length = the previous stage's count, on the device) needs a filter the pair kernels serve (rational_opair_kernel / fir_stream_kernel)");
+        MRHIP_CHECK_HIP(e);
+    }
+    if (int rc = timing_mark(f, c.stream)) return rc;
+    out.rec_current = true;
+    if (c.x_from) {
+        out.n_out = -1;                 // (the host never learns a chained call's length: its view of the state is re-read from the device)
+    } else if (f->mirror_valid || c.capturing) {
+        // the shadow of ONE execution: exact while the host knew the state when the capture (or the run of
+        // asynchronous calls) began; re-read from the device before it is next used either way
+        const CallPlan p = plan_rational(f->kind, f->L, f->M, f->phiIdx, f->inputDeficit, c.x_len);
+        out.n_out = p.n_out;
+        f->phiIdx = p.phi_end;
+        f->inputDeficit = p.d_end;
+    } else {
+        out.n_out = -1;
+    }
+    f->mirror_valid = false;
+    f->last_call_dev_planned = true;
+    f->last_call_rec = f->d_call;
+    if (!c.capturing) f->async_pending = true;
+    return MRHIP_OK;
+}
+
+// A rational-family call the host plans (closed form): the kernel gets count, call-start and end state as arguments.
+static int poly_call_host(mrhip_filter *f, const CallArgs &c, CallOut &out)
+{
+    f->last_call_dev_planned = false;
+    const CallPlan p = plan_rational(f->kind, f->L, f->M, f->phiIdx, f->inputDeficit, c.x_len);
+    out.n_out = p.n_out;
+    // reference: error() before any work, Filters.jl:460 (Standard), :503 (Interpolator), :550 (Rational)
+    if (p.n_out > c.y_capacity) return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small");
+    if (p.n_out > 0) {
+        if (!c.y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
+        if (f->nch > 1 && c.y_stride < p.n_out) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output count");
+        PolyArgs a = poly_call_args(f, c.x, c.y, c.x_stride, c.y_stride, c.x_len, c.continuation);
+        a.n_out = p.n_out;
+        a.u0 = p.phi0 - 1; a.d0 = p.d0;
+        a.rec = f->d_rec; a.dyn = nullptr; a.phi_end = p.phi_end; a.d_end = p.d_end;
+        const TypeKey &tk = c.tk;
+        const bool fused = c.fused;
+        hipStream_t stream = c.stream;
+        bool did_shiftin = false, rec_current = false;
+        if (int rc = timing_mark(f, stream)) return rc;
+        MRHIP_CHECK_HIP(launch_poly(f, tk, fused, a, stream, &f->last_kernel, &did_shiftin, f->d_counters, &rec_current));
+        if (int rc = timing_mark(f, stream)) return rc;
+        out.did_shiftin = did_shiftin; out.rec_current = rec_current;
+    }
+    f->phiIdx = p.phi_end;
+    f->inputDeficit = p.d_end;
+    return MRHIP_OK;
+}
+
+// ---- FIRArbitrary / FIRFarrow -----------------------------------------------------------------------------------------------
+// A call of FIRArbitrary / FIRFarrow and the device buffers its schedule entries are in (set by the schedule source before its first launch_range).
+struct ArbRange {
+    mrhip_filter *f;
+    const CallArgs &c;
+    bool pipe_dynamic;                 // MRHIP_PIPE_DYNAMIC (default 1): the tiled kernels hand their tiles out from a counter
+    const void *sched_dn = nullptr, *sched_dacc = nullptr;
+    // NULL, or (a schedule evaluated on the device, whose host copy launch_range does not get) the largest input span of the aligned tiles of 64 ... 1024 outputs
+    const int *spans = nullptr;
+};
+
+// (a small call -- at most MRHIP_ARB_SMALL_MAX (150 000) outputs x channels -- runs faster on the universal kernel, one lane per output and
+//  nothing to set up: 1 ch x 1e5 samples 6.7 against 8.6 us, the crossover at 1 ch x 3e5 / 2 ch x 1.5e5; profiles/r05/experiments.md O)
+static bool arb_small_call(const mrhip_filter *f, int64_t n_out) { return n_out * f->nch <= static_cast<int64_t>(MRHIP_ENV_INT("MRHIP_ARB_SMALL_MAX", 150000)); }
+
+// launch_range tries arb_lane_kernel on a range of n_out outputs (if the kernel takes its shape: arb_lane_eligible)
+static bool arb_lane_ok(const ArbRange &r, int64_t n_out) { return !r.f->force_generic && !arb_small_call(r.f, n_out) && r.pipe_dynamic; }
+
+// One range [k0, k0+cnt) of a call's outputs, whose schedule entries are already in the device buffers.  n_host: the entries' host copy,
+// or NULL; dyn: the count comes from the call record, cnt is its upper bound.  whole_call: the range is the call (not a piece of a long
+// one): the kernels that can (arb_pipe_kernel, farrow_wave_kernel) then write the next call's history themselves (ShiftFold) -- inside a
+// capture straight into the slot the replay reads, which takes x_len >= H
+static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_t *n_host, const DevCall *dyn, bool whole_call, CallOut &out)
+{
+    mrhip_filter *f = r.f;
+    const CallArgs &c = r.c;
+    const TypeKey &tk = c.tk;
+    const bool fused = c.fused;
+    hipStream_t stream = c.stream;
+    if (!r.sched_dn || !r.sched_dacc) return fail(MRHIP_ERR_HIP, "no phase schedule on the device (internal)");
+    ShiftFold sf{};
+    const bool in_place = c.capturing;
+    if (whole_call && f->H > 0 && !c.x_from && (!in_place || c.x_len >= f->H) && MRHIP_ENV_INT("MRHIP_FOLD_SHIFTIN", 1) != 0) {
+        sf.hist_new = f->d_hist[in_place ? f->hist_cur : c.hist_next];
+        sf.done = in_place ? f->d_counters + 128 : nullptr;
+    }
+    const size_t yelt = dtype_scalar_size(f->ty) * static_cast<size_t>(f->nc);
+    void *yk = static_cast<unsigned char *>(c.y) + static_cast<size_t>(k0) * yelt;
+    // the tiled kernels' tiles are handed out from a counter of the filter (its launches are stream-ordered: one at a time);
+    // MRHIP_PIPE_DYNAMIC=0: every workgroup takes every gridDim-th tile
+    unsigned *tile_counters = r.pipe_dynamic ? f->d_counters : nullptr;
+    bool takes_fold = true;                                            // the kernel chosen below writes the history when sf asks it to
+    if (f->kind == MRHIP_FIR_FARROW) {
+        FarrowArgs fa{};
+        fa.x = c.x; fa.y = yk; fa.hist = f->d_hist[f->hist_cur]; fa.pnfb = f->d_pnfb;
+        fa.n_idx = static_cast<const int *>(r.sched_dn) + k0; fa.acc = static_cast<const double *>(r.sched_dacc) + k0;
+        fa.x_stride = c.x_stride; fa.y_stride = c.y_stride; fa.x_len = c.x_len; fa.n_out = cnt;
+        fa.T = static_cast<int>(f->T); fa.H = static_cast<int>(f->H); fa.polyorder = static_cast<int>(f->polyorder);
+        fa.tap_f32 = f->th == MRHIP_F32; fa.nch = static_cast<int>(f->nch);
+        fa.seam_below = c.continuation ? 0 : static_cast<int>(f->T);
+        fa.dyn = dyn;
+        if (int rc = timing_mark(f, stream)) return rc;
+        ArbTileArgs fta;
+        size_t flds = 0;
+        if (!f->force_generic && f->d_pnfb_t && plan_farrow_wave(fa)) {
+            FarrowArgs fw = fa;
+            fw.pnfb = f->d_pnfb_t;                              // degree-major, padded: [polyorder+1][32]
+            fw.fold = sf;
+            MRHIP_CHECK_HIP(launch_farrow_wave(tk, fused, fw, stream, &f->last_kernel, f->num_cus));
+        }
+        else if (!f->force_generic && plan_farrow_tiled(tk, fa, n_host, r.spans, f->num_cus, &fta, &flds)) {
+            fta.counters = tile_counters;
+            fa.fold = sf;
+            MRHIP_CHECK_HIP(launch_farrow_tiled(tk, fused, fa, fta, flds, stream, &f->last_kernel, f->num_cus));
+        }
+        else {
+            takes_fold = false;
+            MRHIP_CHECK_HIP(launch_farrow(tk, fused, fa, stream, &f->last_kernel));
+        }
+    } else {
+        ArbArgs a{};
+        a.x = c.x; a.y = yk; a.hist = f->d_hist[f->hist_cur]; a.taps = f->d_taps; a.dtaps = f->d_dtaps;
+        a.n_idx = static_cast<const int *>(r.sched_dn) + k0; a.acc = static_cast<const double *>(r.sched_dacc) + k0;
+        a.x_stride = c.x_stride; a.y_stride = c.y_stride; a.x_len = c.x_len; a.n_out = cnt;
+        a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H); a.Nphi = static_cast<int>(f->Nphi);
+        a.nch = static_cast<int>(f->nch);
+        a.dyn = dyn;
+        if (int rc = timing_mark(f, stream)) return rc;
+        ArbTileArgs ta;
+        size_t lds = 0;
+        ArbLaneArgs la;
+        if (arb_lane_ok(r, cnt) && plan_arb_lane(tk, a, f->rate, &la, &lds)) {
+            // (64 channels or more, Float64, a rate >= 1: a lane per channel, the taps in scalar registers -- kernels_arb_lane.hip)
+            la.counters = f->d_counters;
+            a.fold = sf;
+            MRHIP_CHECK_HIP(launch_arb_lane(fused, a, la, lds, stream, &f->last_kernel, f->num_cus));
+        }
+        else if (!f->force_generic && !arb_small_call(f, cnt) && plan_arb_tiled(tk, a, n_host, r.spans, f->num_cus, &ta, &lds)) {
+            ta.counters = tile_counters;
+            a.fold = sf;
+            MRHIP_CHECK_HIP(launch_arb_tiled(tk, fused, a, ta, lds, stream, &f->last_kernel, f->num_cus));
+        }
+        else {
+            a.fold = sf;
+            MRHIP_CHECK_HIP(launch_arb_generic(tk, fused, a, stream, &f->last_kernel));
+        }
+    }
+    if (takes_fold && sf.hist_new) { out.did_shiftin = true; out.hist_in_place = in_place; }
+    return timing_mark(f, stream);
+}
+
+// The schedule is evaluated on the device (arb_schedule.hip), in front of ONE filter launch that takes the output count from the call
+// record: nothing waits in the middle of the call.  A caller that wants the count (the reference's filt! returns it) collects it from
+// the pinned mirror once the schedule's last kernel has run -- by then the filter kernel is already queued behind it.
+static int arb_call_device_sched(ArbRange &r, int64_t est, CallOut &out, ArbState &st)
+{
+    mrhip_filter *f = r.f;
+    const CallArgs &c = r.c;
+    const bool capturing = c.capturing, dev_planned = c.dev_planned;
+    hipStream_t stream = c.stream;
+    if (est >= 0x7fffffffLL) return fail(MRHIP_ERR_INVALID_ARG, "call too long for one launch (internal)");
+    int spans[kSchedSpanSizes];
+    span_bounds(f->rate, spans);
+    // The schedule runs on the filter's schedule stream, BESIDE the filter kernel of the call before (its inputs are
+    // the record, which moved on with that call's FINISH kernel, and nothing else); schedule buffers and call records
+    // alternate, events order writer and reader of each (mrhip_filter.h: s_sched).  Inside a capture: one stream.
+    // (a chained call's schedule reads the previous stage's call record, which is written on the caller's stream: it runs there)
+    // (a call of one small piece -- at most MRHIP_SCHED_INLINE_MAX outputs, default 65 536 -- is launch-bound: its three kernels go down ONE
+    //  queue without the three event operations the second stream costs the host; profiles/r05/experiments.md O)
+    // (calls arb_lane_kernel will serve: that kernel's persistent workgroups hold every vector register of the chip -- the next call's schedule
+    //  cannot run BESIDE it: its tables / chain workgroups either wait for the kernel's end anyway or, when the race at the start lets
+    //  them in, both run much longer -- config 4 on a continuing stream read 3.9 or 4.5-5.1 ms per call.  Behind it, on the caller's
+    //  stream: 3.93 + 0.2 ms, every call.  profiles/r06/experiments.md I; MRHIP_SCHED_BESIDE_LANE=1: as before)
+    //  (the call launches est outputs: launch_range below)
+    const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && arb_lane_ok(r, est) &&
+                            arb_lane_eligible(c.tk, static_cast<int>(f->T), static_cast<int>(f->H), f->nch, f->rate, c.x_len, c.x_stride, c.y_stride) &&
+                            MRHIP_ENV_INT("MRHIP_SCHED_BESIDE_LANE", 0) == 0;
+    const bool inline_sched = est <= MRHIP_ENV_INT("MRHIP_SCHED_INLINE_MAX", 65536) || lane_shape;
+    hipStream_t ss = capturing || !f->s_sched || c.x_from || inline_sched ? stream : f->s_sched;
+    // a chained call's schedule ran on the CALLER's stream (it reads the previous stage's call record there) and wrote the record,
+    // the piece states and the path tables: a schedule on the filter's own schedule stream must come behind it
+    if (ss == f->s_sched && f->chain_pending)
+        if (int rc = chain_event_now(f)) return rc;
+    if (ss == f->s_sched) f->sched_dirty = true;
+    else if (!capturing && f->s_sched && f->sched_dirty) {        // (mrhip_filter.h: sched_dirty)
+        MRHIP_CHECK_HIP(hipEventRecord(f->ev_sdirty, f->s_sched));
+        MRHIP_CHECK_HIP(hipStreamWaitEvent(stream, f->ev_sdirty, 0));
+        f->sched_dirty = false;
+    }
+    out.sched_inline = ss == stream && !capturing && f->s_sched != nullptr;
+    SchedOut so{};
+    so.buf = capturing ? 0 : f->flip;
+    if (!capturing) f->flip ^= 1;
+    if (ss != stream && f->ev_filt_valid[so.buf]) MRHIP_CHECK_HIP(hipStreamWaitEvent(ss, f->ev_filt[so.buf], 0));
+    if (int rc = sched_enqueue(f, c.x_len, est, dev_planned ? c.y_capacity : INT64_MAX, c.count_dev, !dev_planned, ss, &so, c.x_from)) return rc;   // (a call that is waited for checks the count against the room itself)
+    const int b = so.buf;                                         // (a memo hit names the buffer that holds the entries)
+    r.sched_dn = f->ds_n[b]; r.sched_dacc = f->ds_acc[b]; r.spans = spans;
+    auto join = [&]() -> int {                                  // the filter kernel behind its schedule
+        if (ss == stream) return MRHIP_OK;
+        MRHIP_CHECK_HIP(hipEventRecord(f->ev_fin[b], ss));
+        MRHIP_CHECK_HIP(hipStreamWaitEvent(stream, f->ev_fin[b], 0));
+        return MRHIP_OK;
+    };
+    const bool room = c.y && c.y_capacity >= est && (f->nch == 1 || c.y_stride >= est);
+    bool launched = false;
+    if (so.pending && room && est > 0) {
+        if (int rc = join()) return rc;
+        if (int rc = launch_range(r, 0, est, nullptr, f->d_calls[b], true, out)) return rc;
+        launched = true;
+    }
+    out.rec_current = so.pending;
+    if (dev_planned) {
+        // nobody collects: the host's copy of the state is stale from here on
+        f->mirror_valid = false;
+        f->last_call_dev_planned = so.pending && launched;        // (a chained call may follow: its input length is this call's count)
+        f->last_call_rec = f->d_calls[b];
+        if (!capturing) f->async_pending = true;
+        if (!capturing && so.pending && !so.periodic && !c.x_from) {
+            // The host's LOWER BOUND of the drift baseline (it sizes the next calls' pieces: at most 16 x the baseline) moves on
+            // by the fewest outputs this call can have -- xIdx starts at most 1/rate + 1 in and advances at most 1/rate + 1 a
+            // step -- so that a stream of asynchronous calls is not cut into pieces of 4096 forever; mrhip_sync_state brings
+            // the exact value.
+            const double lb = std::floor((static_cast<double>(c.x_len) - 1.0 / f->rate - 3.0) * f->rate) - 2.0;
+            if (lb > 0.0) f->sched_ksteps += lb;
+        }
+        out.n_out = -1;
+    } else {
+        f->last_call_dev_planned = false;
+        for (;;) {
+            bool relaunch = false;
+            if (int rc = sched_collect(f, c.x_len, est, INT64_MAX, c.count_dev, ss, &so, &relaunch)) return rc;
+            if (!relaunch) break;
+            out.rec_current = so.pending;
+            if (so.pending && room) {
+                if (int rc = join()) return rc;
+                if (int rc = launch_range(r, 0, est, nullptr, f->d_calls[b], true, out)) return rc;
+            } else launched = false;
+        }
+        out.n_out = so.count;
+        st = so.end;
+        // (rec_current: the FINISH kernel wrote the record; a call the host evaluated itself pushes it in finish_call)
+        if (out.n_out > c.y_capacity) {
+            if (out.rec_current) {      // the record moved on with the schedule: take the stream back to the call's start
+                f->sched_cached = false;
+                (void)rec_push(f, ss);
+            }
+            return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small");
+        }
+        if (out.n_out > 0 && !launched) {
+            if (!c.y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
+            if (f->nch > 1 && c.y_stride < out.n_out) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output count");
+            if (int rc = join()) return rc;
+            if (int rc = launch_range(r, 0, out.n_out, nullptr, nullptr, true, out)) return rc;
+        }
+        sched_commit(f, so);
+        sched_memo_commit(f, so, c.x_len);
+    }
+    if (ss != stream) {                                          // buffer b's next writer waits for this reader
+        MRHIP_CHECK_HIP(hipEventRecord(f->ev_filt[b], stream));
+        f->ev_filt_valid[b] = true;
+    } else if (!capturing && f->s_sched) {                       // (see chain_pending above; also orders buffer b's next writer)
+        f->chain_stream = stream;
+        f->chain_pending = true;
+    }
+    return MRHIP_OK;
+}
+
+// The host's serial schedule, piece by piece (MRHIP_SCHED_PIECE outputs): each piece is uploaded from the pinned staging and filtered
+// while the host evaluates the next one.
+static int arb_call_host_pieces(ArbRange &r, int64_t est, int64_t piece, CallOut &out, ArbState &st)
+{
+    mrhip_filter *f = r.f;
+    const CallArgs &c = r.c;
+    hipStream_t stream = c.stream;
+    if (f->sched_in_flight) { MRHIP_CHECK_HIP(hipEventSynchronize(f->sched_copied)); f->sched_in_flight = false; }
+    if (int rc = ensure_sched_capacity(f, static_cast<size_t>(est))) return rc;
+    r.sched_dn = f->d_sched_n; r.sched_dacc = f->d_sched_acc;      // (the buffers may just have been (re)allocated)
+    st = ArbState{f->phiAcc, f->phiIdx, f->alpha, f->inputDeficit, f->inputDeficit};   // xIdx starts at inputDeficit (:715)
+    bool done = false;
+    int64_t k0 = 0;
+    static const bool prof = [] { const char *v = std::getenv("MRHIP_DEBUG"); return v && v[0] == '2'; }();
+    double t_rec = 0, t_copy = 0, t_launch = 0;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    // an error in the middle of the pipeline: uploads from the pinned staging may still be in flight, so mark
+    // them (the next call waits before it reuses the staging) and report how far the launches got; the
+    // filter state is not advanced
+    auto bail = [&](int rc) -> int {
+        if (hipEventRecord(f->sched_copied, stream) == hipSuccess) f->sched_in_flight = true;
+        else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
+        if (c.n_written) *c.n_written = k0;
+        return rc;
+    };
+    while (!done) {
+        int32_t *pn = static_cast<int32_t *>(f->pin_n) + k0;
+        double *pa = static_cast<double *>(f->pin_acc) + k0;
+        const int64_t room = std::min<int64_t>(piece, est - k0);
+        if (room <= 0) return bail(fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small"));   // cannot happen: est is an upper bound
+        const double t0 = prof ? now() : 0;
+        const int64_t cnt = run_arbitrary_schedule_piece(st, f->delta, f->Nphi, c.x_len, pn, pa, room, &done, f->mod_form);
+        const double t1 = prof ? now() : 0;
+        if (cnt > 0) {
+            if (hipMemcpyAsync(static_cast<int32_t *>(f->d_sched_n) + k0, pn, static_cast<size_t>(cnt) * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
+                hipMemcpyAsync(static_cast<double *>(f->d_sched_acc) + k0, pa, static_cast<size_t>(cnt) * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess)
+                return bail(fail(MRHIP_ERR_HIP, "uploading the phase schedule failed"));
+            const double t2 = prof ? now() : 0;
+            if (int rc = launch_range(r, k0, cnt, pn, nullptr, false, out)) return bail(rc);
+            if (prof) { t_rec += t1 - t0; t_copy += t2 - t1; t_launch += now() - t2; }
+            k0 += cnt;
+        }
+    }
+    if (prof) std::fprintf(stderr, "[mrhip] arbitrary schedule: recurrence %.2f ms, memcpy enqueue %.2f ms, plan+launch %.2f ms (%lld outputs)\n",
+                           t_rec * 1e3, t_copy * 1e3, t_launch * 1e3, static_cast<long long>(k0));
+    MRHIP_CHECK_HIP(hipEventRecord(f->sched_copied, stream));
+    f->sched_in_flight = true;
+    out.n_out = k0;
+    return MRHIP_OK;
+}
+
+// The host's serial schedule of the whole call (or the one mrhip_next_output_count cached), uploaded in one piece.
+static int arb_call_host_serial(ArbRange &r, CallOut &out, ArbState &st)
+{
+    mrhip_filter *f = r.f;
+    const CallArgs &c = r.c;
+    hipStream_t stream = c.stream;
+    const int64_t n_out = arb_schedule(f, c.x_len, &st);   // update(::FIRFarrow), Filters.jl:780-788, is the same recurrence
+    out.n_out = n_out;
+    if (f->sched_in_flight) { MRHIP_CHECK_HIP(hipEventSynchronize(f->sched_copied)); f->sched_in_flight = false; }
+    if (n_out > c.y_capacity) return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small");
+    if (n_out > 0) {
+        if (!c.y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
+        if (f->nch > 1 && c.y_stride < n_out) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output count");
+        if (int rc = ensure_sched_capacity(f, static_cast<size_t>(n_out))) return rc;
+        r.sched_dn = f->d_sched_n; r.sched_dacc = f->d_sched_acc;
+        std::memcpy(f->pin_n, f->sched_n.data(), static_cast<size_t>(n_out) * sizeof(int32_t));
+        std::memcpy(f->pin_acc, f->sched_acc.data(), static_cast<size_t>(n_out) * sizeof(double));
+        MRHIP_CHECK_HIP(hipMemcpyAsync(f->d_sched_n, f->pin_n, static_cast<size_t>(n_out) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        MRHIP_CHECK_HIP(hipMemcpyAsync(f->d_sched_acc, f->pin_acc, static_cast<size_t>(n_out) * sizeof(double), hipMemcpyHostToDevice, stream));
+        MRHIP_CHECK_HIP(hipEventRecord(f->sched_copied, stream));
+        f->sched_in_flight = true;
+        if (int rc = launch_range(r, 0, n_out, f->sched_n.data(), nullptr, true, out)) return rc;
+    }
+    return MRHIP_OK;
+}
+
+// A FIRArbitrary / FIRFarrow call: its phase schedule from one of three sources, the filter launch(es) behind it, the state it ends in.
+static int arb_call(mrhip_filter *f, const CallArgs &c, CallOut &out)
+{
+    ArbRange r{f, c, MRHIP_ENV_INT("MRHIP_PIPE_DYNAMIC", 1) != 0};
+    // Upper bound of the output count; without the host's copy of the state: for inputDeficit = 1.
+    const int64_t est = c.dev_planned ? c.bound : arb_estimate(f, c.x_len);
+    const bool cached = !c.dev_planned && f->sched_cached && f->sched_xlen == c.x_len && f->sched_acc0 == f->phiAcc && f->sched_deficit0 == f->inputDeficit;
+    static const int64_t piece = [] { const char *v = std::getenv("MRHIP_SCHED_PIECE"); return v && *v ? std::atoll(v) : 262144LL; }();
+    ArbState st;
+    const bool device_sched = c.dev_planned || (!cached && sched_wants_device(f, est));
+    int rc;
+    if (device_sched)
+        rc = arb_call_device_sched(r, est, out, st);
+    else if (!cached && est > 2 * piece && c.y && c.y_capacity >= est && (f->nch == 1 || c.y_stride >= est) && est < 0x7fffffffLL)
+        rc = arb_call_host_pieces(r, est, piece, out, st);
+    else
+        rc = arb_call_host_serial(r, out, st);
+    if (rc) return rc;
+    // commit the post-call state (Filters.jl:731-735)
+    if (!c.dev_planned) {
+        if (!device_sched && f->per_valid) {
+            // the host's loop evaluated this call (a short one): a cycle found earlier moves on by its outputs -- left where it
+            // was, the next ASYNCHRONOUS call would plan from a stale cycle position and be refused by its plan kernel
+            // (tests/stress_random.py --async-mix, seed 111: rate 2.5, N𝜙 = 10)
+            if (f->per_acc[static_cast<size_t>(f->per_pos)] == f->phiAcc) f->per_pos = (f->per_pos + out.n_out) % f->per_Q;
+            else f->per_valid = false;
+        }
+        arb_state_commit(f, st);
+    }
+    f->sched_cached = false;
+    return MRHIP_OK;
+}
+
+// The end of every call: the device record follows in stream order; shiftin! unless a filter kernel did it; the history slot moves on.
+static int finish_call(mrhip_filter *f, const CallArgs &c, const CallOut &out)
+{
+    const bool arb = f->kind == MRHIP_FIR_ARBITRARY || f->kind == MRHIP_FIR_FARROW;
+    const bool capturing = c.capturing;
+    const int hist_next = c.hist_next;
+    const TypeKey &tk = c.tk;
+    hipStream_t stream = c.stream;
+    // the device record follows every call in stream order: a call whose kernels did not file its end state pushes it
+    // (FIRStandard / FIRInterpolator have no state to carry, but the record's count and call counter -- what mrhip_sync_state returns --
+    //  follow every call of every kind)
+    if (!out.rec_current)
+    {
+        // (every write of a FIRArbitrary / FIRFarrow record in program order: on the schedule stream, behind whatever the caller's stream wrote
+        //  last -- or, when this call's schedule ran on the caller's stream, there, with the schedule stream's next user behind it)
+        const bool on_sched = arb && f->s_sched && !capturing && !out.sched_inline;
+        if (on_sched) { if (int rc = sched_stream_behind_chain(f)) return rc; f->sched_dirty = true; }
+        if (int rc = rec_push(f, on_sched ? f->s_sched : stream, -1, std::max<int64_t>(out.n_out, 0))) return rc;
+        if (on_sched) f->async_pending = true;       // (nobody waits for that push: a capture must not start before it has run)
+        if (out.sched_inline) {
+            f->chain_stream = stream;
+            f->chain_pending = true;
+            f->async_pending = true;
+        }
+    }
+
+    // history <- last H samples of [history ; x]   (shiftin!, support.jl:61-80), ping-pong buffers
+    if (f->H > 0 && !out.did_shiftin) {
+        HistArgs ha{};
+        ha.x = c.x; ha.hist_old = f->d_hist[f->hist_cur]; ha.hist_new = f->d_hist[hist_next];
+        ha.x_stride = c.x_stride; ha.x_len = c.x_len; ha.H = static_cast<int>(f->H); ha.nch = static_cast<int>(f->nch);
+        ha.dyn = c.x_from ? f->last_call_rec : nullptr;        // (a chained call: the length its plan / FINISH kernel took from the previous stage)
+        MRHIP_CHECK_HIP(launch_shiftin(tk, ha, stream));
+    }
+    if (f->H > 0) {
+        if (capturing && out.hist_in_place) {
+            // (the filter kernel wrote the slot the replay reads)
+        } else if (capturing) {
+            // a replay reads the slot baked into the node: bring the new history back into it instead of moving on
+            MRHIP_CHECK_HIP(hipMemcpyAsync(f->d_hist[f->hist_cur], f->d_hist[hist_next],
+                                           static_cast<size_t>(f->nch) * f->H * x_elt(f), hipMemcpyDeviceToDevice, stream));
+        } else {
+            f->hist_cur = hist_next;
+        }
+    }
+    if (capturing) f->captured = true;
+    if (c.n_written) *c.n_written = out.n_out;
+    return MRHIP_OK;
+}
+
 // One launch-sized piece of a filt! call.  `continuation`: the piece continues a call whose earlier samples were already
 // filtered (mrhip_filt_device splits calls longer than a launch can index; mrhip_filt_host cuts a call into staging
 // pieces): the Vector seam's start-from-zero (support.jl:46) then applies to none of its outputs -- in the ONE reference
@@ -1115,8 +1619,6 @@ static int filt_device_one(mrhip_filter *f, const void *x, int64_t x_len, int64_
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     DeviceGuard guard(f->device);
     if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
-    const TypeKey tk = type_key(f);
-    const bool fused = f->numerics == MRHIP_NUMERICS_FUSED;
     const bool arb = f->kind == MRHIP_FIR_ARBITRARY || f->kind == MRHIP_FIR_FARROW;
 
     // Stream capture (HIP graphs).  A captured call is replayed with the arguments baked in at capture time while the
@@ -1150,399 +1652,12 @@ static int filt_device_one(mrhip_filter *f, const void *x, int64_t x_len, int64_
         if (f->nch > 1 && y_stride < bound) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output bound");
     }
 
-    int64_t n_out = 0;
-    bool did_shiftin = false;
-    bool sched_inline = false;         // FIRArbitrary / FIRFarrow: this call's schedule ran on the caller's stream although the filter has a schedule stream
-    bool hist_in_place = false;        // ... by a filter kernel inside a capture, straight into the slot the replay reads (ShiftFold)
-    bool rec_current = false;          // the device record has (or will have, in stream order) this call's end state
-    const int hist_next = hist_other(f);
-    if (arb) {
-        // one range [k0, k0+cnt) of this call's outputs: schedule entries are already in the device buffers
-        const size_t yelt = dtype_scalar_size(f->ty) * static_cast<size_t>(f->nc);
-        // (d_n, d_acc: the device schedule; n_host: its host copy, or NULL with `spans` = the largest input span of
-        //  the aligned tiles of 64 ... 1024 outputs when the schedule is evaluated on the device; dyn: the count comes
-        //  from the call record, cnt is its upper bound)
-        const void *sched_dn = nullptr, *sched_dacc = nullptr;      // set by the branch that filled them, before its launch_range
-        const int *sched_spans = nullptr;
-        // (a small call -- at most MRHIP_ARB_SMALL_MAX (150 000) outputs x channels -- runs faster on the universal kernel, one lane per output and
-        //  nothing to set up: 1 ch x 1e5 samples 6.7 against 8.6 us, the crossover at 1 ch x 3e5 / 2 ch x 1.5e5; profiles/r05/experiments.md O)
-        auto small_call = [&](int64_t n_out) { return n_out * f->nch <= static_cast<int64_t>(MRHIP_ENV_INT("MRHIP_ARB_SMALL_MAX", 150000)); };
-        // the FIRArbitrary dispatch below tries arb_lane_kernel on a call of n_out outputs (if the kernel takes its shape: arb_lane_eligible)
-        auto lane_ok = [&](int64_t n_out) { return !f->force_generic && !small_call(n_out) && MRHIP_ENV_INT("MRHIP_PIPE_DYNAMIC", 1) != 0; };
-        // whole_call: the range is the call (not a piece of a long one): the kernels that can (arb_pipe_kernel, farrow_wave_kernel) then write the
-        // next call's history themselves (ShiftFold) -- inside a capture straight into the slot the replay reads, which takes x_len >= H
-        auto launch_range = [&](int64_t k0, int64_t cnt, const int32_t *n_host, const DevCall *dyn, bool whole_call = false) -> int {
-            if (!sched_dn || !sched_dacc) return fail(MRHIP_ERR_HIP, "no phase schedule on the device (internal)");
-            ShiftFold sf{};
-            const bool in_place = capturing;
-            if (whole_call && f->H > 0 && !x_from && (!in_place || x_len >= f->H) && MRHIP_ENV_INT("MRHIP_FOLD_SHIFTIN", 1) != 0) {
-                sf.hist_new = f->d_hist[in_place ? f->hist_cur : hist_next];
-                sf.done = in_place ? f->d_counters + 128 : nullptr;
-            }
-            void *yk = static_cast<unsigned char *>(y) + static_cast<size_t>(k0) * yelt;
-            if (f->kind == MRHIP_FIR_FARROW) {
-                FarrowArgs fa{};
-                fa.x = x; fa.y = yk; fa.hist = f->d_hist[f->hist_cur]; fa.pnfb = f->d_pnfb;
-                fa.n_idx = static_cast<const int *>(sched_dn) + k0; fa.acc = static_cast<const double *>(sched_dacc) + k0;
-                fa.x_stride = x_stride; fa.y_stride = y_stride; fa.x_len = x_len; fa.n_out = cnt;
-                fa.T = static_cast<int>(f->T); fa.H = static_cast<int>(f->H); fa.polyorder = static_cast<int>(f->polyorder);
-                fa.tap_f32 = f->th == MRHIP_F32; fa.nch = static_cast<int>(f->nch);
-                fa.seam_below = continuation ? 0 : static_cast<int>(f->T);
-                fa.dyn = dyn;
-                if (int rc = timing_mark(f, stream)) return rc;
-                ArbTileArgs fta;
-                size_t flds = 0;
-                if (!f->force_generic && f->d_pnfb_t && plan_farrow_wave(fa)) {
-                    FarrowArgs fw = fa;
-                    fw.pnfb = f->d_pnfb_t;                              // degree-major, padded: [polyorder+1][32]
-                    fw.fold = sf;
-                    if (sf.hist_new) { did_shiftin = true; hist_in_place = in_place; }
-                    MRHIP_CHECK_HIP(launch_farrow_wave(tk, fused, fw, stream, &f->last_kernel, f->num_cus));
-                }
-                else if (!f->force_generic && plan_farrow_tiled(tk, fa, n_host, sched_spans, f->num_cus, &fta, &flds)) {
-                    fta.counters = MRHIP_ENV_INT("MRHIP_PIPE_DYNAMIC", 1) != 0 ? f->d_counters : nullptr;   // (as for FIRArbitrary below)
-                    if (sf.hist_new) { fa.fold = sf; did_shiftin = true; hist_in_place = in_place; }
-                    MRHIP_CHECK_HIP(launch_farrow_tiled(tk, fused, fa, fta, flds, stream, &f->last_kernel, f->num_cus));
-                }
-                else
-                    MRHIP_CHECK_HIP(launch_farrow(tk, fused, fa, stream, &f->last_kernel));
-                return timing_mark(f, stream);
-            }
-            ArbArgs a{};
-            a.x = x; a.y = yk; a.hist = f->d_hist[f->hist_cur]; a.taps = f->d_taps; a.dtaps = f->d_dtaps;
-            a.n_idx = static_cast<const int *>(sched_dn) + k0; a.acc = static_cast<const double *>(sched_dacc) + k0;
-            a.x_stride = x_stride; a.y_stride = y_stride; a.x_len = x_len; a.n_out = cnt;
-            a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H); a.Nphi = static_cast<int>(f->Nphi);
-            a.nch = static_cast<int>(f->nch);
-            a.dyn = dyn;
-            if (int rc = timing_mark(f, stream)) return rc;
-            ArbTileArgs ta;
-            size_t lds = 0;
-            ArbLaneArgs la;
-            if (lane_ok(cnt) && plan_arb_lane(tk, a, f->rate, &la, &lds)) {
-                // (64 channels or more, Float64, a rate >= 1: a lane per channel, the taps in scalar registers -- kernels_arb_lane.hip)
-                la.counters = f->d_counters;
-                if (sf.hist_new) { a.fold = sf; did_shiftin = true; hist_in_place = in_place; }
-                MRHIP_CHECK_HIP(launch_arb_lane(fused, a, la, lds, stream, &f->last_kernel, f->num_cus));
-            }
-            else if (!f->force_generic && !small_call(cnt) && plan_arb_tiled(tk, a, n_host, sched_spans, f->num_cus, &ta, &lds)) {
-                // the pipe kernel's tiles are handed out from a counter of the filter (its launches are stream-ordered: one at a
-                // time); MRHIP_PIPE_DYNAMIC=0: every workgroup takes every gridDim-th tile
-                ta.counters = MRHIP_ENV_INT("MRHIP_PIPE_DYNAMIC", 1) != 0 ? f->d_counters : nullptr;
-                if (sf.hist_new) { a.fold = sf; did_shiftin = true; hist_in_place = in_place; }
-                MRHIP_CHECK_HIP(launch_arb_tiled(tk, fused, a, ta, lds, stream, &f->last_kernel, f->num_cus));
-            }
-            else {
-                if (sf.hist_new) { a.fold = sf; did_shiftin = true; hist_in_place = in_place; }
-                MRHIP_CHECK_HIP(launch_arb_generic(tk, fused, a, stream, &f->last_kernel));
-            }
-            return timing_mark(f, stream);
-        };
-        ArbState st;
-        bool host_loop = false;            // this call's schedule came from the host's serial loop (not from sched_enqueue)
-        // Upper bound of the output count (the reference's outputlength estimate, Filters.jl:375-381, + 2 for the
-        // rounding of its Float64 recurrence); without the host's copy of the state: for inputDeficit = 1.
-        const int64_t est = dev_planned ? bound
-            : (x_len >= f->inputDeficit ? static_cast<int64_t>(std::ceil(static_cast<double>(x_len - f->inputDeficit + 1) * f->rate)) + 2 : 0);
-        const bool cached = !dev_planned && f->sched_cached && f->sched_xlen == x_len && f->sched_acc0 == f->phiAcc && f->sched_deficit0 == f->inputDeficit;
-        static const int64_t piece = [] { const char *v = std::getenv("MRHIP_SCHED_PIECE"); return v && *v ? std::atoll(v) : 262144LL; }();
-        if (dev_planned || (!cached && sched_wants_device(f, est))) {
-            // The schedule is evaluated on the device (arb_schedule.hip), in front of ONE filter launch that takes the
-            // output count from the call record: nothing waits in the middle of the call.  A caller that wants the count
-            // (the reference's filt! returns it) collects it from the pinned mirror once the schedule's last kernel has
-            // run -- by then the filter kernel is already queued behind it.
-            if (est >= 0x7fffffffLL) return fail(MRHIP_ERR_INVALID_ARG, "call too long for one launch (internal)");
-            int spans[kSchedSpanSizes];
-            span_bounds(f->rate, spans);
-            // The schedule runs on the filter's schedule stream, BESIDE the filter kernel of the call before (its inputs are
-            // the record, which moved on with that call's FINISH kernel, and nothing else); schedule buffers and call records
-            // alternate, events order writer and reader of each (mrhip_filter.h: s_sched).  Inside a capture: one stream.
-            // (a chained call's schedule reads the previous stage's call record, which is written on the caller's stream: it runs there)
-            // (a call of one small piece -- at most MRHIP_SCHED_INLINE_MAX outputs, default 65 536 -- is launch-bound: its three kernels go down ONE
-            //  queue without the three event operations the second stream costs the host; profiles/r05/experiments.md O)
-            // (calls arb_lane_kernel will serve: that kernel's persistent workgroups hold every vector register of the chip -- the next call's schedule
-            //  cannot run BESIDE it: its tables / chain workgroups either wait for the kernel's end anyway or, when the race at the start lets
-            //  them in, both run much longer -- config 4 on a continuing stream read 3.9 or 4.5-5.1 ms per call.  Behind it, on the caller's
-            //  stream: 3.93 + 0.2 ms, every call.  profiles/r06/experiments.md I; MRHIP_SCHED_BESIDE_LANE=1: as before)
-            //  (the call launches est outputs: launch_range below)
-            const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && lane_ok(est) &&
-                                    arb_lane_eligible(tk, static_cast<int>(f->T), static_cast<int>(f->H), f->nch, f->rate, x_len, x_stride, y_stride) &&
-                                    MRHIP_ENV_INT("MRHIP_SCHED_BESIDE_LANE", 0) == 0;
-            const bool inline_sched = est <= MRHIP_ENV_INT("MRHIP_SCHED_INLINE_MAX", 65536) || lane_shape;
-            hipStream_t ss = capturing || !f->s_sched || x_from || inline_sched ? stream : f->s_sched;
-            // a chained call's schedule ran on the CALLER's stream (it reads the previous stage's call record there) and wrote the record,
-            // the piece states and the path tables: a schedule on the filter's own schedule stream must come behind it
-            if (ss == f->s_sched && f->chain_pending)
-                if (int rc = chain_event_now(f)) return rc;
-            if (ss == f->s_sched) f->sched_dirty = true;
-            else if (!capturing && f->s_sched && f->sched_dirty) {        // (mrhip_filter.h: sched_dirty)
-                MRHIP_CHECK_HIP(hipEventRecord(f->ev_sdirty, f->s_sched));
-                MRHIP_CHECK_HIP(hipStreamWaitEvent(stream, f->ev_sdirty, 0));
-                f->sched_dirty = false;
-            }
-            sched_inline = ss == stream && !capturing && f->s_sched != nullptr;
-            SchedOut so{};
-            so.buf = capturing ? 0 : f->flip;
-            if (!capturing) f->flip ^= 1;
-            if (ss != stream && f->ev_filt_valid[so.buf]) MRHIP_CHECK_HIP(hipStreamWaitEvent(ss, f->ev_filt[so.buf], 0));
-            if (int rc = sched_enqueue(f, x_len, est, dev_planned ? y_capacity : INT64_MAX, count_dev, !dev_planned, ss, &so, x_from)) return rc;   // (a call that is waited for checks the count against the room itself)
-            const int b = so.buf;                                         // (a memo hit names the buffer that holds the entries)
-            sched_dn = f->ds_n[b]; sched_dacc = f->ds_acc[b]; sched_spans = spans;
-            auto join = [&]() -> int {                                  // the filter kernel behind its schedule
-                if (ss == stream) return MRHIP_OK;
-                MRHIP_CHECK_HIP(hipEventRecord(f->ev_fin[b], ss));
-                MRHIP_CHECK_HIP(hipStreamWaitEvent(stream, f->ev_fin[b], 0));
-                return MRHIP_OK;
-            };
-            const bool room = y && y_capacity >= est && (f->nch == 1 || y_stride >= est);
-            bool launched = false;
-            if (so.pending && room && est > 0) {
-                if (int rc = join()) return rc;
-                if (int rc = launch_range(0, est, nullptr, f->d_calls[b], true)) return rc;
-                launched = true;
-            }
-            rec_current = so.pending;
-            if (dev_planned) {
-                // nobody collects: the host's copy of the state is stale from here on
-                f->mirror_valid = false;
-                f->last_call_dev_planned = so.pending && launched;        // (a chained call may follow: its input length is this call's count)
-                f->last_call_rec = f->d_calls[b];
-                if (!capturing) f->async_pending = true;
-                if (!capturing && so.pending && !so.periodic && !x_from) {
-                    // The host's LOWER BOUND of the drift baseline (it sizes the next calls' pieces: at most 16 x the baseline) moves on
-                    // by the fewest outputs this call can have -- xIdx starts at most 1/rate + 1 in and advances at most 1/rate + 1 a
-                    // step -- so that a stream of asynchronous calls is not cut into pieces of 4096 forever; mrhip_sync_state brings
-                    // the exact value.
-                    const double lb = std::floor((static_cast<double>(x_len) - 1.0 / f->rate - 3.0) * f->rate) - 2.0;
-                    if (lb > 0.0) f->sched_ksteps += lb;
-                }
-                n_out = -1;
-                st = ArbState{f->phiAcc, f->phiIdx, f->alpha, f->xIdx, f->inputDeficit};
-            } else {
-                f->last_call_dev_planned = false;
-                for (;;) {
-                    bool relaunch = false;
-                    if (int rc = sched_collect(f, x_len, est, INT64_MAX, count_dev, ss, &so, &relaunch)) return rc;
-                    if (!relaunch) break;
-                    rec_current = so.pending;
-                    if (so.pending && room) {
-                        if (int rc = join()) return rc;
-                        if (int rc = launch_range(0, est, nullptr, f->d_calls[b], true)) return rc;
-                    } else launched = false;
-                }
-                n_out = so.count;
-                st = so.end;
-                // (rec_current: the FINISH kernel wrote the record; a call the host evaluated itself pushes it below)
-                if (n_out > y_capacity) {
-                    if (rec_current) {      // the record moved on with the schedule: take the stream back to the call's start
-                        f->sched_cached = false;
-                        (void)rec_push(f, ss);
-                    }
-                    return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small");
-                }
-                if (n_out > 0 && !launched) {
-                    if (!y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
-                    if (f->nch > 1 && y_stride < n_out) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output count");
-                    if (int rc = join()) return rc;
-                    if (int rc = launch_range(0, n_out, nullptr, nullptr, true)) return rc;
-                }
-                f->sched_drift = so.drift; f->sched_ksteps = so.ksteps;
-                if (so.periodic || f->per_valid) f->per_pos = so.per_pos_end;
-                // this call becomes the memo entry of buffer b (arb_schedule.hip): its entries stay there until b is rewritten
-                if (!so.memo_hit) {
-                    f->memo_valid = true; f->memo_buf = b;
-                    f->memo_acc0 = so.memo_acc0; f->memo_d0 = so.memo_d0; f->memo_xlen = x_len;
-                    f->memo_count = n_out; f->memo_end = st; f->memo_drift = so.drift; f->memo_ksteps = so.ksteps;
-                    f->memo_per_pos_end = so.per_pos_end;
-                }
-            }
-            if (ss != stream) {                                          // buffer b's next writer waits for this reader
-                MRHIP_CHECK_HIP(hipEventRecord(f->ev_filt[b], stream));
-                f->ev_filt_valid[b] = true;
-            } else if (!capturing && f->s_sched) {                       // (see chain_pending above; also orders buffer b's next writer)
-                f->chain_stream = stream;
-                f->chain_pending = true;
-            }
-        } else if (!cached && est > 2 * piece && y && y_capacity >= est && (f->nch == 1 || y_stride >= est) && est < 0x7fffffffLL) {
-            host_loop = true;
-            if (f->sched_in_flight) { MRHIP_CHECK_HIP(hipEventSynchronize(f->sched_copied)); f->sched_in_flight = false; }
-            if (int rc = ensure_sched_capacity(f, static_cast<size_t>(est))) return rc;
-            sched_dn = f->d_sched_n; sched_dacc = f->d_sched_acc;      // (the buffers may just have been (re)allocated)
-            st = ArbState{f->phiAcc, f->phiIdx, f->alpha, f->inputDeficit, f->inputDeficit};   // xIdx starts at inputDeficit (:715)
-            bool done = false;
-            int64_t k0 = 0;
-            static const bool prof = [] { const char *v = std::getenv("MRHIP_DEBUG"); return v && v[0] == '2'; }();
-            double t_rec = 0, t_copy = 0, t_launch = 0;
-            auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-            // an error in the middle of the pipeline: uploads from the pinned staging may still be in flight, so mark
-            // them (the next call waits before it reuses the staging) and report how far the launches got; the
-            // filter state is not advanced
-            auto bail = [&](int rc) -> int {
-                if (hipEventRecord(f->sched_copied, stream) == hipSuccess) f->sched_in_flight = true;
-                else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
-                if (n_written) *n_written = k0;
-                return rc;
-            };
-            while (!done) {
-                int32_t *pn = static_cast<int32_t *>(f->pin_n) + k0;
-                double *pa = static_cast<double *>(f->pin_acc) + k0;
-                const int64_t room = std::min<int64_t>(piece, est - k0);
-                if (room <= 0) return bail(fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small"));   // cannot happen: est is an upper bound
-                const double t0 = prof ? now() : 0;
-                const int64_t cnt = run_arbitrary_schedule_piece(st, f->delta, f->Nphi, x_len, pn, pa, room, &done, f->mod_form);
-                const double t1 = prof ? now() : 0;
-                if (cnt > 0) {
-                    if (hipMemcpyAsync(static_cast<int32_t *>(f->d_sched_n) + k0, pn, static_cast<size_t>(cnt) * sizeof(int32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
-                        hipMemcpyAsync(static_cast<double *>(f->d_sched_acc) + k0, pa, static_cast<size_t>(cnt) * sizeof(double), hipMemcpyHostToDevice, stream) != hipSuccess)
-                        return bail(fail(MRHIP_ERR_HIP, "uploading the phase schedule failed"));
-                    const double t2 = prof ? now() : 0;
-                    if (int rc = launch_range(k0, cnt, pn, nullptr)) return bail(rc);
-                    if (prof) { t_rec += t1 - t0; t_copy += t2 - t1; t_launch += now() - t2; }
-                    k0 += cnt;
-                }
-            }
-            if (prof) std::fprintf(stderr, "[mrhip] arbitrary schedule: recurrence %.2f ms, memcpy enqueue %.2f ms, plan+launch %.2f ms (%lld outputs)\n",
-                                   t_rec * 1e3, t_copy * 1e3, t_launch * 1e3, static_cast<long long>(k0));
-            MRHIP_CHECK_HIP(hipEventRecord(f->sched_copied, stream));
-            f->sched_in_flight = true;
-            n_out = k0;
-        } else {
-        host_loop = true;
-        n_out = arb_schedule(f, x_len, &st);   // update(::FIRFarrow), Filters.jl:780-788, is the same recurrence
-        if (f->sched_in_flight) { MRHIP_CHECK_HIP(hipEventSynchronize(f->sched_copied)); f->sched_in_flight = false; }
-        if (n_out > y_capacity) return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small");
-        if (n_out > 0) {
-            if (!y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
-            if (f->nch > 1 && y_stride < n_out) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output count");
-            if (int rc = ensure_sched_capacity(f, static_cast<size_t>(n_out))) return rc;
-            sched_dn = f->d_sched_n; sched_dacc = f->d_sched_acc;
-            std::memcpy(f->pin_n, f->sched_n.data(), static_cast<size_t>(n_out) * sizeof(int32_t));
-            std::memcpy(f->pin_acc, f->sched_acc.data(), static_cast<size_t>(n_out) * sizeof(double));
-            MRHIP_CHECK_HIP(hipMemcpyAsync(f->d_sched_n, f->pin_n, static_cast<size_t>(n_out) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-            MRHIP_CHECK_HIP(hipMemcpyAsync(f->d_sched_acc, f->pin_acc, static_cast<size_t>(n_out) * sizeof(double), hipMemcpyHostToDevice, stream));
-            MRHIP_CHECK_HIP(hipEventRecord(f->sched_copied, stream));
-            f->sched_in_flight = true;
-            if (int rc = launch_range(0, n_out, f->sched_n.data(), nullptr, true)) return rc;
-        }
-        }
-        // commit the post-call state (Filters.jl:731-735)
-        if (!dev_planned) {
-            if (host_loop && f->per_valid) {
-                // the host's loop evaluated this call (a short one): a cycle found earlier moves on by its outputs -- left where it
-                // was, the next ASYNCHRONOUS call would plan from a stale cycle position and be refused by its plan kernel
-                // (tests/stress_random.py --async-mix, seed 111: rate 2.5, N𝜙 = 10)
-                if (f->per_acc[static_cast<size_t>(f->per_pos)] == f->phiAcc) f->per_pos = (f->per_pos + n_out) % f->per_Q;
-                else f->per_valid = false;
-            }
-            f->phiAcc = st.acc; f->phiIdx = st.phiIdx; f->alpha = st.alpha; f->xIdx = st.xIdx;
-            f->inputDeficit = st.inputDeficit;
-        }
-        f->sched_cached = false;
-    } else if (dev_planned) {
-        PolyArgs a{};
-        a.x = x; a.y = y; a.hist = f->d_hist[f->hist_cur]; a.hist_new = f->d_hist[hist_next]; a.taps = f->d_taps;
-        a.x_stride = x_stride; a.y_stride = y_stride; a.x_len = x_len;
-        a.n_out = std::max<int64_t>(bound, 1);                          // upper bounds: the plan kernel leaves the call's own values in the call record
-        a.u0 = 0; a.d0 = 1;
-        a.zero_start_below = continuation ? 0
-                           : f->kind == MRHIP_FIR_STANDARD ? f->hLen + 1
-                           : f->kind == MRHIP_FIR_DECIMATOR ? f->hLen : 0;
-        a.L = static_cast<int>(f->L); a.M = static_cast<int>(f->M);
-        a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H);
-        a.nch = static_cast<int>(f->nch);
-        a.rec = f->d_rec; a.dyn = f->d_call;
-        if (int rc = timing_mark(f, stream)) return rc;
-        {
-            const hipError_t e = launch_poly_dyn(f, tk, fused, a, x_len, y_capacity, count_dev, stream, &f->last_kernel, &did_shiftin, x_from);
-            if (e == hipErrorNotSupported && x_from)
-                return fail(MRHIP_ERR_UNSUPPORTED, "a chained call (input length = the previous stage's count, on the device) needs a filter the pair kernels serve (rational_opair_kernel / fir_stream_kernel)");
-            MRHIP_CHECK_HIP(e);
-        }
-        if (int rc = timing_mark(f, stream)) return rc;
-        rec_current = true;
-        if (x_from) {
-            n_out = -1;                 // (the host never learns a chained call's length: its view of the state is re-read from the device)
-        } else if (f->mirror_valid || capturing) {
-            // the shadow of ONE execution: exact while the host knew the state when the capture (or the run of
-            // asynchronous calls) began; re-read from the device before it is next used either way
-            const CallPlan p = plan_rational(f->kind, f->L, f->M, f->phiIdx, f->inputDeficit, x_len);
-            n_out = p.n_out;
-            f->phiIdx = p.phi_end;
-            f->inputDeficit = p.d_end;
-        } else {
-            n_out = -1;
-        }
-        f->mirror_valid = false;
-        f->last_call_dev_planned = true;
-        f->last_call_rec = f->d_call;
-        if (!capturing) f->async_pending = true;
-    } else {
-        f->last_call_dev_planned = false;
-        const CallPlan p = plan_rational(f->kind, f->L, f->M, f->phiIdx, f->inputDeficit, x_len);
-        n_out = p.n_out;
-        // reference: error() before any work, Filters.jl:460 (Standard), :503 (Interpolator), :550 (Rational)
-        if (n_out > y_capacity) return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small");
-        if (n_out > 0) {
-            if (!y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
-            if (f->nch > 1 && y_stride < n_out) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output count");
-            PolyArgs a{};
-            a.x = x; a.y = y; a.hist = f->d_hist[f->hist_cur]; a.hist_new = f->d_hist[hist_next]; a.taps = f->d_taps;
-            a.x_stride = x_stride; a.y_stride = y_stride; a.x_len = x_len; a.n_out = n_out;
-            a.u0 = p.phi0 - 1; a.d0 = p.d0;
-            a.zero_start_below = continuation ? 0
-                               : f->kind == MRHIP_FIR_STANDARD ? f->hLen + 1
-                               : f->kind == MRHIP_FIR_DECIMATOR ? f->hLen : 0;
-            a.L = static_cast<int>(f->L); a.M = static_cast<int>(f->M);
-            a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H);
-            a.nch = static_cast<int>(f->nch);
-            a.rec = f->d_rec; a.dyn = nullptr; a.phi_end = p.phi_end; a.d_end = p.d_end;
-            if (int rc = timing_mark(f, stream)) return rc;
-            MRHIP_CHECK_HIP(launch_poly(f, tk, fused, a, stream, &f->last_kernel, &did_shiftin, f->d_counters, &rec_current));
-            if (int rc = timing_mark(f, stream)) return rc;
-        }
-        f->phiIdx = p.phi_end;
-        f->inputDeficit = p.d_end;
-    }
-    // the device record follows every call in stream order: a call whose kernels did not file its end state pushes it
-    // (FIRStandard / FIRInterpolator have no state to carry, but the record's count and call counter -- what mrhip_sync_state returns --
-    //  follow every call of every kind)
-    if (!rec_current)
-    {
-        // (every write of a FIRArbitrary / FIRFarrow record in program order: on the schedule stream, behind whatever the caller's stream wrote
-        //  last -- or, when this call's schedule ran on the caller's stream, there, with the schedule stream's next user behind it)
-        const bool on_sched = arb && f->s_sched && !capturing && !sched_inline;
-        if (on_sched) { if (int rc = sched_stream_behind_chain(f)) return rc; f->sched_dirty = true; }
-        if (int rc = rec_push(f, on_sched ? f->s_sched : stream, -1, std::max<int64_t>(n_out, 0))) return rc;
-        if (on_sched) f->async_pending = true;       // (nobody waits for that push: a capture must not start before it has run)
-        if (sched_inline) {
-            f->chain_stream = stream;
-            f->chain_pending = true;
-            f->async_pending = true;
-        }
-    }
-
-    // history <- last H samples of [history ; x]   (shiftin!, support.jl:61-80), ping-pong buffers
-    if (f->H > 0 && !did_shiftin) {
-        HistArgs ha{};
-        ha.x = x; ha.hist_old = f->d_hist[f->hist_cur]; ha.hist_new = f->d_hist[hist_next];
-        ha.x_stride = x_stride; ha.x_len = x_len; ha.H = static_cast<int>(f->H); ha.nch = static_cast<int>(f->nch);
-        ha.dyn = x_from ? f->last_call_rec : nullptr;          // (a chained call: the length its plan / FINISH kernel took from the previous stage)
-        MRHIP_CHECK_HIP(launch_shiftin(tk, ha, stream));
-    }
-    if (f->H > 0) {
-        if (capturing && hist_in_place) {
-            // (the filter kernel wrote the slot the replay reads)
-        } else if (capturing) {
-            // a replay reads the slot baked into the node: bring the new history back into it instead of moving on
-            MRHIP_CHECK_HIP(hipMemcpyAsync(f->d_hist[f->hist_cur], f->d_hist[hist_next],
-                                           static_cast<size_t>(f->nch) * f->H * x_elt(f), hipMemcpyDeviceToDevice, stream));
-        } else {
-            f->hist_cur = hist_next;
-        }
-    }
-    if (capturing) f->captured = true;
-    if (n_written) *n_written = n_out;
-    return MRHIP_OK;
+    const CallArgs c{x, x_len, x_stride, y, y_capacity, y_stride, n_written, stream, continuation, capturing, dev_planned,
+                     count_dev, x_from, type_key(f), f->numerics == MRHIP_NUMERICS_FUSED, bound, hist_other(f)};
+    CallOut out;
+    const int rc = arb ? arb_call(f, c, out) : dev_planned ? poly_call_device(f, c, out) : poly_call_host(f, c, out);
+    if (rc) return rc;
+    return finish_call(f, c, out);
 }
 
 // filt!(buffer, self, x) on device memory.  The reference takes a Vector of any length (Int64 indices); a launch indexes
@@ -1563,7 +1678,7 @@ static int filt_device_any(mrhip_filter *f, const void *x, int64_t x_len, int64_
     if (env_max <= 0 && (f->kind == MRHIP_FIR_INTERPOLATOR || f->kind == MRHIP_FIR_RATIONAL) && f->L > f->M)
         step = std::max<int64_t>(static_cast<int64_t>((static_cast<__int128>(step) * f->M) / f->L), 1);
     if (f->kind == MRHIP_FIR_INTERPOLATOR && env_max > 0) step = std::max<int64_t>(step / f->L, 1);
-    if (arb && env_max <= 0) step = std::max<int64_t>(4096, std::min<int64_t>(step, static_cast<int64_t>(static_cast<double>(1LL << 24) / f->rate)));
+    if (arb && env_max <= 0) step = std::min(step, arb_launch_step(f));
     if (x_len <= step) return filt_device_one(f, x, x_len, x_stride, y, y_capacity, y_stride, n_written, stream, false, async, count_dev);
     if (x_len < 0 || y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "negative length");
     if (!x) return fail(MRHIP_ERR_INVALID_ARG, "x is NULL");
@@ -1674,12 +1789,9 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
         nch_total += f->nch;
     }
     if (n_out_max < 1) return single_calls();                        // (short inputs only: history shifts, no kernel worth sharing)
-    PolyArgs a{};
-    a.x = x[0]; a.y = y[0]; a.hist = f0->d_hist[f0->hist_cur]; a.hist_new = f0->d_hist[hist_other(f0)]; a.taps = f0->d_taps;
-    a.x_stride = x_len_max; a.y_stride = n_out_max; a.x_len = x_len_max; a.n_out = n_out_max;
+    PolyArgs a = poly_call_args(f0, x[0], y[0], x_len_max, n_out_max, x_len_max, false);   // support.jl:46 (per call: every stream's call starts here)
+    a.n_out = n_out_max;
     a.u0 = 0; a.d0 = 1;
-    a.zero_start_below = f0->kind == MRHIP_FIR_STANDARD ? f0->hLen + 1 : f0->kind == MRHIP_FIR_DECIMATOR ? f0->hLen : 0;   // support.jl:46 (per call: every stream's call starts here)
-    a.L = static_cast<int>(f0->L); a.M = static_cast<int>(f0->M); a.T = static_cast<int>(f0->T); a.H = static_cast<int>(f0->H);
     a.nch = static_cast<int>(std::min<int64_t>(nch_total, 0x7fffffff));
     PairArgs pa;
     dim3 block;
@@ -1703,7 +1815,7 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
         m.u0 = p.phi0 - 1; m.d0 = p.d0; m.phi_end = p.phi_end; m.d_end = p.d_end;
         m.steps_per_channel = static_cast<unsigned>(spc);
         m.total_steps = static_cast<unsigned>(spc * f->nch);
-        m.spc_magic = spc <= 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+        m.spc_magic = step_magic(spc);
         m.nch = static_cast<int>(f->nch);
         m.P_blk = 0; m.q0 = 0;
         steps_max = std::max(steps_max, m.total_steps);

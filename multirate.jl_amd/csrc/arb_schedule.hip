@@ -581,4 +581,20 @@ int sched_collect(mrhip_filter *f, int64_t x_len, int64_t est, int64_t y_capacit
     return MRHIP_OK;
 }
 
+void sched_commit(mrhip_filter *f, const SchedOut &so)
+{
+    f->sched_drift = so.drift; f->sched_ksteps = so.ksteps;
+    if (so.periodic || f->per_valid) f->per_pos = so.per_pos_end;
+}
+
+// the call becomes the memo entry of buffer so.buf: its entries stay there until that buffer is rewritten
+void sched_memo_commit(mrhip_filter *f, const SchedOut &so, int64_t x_len)
+{
+    if (so.memo_hit) return;
+    f->memo_valid = true; f->memo_buf = so.buf;
+    f->memo_acc0 = so.memo_acc0; f->memo_d0 = so.memo_d0; f->memo_xlen = x_len;
+    f->memo_count = so.count; f->memo_end = so.end; f->memo_drift = so.drift; f->memo_ksteps = so.ksteps;
+    f->memo_per_pos_end = so.per_pos_end;
+}
+
 }  // namespace mrhip

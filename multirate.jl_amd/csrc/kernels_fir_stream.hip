@@ -134,7 +134,7 @@ bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs
     if (spc * a.nch >= (1LL << 31)) return false;
     pa.steps_per_channel = static_cast<unsigned>(spc);
     pa.total_steps = static_cast<unsigned>(spc * a.nch);
-    pa.spc_magic = spc == 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+    pa.spc_magic = step_magic(spc);
     pa.flags_off = static_cast<int>(ns * stage_bytes);
     *lds = ns * stage_bytes + 8 * ns;
 #if MRHIP_STREAM_TAPS_LDS

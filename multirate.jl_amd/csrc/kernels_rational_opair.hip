@@ -175,7 +175,7 @@ bool plan_rational_opair(const TypeKey &tk, bool fused, const PolyArgs &a, int n
     // checked per tile by the loader (checked register path otherwise), so nothing is assumed here
     pa.steps_per_channel = static_cast<unsigned>(spc);
     pa.total_steps = static_cast<unsigned>(spc * a.nch);
-    pa.spc_magic = spc == 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+    pa.spc_magic = step_magic(spc);
     pa.flags_off = static_cast<int>(ns * stage_bytes);
     {   // the tap bank goes through the last stage's LDS when it fits (see the kernel); MRHIP_OPAIR_BANK=0: gather from global
         const long long pt = (a.T + 4) | 1;
@@ -268,7 +268,7 @@ bool plan_rational_opair_blocks(const TypeKey &tk, bool fused, const PolyArgs &a
     pa.total_tiles = pa.tiles_per_channel * a.nch * nblocks;
     pa.steps_per_channel = static_cast<unsigned>(spc);
     pa.total_steps = static_cast<unsigned>(spc * a.nch);
-    pa.spc_magic = spc <= 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+    pa.spc_magic = step_magic(spc);
     pa.flags_off = static_cast<int>(ns * stage_bytes);
     pa.bank_off = -1;                                                       // (a bank of L > 512 columns does not fit a stage: the two columns of a lane come straight from global memory, once per workgroup)
     *out = pa;

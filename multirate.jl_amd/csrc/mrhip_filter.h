@@ -192,6 +192,9 @@ struct SchedOut {
 int sched_enqueue(mrhip_filter *f, int64_t x_len, int64_t est, int64_t y_capacity, long long *count_out, bool host_ok, hipStream_t s, SchedOut *out,
                   const mrhip::DevCall *x_from = nullptr);
 int sched_collect(mrhip_filter *f, int64_t x_len, int64_t est, int64_t y_capacity, long long *count_out, hipStream_t s, SchedOut *io, bool *relaunch);
+// after sched_collect: the drift estimate and the cycle position move on with the call; a filt! call's schedule becomes the memo entry
+void sched_commit(mrhip_filter *f, const SchedOut &so);
+void sched_memo_commit(mrhip_filter *f, const SchedOut &so, int64_t x_len);
 // stream_state.hip: the device record
 int rec_alloc(mrhip_filter *f);
 void rec_free(mrhip_filter *f);

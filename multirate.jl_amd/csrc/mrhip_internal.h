@@ -215,6 +215,11 @@ struct DevCall {                      // what the kernels of ONE device-planned 
     long long k_done;                 // schedule entries valid so far (a call whose schedule is continued after a host redo)
     long long x_len;                  // rational family: the call's input length (a chained call takes it from the previous stage's count)
 };
+// spc_magic of the pair kernels' step walk: floor(2^32 / steps_per_channel), 0xffffffff for one step (step number -> channel by multiply-high)
+__host__ __device__ inline unsigned step_magic(long long spc)
+{
+    return spc <= 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+}
 // Closed form of the rational loop (host_logic.cpp: plan_rational), usable on both sides
 struct CallPlanPOD { long long n_out, phi0, d0, phi_end, d_end; int short_input; };
 __host__ __device__ inline CallPlanPOD plan_rational_pod(int kind, long long L, long long M, long long phiIdx, long long inputDeficit, long long xLen)

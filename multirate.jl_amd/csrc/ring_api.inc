@@ -360,7 +360,7 @@ int mrhip_ring_push(mrhip_ring *r, const void *x, int64_t x_len, int64_t x_strid
     d.steps_per_channel = static_cast<unsigned>(std::max<int64_t>(spc, 1));
     d.total_steps = static_cast<unsigned>(spc * f->nch);
     d.ngrabs = std::max(1u, (d.total_steps + r->pa.steps_per_group - 1u) / r->pa.steps_per_group);
-    d.spc_magic = spc <= 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+    d.spc_magic = step_magic(spc);
     // a chunk of less than MRHIP_RING_FLUSH_MIN_MB (32) of outputs is stored write-through: one L2 write-back per XCD serves every chunk filed
     // so far, but costs the same whatever they hold -- at one channel of 1e6 samples (3.7 MB) more than the write-through stores it saves
     {

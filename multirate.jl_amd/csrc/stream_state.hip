@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64) void poly_plan_kernel(PlanArgs a)
     const long long spc = (c.n_out + a.P - 1) / a.P;
     c.steps_per_channel = static_cast<unsigned>(spc);
     c.total_steps = static_cast<unsigned>(spc * a.nch);
-    c.spc_magic = spc <= 1 ? 0xffffffffu : static_cast<unsigned>((1ULL << 32) / static_cast<unsigned long long>(spc));
+    c.spc_magic = step_magic(spc);
     *a.call = c;
     if (a.kind == MRHIP_FIR_DECIMATOR || a.kind == MRHIP_FIR_RATIONAL) {
         r.phiIdx = a.kind == MRHIP_FIR_DECIMATOR ? r.phiIdx : p.phi_end;
