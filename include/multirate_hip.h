@@ -45,10 +45,11 @@ typedef enum {
     MRHIP_ERR_BUFFER_TOO_SMALL = 2, /* reference: error("buffer is too small"), Filters.jl:460,503,550 */
     MRHIP_ERR_HIP = 3,              /* a HIP runtime call failed; message holds hipGetErrorString */
     MRHIP_ERR_NO_DEVICE = 4,        /* no gfx950 device visible: the engine has no CPU fallback */
-    MRHIP_ERR_UNSUPPORTED = 5       /* e.g. complex taps (the reference tests never use them) */
+    MRHIP_ERR_UNSUPPORTED = 5       /* e.g. complex taps on FIRArbitrary / FIRFarrow, FUSED numerics with complex taps */
 } mrhip_status;
 
-/* element types: Th in {F32,F64}; Tx in {F32,F64,C64,C128}; Tb = promote_type(Th,Tx) */
+/* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational);
+ * Tx in {F32,F64,C64,C128}; Tb = promote_type(Th,Tx) -- complex as soon as either side is */
 typedef enum { MRHIP_F32 = 0, MRHIP_F64 = 1, MRHIP_C64 = 2, MRHIP_C128 = 3 } mrhip_dtype;
 
 /* kernel kinds == the reference's FIRKernel subtypes, src/Filters.jl:15-117 */
@@ -68,6 +69,18 @@ typedef enum {
  *   FUSED : same order, each step one fused multiply-add.  Faster where the kernel is
  *           VALU-bound; differs from STRICT by <= 1 rounding per tap. */
 typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numerics;
+/* Complex taps (Th in {C64,C128}; the rational family).  The reference is generic over the tap type: the unsafedot
+ * methods (src/support.jl:5-55) only multiply and add, so the contract is the one above with Julia's complex products
+ * written out.  Let R be the promoted real scalar (Float64 if either side is 64-bit, else Float32); every multiply, add
+ * and subtract is rounded separately in R, a narrower operand is widened exactly before use:
+ *   - the window is visited oldest sample first; the first product initialises the accumulator;
+ *   - the start-from-zero seam of support.jl:46 applies as 0 + p on each component;
+ *   - real sample x, tap (hr,hi):        p = (hr*x, hi*x)                          Complex*Real
+ *   - complex sample (xr,xi):            p = (hr*xr - hi*xi, hr*xi + hi*xr)        Complex*Complex, operands in this order
+ *   - acc = acc + p, component-wise.
+ * The output is always complex (C128 if either side is 64-bit, else C64); the history stays in Tx (real for real
+ * samples).  No FUSED form is defined: mrhip_set_numerics(f, FUSED) returns MRHIP_ERR_UNSUPPORTED on such a filter.
+ * mrhip_create_arbitrary / mrhip_create_farrow with complex taps return MRHIP_ERR_UNSUPPORTED. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -102,7 +115,8 @@ int mrhip_device_count(void);
 
 /* ---- host-only helpers (no GPU needed) ------------------------------------------------ */
 /* replaces taps2pfb(h, Nphi), src/Filters.jl:284-298.  `pfb` receives tapsPerPhi*Nphi elements,
- * column-major (column = phase, contiguous); pass pfb = NULL to query.  Returns tapsPerPhi. */
+ * column-major (column = phase, contiguous); pass pfb = NULL to query.  Returns tapsPerPhi.  Any tap_dtype,
+ * complex ones included. */
 int64_t mrhip_taps2pfb(const void *h, int64_t hLen, int tap_dtype, int64_t Nphi, void *pfb);
 /* replaces nextphase(currentphase, ratio), src/Filters.jl:433-439 */
 int64_t mrhip_nextphase(int64_t currentphase, int64_t interpolation, int64_t decimation);
@@ -116,7 +130,7 @@ int64_t mrhip_inputlength_ratio(int64_t outputlength, int64_t interpolation, int
  * coef receives polyorder+1 coefficients, ascending powers (Poly.a).  Returns 0, or MRHIP_ERR_INVALID_ARG when
  * n < polyorder+1.  Float64 throughout (Julia's A \\ y promotes to Float64). */
 int mrhip_polyfit(const double *y, int64_t n, int64_t polyorder, double *coef);
-/* promote_type(Th, Tx) as used by every filt wrapper, e.g. src/Filters.jl:581 */
+/* promote_type(Th, Tx) as used by every filt wrapper, e.g. src/Filters.jl:581 (complex if either argument is) */
 int mrhip_output_dtype(int tap_dtype, int sample_dtype);
 
 /* ---- FIR design, host only (src/FIRDesign.jl) ----------------------------------------------- */
@@ -146,7 +160,8 @@ int64_t mrhip_firdes_kaiser(const double *cutoff, int ncutoff, double transition
 /* replaces FIRFilter(h::Vector, resampleRatio::Rational = 1//1), src/Filters.jl:158-180.
  * num//den is reduced like a Julia Rational; the kernel kind is chosen exactly as :163-175
  * (ratio == 1 -> STANDARD, L == 1 -> DECIMATOR, M == 1 -> INTERPOLATOR, else RATIONAL).
- * `h` is a host pointer to hLen taps of tap_dtype (F32 | F64).  `device` is a HIP ordinal. */
+ * `h` is a host pointer to hLen taps of tap_dtype (F32 | F64 | C64 | C128; complex taps are interleaved (re, im)
+ * pairs and make the output complex: see "Complex taps" above).  `device` is a HIP ordinal. */
 int mrhip_create_rational(const void *h, int64_t hLen, int tap_dtype, int64_t num, int64_t den,
                           int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer = 32), src/Filters.jl:183-189

@@ -84,7 +84,7 @@ bool device_is_gfx950(int dev)
 
 TypeKey type_key(const mrhip_filter *f)
 {
-    return TypeKey{dtype_is_f64(f->tx), f->r_f64, f->nc == 2};
+    return TypeKey{dtype_is_f64(f->tx), f->r_f64, f->nc == 2, dtype_is_complex(f->th)};
 }
 
 size_t r_size(const mrhip_filter *f) { return f->r_f64 ? 8 : 4; }
@@ -92,7 +92,8 @@ size_t x_elt(const mrhip_filter *f) { return dtype_size(f->tx); }
 size_t y_elt(const mrhip_filter *f) { return dtype_size(f->ty); }
 
 // upload taps (tap dtype on the host) as R-typed device array; f32 -> f64 widening is exact and is
-// what Julia's promotion does on every multiply (Real*Real / Real*Complex methods).
+// what Julia's promotion does on every multiply (Real*Real / Real*Complex methods).  Complex taps are
+// interleaved (re, im) pairs: the same array of scalars, widened the same way.
 // The vector sits between two runs of kTapPad zero elements: fir_stream_rt_kernel reads whole blocks of taps around the
 // ends of a window (it discards what the out-of-window ones produce) without a clamp per tap.
 int upload_taps(mrhip_filter *f, const std::vector<unsigned char> &src, void **dptr, void **alloc)
@@ -103,7 +104,7 @@ int upload_taps(mrhip_filter *f, const std::vector<unsigned char> &src, void **d
     MRHIP_CHECK_HIP(hipMalloc(alloc, bytes));
     MRHIP_CHECK_HIP(hipMemset(*alloc, 0, bytes));
     *dptr = static_cast<unsigned char *>(*alloc) + pad;
-    if (f->r_f64 && f->th == MRHIP_F32) {
+    if (f->r_f64 && !dtype_is_f64(f->th)) {
         std::vector<double> w(n);
         const float *s = reinterpret_cast<const float *>(src.data());
         for (size_t i = 0; i < n; ++i) w[i] = static_cast<double>(s[i]);
@@ -199,13 +200,15 @@ int drain_filter(mrhip_filter *f)
     return MRHIP_OK;
 }
 
-int check_create_args(const void *h, int64_t hLen, int th, int tx, int64_t nch, int device, mrhip_filter **out)
+int check_create_args(const void *h, int64_t hLen, int th, int tx, int64_t nch, int device, mrhip_filter **out, bool complex_taps_ok = false)
 {
     if (!out) return fail(MRHIP_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!h || hLen < 1) return fail(MRHIP_ERR_INVALID_ARG, "h must hold at least one tap");
-    if (th != MRHIP_F32 && th != MRHIP_F64)
-        return fail(MRHIP_ERR_UNSUPPORTED, "taps must be Float32 or Float64 (complex taps are not supported)");
+    if (th < MRHIP_F32 || th > MRHIP_C128) return fail(MRHIP_ERR_INVALID_ARG, "bad tap dtype");
+    if (dtype_is_complex(th) && !complex_taps_ok)
+        return fail(MRHIP_ERR_UNSUPPORTED, "complex taps are supported by the rational family only (mrhip_create_rational: FIRStandard, FIRDecimator, "
+                                           "FIRInterpolator, FIRRational); FIRArbitrary and FIRFarrow take Float32 or Float64 taps");
     if (tx < MRHIP_F32 || tx > MRHIP_C128) return fail(MRHIP_ERR_INVALID_ARG, "bad sample dtype");
     if (nch < 1) return fail(MRHIP_ERR_INVALID_ARG, "nchannels must be >= 1");
     int ndev = 0;
@@ -295,6 +298,14 @@ hipError_t launch_poly(const mrhip_filter *f, const TypeKey &tk, bool fused, con
 {
     *did_shiftin = false;
     *rec_written = false;             // the pair kernels and the universal kernel file the call's end state in the device record
+    if (tk.complex_h) {               // complex taps (kernels_ctaps.hip): no plan_* below ever sees such a call
+        *rec_written = true;
+        ArbTileArgs ct;
+        size_t cl = 0;
+        if (!f->force_generic && plan_ctaps_tiled(tk, a, f->num_cus, &ct, &cl))
+            return launch_poly_ctaps_tiled(tk, a, ct, cl, s, kname, f->num_cus);
+        return launch_poly_ctaps_generic(tk, a, s, kname);
+    }
     if (!f->force_generic) {
         if (a.L == 1) {
             PairArgs spa;
@@ -373,14 +384,14 @@ int64_t mrhip_inputlength_ratio(int64_t n, int64_t L, int64_t M, int64_t phi) { 
 int mrhip_output_dtype(int th, int tx)
 {
     const bool f64 = dtype_is_f64(th) || dtype_is_f64(tx);
-    if (dtype_is_complex(tx)) return f64 ? MRHIP_C128 : MRHIP_C64;
+    if (dtype_is_complex(tx) || dtype_is_complex(th)) return f64 ? MRHIP_C128 : MRHIP_C64;
     return f64 ? MRHIP_F64 : MRHIP_F32;
 }
 
 int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
                           int device, mrhip_filter **out)
 {
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
     if (num < 1 || den < 1) return fail(MRHIP_ERR_INVALID_ARG, "ratio must be positive");
     const int64_t g = std::gcd(num, den);
     const int64_t L = num / g, M = den / g;
@@ -394,7 +405,7 @@ int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int6
     f->nc = dtype_is_complex(tx) ? 2 : 1;
     f->r_f64 = dtype_is_f64(f->ty);
     f->nch = nch; f->hLen = hLen; f->L = L; f->M = M; f->device = device;
-    const size_t es = dtype_scalar_size(th);
+    const size_t es = dtype_size(th);
 
     if (L == 1) {            // STANDARD (Filters.jl:163-165) / DECIMATOR (:166-168): h = flipud(h)
         f->kind = M == 1 ? MRHIP_FIR_STANDARD : MRHIP_FIR_DECIMATOR;
@@ -937,6 +948,8 @@ int mrhip_set_numerics(mrhip_filter *f, int numerics)
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
     if (numerics != MRHIP_NUMERICS_STRICT && numerics != MRHIP_NUMERICS_FUSED)
         return fail(MRHIP_ERR_INVALID_ARG, "unknown numerics mode");
+    if (numerics == MRHIP_NUMERICS_FUSED && dtype_is_complex(f->th))
+        return fail(MRHIP_ERR_UNSUPPORTED, "no FUSED form is defined for complex taps (include/multirate_hip.h: complex taps)");
     f->numerics = numerics;
     return MRHIP_OK;
 }
@@ -1092,6 +1105,11 @@ static hipError_t launch_poly_dyn(mrhip_filter *f, const TypeKey &tk, bool fused
                                   long long *count_dev, hipStream_t s, const char **kname, bool *did_shiftin, const DevCall *x_from = nullptr)
 {
     *did_shiftin = false;
+    if (tk.complex_h) {               // complex taps: the universal complex-tap kernel reads the call record
+        hipError_t e = launch_poly_plan(f, x_len, 1, y_capacity, count_dev, s, x_from);
+        if (e != hipSuccess) return e;
+        return launch_poly_ctaps_generic(tk, a, s, kname);
+    }
     if (!f->force_generic) {
         PairArgs pa;
         dim3 block;
@@ -1693,7 +1711,7 @@ static int filt_device_any(mrhip_filter *f, const void *x, int64_t x_len, int64_
         if (f->nch > 1 && y_stride < total) return fail(MRHIP_ERR_INVALID_ARG, "y_stride < output count");
     }
     const size_t xelt = dtype_scalar_size(f->tx) * static_cast<size_t>(f->nc);
-    const size_t yelt = dtype_scalar_size(f->ty) * static_cast<size_t>(f->nc);
+    const size_t yelt = dtype_size(f->ty);             // (not nc components: complex taps give real samples a complex output)
     int64_t k = 0;
     for (int64_t a = 0; a < x_len; a += step) {
         const int64_t len = std::min<int64_t>(step, x_len - a);
@@ -1761,7 +1779,8 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
         }
         return MRHIP_OK;
     };
-    bool same = !(f0->kind == MRHIP_FIR_ARBITRARY || f0->kind == MRHIP_FIR_FARROW) && !f0->force_generic && n > 1 && n <= 4096;
+    bool same = !(f0->kind == MRHIP_FIR_ARBITRARY || f0->kind == MRHIP_FIR_FARROW) && !f0->force_generic && n > 1 && n <= 4096 &&
+                !dtype_is_complex(f0->th);               // (complex taps: no pair kernel serves them -- single calls)
     for (int i = 0; i < n && same; ++i) {
         const mrhip_filter *f = filters[i];
         if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
@@ -1872,7 +1891,7 @@ int mrhip_filt_device_chunked(mrhip_filter *f, const void *x, int64_t x_len, int
     if (chunk < 1) return fail(MRHIP_ERR_INVALID_ARG, "chunk must be >= 1");
     if (x_len < 0 || y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "negative length");
     const size_t xelt = dtype_scalar_size(f->tx) * static_cast<size_t>(f->nc);
-    const size_t yelt = dtype_scalar_size(f->ty) * static_cast<size_t>(f->nc);
+    const size_t yelt = dtype_size(f->ty);
     // The signal is resident, so for the pfb kernels the chunk loop collapses: the outputs of consecutive filt! calls
     // are the outputs of one call over the concatenation (the dot product runs over the LOGICAL window [history ; x],
     // support.jl:16-31, and the state recurrence is the same closed form, Filters.jl:558-571), bit for bit, and they

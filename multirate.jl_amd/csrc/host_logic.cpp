@@ -22,7 +22,7 @@ int64_t taps2pfb(const void *h, int64_t hLen, int th, int64_t Nphi, void *out)
 {
     const int64_t T = (hLen + Nphi - 1) / Nphi;
     if (!out) return T;
-    const size_t es = dtype_scalar_size(th);
+    const size_t es = dtype_size(th);                 // (complex taps: an (re, im) pair moves as one element)
     auto *dst = static_cast<unsigned char *>(out);
     const auto *src = static_cast<const unsigned char *>(h);
     for (int64_t c = 0; c < Nphi; ++c) {

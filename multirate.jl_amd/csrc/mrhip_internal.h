@@ -558,6 +558,7 @@ struct TypeKey {
     bool x_f64;      // Tx scalar is double
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
+    bool complex_h = false;   // complex taps (rational family): R-typed (re, im) pairs, complex output; kernels_ctaps.hip only
 };
 
 // ---------------------------------------------------------------------------------------
@@ -606,6 +607,11 @@ hipError_t launch_arb_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, con
 bool plan_poly_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
 hipError_t launch_poly_tiled(const TypeKey &tk, bool fused, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                              const char **kname, int num_cus);
+// complex taps (kernels_ctaps.hip): the universal kernel (host- and device-planned calls) and the LDS-tiled one
+hipError_t launch_poly_ctaps_generic(const TypeKey &tk, const PolyArgs &a, hipStream_t s, const char **kname);
+bool plan_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
+hipError_t launch_poly_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
+                                   const char **kname, int num_cus);
 bool plan_phase_stationary(const TypeKey &tk, const PolyArgs &a, int num_cus, TileArgs *out, dim3 *grid, dim3 *block,
                            size_t *lds);
 hipError_t launch_poly_phase_stationary(const TypeKey &tk, bool fused, const PolyArgs &a, const TileArgs &ta, dim3 grid,

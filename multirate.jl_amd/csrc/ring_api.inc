@@ -240,7 +240,7 @@ int mrhip_ring_open(mrhip_filter *f, mrhip_ring **out)
     if (int rc = adopt_stream(f, r->stream)) return bail(rc);            // behind whatever the filter enqueued before
     const TypeKey tk = type_key(f);
     // the resident kernel: FIRRational / FIRInterpolator shapes the output-pair kernel has a RING instantiation for
-    bool resident = (f->kind == MRHIP_FIR_RATIONAL || f->kind == MRHIP_FIR_INTERPOLATOR) && !f->force_generic &&
+    bool resident = (f->kind == MRHIP_FIR_RATIONAL || f->kind == MRHIP_FIR_INTERPOLATOR) && !f->force_generic && !tk.complex_h &&
                     f->numerics == MRHIP_NUMERICS_STRICT && MRHIP_ENV_INT("MRHIP_RING_RESIDENT", 1) != 0 && f->device >= 0 && f->device < 64;
     if (resident) {
         std::lock_guard<std::mutex> g(g_ring_mutex);
@@ -364,7 +364,7 @@ int mrhip_ring_push(mrhip_ring *r, const void *x, int64_t x_len, int64_t x_strid
     // a chunk of less than MRHIP_RING_FLUSH_MIN_MB (32) of outputs is stored write-through: one L2 write-back per XCD serves every chunk filed
     // so far, but costs the same whatever they hold -- at one channel of 1e6 samples (3.7 MB) more than the write-through stores it saves
     {
-        const long long out_bytes = static_cast<long long>(p.n_out) * f->nch * static_cast<long long>(dtype_scalar_size(f->ty)) * f->nc;
+        const long long out_bytes = static_cast<long long>(p.n_out) * f->nch * static_cast<long long>(dtype_size(f->ty));
         const long long min_bytes = static_cast<long long>(MRHIP_ENV_INT("MRHIP_RING_FLUSH_MIN_MB", 32)) << 20;
         // The write-back protocol waits for EVERY one of eight XCDs to have written its L2 back (pair_loader.h: ring_flush_duty takes the minimum
         // over flush_done[0..8)), and an XCD's count only moves when one of its workgroups' loader waves wins the duty: on a device that does
@@ -395,7 +395,7 @@ int mrhip_ring_push_chunks(mrhip_ring *r, const void *x, int64_t x_len, int64_t 
     if (n_written) *n_written = 0;
     if (chunk < 1) return fail(MRHIP_ERR_INVALID_ARG, "chunk must be >= 1");
     const mrhip_filter *f = r->f;
-    const size_t xelt = dtype_scalar_size(f->tx) * static_cast<size_t>(f->nc), yelt = dtype_scalar_size(f->ty) * static_cast<size_t>(f->nc);
+    const size_t xelt = dtype_scalar_size(f->tx) * static_cast<size_t>(f->nc), yelt = dtype_size(f->ty);
     int64_t k = 0;
     for (int64_t a0 = 0; a0 < x_len; a0 += chunk) {
         const int64_t len = std::min<int64_t>(chunk, x_len - a0);

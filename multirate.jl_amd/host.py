@@ -176,13 +176,19 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def _as_taps(h) -> np.ndarray:
+def _as_taps(h, allow_complex: bool = False) -> np.ndarray:
     h = np.ascontiguousarray(h)
     if h.dtype == np.float32 or h.dtype == np.float64:
         return h
     if np.issubdtype(h.dtype, np.integer) or h.dtype == np.float16:
         return h.astype(np.float64)
-    raise MultirateHIPError(5, f"unsupported tap dtype {h.dtype} (taps must be Float32/Float64)")
+    if h.dtype == np.complex64 or h.dtype == np.complex128:
+        if allow_complex:
+            return h
+        raise MultirateHIPError(5, f"tap dtype {h.dtype}: complex taps are built with FIRFilter.complex_taps(h, ratio) "
+                                   "(the rational family only); this constructor takes Float32/Float64 taps")
+    raise MultirateHIPError(5, f"unsupported tap dtype {h.dtype} (taps must be Float32/Float64, or Complex64/Complex128 "
+                               "through FIRFilter.complex_taps)")
 
 
 def _is_torch(x) -> bool:
@@ -201,8 +207,8 @@ def _np_torch_dtype(d):
 
 # ---- host-only helpers ------------------------------------------------------------------------
 def taps2pfb(h, Nphi: int) -> np.ndarray:
-    """taps2pfb(h, N𝜙), src/Filters.jl:284-298.  Returns the tapsPer𝜙 x N𝜙 matrix."""
-    h = _as_taps(h)
+    """taps2pfb(h, N𝜙), src/Filters.jl:284-298.  Returns the tapsPer𝜙 x N𝜙 matrix (complex for complex h)."""
+    h = _as_taps(h, allow_complex=True)
     lib = load_library()
     T = lib.mrhip_taps2pfb(_ptr(h), len(h), _NP2DT[h.dtype], Nphi, None)
     if T < 0:
@@ -239,9 +245,9 @@ class FIRFilter:
     """
 
     def __init__(self, h, ratio=Fraction(1, 1), Nphi: int = 32, polyorder=None, *, device: int = 0,
-                 numerics: int = NUMERICS_STRICT, pnfb=None):
+                 numerics: int = NUMERICS_STRICT, pnfb=None, _complex_taps: bool = False):
         self._lib = load_library()
-        self.h = _as_taps(h).copy()
+        self.h = _as_taps(h, allow_complex=_complex_taps).copy()
         if len(self.h) < 1:
             raise MultirateHIPError(1, "h must hold at least one tap")
         self.device = int(device)
@@ -284,6 +290,20 @@ class FIRFilter:
             self.Nphi = L
             self.tapsPerPhi = len(self.h) if L == 1 else -(-len(self.h) // L)
             self.historyLen = self.tapsPerPhi - 1
+
+    @classmethod
+    def complex_taps(cls, h, ratio=1, *, device: int = 0):
+        """FIRFilter(h::Vector{Complex64 / Complex128}, ratio::Rational): the reference is generic over the tap type
+        (src/Filters.jl:158-180, src/support.jl:5-55), so a rotated low-pass, a Hilbert or a single-sideband filter in
+        front of a resampler is just a FIRFilter there.  Rational family only (FIRStandard, FIRDecimator, FIRInterpolator,
+        FIRRational); the output is always complex (Complex128 if either side is 64-bit).  Real ``h`` is promoted to
+        complex.  STRICT numerics only (include/multirate_hip.h: complex taps)."""
+        if isinstance(ratio, (float, np.floating)):
+            raise MultirateHIPError(5, "complex taps: the rational family only (FIRArbitrary / FIRFarrow take Float32/Float64 taps)")
+        h = np.ascontiguousarray(h)
+        if h.dtype != np.complex64 and h.dtype != np.complex128:
+            h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
+        return cls(h, ratio, device=device, _complex_taps=True)
 
     # -- lifetime
     def _ensure(self, tx: np.dtype, nch: int):

@@ -69,7 +69,8 @@ function kindof(ratio::Rational)
 end
 
 # FIRFilter(h, resampleRatio::Rational = 1//1)            src/Filters.jl:158-180
-function FIRFilter(h::Vector{Th}, ratio::Rational = 1//1; device::Integer = 0) where {Th<:Union{Float32,Float64}}
+# (complex taps -- the reference is generic over Th -- for this, the rational family: the output is complex for every sample type)
+function FIRFilter(h::Vector{Th}, ratio::Rational = 1//1; device::Integer = 0) where {Th<:Union{Float32,Float64,ComplexF32,ComplexF64}}
     r = Rational{Int}(ratio)
     f = FIRFilter{kindof(r){Th}}(copy(h), r, 0.0, 0, -1, device, C_NULL, nothing, 0)
     finalizer(destroy!, f)
@@ -175,7 +176,7 @@ end
 
 # ---- bookkeeping ---------------------------------------------------------------------------------
 # taps2pfb(h, Nphi)                                        src/Filters.jl:284-298
-function taps2pfb(h::Vector{T}, Nphi::Integer) where {T<:Union{Float32,Float64}}
+function taps2pfb(h::Vector{T}, Nphi::Integer) where {T<:Union{Float32,Float64,ComplexF32,ComplexF64}}
     t = ccall((:mrhip_taps2pfb, libmr), Int64, (Ptr{Cvoid}, Int64, Cint, Int64, Ptr{Cvoid}), h, length(h), dtypecode(T), Nphi, C_NULL)
     pfb = Matrix{T}(undef, t, Nphi)                       # column-major tapsPerPhi x Nphi, as the reference's
     ccall((:mrhip_taps2pfb, libmr), Int64, (Ptr{Cvoid}, Int64, Cint, Int64, Ptr{Cvoid}), h, length(h), dtypecode(T), Nphi, pfb)

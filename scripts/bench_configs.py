@@ -41,7 +41,10 @@ def rand(shape, dtype):
 def run(name, h, ratio, nphi, nch, n, dtype, bytes_per_in, flops_per_in, reps=5, chunk=None, polyorder=None, per_call=False, note=None):
     """bytes_per_in / flops_per_in: algorithmic bytes and flops (2 per tap per real component) per input sample per channel"""
     x = rand((nch, n), dtype)
-    f = pkg.FIRFilter(h, ratio, nphi, polyorder, device=dev.index or 0, numerics=pkg.NUMERICS_FUSED if FUSED else pkg.NUMERICS_STRICT)
+    if np.iscomplexobj(h):                     # complex taps: the rational family, STRICT only (FIRFilter.complex_taps)
+        f = pkg.FIRFilter.complex_taps(h, ratio, device=dev.index or 0)
+    else:
+        f = pkg.FIRFilter(h, ratio, nphi, polyorder, device=dev.index or 0, numerics=pkg.NUMERICS_FUSED if FUSED else pkg.NUMERICS_STRICT)
     chunk = chunk or n
     f.filt(x[:, :chunk])                       # warm-up + bind
     out_dtype = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
@@ -296,6 +299,25 @@ def rows(which):
                     run(f"AF {kind} rate {rate:.9g} {str(dt).replace('torch.', '')} 1ch x 1e7 (Arb-Farrow Speed Comparison.jl shape)", haf, float(rate), 32, 1,
                         10_000_000, dt, sb + ob * rate, fl, reps=2, polyorder=po)
 
+    def _xct():
+        # complex taps (kernels_ctaps.hip): a low-pass prototype rotated to a band centre, in front of a decimator (c64 x c64) and of the
+        # headline ratio on real samples (c64 taps x f32 -> c64).  Each shape on the kernel the plan picks and on the universal one
+        # (MRHIP_FORCE_GENERIC is read when the device object is created).  Flops: 8 per tap and output for Complex*Complex, 4 for Complex*Real.
+        rot128 = (h128 * np.exp(2j * np.pi * 0.05 * np.arange(len(h128)))).astype(np.complex64)
+        rot147 = (h147 * np.exp(2j * np.pi * 0.001 * np.arange(len(h147)))).astype(np.complex64)
+        was = os.environ.get("MRHIP_FORCE_GENERIC")
+        try:
+            for generic in ("0", "1"):
+                os.environ["MRHIP_FORCE_GENERIC"] = generic
+                tag = " (MRHIP_FORCE_GENERIC=1)" if generic == "1" else ""
+                run(f"X complex taps: decimator 1//4 128 taps c64 x c64 64ch x 1e6{tag}", rot128, Fraction(1, 4), 32, 64, 1_000_000, torch.complex64, 10.0, 8 * 128 / 4, reps=20)
+                run(f"X complex taps: rational 147//160 3528 taps c64 x f32 64ch x 1e6{tag}", rot147, Fraction(147, 160), 32, 64, 1_000_000, torch.float32, 4 + 8 * R147, 4 * 24 * R147, reps=20)
+        finally:
+            if was is None:
+                os.environ.pop("MRHIP_FORCE_GENERIC", None)
+            else:
+                os.environ["MRHIP_FORCE_GENERIC"] = was
+
     def _ms():
         # the north star's "one-channel-per-stream": 64 INDEPENDENT single-channel FIRFilters (README.md:87-141: one object per
         # signal), chunks of about 1e6 samples of UNEQUAL lengths arriving round after round, one launch per round
@@ -345,7 +367,7 @@ def rows(which):
         for f in fs:
             f.close()
 
-    table = {"ms": _ms, "c1": _c1, "c2": _c2, "c2s": _c2s, "c2r": _c2r, "c3a": _c3a, "c3b": _c3b, "c4": _c4, "c4f": _c4f, "c5": _c5, "x160": _x160, "xf64": _xf64, "xmix": _xmix, "xstd": _xstd, "x32": _x32, "xc32": _xc32, "xarb": _xarb, "xmix64": _xmix64, "af": _af, "xdec": _xdec, "xlarge": _xlarge}
+    table = {"ms": _ms, "c1": _c1, "c2": _c2, "c2s": _c2s, "c2r": _c2r, "c3a": _c3a, "c3b": _c3b, "c4": _c4, "c4f": _c4f, "c5": _c5, "x160": _x160, "xf64": _xf64, "xmix": _xmix, "xstd": _xstd, "x32": _x32, "xc32": _xc32, "xarb": _xarb, "xmix64": _xmix64, "af": _af, "xdec": _xdec, "xlarge": _xlarge, "xct": _xct}
     for name in which:                # in the order asked for (bench.py wants the BASELINE rows last)
         table[name]()
 
