@@ -74,7 +74,7 @@ __device__ __forceinline__ long long uniform_ll(long long v)
 }
 
 // A wave-uniform GLOBAL pointer the compiler can no longer fold into vector address arithmetic: base (SGPR pair) + 32-bit lane offset
-// then selects the scalar-base form of global_load / global_store (kernels_arb_pipe.hip: opaque_uniform).
+// then selects the scalar-base form of global_load / global_store (pipe_stage.h: opaque_uniform).
 template <typename P>
 using gptr_t = __attribute__((address_space(1))) P *;
 template <typename P>

@@ -18,11 +18,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
-#include <algorithm>
 
 #include "mrhip_internal.h"
 #include "pair_device.h"
+#include "pipe_stage.h"
 
 #pragma clang fp contract(off)
 
@@ -31,25 +30,8 @@ namespace {
 
 using dev::v2u_t;
 
-#ifdef MRHIP_AP_TRACE
-// debug builds (-DMRHIP_AP_TRACE): start / end time of every workgroup of the last 64 launches, dumped at process exit
-__device__ unsigned long long g_ap_trace[64][2048][2];
-__device__ unsigned g_ap_slot;
-#endif
 constexpr int kPipeThreads = 256;
 constexpr int kPipeElems = 8;        // 8-byte samples a thread stages per tile: CPL channels x ROWS rows of 256 samples
-
-template <bool FUSED, typename R>
-__device__ __forceinline__ R macd(R t, R x, R acc)
-{
-    if constexpr (FUSED) {
-        if constexpr (sizeof(R) == 4) return __builtin_fmaf(t, x, acc);
-        else return __builtin_fma(t, x, acc);
-    } else {
-        const R p = t * x;
-        return acc + p;
-    }
-}
 
 // a tap as the LDS read delivers it: 8 bytes (Float64 arithmetic) or 4 (Float32)
 template <typename R> struct TapBits { using type = v2u_t; };
@@ -61,32 +43,6 @@ __device__ __forceinline__ typename TapBits<R>::type lds_read_tap(unsigned byte_
     else return dev::lds_read_b32<OFF>(byte_addr);
 }
 
-// A wave-uniform GLOBAL pointer the compiler can no longer fold into vector address arithmetic: base (SGPR pair) + 32-bit
-// lane offset then selects the scalar-base form of global_load / global_store (no 64-bit vector adds per access).  The result
-// is typed as an address-space-1 pointer: rebuilt from integers as a generic pointer it is accessed with flat_load /
-// flat_store, which also count in lgkmcnt -- the counter the hand-issued LDS pipeline waits on.
-template <typename P>
-using global_ptr = __attribute__((address_space(1))) P *;
-template <typename P>
-__device__ __forceinline__ global_ptr<P> opaque_uniform(P *p)
-{
-    unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p)));
-    unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) >> 32));
-    asm volatile("" : "+s"(lo), "+s"(hi));
-    return reinterpret_cast<global_ptr<P>>((static_cast<unsigned long long>(hi) << 32) | lo);
-}
-
-template <typename TX, typename R, int NC>
-__device__ __forceinline__ R sample_part(v2u_t v, int c)          // 8-byte sample: component c
-{
-    if constexpr (NC == 1) {
-        static_assert(sizeof(TX) == 8 && sizeof(R) == 8, "one 8-byte real sample");
-        return __builtin_bit_cast(double, v);
-    } else {
-        static_assert(sizeof(TX) == 4 && NC == 2, "one ComplexF32 sample");
-        return static_cast<R>(__builtin_bit_cast(float, c == 0 ? v.x : v.y));
-    }
-}
 template <typename R>
 __device__ __forceinline__ R sample_of_pair(v2u_t v, int which)   // two Float32 samples in one 8-byte read
 {
@@ -96,11 +52,6 @@ __device__ __forceinline__ R sample_of_pair(v2u_t v, int which)   // two Float32
 // DMA: the sample rows go HBM -> LDS by LDS-DMA (global_load_lds, 16 bytes per lane: no staging registers, no ds_write); the
 // rows then have a pitch of whole 16-byte chunks.  First / last tiles and partial channel groups are staged synchronously
 // through registers.
-// (experiment, profiles/r04/experiments.md: C4 4.97 ms with the 16-byte tap reads vs 4.83-4.9 without -- the LDS cost follows the
-//  bytes, not the instruction count)
-#ifndef MRHIP_AP_TD128
-#define MRHIP_AP_TD128 0
-#endif
 // TEX > 0: tapsPerPhi == TEX exactly (a multiple of 4): the tap-pair pipeline is unrolled whole with immediate LDS offsets -- no
 // running bases to advance (6 vector adds per two pairs), no loop counter.
 template <typename TX, typename R, int NC, bool FUSED, int CPL, bool DMA, int TEX = 0>
@@ -112,10 +63,7 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
                                                                       // kept twice, one sample apart (copy B: odd window starts)
     static_assert(SB == 8 || (SB == 4 && NC == 1), "8-byte samples, or Float32");
     using StageT = std::conditional_t<SB == 8, unsigned long long, unsigned>;
-    // TD: Float64 taps -- tap i of a phase and its difference-bank partner sit side by side in LDS (16 bytes) and come with ONE
-    // ds_read_b128: two tap reads per tap pair instead of four
-    constexpr bool TD = sizeof(R) == 8 && MRHIP_AP_TD128 != 0;
-    constexpr int NR = (TD ? 2 : 4) + (PAIR ? 1 : 2) * CPL;           // LDS reads per tap pair
+    constexpr int NR = 4 + (PAIR ? 1 : 2) * CPL;                      // LDS reads per tap pair
     static_assert(NR <= 15, "lgkmcnt is a 4-bit counter");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(smem));
@@ -131,8 +79,7 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
         const int total = a.Nphi * T;
         for (int e = tid; e < total; e += kPipeThreads) {
             const int phi = e / T, i = e - phi * T;
-            if constexpr (TD) { lpfb[(phi * TP + i) * 2] = g0[e]; lpfb[(phi * TP + i) * 2 + 1] = g1[e]; }
-            else { lpfb[phi * TP + i] = g0[e]; ldpfb[phi * TP + i] = g1[e]; }
+            lpfb[phi * TP + i] = g0[e]; ldpfb[phi * TP + i] = g1[e];
         }
     }
     const int RP = DMA ? ta.row_pitch : MS;                          // row pitch in samples (DMA: whole 16-byte chunks)
@@ -146,9 +93,6 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
     tiles_take_dyn(a.n_out, ta, ngroups_ll, a.dyn);                 // (a device-planned call: the count from the call record)
     const int ngroups = static_cast<int>(ngroups_ll);
     long long tile = blockIdx.x;
-#ifdef MRHIP_AP_TRACE
-    if (tid == 0 && blockIdx.x < 2048) g_ap_trace[g_ap_slot & 63][blockIdx.x][0] = wall_clock64();
-#endif
     // Tiles are HANDED OUT in runs of ta.run_tiles consecutive tiles (ta.counters): a workgroup's first run is its index, every
     // further one the next the whole grid has not taken -- time-major like the static order, so the workgroups that run together
     // still share a stretch of the schedule.  With tile += gridDim every workgroup owns 1/grid of the tiles whatever happens to
@@ -191,21 +135,7 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
     };
     long long t1 = after(tile), t2 = after(t1);                 // this workgroup's next tile and the one after it
 
-    // n_idx[first output of a tile].  In the tile loop it is loaded TWO tiles ahead by an ordinary load and taken over into a scalar
-    // behind the staging wait at the end of a tile, where nothing is in flight any more: left to a load at the top of the tile the
-    // compiler waits s_waitcnt vmcnt(0) there -- the previous tile's output stores included, microseconds per tile.  (Round 3 first
-    // issued it as an asynchronous s_load_dword from inline assembly and waited a tile later: the compiler, which takes an asm
-    // output for valid at once, spilled and re-used that SGPR while the load was still in flight, and the landing data overwrote
-    // whatever lived there -- whole tiles of zeros in workgroups that take more than one tile, for some instantiations only.)
-    auto first_index_sync = [&](long long tau_) -> int {
-        const int *p = a.n_idx + tau_ * kPipeThreads;
-        const unsigned plo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p)));
-        const unsigned phi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) >> 32));
-        const unsigned long long pu = (static_cast<unsigned long long>(phi) << 32) | plo;
-        int v;
-        asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(pu));   // (valid when the statement ends)
-        return v;
-    };
+    // (n_idx[first output of a tile]: first_index_sync, pipe_stage.h, or loaded two tiles ahead and taken over behind the staging wait)
     struct Tile { long long k0, o; int nout, ch0, nchl, n_lo, interior; };
     auto make_tile = [&](long long tau_, int cg_, int n_lo_) {
         Tile t;
@@ -296,7 +226,7 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
         }
     };
 
-    const int n_lo0 = first_index_sync(tau);
+    const int n_lo0 = first_index_sync(a.n_idx, tau, kPipeThreads);
     Tile cur = make_tile(tau, cg, n_lo0);
     load_tile(cur);
     int n_pre = 0;
@@ -311,7 +241,7 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
     bool have_next = t1 < ta.total_tiles;
     if (have_next) (void)split(t1, ntau, ncg);
     int n_lo_next = 0;
-    if (have_next) n_lo_next = first_index_sync(ntau);
+    if (have_next) n_lo_next = first_index_sync(a.n_idx, ntau, kPipeThreads);
     store_tile(0);
     __syncthreads();       // the tap banks and the first tile are in LDS
     int buf = 0;
@@ -348,8 +278,8 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
             const double alpha = acc_mine - phif;                 // src/Filters.jl:671-672
             const int phi = static_cast<int>(phif) - 1;           // 0-based column
             const int w = n_mine - cur.n_lo;                      // oldest sample of this output's window, within the tile
-            unsigned tpa = lds0 + static_cast<unsigned>(phi * TP) * (TD ? 2u * RS : RS);  // taps of this phase
-            unsigned dpa = tpa + static_cast<unsigned>(ta.bank_elems) * RS;              // ... of the difference bank (TD: unused)
+            unsigned tpa = lds0 + static_cast<unsigned>(phi * TP) * RS;                   // taps of this phase
+            unsigned dpa = tpa + static_cast<unsigned>(ta.bank_elems) * RS;              // ... of the difference bank
             unsigned sa[CPL];
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) {
@@ -364,17 +294,15 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) dev::pin(sa[cc]);
 
-            struct Blk { TapReg t0, t1, d0, d1; dev::v4u_t td0, td1; v2u_t s0[CPL], s1[PAIR ? 1 : CPL]; };
+            struct Blk { TapReg t0, t1, d0, d1; v2u_t s0[CPL], s1[PAIR ? 1 : CPL]; };
             auto issue = [&](Blk &b, auto off_c) {              // taps i, i + 1 at byte offset OFF from the running bases
                 constexpr int OFF = decltype(off_c)::value;
                 constexpr int TOFF = OFF / 8 * static_cast<int>(RS);           // the same tap pair in the tap banks
                 constexpr int SOFF = OFF / 8 * static_cast<int>(SB);           // ... in the sample tile
-                if constexpr (TD) {
-                    b.td0 = dev::lds_read_b128<2 * TOFF>(tpa); b.td1 = dev::lds_read_b128<2 * TOFF + 16>(tpa);
-                } else {
-                    b.t0 = lds_read_tap<R, TOFF>(tpa); b.t1 = lds_read_tap<R, TOFF + static_cast<int>(RS)>(tpa);
-                    b.d0 = lds_read_tap<R, TOFF>(dpa); b.d1 = lds_read_tap<R, TOFF + static_cast<int>(RS)>(dpa);
-                }
+                // (both banks side by side and ONE 16-byte read per tap measured slower: C4 4.97 ms against 4.83-4.9, the LDS cost follows
+                //  the bytes, not the instruction count -- profiles/r04/experiments.md)
+                b.t0 = lds_read_tap<R, TOFF>(tpa); b.t1 = lds_read_tap<R, TOFF + static_cast<int>(RS)>(tpa);
+                b.d0 = lds_read_tap<R, TOFF>(dpa); b.d1 = lds_read_tap<R, TOFF + static_cast<int>(RS)>(dpa);
 #pragma unroll
                 for (int cc = 0; cc < CPL; ++cc) {
                     b.s0[cc] = dev::lds_read_b64<SOFF>(sa[cc]);
@@ -384,8 +312,7 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
             auto landed = [&](Blk &b, auto n_c) {               // at most N later reads still in flight => b has landed
                 constexpr int N = decltype(n_c)::value;
                 asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-                if constexpr (TD) { dev::pin(b.td0); dev::pin(b.td1); }
-                else { dev::pin(b.t0); dev::pin(b.t1); dev::pin(b.d0); dev::pin(b.d1); }
+                dev::pin(b.t0); dev::pin(b.t1); dev::pin(b.d0); dev::pin(b.d1);
 #pragma unroll
                 for (int cc = 0; cc < CPL; ++cc) { dev::pin(b.s0[cc]); if constexpr (!PAIR) dev::pin(b.s1[cc]); }
             };
@@ -397,14 +324,8 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
                 for (int c = 0; c < NC; ++c) { lo[cc][c] = static_cast<R>(-0.0); up[cc][c] = static_cast<R>(-0.0); }
             }
             auto compute = [&](const Blk &b) {
-                R t0, t1, d0, d1;
-                if constexpr (TD) {
-                    t0 = __builtin_bit_cast(R, v2u_t{b.td0.x, b.td0.y}); d0 = __builtin_bit_cast(R, v2u_t{b.td0.z, b.td0.w});
-                    t1 = __builtin_bit_cast(R, v2u_t{b.td1.x, b.td1.y}); d1 = __builtin_bit_cast(R, v2u_t{b.td1.z, b.td1.w});
-                } else {
-                    t0 = __builtin_bit_cast(R, b.t0); t1 = __builtin_bit_cast(R, b.t1);
-                    d0 = __builtin_bit_cast(R, b.d0); d1 = __builtin_bit_cast(R, b.d1);
-                }
+                const R t0 = __builtin_bit_cast(R, b.t0), t1 = __builtin_bit_cast(R, b.t1);
+                const R d0 = __builtin_bit_cast(R, b.d0), d1 = __builtin_bit_cast(R, b.d1);
 #pragma unroll
                 for (int cc = 0; cc < CPL; ++cc) {
 #pragma unroll
@@ -412,15 +333,15 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
                         R x0, x1;
                         if constexpr (PAIR) { x0 = sample_of_pair<R>(b.s0[cc], 0); x1 = sample_of_pair<R>(b.s0[cc], 1); }
                         else { x0 = sample_part<TX, R, NC>(b.s0[cc], c); x1 = sample_part<TX, R, NC>(b.s1[cc], c); }
-                        lo[cc][c] = macd<FUSED>(t0, x0, lo[cc][c]);
-                        up[cc][c] = macd<FUSED>(d0, x0, up[cc][c]);
-                        lo[cc][c] = macd<FUSED>(t1, x1, lo[cc][c]);
-                        up[cc][c] = macd<FUSED>(d1, x1, up[cc][c]);
+                        lo[cc][c] = mac<FUSED>(t0, x0, lo[cc][c]);
+                        up[cc][c] = mac<FUSED>(d0, x0, up[cc][c]);
+                        lo[cc][c] = mac<FUSED>(t1, x1, lo[cc][c]);
+                        up[cc][c] = mac<FUSED>(d1, x1, up[cc][c]);
                     }
                 }
             };
             auto advance = [&](unsigned bytes) {                  // `bytes` of samples = bytes / 8 taps
-                tpa += bytes / 8u * (TD ? 2u * RS : RS); dpa += bytes / 8u * RS;
+                tpa += bytes / 8u * RS; dpa += bytes / 8u * RS;
 #pragma unroll
                 for (int cc = 0; cc < CPL; ++cc) sa[cc] += bytes / 8u * SB;
             };
@@ -465,12 +386,12 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
                     if (p + 1 < nblk) compute(B);
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)");            // the unused last reads
-                if constexpr (TD) dev::pin(A.td0); else dev::pin(A.t0);
+                dev::pin(A.t0);
             }
             if (TEX == 0 && (T & 1)) {                           // odd tapsPerPhi: the last tap alone
                 const int i = T - 1;
-                const unsigned tl = lds0 + static_cast<unsigned>(phi * TP + i) * (TD ? 2u * RS : RS);
-                TapReg t = lds_read_tap<R, 0>(tl), d = lds_read_tap<R, 0>(tl + (TD ? RS : static_cast<unsigned>(ta.bank_elems) * RS));
+                const unsigned tl = lds0 + static_cast<unsigned>(phi * TP + i) * RS;
+                TapReg t = lds_read_tap<R, 0>(tl), d = lds_read_tap<R, 0>(tl + static_cast<unsigned>(ta.bank_elems) * RS);
                 std::conditional_t<PAIR, unsigned, v2u_t> s[CPL];     // (copy A holds every sample at its own index)
 #pragma unroll
                 for (int cc = 0; cc < CPL; ++cc) {
@@ -490,8 +411,8 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
                         R x;
                         if constexpr (PAIR) x = static_cast<R>(__builtin_bit_cast(float, s[cc]));
                         else x = sample_part<TX, R, NC>(s[cc], c);
-                        lo[cc][c] = macd<FUSED>(tt, x, lo[cc][c]);
-                        up[cc][c] = macd<FUSED>(dd, x, up[cc][c]);
+                        lo[cc][c] = mac<FUSED>(tt, x, lo[cc][c]);
+                        up[cc][c] = mac<FUSED>(dd, x, up[cc][c]);
                     }
                 }
             }
@@ -549,59 +470,22 @@ __global__ __launch_bounds__(kPipeThreads, 4) void arb_pipe_kernel(ArbArgs a, Ar
     }
     leave();
     dev::shiftin_by_last_workgroup<TX, NC>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
-#ifdef MRHIP_AP_TRACE
-    if (tid == 0 && blockIdx.x < 2048) g_ap_trace[g_ap_slot & 63][blockIdx.x][1] = wall_clock64();
-#endif
 }
 
 template <typename TX, typename R, int NC, bool DMA>
 hipError_t launch_pipe_t(bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s, int num_cus)
 {
     auto go = [&](auto kfn) -> hipError_t {
-        int per_cu = 0;
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kPipeThreads, lds, &per_cu);
-        if (eo != hipSuccess) return eo;
-        if (per_cu < 1) per_cu = 1;
-        const int bpc = MRHIP_ENV_INT("MRHIP_PIPE_BPC", 0);           // experiments: fewer workgroups per CU than fit
-        if (bpc > 0 && bpc < per_cu) per_cu = bpc;
-        long long g = static_cast<long long>(num_cus) * per_cu;
-        if (g > ta.total_tiles) g = ta.total_tiles;
-        if (g < 1) g = 1;
+        const PipeGrid pg = pipe_grid(reinterpret_cast<const void *>(kfn), kPipeThreads, lds, num_cus, ta.total_tiles,
+                                      MRHIP_ENV_INT("MRHIP_PIPE_BPC", 0));           // experiments: fewer workgroups per CU than fit
+        if (pg.err != hipSuccess) return pg.err;
+        const long long g = pg.grid;
         if (MRHIP_ENV_INT("MRHIP_DEBUG", 0) == 1) {
             hipFuncAttributes fa;
             (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));
             std::fprintf(stderr, "[mrhip] arb_pipe T=%d Nphi=%d cpl=%d grid=%lld lds=%zu occ/CU=%d regs=%d max_span=%d tiles=%lld\n",
-                         a.T, a.Nphi, ta.cpl, g, lds, per_cu, fa.numRegs, ta.max_span, ta.total_tiles);
+                         a.T, a.Nphi, ta.cpl, g, lds, pg.per_cu, fa.numRegs, ta.max_span, ta.total_tiles);
         }
-#ifdef MRHIP_AP_TRACE
-        {
-            static unsigned slot = 0;
-            static bool armed = false;
-            static std::vector<long long> grids(64, 0);
-            grids[slot & 63] = g;
-            (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ap_slot), &slot, sizeof(slot), 0, hipMemcpyHostToDevice, s);
-            ++slot;
-            if (!armed) {
-                armed = true;
-                std::atexit([] {
-                    (void)hipDeviceSynchronize();
-                    static unsigned long long h[64][2048][2];
-                    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ap_trace), sizeof(h)) != hipSuccess) return;
-                    for (unsigned l = 0; l < 64 && l < slot; ++l) {
-                        const unsigned sl = (slot - 1 - l) & 63;
-                        const long long gg = std::min<long long>(grids[sl], 2048);
-                        if (gg < 2) continue;
-                        unsigned long long s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
-                        int late = 0;
-                        for (long long b = 0; b < gg; ++b) { s0 = std::min(s0, h[sl][b][0]); s1 = std::max(s1, h[sl][b][0]); e0 = std::min(e0, h[sl][b][1]); e1 = std::max(e1, h[sl][b][1]); }
-                        for (long long b = 0; b < gg; ++b) late += h[sl][b][0] - s0 > 5000;     // 100 MHz clock: 50 us
-                        std::fprintf(stderr, "[ap_trace] launch -%u grid=%lld: starts spread %.1f us (%d workgroups more than 50 us late), ends spread %.1f us, kernel %.1f us\n",
-                                     l, gg, (s1 - s0) / 100.0, late, (e1 - e0) / 100.0, (e1 - s0) / 100.0);
-                    }
-                });
-            }
-        }
-#endif
         // Hand-outs of tiles (ta.counters): for launches long enough to have a tail worth balancing and few enough requests for the
         // one address they all go to -- at least 64 tiles a workgroup, about 40 runs each (a power of two, 2 ... 32 tiles)
         ArbTileArgs tq = ta;
@@ -656,23 +540,11 @@ bool plan_arb_pipe(const TypeKey &tk, const ArbArgs &a, long long span256, ArbTi
     if (env_cpl == 1 || env_cpl == 2 || env_cpl == 4) cpl = env_cpl;
     while (cpl > 1 && max_span > static_cast<long long>(kPipeElems / cpl) * kPipeThreads) cpl /= 2;
     if (max_span > static_cast<long long>(kPipeElems / cpl) * kPipeThreads) return false;
-    // copy B starts 128 B (mod 256) behind copy A: the lanes of one read that use it do not land on their neighbours' banks
-    // LDS-DMA staging: rows of whole 16-byte chunks, a copy rounded up to whole 1 KiB wave transfers, at most 16 of them;
-    // the lane offsets of the transfers are 32-bit: the channels of a group must lie within 2 GiB of each other
-    const long long row_chunks = (max_span * static_cast<long long>(sb) + 15) / 16;
-    const long long nslots = (row_chunks * cpl + 63) / 64;
-    const bool dma = MRHIP_ENV_INT("MRHIP_PIPE_DMA", 1) != 0 && nslots <= 16 &&
-                     static_cast<double>(cpl) * static_cast<double>(a.x_stride) * static_cast<double>(sb) < 2147483648.0;
+    PipeStagePlan sp = pipe_stage_plan(sb, cpl, max_span, a.x_stride, copies);
     // (register staging of four ComplexF32 channels with Float64 arithmetic does not fit 128 VGPRs: that instantiation spills, and
     //  a spilled register of the hand-issued LDS pipeline would be saved before its data has landed -- two channels per lane then)
-    if (!dma && tk.complex_x && tk.r_f64 && cpl > 2) cpl = 2;
-    int copyb_pad = copies == 2 ? static_cast<int>((128 + 256 - (static_cast<size_t>(max_span) * sb * cpl) % 256) % 256 / sb) : 0;
-    size_t buf_bytes = (static_cast<size_t>(max_span) * cpl * copies + copyb_pad) * sb;
-    if (dma) {
-        copyb_pad = copies == 2 ? static_cast<int>(128 / sb) : 0;            // (a copy is a multiple of 1 KiB)
-        buf_bytes = static_cast<size_t>(nslots) * 1024 * copies + copyb_pad * sb;
-    }
-    const size_t total = banks_bytes + 2 * buf_bytes + 64;   // (+ pad: the pipeline reads one tap pair past a window)
+    if (!sp.prefetch && tk.complex_x && tk.r_f64 && cpl > 2) { cpl = 2; sp = pipe_stage_plan(sb, cpl, max_span, a.x_stride, copies, false); }
+    const size_t total = banks_bytes + 2 * sp.buf_bytes + 64;   // (+ pad: the pipeline reads one tap pair past a window)
     if (total > 150 * 1024) return false;
     ArbTileArgs ta{};
     ta.pipe = 1;
@@ -681,10 +553,10 @@ bool plan_arb_pipe(const TypeKey &tk, const ArbArgs &a, long long span256, ArbTi
     ta.bank_elems = static_cast<int>(bank_elems);
     ta.x_offset_bytes = static_cast<int>(banks_bytes);
     ta.max_span = static_cast<int>(max_span);
-    ta.copyb_pad = copyb_pad;
-    ta.prefetch = dma ? 1 : 0;
-    ta.row_pitch = static_cast<int>(row_chunks * 16 / static_cast<long long>(sb));
-    ta.dma_slots = static_cast<int>(nslots);
+    ta.copyb_pad = sp.copyb_pad;
+    ta.prefetch = sp.prefetch;
+    ta.row_pitch = sp.row_pitch;
+    ta.dma_slots = sp.dma_slots;
     ta.tile_out = kPipeThreads;
     ta.tiles_per_channel = (a.n_out + kPipeThreads - 1) / kPipeThreads;
     ta.total_tiles = ta.tiles_per_channel * ((a.nch + cpl - 1) / cpl);

@@ -20,6 +20,7 @@
 
 #include "mrhip_internal.h"
 #include "pair_device.h"
+#include "pipe_stage.h"
 
 #pragma clang fp contract(off)
 
@@ -28,18 +29,6 @@ namespace {
 
 constexpr int kArbThreads = 256;
 constexpr int kArbPrefetch = 6;      // samples a thread holds in registers for the next tile (arb_tiled_kernel)
-
-template <typename R, bool FUSED>
-__device__ __forceinline__ R mac(R t, R x, R acc)
-{
-    if constexpr (FUSED) {
-        if constexpr (sizeof(R) == 4) return __builtin_fmaf(t, x, acc);
-        else return __builtin_fma(t, x, acc);
-    } else {
-        R p = t * x;
-        return acc + p;
-    }
-}
 
 // LDS reads are what bounded round 2's form of this kernel (PMC: the LDS busy 74 % of the launch at 8.5 cycles per read
 // instruction -- the compiler merged the 8-byte reads of a lane into ds_read2_b64, 128 B/clk -- while the Float64 VALU
@@ -54,46 +43,7 @@ __device__ __forceinline__ R mac(R t, R x, R acc)
 //     (16-byte samples -- ComplexF64 -- are one read each and need no second copy).
 // The next tile's samples (and the lanes' schedule entries) are loaded into registers BEFORE the current tile is
 // computed and written to LDS after it, so no wave waits for HBM inside a tile.
-// Tiles handed out in runs (ArbTileArgs::counters; kernels_arb_pipe.hip has the story): the workgroups of a CU do not advance evenly,
-// with tile += gridDim the kernel's tail runs under-occupied.  Two runs are always in hand; lane 0 asks for another when one is
-// taken into use and publishes the answer before the barrier at the top of the next tile.
-struct TileHandout {
-    unsigned *ctr;
-    long long G, q0, q1;
-    int run;
-    static constexpr long long kNone = -1;
-    __device__ __forceinline__ long long first(unsigned *counters, int run_tiles, unsigned *s_grab, int tid)
-    {
-        ctr = counters; G = gridDim.x; run = ctr ? run_tiles : 1; q0 = q1 = kNone;
-        if (ctr) {
-            if (tid == 0) { const unsigned b = atomicAdd(ctr, 2u); s_grab[0] = b; s_grab[1] = b + 1u; }
-            __syncthreads();
-            q0 = (G + s_grab[0]) * run; q1 = (G + s_grab[1]) * run;
-            __syncthreads();
-        }
-        return static_cast<long long>(blockIdx.x) * run;
-    }
-    __device__ __forceinline__ long long after(long long t)
-    {
-        if (!ctr) return t + G;
-        if (((t + 1) & (run - 1)) != 0) return t + 1;          // (run is a power of two)
-        const long long r = q0;
-        q0 = q1; q1 = kNone;
-        return r;
-    }
-    __device__ __forceinline__ bool wants() const { return ctr && q1 == kNone; }
-    __device__ __forceinline__ void take(const unsigned *s_grab, unsigned it) { q1 = (G + s_grab[it & 1]) * run; }
-    __device__ __forceinline__ void leave(int tid) const
-    {
-        if (ctr && tid == 0) {
-            __threadfence();
-            if (atomicAdd(ctr + 64, 1u) == static_cast<unsigned>(G) - 1u) {
-                __threadfence();
-                ctr[0] = 0u; ctr[64] = 0u;                        // re-armed for the next launch
-            }
-        }
-    }
-};
+// (the hand-out of tiles in runs: TileHandout, pipe_stage.h)
 
 // hand-outs of tiles only where a workgroup has tiles to balance (per_wg tiles each): run length, or 0 for tile += gridDim
 static int handout_run(long long per_wg, long long min_tiles)
@@ -269,9 +219,9 @@ __global__ __launch_bounds__(kArbThreads, 4) void arb_tiled_kernel(ArbArgs a, Ar
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
                         if (first) { lo[cc][c] = t0 * static_cast<R>(v0.c[c]); up[cc][c] = d0 * static_cast<R>(v0.c[c]); }
-                        else { lo[cc][c] = mac<R, FUSED>(t0, static_cast<R>(v0.c[c]), lo[cc][c]); up[cc][c] = mac<R, FUSED>(d0, static_cast<R>(v0.c[c]), up[cc][c]); }
-                        lo[cc][c] = mac<R, FUSED>(t1, static_cast<R>(v1.c[c]), lo[cc][c]);
-                        up[cc][c] = mac<R, FUSED>(d1, static_cast<R>(v1.c[c]), up[cc][c]);
+                        else { lo[cc][c] = mac<FUSED>(t0, static_cast<R>(v0.c[c]), lo[cc][c]); up[cc][c] = mac<FUSED>(d0, static_cast<R>(v0.c[c]), up[cc][c]); }
+                        lo[cc][c] = mac<FUSED>(t1, static_cast<R>(v1.c[c]), lo[cc][c]);
+                        up[cc][c] = mac<FUSED>(d1, static_cast<R>(v1.c[c]), up[cc][c]);
                     }
                 }
             };
@@ -283,7 +233,7 @@ __global__ __launch_bounds__(kArbThreads, 4) void arb_tiled_kernel(ArbArgs a, Ar
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
                         if (first) { lo[cc][c] = t * static_cast<R>(v.c[c]); up[cc][c] = d * static_cast<R>(v.c[c]); }
-                        else { lo[cc][c] = mac<R, FUSED>(t, static_cast<R>(v.c[c]), lo[cc][c]); up[cc][c] = mac<R, FUSED>(d, static_cast<R>(v.c[c]), up[cc][c]); }
+                        else { lo[cc][c] = mac<FUSED>(t, static_cast<R>(v.c[c]), lo[cc][c]); up[cc][c] = mac<FUSED>(d, static_cast<R>(v.c[c]), up[cc][c]); }
                     }
                 }
             };
@@ -479,7 +429,7 @@ __global__ __launch_bounds__(kArbThreads, 3) void farrow_tiled_kernel(FarrowArgs
                                 acc[cc][c] = t * static_cast<R>(v.c[c]);
                                 if (seam) acc[cc][c] = static_cast<R>(0) + acc[cc][c];       // support.jl:46: the seam dot starts from zero
                             } else {
-                                acc[cc][c] = mac<R, FUSED>(t, static_cast<R>(v.c[c]), acc[cc][c]);
+                                acc[cc][c] = mac<FUSED>(t, static_cast<R>(v.c[c]), acc[cc][c]);
                             }
                         }
                     }
@@ -500,9 +450,9 @@ __global__ __launch_bounds__(kArbThreads, 3) void farrow_tiled_kernel(FarrowArgs
                                 acc[cc][c] = t0 * static_cast<R>(v0.c[c]);
                                 if (seam) acc[cc][c] = static_cast<R>(0) + acc[cc][c];
                             } else {
-                                acc[cc][c] = mac<R, FUSED>(t0, static_cast<R>(v0.c[c]), acc[cc][c]);
+                                acc[cc][c] = mac<FUSED>(t0, static_cast<R>(v0.c[c]), acc[cc][c]);
                             }
-                            acc[cc][c] = mac<R, FUSED>(t1, static_cast<R>(v1.c[c]), acc[cc][c]);
+                            acc[cc][c] = mac<FUSED>(t1, static_cast<R>(v1.c[c]), acc[cc][c]);
                         }
                     }
                 };

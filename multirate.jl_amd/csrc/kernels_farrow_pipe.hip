@@ -23,6 +23,7 @@
 
 #include "mrhip_internal.h"
 #include "pair_device.h"
+#include "pipe_stage.h"
 
 #pragma clang fp contract(off)
 
@@ -34,45 +35,6 @@ using dev::v2u_t;
 constexpr int kFpThreads = 256;
 constexpr int kFpElems = 8;          // 8-byte samples a thread stages per channel group: CPL channels x ROWS rows of 256 samples
 constexpr int kFpDepth = 4;          // register sets: the reads of taps i + 1 and i + 2 are in flight while tap i is multiplied
-
-template <bool FUSED, typename R>
-__device__ __forceinline__ R fmacd(R t, R x, R acc)
-{
-    if constexpr (FUSED) {
-        if constexpr (sizeof(R) == 4) return __builtin_fmaf(t, x, acc);
-        else return __builtin_fma(t, x, acc);
-    } else {
-        const R p = t * x;
-        return acc + p;
-    }
-}
-
-// A wave-uniform GLOBAL pointer the compiler can no longer fold into vector address arithmetic: base (SGPR pair) + 32-bit
-// lane offset then selects the scalar-base form of global_load / global_store (no 64-bit vector adds per access).  The result
-// is typed as an address-space-1 pointer: rebuilt from integers as a generic pointer it is accessed with flat_load /
-// flat_store, which also count in lgkmcnt -- the counter the hand-issued LDS pipeline waits on.
-template <typename P>
-using global_ptr = __attribute__((address_space(1))) P *;
-template <typename P>
-__device__ __forceinline__ global_ptr<P> opaque_uniform(P *p)
-{
-    unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p)));
-    unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) >> 32));
-    asm volatile("" : "+s"(lo), "+s"(hi));
-    return reinterpret_cast<global_ptr<P>>((static_cast<unsigned long long>(hi) << 32) | lo);
-}
-
-template <typename TX, typename R, int NC>
-__device__ __forceinline__ R fsample_part(v2u_t v, int c)
-{
-    if constexpr (NC == 1) {
-        static_assert(sizeof(TX) == 8 && sizeof(R) == 8, "one 8-byte real sample");
-        return __builtin_bit_cast(double, v);
-    } else {
-        static_assert(sizeof(TX) == 4 && NC == 2, "one ComplexF32 sample");
-        return static_cast<R>(__builtin_bit_cast(float, c == 0 ? v.x : v.y));
-    }
-}
 
 // EXACT: tapsPerPhi == TREG (no per-tap guards: the unrolled pipeline is one basic block)
 // R = the arithmetic type: Float64, or Float32 (ComplexF32 samples x Float32 taps)
@@ -138,17 +100,8 @@ __global__ __launch_bounds__(kFpThreads, 3) void farrow_pipe_kernel(FarrowArgs a
     double *const lcoef = reinterpret_cast<double *>(smem + ta.x_offset_bytes);
     for (int e = tid; e < T * (P + 1); e += kFpThreads) lcoef[e] = a.pnfb[e];
 
-    // n_idx[first output of a tile]: loaded two tiles ahead by an ordinary load, taken over into a scalar behind the first staging
-    // wait of a tile (see kernels_arb_pipe.hip: an asynchronous s_load from inline assembly is not safe, the compiler re-uses its SGPR)
-    auto first_index_sync = [&](long long tau_) -> int {
-        const int *p = a.n_idx + tau_ * kFpThreads;
-        const unsigned plo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p)));
-        const unsigned phi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) >> 32));
-        const unsigned long long pu = (static_cast<unsigned long long>(phi) << 32) | plo;
-        int v;
-        asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(pu));   // (valid when the statement ends)
-        return v;
-    };
+    // n_idx[first output of a tile]: first_index_sync (pipe_stage.h) for the first two tiles, then loaded two tiles ahead by an ordinary
+    // load and taken over into a scalar behind the first staging wait of a tile
 
     // Staging: element j of a thread is sample r*256 + tid of channel cc (j = cc*ROWS + r); lanes past the span re-read its
     // last sample (same cache line, no branch)
@@ -226,8 +179,8 @@ __global__ __launch_bounds__(kFpThreads, 3) void farrow_pipe_kernel(FarrowArgs a
         }
     };
 
-    int n_lo = first_index_sync(tau);
-    int n_lo_next = (ctr ? t1 : tau + G) < ntiles ? first_index_sync(ctr ? t1 : tau + G) : 0;
+    int n_lo = first_index_sync(a.n_idx, tau, kFpThreads);
+    int n_lo_next = (ctr ? t1 : tau + G) < ntiles ? first_index_sync(a.n_idx, ctr ? t1 : tau + G, kFpThreads) : 0;
     int n_pre = 0;
     double ph_pre = 0.0;
     {
@@ -351,8 +304,8 @@ __global__ __launch_bounds__(kFpThreads, 3) void farrow_pipe_kernel(FarrowArgs a
                                     for (int c = 0; c < NC; ++c) {
                                         R xs;
                                         if constexpr (PAIR) xs = static_cast<R>(__builtin_bit_cast(float, TT == 0 ? q.s[cc].x : q.s[cc].y));
-                                        else xs = fsample_part<TX, R, NC>(q.s[cc], c);
-                                        acc[cc][c] = fmacd<FUSED, R>(treg[I], xs, acc[cc][c]);
+                                        else xs = sample_part<TX, R, NC>(q.s[cc], c);
+                                        acc[cc][c] = mac<FUSED>(treg[I], xs, acc[cc][c]);
                                     }
                                 }
                             }
@@ -436,18 +389,14 @@ template <typename TX, typename R, int NC>
 hipError_t launch_fpipe_t(bool fused, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s, int num_cus)
 {
     auto go = [&](auto kfn) -> hipError_t {
-        int per_cu = 0;
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kFpThreads, lds, &per_cu);
-        if (eo != hipSuccess) return eo;
-        if (per_cu < 1) per_cu = 1;
-        long long g = static_cast<long long>(num_cus) * per_cu;
-        if (g > ta.total_tiles) g = ta.total_tiles;
-        if (g < 1) g = 1;
+        const PipeGrid pg = pipe_grid(reinterpret_cast<const void *>(kfn), kFpThreads, lds, num_cus, ta.total_tiles, 0);
+        if (pg.err != hipSuccess) return pg.err;
+        const long long g = pg.grid;
         if (MRHIP_ENV_INT("MRHIP_DEBUG", 0) == 1) {
             hipFuncAttributes fa;
             (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));
             std::fprintf(stderr, "[mrhip] farrow_pipe T=%d P=%d cpl=%d grid=%lld lds=%zu occ/CU=%d regs=%d max_span=%d tiles=%lld\n",
-                         a.T, a.polyorder, ta.cpl, g, lds, per_cu, fa.numRegs, ta.max_span, ta.total_tiles);
+                         a.T, a.polyorder, ta.cpl, g, lds, pg.per_cu, fa.numRegs, ta.max_span, ta.total_tiles);
         }
         ArbTileArgs tq = ta;                                       // hand-outs only where a workgroup has a few tiles to balance
         if (tq.counters && ta.total_tiles / g < MRHIP_ENV_INT("MRHIP_PIPE_DYN_MIN_F", 8)) tq.counters = nullptr;
@@ -487,30 +436,19 @@ bool plan_farrow_pipe(const TypeKey &tk, const FarrowArgs &a, long long span256,
     int cpl = a.nch >= 4 ? 4 : (a.nch >= 2 ? 2 : 1);
     while (cpl > 1 && max_span > static_cast<long long>(kFpElems / cpl) * kFpThreads) cpl /= 2;
     if (max_span > static_cast<long long>(kFpElems / cpl) * kFpThreads) return false;
-    // LDS-DMA staging: rows of whole 16-byte chunks, a copy rounded up to whole 1 KiB wave transfers, at most 16 of them;
-    // the lane offsets of the transfers are 32-bit: the channels of a group must lie within 2 GiB of each other
-    const long long row_chunks = (max_span * static_cast<long long>(sb) + 15) / 16;
-    const long long nslots = (row_chunks * cpl + 63) / 64;
-    const bool dma = MRHIP_ENV_INT("MRHIP_PIPE_DMA", 1) != 0 && nslots <= 16 &&
-                     static_cast<double>(cpl) * static_cast<double>(a.x_stride) * static_cast<double>(sb) < 2147483648.0;
-    int copyb_pad = copies == 2 ? static_cast<int>((128 + 256 - (static_cast<size_t>(max_span) * sb * cpl) % 256) % 256 / sb) : 0;
-    size_t buf_bytes = (static_cast<size_t>(max_span) * cpl * copies + copyb_pad) * sb;
-    if (dma) {
-        copyb_pad = copies == 2 ? static_cast<int>(128 / sb) : 0;            // (a copy is a multiple of 1 KiB)
-        buf_bytes = static_cast<size_t>(nslots) * 1024 * copies + copyb_pad * sb;
-    }
+    const PipeStagePlan sp = pipe_stage_plan(sb, cpl, max_span, a.x_stride, copies);
     // (+ pad: the pipeline reads whole register sets, up to 33 samples from a window's start)
-    const size_t coef_off = (2 * buf_bytes + 320 + 15) / 16 * 16;
+    const size_t coef_off = (2 * sp.buf_bytes + 320 + 15) / 16 * 16;
     const size_t total = coef_off + static_cast<size_t>(a.T) * (a.polyorder + 1) * 8;
     if (total > 150 * 1024) return false;
     ArbTileArgs ta{};
     ta.pipe = 1;
     ta.cpl = cpl;
     ta.max_span = static_cast<int>(max_span);
-    ta.copyb_pad = copyb_pad;
-    ta.prefetch = dma ? 1 : 0;
-    ta.row_pitch = static_cast<int>(row_chunks * 16 / static_cast<long long>(sb));
-    ta.dma_slots = static_cast<int>(nslots);
+    ta.copyb_pad = sp.copyb_pad;
+    ta.prefetch = sp.prefetch;
+    ta.row_pitch = sp.row_pitch;
+    ta.dma_slots = sp.dma_slots;
     ta.x_offset_bytes = static_cast<int>(coef_off);   // (here: where the polynomial coefficients live)
     ta.tile_out = kFpThreads;
     ta.tiles_per_channel = (a.n_out + kFpThreads - 1) / kFpThreads;

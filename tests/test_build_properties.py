@@ -1,6 +1,6 @@
 """Properties of the built device code that the hand-scheduled kernels rely on (CPU only: reads the objects the build made).
 
-The pipe kernels (kernels_arb_pipe.hip, kernels_farrow_pipe.hip) issue their LDS reads from inline assembly and wait for them
+The pipe kernels (kernels_arb_pipe.hip, kernels_farrow_pipe.hip; their shared staging: pipe_stage.h) issue their LDS reads from inline assembly and wait for them
 with counted s_waitcnt: between issue and wait the destination registers are NOT valid, which the compiler does not know.  A
 register spill inside that window would save a register before its data has landed (round 3 met the same hazard with an
 asynchronous s_load).  So no instantiation of these kernels may use scratch memory at all."""
