@@ -91,6 +91,60 @@ CallPlan plan_rational(int kind, int64_t L, int64_t M, int64_t phiIdx, int64_t i
     return p;
 }
 
+// Grid of a persistent kernel: as many workgroups as the chip holds, at most one per tile, at least one.  bpc > 0 (a launcher's
+// MRHIP_*_BPC knob): workgroups per CU -- it replaces the occupancy figure (bpc_replaces: opair, fir_stream, phase-stationary)
+// or only lowers it (the pipe and lane kernels).  *per_cu is updated to the figure the grid was sized with.
+long long persistent_grid_size(int *per_cu, int num_cus, long long total_tiles, int bpc, bool bpc_replaces)
+{
+    if (*per_cu < 1) *per_cu = 1;
+    if (bpc > 0 && (bpc_replaces || bpc < *per_cu)) *per_cu = bpc;
+    long long g = static_cast<long long>(num_cus) * *per_cu;
+    if (g > total_tiles) g = total_tiles;
+    return g < 1 ? 1 : g;
+}
+
+// rational_opair_kernel in six-wave workgroups: the fourth never fits next to three running ones (see kernels_rational_opair.hip),
+// so a launch of more tiles than three rounds of the chip is sized with three per CU.  The step in front of pair_grid() at the
+// one opair call site (MRHIP_OPAIR_BPC, where set, replaces the result).
+int opair_six_wave_cap(int per_cu, int num_cus, unsigned total_steps, int J, unsigned block_x)
+{
+    if (per_cu < 1) per_cu = 1;
+    const long long tiles = (static_cast<long long>(total_steps) + J - 1) / J;
+    return block_x == 6 * 64 && per_cu > 3 && tiles > 3LL * num_cus * per_cu ? 3 : per_cu;
+}
+
+// Launch of a pair kernel (rational_opair, fir_stream, fir_stream_rt) from the workgroups a CU holds: grid, scheduling groups
+// (workgroup b draws grabs of J steps from group b % ngroups), and whether the grabs are dealt without atomics (at most three
+// tiles a workgroup).  multi_n > 0: independent streams -- group = stream, its workgroups deal its tiles round-robin
+// (total_steps: the longest stream's).  ring: the resident consumer takes every workgroup the chip holds at once (workgroup 0:
+// the feeder), at most grid_cap where that is > 1; its steps_per_group is the ring's own (ring_api.inc) and reported as 0 here.
+PairGrid pair_grid(int per_cu, int num_cus, unsigned total_steps, int J, int max_groups, int multi_n, bool ring, int grid_cap)
+{
+    PairGrid p{};
+    const long long chip = static_cast<long long>(num_cus) * per_cu;
+    const long long tiles = (static_cast<long long>(total_steps) + J - 1) / J;
+    long long g = chip;
+    if (ring) {
+        if (grid_cap > 1 && g > grid_cap) g = grid_cap;
+    } else {
+        if (g > static_cast<long long>(total_steps)) g = total_steps;
+        if (g < 1) g = 1;
+    }
+    p.ngroups = static_cast<int>(g < max_groups ? g : max_groups);
+    p.steps_per_group = ring ? 0u : static_cast<unsigned>((total_steps + p.ngroups - 1) / p.ngroups);
+    p.static_grabs = tiles <= 3 * g;
+    if (multi_n > 0) {
+        long long w = chip / multi_n;
+        if (w > tiles) w = tiles;
+        if (w < 1) w = 1;
+        g = w * multi_n;
+        p.ngroups = multi_n;
+        p.static_grabs = 1;
+    }
+    p.grid = g;
+    return p;
+}
+
 // FIRArbitrary / FIRFarrow: the phase accumulator is a serial Float64 recurrence whose roundings the reference's
 // outputs depend on (src/Filters.jl:663-673), so it is evaluated here, in order, once per call; every channel shares
 // the result.  One step of update():  acc += delta; if acc > N: xIdx += ifloor((acc-1)/N); acc = mod(acc-1, N) + 1.

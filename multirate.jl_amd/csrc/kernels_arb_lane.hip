@@ -408,16 +408,11 @@ template <int T>
 hipError_t launch_lane_t(bool fused, const ArbArgs &a, const ArbLaneArgs &la, size_t lds, hipStream_t s, int num_cus)
 {
     auto go = [&](auto kfn) -> hipError_t {
-        int per_cu = 0;
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kLaneThreads, lds, &per_cu);
-        if (eo != hipSuccess) return eo;
-        if (per_cu < 1) per_cu = 1;
-        const int bpc = MRHIP_ENV_INT("MRHIP_LANE_BPC", 0);
-        if (bpc > 0 && bpc < per_cu) per_cu = bpc;
-        const long long items = (a.n_out + la.stretch - 1) / la.stretch * la.ngroups;
-        long long g = static_cast<long long>(num_cus) * per_cu;
-        if (g > items) g = items;                               // (workgroups beyond the stretches would only ask the counter and leave)
-        if (g < 1) g = 1;
+        const long long items = (a.n_out + la.stretch - 1) / la.stretch * la.ngroups;   // (workgroups beyond the stretches would only ask the counter and leave)
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kLaneThreads, lds, num_cus, items, MRHIP_ENV_INT("MRHIP_LANE_BPC", 0));
+        if (pg.err != hipSuccess) return pg.err;
+        const long long g = pg.grid;
+        const int per_cu = pg.per_cu;
         if (MRHIP_ENV_INT("MRHIP_DEBUG", 0) == 1) {
             hipFuncAttributes fa;
             (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));

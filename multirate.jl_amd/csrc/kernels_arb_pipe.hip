@@ -476,7 +476,7 @@ template <typename TX, typename R, int NC, bool DMA>
 hipError_t launch_pipe_t(bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s, int num_cus)
 {
     auto go = [&](auto kfn) -> hipError_t {
-        const PipeGrid pg = pipe_grid(reinterpret_cast<const void *>(kfn), kPipeThreads, lds, num_cus, ta.total_tiles,
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kPipeThreads, lds, num_cus, ta.total_tiles,
                                       MRHIP_ENV_INT("MRHIP_PIPE_BPC", 0));           // experiments: fewer workgroups per CU than fit
         if (pg.err != hipSuccess) return pg.err;
         const long long g = pg.grid;

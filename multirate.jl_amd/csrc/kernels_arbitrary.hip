@@ -273,23 +273,14 @@ __global__ __launch_bounds__(kArbThreads, 4) void arb_tiled_kernel(ArbArgs a, Ar
 template <typename TX, typename R, int NC>
 hipError_t launch_arb(bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s, int num_cus)
 {
+    const void *const key = reinterpret_cast<const void *>(arb_tiled_kernel<TX, R, NC, false, 1, false>);   // one report per (TX, R, NC)
     auto go = [&](auto kfn) -> hipError_t {
-        int per_cu = 0;
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kArbThreads, lds, &per_cu);
-        if (eo != hipSuccess) return eo;
-        if (per_cu < 1) per_cu = 1;
-        long long g = static_cast<long long>(num_cus) * per_cu;
-        if (g > ta.total_tiles) g = ta.total_tiles;
-        if (g < 1) g = 1;
-        static int dbg = -1;
-        if (dbg < 0) { const char *v = std::getenv("MRHIP_DEBUG"); dbg = (v && v[0] == '1') ? 1 : 0; }
-        if (dbg == 1) {
-            dbg = 0;
-            hipFuncAttributes fa;
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kArbThreads, lds, num_cus, ta.total_tiles);
+        if (pg.err != hipSuccess) return pg.err;
+        const long long g = pg.grid;
+        if (int regs; debug_first_launch(key, reinterpret_cast<const void *>(kfn), &regs))
             std::fprintf(stderr, "[mrhip] arb_tiled T=%d Nphi=%d grid=%lld lds=%zu occ/CU=%d regs=%d tile_out=%lld max_span=%d tiles=%lld\n",
-                         a.T, a.Nphi, g, lds, per_cu, fa.numRegs, ta.tile_out, ta.max_span, ta.total_tiles);
-        }
+                         a.T, a.Nphi, g, lds, pg.per_cu, regs, ta.tile_out, ta.max_span, ta.total_tiles);
         ArbTileArgs tq = ta;
         tq.run_tiles = tq.counters ? handout_run(ta.total_tiles / g, 64) : 0;
         if (tq.run_tiles == 0) tq.counters = nullptr;
@@ -496,13 +487,9 @@ template <typename TX, typename R, int NC>
 hipError_t launch_farrow_t(bool fused, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s, int num_cus)
 {
     auto go = [&](auto kfn) -> hipError_t {
-        int per_cu = 0;
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kArbThreads, lds, &per_cu);
-        if (eo != hipSuccess) return eo;
-        if (per_cu < 1) per_cu = 1;
-        long long g = static_cast<long long>(num_cus) * per_cu;
-        if (g > ta.total_tiles) g = ta.total_tiles;
-        if (g < 1) g = 1;
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kArbThreads, lds, num_cus, ta.total_tiles);
+        if (pg.err != hipSuccess) return pg.err;
+        const long long g = pg.grid;
         // (a tile is a stretch of outputs x all channel groups: few, long tiles that the workgroups finish evenly -- handing them
         //  out, one per request, measured 4.22 against 4.18 ms at config 4's shape in ComplexF64: off unless MRHIP_FARROW_TILED_DYNAMIC=1)
         ArbTileArgs tq = ta;

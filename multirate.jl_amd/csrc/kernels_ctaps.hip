@@ -274,14 +274,9 @@ hipError_t launch_poly_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, const A
     *kname = "poly_ctaps_tiled_kernel";
     return dispatch_ctaps(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
         auto go = [&](auto kfn) -> hipError_t {
-            int per_cu = 0;
-            hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kCtapsThreads, lds, &per_cu);
-            if (eo != hipSuccess) return eo;
-            if (per_cu < 1) per_cu = 1;
-            long long g = static_cast<long long>(num_cus) * per_cu;
-            if (g > ta.total_tiles) g = ta.total_tiles;
-            if (g < 1) g = 1;
-            launch_kernel(kfn, dim3(static_cast<unsigned>(g)), dim3(kCtapsThreads), lds, s, a, ta);
+            const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kCtapsThreads, lds, num_cus, ta.total_tiles);
+            if (pg.err != hipSuccess) return pg.err;
+            launch_kernel(kfn, dim3(static_cast<unsigned>(pg.grid)), dim3(kCtapsThreads), lds, s, a, ta);
             return hipGetLastError();
         };
         switch (ta.cpl) {

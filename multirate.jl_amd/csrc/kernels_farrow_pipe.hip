@@ -389,7 +389,7 @@ template <typename TX, typename R, int NC>
 hipError_t launch_fpipe_t(bool fused, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s, int num_cus)
 {
     auto go = [&](auto kfn) -> hipError_t {
-        const PipeGrid pg = pipe_grid(reinterpret_cast<const void *>(kfn), kFpThreads, lds, num_cus, ta.total_tiles, 0);
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kFpThreads, lds, num_cus, ta.total_tiles, 0);
         if (pg.err != hipSuccess) return pg.err;
         const long long g = pg.grid;
         if (MRHIP_ENV_INT("MRHIP_DEBUG", 0) == 1) {

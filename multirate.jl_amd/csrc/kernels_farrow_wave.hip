@@ -174,12 +174,10 @@ template <typename TX, typename R, int NC>
 hipError_t launch_fw_t(bool fused, const FarrowArgs &a, hipStream_t s, int num_cus)
 {
     auto go = [&](auto kfn) -> hipError_t {
-        long long g = (std::max<long long>(a.n_out, 1) + kFwThreads - 1) / kFwThreads;
-        int per_cu = 0;                                                  // exactly the workgroups the chip holds at once, grid-stride beyond:
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kFwThreads, 0, &per_cu);   // a second, part-filled round costs a fifth
-        if (eo != hipSuccess) return eo;
-        const long long cap = static_cast<long long>(num_cus) * std::max(per_cu, 1);
-        if (g > cap) g = cap;
+        // exactly the workgroups the chip holds at once, grid-stride beyond: a second, part-filled round costs a fifth
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kFwThreads, 0, num_cus, (std::max<long long>(a.n_out, 1) + kFwThreads - 1) / kFwThreads);
+        if (pg.err != hipSuccess) return pg.err;
+        const long long g = pg.grid;
         if (MRHIP_ENV_INT("MRHIP_DEBUG", 0) == 1) {
             hipFuncAttributes fa;
             (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));

@@ -46,16 +46,16 @@ hipError_t launch_fir_stream_rt(bool fused, dim3 block, size_t lds, hipStream_t 
 // (the caller goes on to poly_tiled_kernel).
 bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs *out, dim3 *block, size_t *lds)
 {
-    if (!stream_env_int("MRHIP_STREAM", 1)) return false;   // read per call: tests switch kernels at run time
+    if (!MRHIP_ENV_INT("MRHIP_STREAM", 1)) return false;   // read per call: tests switch kernels at run time
     if (a.L != 1 || (tk.x_f64 && !tk.r_f64)) return false;
-    if (tk.r_f64 && !stream_env_int("MRHIP_STREAM_F64", 1)) return false;
+    if (tk.r_f64 && !MRHIP_ENV_INT("MRHIP_STREAM_F64", 1)) return false;
     const int nc = tk.complex_x ? 2 : 1;
     const long long es = (tk.x_f64 ? 8 : 4) * nc;
     int pad_every = 0, min_taps = 0;   // (min_taps: one block of reads; shorter filters take the kernel's per-sample loop)
     const bool have_ct = a.M <= 64 && (es == 16 ? stream_geometry<16>(static_cast<int>(a.M), &pad_every, &min_taps)
                                        : es == 8 ? stream_geometry<8>(static_cast<int>(a.M), &pad_every, &min_taps) : stream_geometry<4>(static_cast<int>(a.M), &pad_every, &min_taps));
     // MRHIP_STREAM_RT: 0 = only the per-M instantiations, 1 = the run-time-M kernel where M is not instantiated, 2 = always
-    const int rt_mode = stream_env_int("MRHIP_STREAM_RT", 1);
+    const int rt_mode = MRHIP_ENV_INT("MRHIP_STREAM_RT", 1);
     const bool rt = rt_mode == 2 || (rt_mode == 1 && !have_ct);
     if (!rt && !have_ct) return false;
     int rt_rd = 16;
@@ -68,12 +68,12 @@ bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs
         // output per lane wins (up to 1.8x) except where M is a whole number of blocks AND the pair still fills its waves
         // (128 <= M * es <= 192: 1//32 and 1//48 Float32, 1//16 ComplexF32 / Float64).  Its lane stride M * es must keep the
         // reads 8-byte aligned (Float32 with an odd M: pairs).  MRHIP_STREAM_RT_SINGLE=0|1 forces either.
-        const int sm = stream_env_int("MRHIP_STREAM_RT_SINGLE", -1);
+        const int sm = MRHIP_ENV_INT("MRHIP_STREAM_RT_SINGLE", -1);
         const long long bs = es == 16 ? 8 : 16;             // the kernel's block of samples
         const bool pair_pref = a.M % bs == 0 && a.M * es >= 128 && a.M * es <= 192;
         single = (a.M * es) % 8 == 0 && (sm == 1 || (sm < 0 && !pair_pref));
         // ComplexF64 beyond 1//32: poly_tiled_kernel is ahead (1//36, 128 taps: 0.32 vs 0.68 ms)
-        if (es == 16 && a.M > 32 && stream_env_int("MRHIP_STREAM_RT_ONE_WG", 0) == 0) return false;
+        if (es == 16 && a.M > 32 && MRHIP_ENV_INT("MRHIP_STREAM_RT_ONE_WG", 0) == 0) return false;
         const long long S = (single ? 1 : 2) * a.M * es;
         rt_rd = S % 16 ? 8 : 16;
         const long long cd = rt_rd == 16 ? S / 16 : 0;
@@ -82,7 +82,7 @@ bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs
     const long long opw = single ? 64 : 128;                // outputs per compute wave and step
     if (a.T < 1 || a.T > 16384) return false;   // (a tile must hold T samples: checked below)
     // compute waves: 3 (+ loader = a 256-thread workgroup) unless overridden; a step is 2 outputs per lane
-    int ncw = stream_env_int("MRHIP_STREAM_WAVES", 3);
+    int ncw = MRHIP_ENV_INT("MRHIP_STREAM_WAVES", 3);
     if (ncw < 1) ncw = 1;
     if (ncw > 7) ncw = 7;
     while (ncw > 1 && opw * ncw * a.M * es > 24 * 1024) --ncw;   // a step of wide samples at a large decimation must leave room for two stages
@@ -97,7 +97,7 @@ bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs
         return pad_every > 0 ? (nchunks + pad_every - 1) / pad_every * (pad_every + 1) : nchunks;
     };
     const long long budget = (150LL * 1024 / wg_per_cu - 64) / ns;
-    long long J = stream_env_int("MRHIP_STREAM_J", 0);
+    long long J = MRHIP_ENV_INT("MRHIP_STREAM_J", 0);
     if (J <= 0) {
         J = 1;
         while (J < 64 && (lds_chunks(J + 1) + 63) / 64 * 1024 <= budget && (lds_chunks(J + 1) + 63) / 64 <= 60) ++J;
@@ -108,7 +108,7 @@ bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs
     if (nslots > 60 || nslots * 1024 * ns > 150 * 1024) return false;
     // Pairs with one workgroup (= one compute wave at these sizes) per CU: 8- and 16-byte samples are then faster on poly_tiled_kernel
     // (measured, profiles/r04/stream_rt_vs_per_m.txt: 1//38 ComplexF32 0.31 vs 0.25 ms); Float32 samples are not (1//80: 0.22 vs 0.46)
-    if (rt && !single && es >= 8 && nslots * 1024 * ns + 64 > 78 * 1024 && stream_env_int("MRHIP_STREAM_RT_ONE_WG", 0) == 0) return false;
+    if (rt && !single && es >= 8 && nslots * 1024 * ns + 64 > 78 * 1024 && MRHIP_ENV_INT("MRHIP_STREAM_RT_ONE_WG", 0) == 0) return false;
     const size_t stage_bytes = static_cast<size_t>(nslots) * 1024;
     PairArgs pa{};
     pa.c = ncw; pa.P = static_cast<int>(P); pa.cM = static_cast<int>(cM);
@@ -146,6 +146,31 @@ bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs
     *out = pa;
     *block = dim3(static_cast<unsigned>(64 * (ncw + 1)));
     return true;
+}
+
+// The launch of every fir_stream_kernel and fir_stream_rt_kernel instantiation (their units select kfn)
+hipError_t launch_stream_kernel(PairKernelFn kfn, const void *key, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, PairArgs pa, int num_cus)
+{
+    int per_cu = 0;
+    hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), block.x, lds, &per_cu);
+    if (eo != hipSuccess) return eo;
+    if (per_cu < 1) per_cu = 1;
+    if (const int bpc = MRHIP_ENV_INT("MRHIP_STREAM_BPC", 0); bpc > 0) per_cu = bpc;
+    const PairGrid pg = pair_grid(per_cu, num_cus, pa.total_steps, pa.J, kPairGroups, a.multi ? a.multi_n : 0);
+    pa.ngroups = pg.ngroups;
+    pa.steps_per_group = pg.steps_per_group;
+    pa.static_grabs = pg.static_grabs;
+    if (int regs; debug_first_launch(key, reinterpret_cast<const void *>(kfn), &regs)) {
+        const size_t in = static_cast<size_t>(pa.x_f64 ? 8 : 4) * pa.nc, arith = pa.r_f64 ? 8 : 4;
+        if (pa.rt)   // (the run-time-M kernel also reports its bytes per LDS read)
+            std::fprintf(stderr, "[mrhip] fir_stream_rt in=%zuB arith=%zuB T=%d M=%d nc=%d rd=%d grid=%lld block=%u lds=%zu occ/CU=%d regs=%d P=%d cM=%d J=%d ns=%d pad_every=%d\n",
+                         in, arith, a.T, a.M, pa.nc, pa.rt_rd == 8 ? 8 : 16, pg.grid, block.x, lds, per_cu, regs, pa.P, pa.cM, pa.J, pa.ns, pa.pad_every);
+        else
+            std::fprintf(stderr, "[mrhip] fir_stream in=%zuB arith=%zuB T=%d M=%d nc=%d grid=%lld block=%u lds=%zu occ/CU=%d regs=%d P=%d cM=%d J=%d ns=%d pad_every=%d\n",
+                         in, arith, a.T, a.M, pa.nc, pg.grid, block.x, lds, per_cu, regs, pa.P, pa.cM, pa.J, pa.ns, pa.pad_every);
+    }
+    launch_kernel(kfn, dim3(static_cast<unsigned>(pg.grid)), block, lds, s, a, pa);
+    return hipGetLastError();
 }
 
 hipError_t launch_fir_stream(bool fused, const PolyArgs &a, const PairArgs &pa_in, dim3 block, size_t lds, hipStream_t s,

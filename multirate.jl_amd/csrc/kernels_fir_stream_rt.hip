@@ -44,7 +44,6 @@ namespace {
 using namespace dev;
 
 constexpr int kRtMaxThreads = 512;
-constexpr int kRtGroups = 32;
 
 template <typename TXS, typename R, int NC, int RD, bool FUSED>
 __global__ __launch_bounds__(kRtMaxThreads + 64)
@@ -257,40 +256,8 @@ void fir_stream_rt_kernel(PolyArgs a, PairArgs pa)
 template <typename TXS, typename R, int NC, int RD>
 hipError_t launch_rt_t(bool fused, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, PairArgs pa, int num_cus)
 {
-    auto go = [&](auto kfn) -> hipError_t {
-        int per_cu = 0;
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), block.x, lds, &per_cu);
-        if (eo != hipSuccess) return eo;
-        if (per_cu < 1) per_cu = 1;
-        const int bpc = MRHIP_ENV_INT("MRHIP_STREAM_BPC", 0);
-        if (bpc > 0) per_cu = bpc;
-        long long g = static_cast<long long>(num_cus) * per_cu;
-        if (g > static_cast<long long>(pa.total_steps)) g = pa.total_steps;
-        if (g < 1) g = 1;
-        pa.ngroups = static_cast<int>(g < kRtGroups ? g : kRtGroups);
-        pa.steps_per_group = static_cast<unsigned>((pa.total_steps + pa.ngroups - 1) / pa.ngroups);
-        pa.static_grabs = (static_cast<long long>(pa.total_steps) + pa.J - 1) / pa.J <= 3 * g;
-        if (a.multi) {   // independent streams: group = stream, its workgroups deal its tiles round-robin (pa.total_steps: the longest stream's)
-            long long w = static_cast<long long>(num_cus) * per_cu / a.multi_n;
-            const long long tiles = (static_cast<long long>(pa.total_steps) + pa.J - 1) / pa.J;
-            if (w > tiles) w = tiles;
-            if (w < 1) w = 1;
-            g = w * a.multi_n;
-            pa.ngroups = a.multi_n;
-            pa.static_grabs = 1;
-        }
-        static int dbg = MRHIP_ENV_INT("MRHIP_DEBUG", 0);
-        if (dbg == 1) {
-            dbg = 0;
-            hipFuncAttributes fa;
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));
-            std::fprintf(stderr, "[mrhip] fir_stream_rt in=%zuB arith=%zuB T=%d M=%lld nc=%d rd=%d grid=%lld block=%u lds=%zu occ/CU=%d regs=%d P=%d cM=%d J=%d ns=%d pad_every=%d\n",
-                         sizeof(TXS) * NC, sizeof(R), a.T, static_cast<long long>(a.M), NC, RD, g, block.x, lds, per_cu, fa.numRegs, pa.P, pa.cM, pa.J, pa.ns, pa.pad_every);
-        }
-        launch_kernel(kfn, dim3(static_cast<unsigned>(g)), block, lds, s, a, pa);
-        return hipGetLastError();
-    };
-    return fused ? go(fir_stream_rt_kernel<TXS, R, NC, RD, true>) : go(fir_stream_rt_kernel<TXS, R, NC, RD, false>);
+    const PairKernelFn base = fir_stream_rt_kernel<TXS, R, NC, RD, false>;
+    return launch_stream_kernel(fused ? fir_stream_rt_kernel<TXS, R, NC, RD, true> : base, reinterpret_cast<const void *>(base), block, lds, s, a, pa, num_cus);
 }
 
 }  // namespace

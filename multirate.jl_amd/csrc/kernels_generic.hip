@@ -10,6 +10,9 @@
 // accumulator, and in STRICT mode every multiply and add is separately rounded in
 // R = promote_type(Th, Tx) -- the order the reference source states (src/support.jl:5-55).
 // This file is compiled with -ffp-contract=off; FUSED mode calls fma explicitly.
+#include <mutex>
+#include <set>
+
 #include "mrhip_internal.h"
 #include "pair_device.h"
 
@@ -231,6 +234,22 @@ inline dim3 grid_for(long long n_out, int nch)
 }
 
 }  // namespace
+
+// MRHIP_DEBUG=1 (mrhip_internal.h): true the first time `key` is seen; *regs = the VGPRs of kfn
+bool debug_first_launch(const void *key, const void *kfn, int *regs)
+{
+    if (MRHIP_ENV_INT("MRHIP_DEBUG", 0) != 1) return false;
+    static std::mutex mu;
+    static std::set<const void *> seen;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        if (!seen.insert(key).second) return false;
+    }
+    hipFuncAttributes fa{};
+    (void)hipFuncGetAttributes(&fa, kfn);
+    *regs = fa.numRegs;
+    return true;
+}
 
 hipError_t launch_poly_generic(const TypeKey &tk, bool fused, const PolyArgs &a, hipStream_t s, const char **kname)
 {

@@ -42,20 +42,6 @@ namespace {
 constexpr int kMaxThreads = 512;
 constexpr int kMaxDmaRounds = 4;   // LDS-DMA instructions per wave, per copy, per tile
 
-inline bool debug_once()
-{
-    static int state = -1;   // -1 unknown, 0 off, 1 armed
-    if (state < 0) { const char *v = std::getenv("MRHIP_DEBUG"); state = (v && v[0] == '1') ? 1 : 0; }
-    if (state == 1) { state = 0; return true; }
-    return false;
-}
-
-inline int env_int(const char *name, int dflt)
-{
-    const char *v = std::getenv(name);
-    return v && *v ? std::atoi(v) : dflt;
-}
-
 template <typename R, bool FUSED>
 __device__ __forceinline__ R mac(R t, R x, R acc)
 {
@@ -350,32 +336,26 @@ __global__ __launch_bounds__(kMaxThreads) void poly_phase_stationary_kernel(Poly
     }
 }
 
-template <typename TX, typename R, int NC, bool FUSED>
-hipError_t launch_T(int T, dim3 grid, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, const TileArgs &ta,
-                    int num_cus, int blocks_per_cu_override)
+// The launch of every instantiation (launch_T selects kfn): persistent grid = what is actually co-resident (registers, LDS and
+// waves all count), or MRHIP_PS_BPC workgroups per CU
+using PsKernelFn = void (*)(PolyArgs, TileArgs);
+hipError_t launch_ps_kernel(PsKernelFn kfn, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, const TileArgs &ta, int num_cus)
 {
-#define MRHIP_CASE(TT)                                                                              \
-    case TT: {                                                                                      \
-        auto kfn = poly_phase_stationary_kernel<TT, TX, R, NC, FUSED>;                              \
-        /* persistent grid = what is actually co-resident (registers, LDS and waves all count) */   \
-        int per_cu = 0;                                                                             \
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), block.x, lds, &per_cu); \
-        if (eo != hipSuccess) return eo;                                                            \
-        if (per_cu < 1) per_cu = 1;                                                                 \
-        if (blocks_per_cu_override > 0) per_cu = blocks_per_cu_override;                            \
-        long long g = static_cast<long long>(num_cus) * per_cu;                                     \
-        if (g > ta.total_tiles) g = ta.total_tiles;                                                 \
-        grid = dim3(static_cast<unsigned>(g < 1 ? 1 : g));                                          \
-        if (debug_once()) {                                                                         \
-            hipFuncAttributes fa;                                                                   \
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));                   \
-            std::fprintf(stderr, "[mrhip] phase_stationary T=%d grid=%u block=%u lds=%zu occ/CU=%d regs=%d c=%d P=%d J=%d " \
-                         "bypos=%d tile_len=%d dma_rounds=%d tiles=%lld\n", TT, grid.x, block.x, lds, per_cu, fa.numRegs, \
-                         ta.c, ta.P, ta.J, ta.by_position, ta.tile_len, ta.dma_rounds, ta.total_tiles); \
-        }                                                                                           \
-        launch_kernel(kfn, grid, block, lds, s, a, ta);                                        \
-        return hipGetLastError();                                                                   \
-    }
+    const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), block.x, lds, num_cus, ta.total_tiles, MRHIP_ENV_INT("MRHIP_PS_BPC", 0), true);
+    if (pg.err != hipSuccess) return pg.err;
+    const dim3 grid(static_cast<unsigned>(pg.grid));
+    if (int regs; debug_first_launch(reinterpret_cast<const void *>(kfn), reinterpret_cast<const void *>(kfn), &regs))
+        std::fprintf(stderr, "[mrhip] phase_stationary T=%d grid=%u block=%u lds=%zu occ/CU=%d regs=%d c=%d P=%d J=%d "
+                     "bypos=%d tile_len=%d dma_rounds=%d tiles=%lld\n", a.T, grid.x, block.x, lds, pg.per_cu, regs,
+                     ta.c, ta.P, ta.J, ta.by_position, ta.tile_len, ta.dma_rounds, ta.total_tiles);
+    launch_kernel(kfn, grid, block, lds, s, a, ta);
+    return hipGetLastError();
+}
+
+template <typename TX, typename R, int NC, bool FUSED>
+hipError_t launch_T(int T, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, const TileArgs &ta, int num_cus)
+{
+#define MRHIP_CASE(TT) case TT: return launch_ps_kernel(poly_phase_stationary_kernel<TT, TX, R, NC, FUSED>, block, lds, s, a, ta, num_cus);
     switch (T) {
 #ifdef MRHIP_PS_FAST_BUILD   /* developer builds: one tap count only (seconds instead of minutes) */
         MRHIP_CASE(24)
@@ -405,8 +385,7 @@ bool plan_phase_stationary(const TypeKey &tk, const PolyArgs &a, int num_cus, Ti
     const int sw = (tk.x_f64 ? 2 : 1) * (tk.complex_x ? 2 : 1);
     const int vps = 4 / sw;
     // tuning overrides for experiments (unset in production): MRHIP_PS_C / _J / _BYPOS / _BPC
-    static const int env_c = env_int("MRHIP_PS_C", 0), env_j = env_int("MRHIP_PS_J", 0),
-                     env_bypos = env_int("MRHIP_PS_BYPOS", -1);
+    const int env_c = MRHIP_ENV_INT("MRHIP_PS_C", 0), env_j = MRHIP_ENV_INT("MRHIP_PS_J", 0), env_bypos = MRHIP_ENV_INT("MRHIP_PS_BYPOS", -1);
     // lane map: by output (M <= L) or by input position (M > L, worthwhile while >= 70 % of lanes work)
     bool by_position = a.M > a.L && static_cast<double>(a.L) / a.M >= 0.70;
     if (env_bypos >= 0) by_position = env_bypos != 0 && a.M > a.L;
@@ -460,8 +439,7 @@ bool plan_phase_stationary(const TypeKey &tk, const PolyArgs &a, int num_cus, Ti
     TileArgs ta{};
     ta.c = c; ta.P = P; ta.J = static_cast<int>(J);
     ta.by_position = by_position ? 1 : 0;
-    static const int env_ablate = env_int("MRHIP_PS_ABLATE", 0);   // timing experiments: 1 = no staging, 2 = no stores
-    ta.ablate = env_ablate;
+    ta.ablate = MRHIP_ENV_INT("MRHIP_PS_ABLATE", 0);   // timing experiments: 1 = no staging, 2 = no stores
     ta.tile_len = static_cast<int>(tile_len);
     ta.dma_rounds = static_cast<int>(rounds);
     ta.copyB_offset_bytes = static_cast<int>(copyB_off);
@@ -483,10 +461,9 @@ hipError_t launch_poly_phase_stationary(const TypeKey &tk, bool fused, const Pol
                                         dim3 block, size_t lds, hipStream_t s, const char **kname, int num_cus)
 {
     *kname = "poly_phase_stationary_kernel";
-    static const int bpc = env_int("MRHIP_PS_BPC", 0);
-#define MRHIP_GO(TX, R, NC)                                                                          \
-    return fused ? launch_T<TX, R, NC, true>(a.T, grid, block, lds, s, a, ta, num_cus, bpc)          \
-                 : launch_T<TX, R, NC, false>(a.T, grid, block, lds, s, a, ta, num_cus, bpc)
+    (void)grid;                 // (sized at launch: launch_ps_kernel)
+#define MRHIP_GO(TX, R, NC) \
+    return fused ? launch_T<TX, R, NC, true>(a.T, block, lds, s, a, ta, num_cus) : launch_T<TX, R, NC, false>(a.T, block, lds, s, a, ta, num_cus)
     if (!tk.x_f64 && !tk.r_f64) { if (tk.complex_x) { MRHIP_GO(float, float, 2); } else { MRHIP_GO(float, float, 1); } }
     if (!tk.x_f64 && tk.r_f64) { if (tk.complex_x) { MRHIP_GO(float, double, 2); } else { MRHIP_GO(float, double, 1); } }
     if (tk.x_f64 && tk.r_f64) { if (tk.complex_x) { MRHIP_GO(double, double, 2); } else { MRHIP_GO(double, double, 1); } }

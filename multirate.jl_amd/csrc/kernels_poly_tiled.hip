@@ -143,23 +143,14 @@ __global__ __launch_bounds__(kTiledThreads) void poly_tiled_kernel(PolyArgs a, A
 template <typename TX, typename R, int NC>
 hipError_t launch_tiled(bool fused, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s, int num_cus)
 {
+    const void *const key = reinterpret_cast<const void *>(poly_tiled_kernel<TX, R, NC, false, 1>);   // one report per (TX, R, NC)
     auto go = [&](auto kfn) -> hipError_t {
-        int per_cu = 0;
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), kTiledThreads, lds, &per_cu);
-        if (eo != hipSuccess) return eo;
-        if (per_cu < 1) per_cu = 1;
-        long long g = static_cast<long long>(num_cus) * per_cu;
-        if (g > ta.total_tiles) g = ta.total_tiles;
-        if (g < 1) g = 1;
-        static int dbg = -1;
-        if (dbg < 0) { const char *v = std::getenv("MRHIP_DEBUG"); dbg = (v && v[0] == '1') ? 1 : 0; }
-        if (dbg == 1) {
-            dbg = 0;
-            hipFuncAttributes fa;
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kTiledThreads, lds, num_cus, ta.total_tiles);
+        if (pg.err != hipSuccess) return pg.err;
+        const long long g = pg.grid;
+        if (int regs; debug_first_launch(key, reinterpret_cast<const void *>(kfn), &regs))
             std::fprintf(stderr, "[mrhip] poly_tiled T=%d L=%d M=%d grid=%lld lds=%zu occ/CU=%d regs=%d cpl=%d tile_out=%lld max_span=%d tiles=%lld\n",
-                         a.T, a.L, a.M, g, lds, per_cu, fa.numRegs, ta.cpl, ta.tile_out, ta.max_span, ta.total_tiles);
-        }
+                         a.T, a.L, a.M, g, lds, pg.per_cu, regs, ta.cpl, ta.tile_out, ta.max_span, ta.total_tiles);
         launch_kernel(kfn, dim3(static_cast<unsigned>(g)), dim3(kTiledThreads), lds, s, a, ta);
         return hipGetLastError();
     };

@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "mrhip_internal.h"
 
@@ -61,7 +62,6 @@ hipError_t launch_opair_cmix_s1(bool x_f64, bool fused, int T, dim3 block, size_
 
 namespace {
 constexpr int kOMaxThreads = 512;
-#define opair_env_int(name, dflt) MRHIP_ENV_INT(name, dflt)   // cached per call site (mrhip_internal.h)
 }  // namespace
 
 // Covers FIRRational and FIRInterpolator with tapsPerPhi <= 48 (Float32 samples with M < 2L: 64; Float64 arithmetic: 32) and M/L < 6 (L >= 2, SMIN = floor(M/L);
@@ -70,7 +70,7 @@ constexpr int kOMaxThreads = 512;
 // (the caller tries the next kernel).
 bool plan_rational_opair(const TypeKey &tk, bool fused, const PolyArgs &a, int num_cus, PairArgs *out, dim3 *block, size_t *lds, int force_wgpc)
 {
-    if (!opair_env_int("MRHIP_OPAIR", 1)) return false;   // read per call: tests switch kernels at run time
+    if (!MRHIP_ENV_INT("MRHIP_OPAIR", 1)) return false;   // read per call: tests switch kernels at run time
     if (tk.x_f64 && !tk.r_f64) return false;
     const int nc = tk.complex_x ? 2 : 1;
     const long long es = (tk.x_f64 ? 8 : 4) * nc;        // bytes per input sample
@@ -83,7 +83,7 @@ bool plan_rational_opair(const TypeKey &tk, bool fused, const PolyArgs &a, int n
     if (smin > 5) return false;
     if (!opair_instantiated(fused, smin, a.T)) return false;   // (FUSED: M/L < 2 and tapsPerPhi a multiple of 4)
     if (smin >= 2 && (tk.r_f64 || a.T > 32)) return false;   // instantiated for Float32 arithmetic, tapsPerPhi <= 32
-    const int env_c = opair_env_int("MRHIP_OPAIR_C", 0), env_j = opair_env_int("MRHIP_OPAIR_J", 0), env_ns = opair_env_int("MRHIP_OPAIR_NS", 0);
+    const int env_c = MRHIP_ENV_INT("MRHIP_OPAIR_C", 0), env_j = MRHIP_ENV_INT("MRHIP_OPAIR_J", 0), env_ns = MRHIP_ENV_INT("MRHIP_OPAIR_NS", 0);
     // c: lanes = c*L/2 <= 512; c*L and c*M even (a lane owns two outputs; the run base keeps its parity from step to
     // step) => c even, L and M being coprime.  Among the sizes with 3..7 full-ish compute waves take the fullest.
     // Among the sizes with 3..7 compute waves take the fullest: 147//160 -> c = 6, 441 lanes = 98 % of 7 waves (measured
@@ -125,7 +125,7 @@ bool plan_rational_opair(const TypeKey &tk, bool fused, const PolyArgs &a, int n
     //  147//160 Float64 51.8 -> 54.3 %, the README's mixed case 40.0 -> 41.0 %; profiles/r05/experiments.md T)
     if (nwaves + 1 == 6 && tk.r_f64) wg_per_cu = 1;
     if (force_wgpc > 0) wg_per_cu = force_wgpc;   // (the ring's RING instantiation holds 128 VGPRs: two workgroups per CU, larger tiles)
-    if (const int env_w = opair_env_int("MRHIP_OPAIR_WGPC", 0); env_w > 0) wg_per_cu = env_w;   // experiments
+    if (const int env_w = MRHIP_ENV_INT("MRHIP_OPAIR_WGPC", 0); env_w > 0) wg_per_cu = env_w;   // experiments
     // TWO pipeline stages of tiles as large as the LDS allows (the DMA runs one tile ahead, far more than the HBM
     // latency; every tile costs ~1000 cycles of barrier skew, ring priming and drain).  Measured on 147//160 Float32,
     // c = 6: two stages of J = 6 steps 65.7 % / 56.1 % (one call / 1e6-sample launches) vs three stages of J = 4 63.5 / 52.3.
@@ -180,7 +180,7 @@ bool plan_rational_opair(const TypeKey &tk, bool fused, const PolyArgs &a, int n
     {   // the tap bank goes through the last stage's LDS when it fits (see the kernel); MRHIP_OPAIR_BANK=0: gather from global
         const long long pt = (a.T + 4) | 1;
         const bool fits = static_cast<size_t>(a.L * pt * (tk.r_f64 ? 8 : 4)) <= stage_bytes;
-        pa.bank_off = (fits && opair_env_int("MRHIP_OPAIR_BANK", 1)) ? static_cast<int>((ns - 1) * stage_bytes) : -1;
+        pa.bank_off = (fits && MRHIP_ENV_INT("MRHIP_OPAIR_BANK", 1)) ? static_cast<int>((ns - 1) * stage_bytes) : -1;
     }
     *out = pa;
     *block = dim3(static_cast<unsigned>(padded + 64));   // + the loader wave
@@ -197,7 +197,7 @@ bool plan_rational_opair(const TypeKey &tk, bool fused, const PolyArgs &a, int n
 // descriptor per block and call).  Same slots, same order, same roundings as every other shape of the kernel.
 bool plan_rational_opair_blocks(const TypeKey &tk, bool fused, const PolyArgs &a, int num_cus, PairArgs *out, dim3 *block, size_t *lds, int *nblocks_out)
 {
-    if (!opair_env_int("MRHIP_OPAIR", 1) || !opair_env_int("MRHIP_OPAIR_BLOCKS", 1)) return false;
+    if (!MRHIP_ENV_INT("MRHIP_OPAIR", 1) || !MRHIP_ENV_INT("MRHIP_OPAIR_BLOCKS", 1)) return false;
     if (tk.x_f64 && !tk.r_f64) return false;
     if (a.L <= 512 || a.L > 4096 || a.M < 1 || a.zero_start_below > 0 || a.dyn || a.multi) return false;
     const int smin = static_cast<int>(a.M / a.L);
@@ -211,7 +211,7 @@ bool plan_rational_opair_blocks(const TypeKey &tk, bool fused, const PolyArgs &a
     const int epc = static_cast<int>(16 / es) > 0 ? static_cast<int>(16 / es) : 1;     // samples per 16-byte chunk
     const long long Sout = 2LL * a.L, Sin = 2LL * a.M;
     // lanes per workgroup: up to seven compute waves (Float64 arithmetic with many taps: fewer registers, see plan_rational_opair)
-    int max_lanes = opair_env_int("MRHIP_OPAIR_BLK_LANES", 0);
+    int max_lanes = MRHIP_ENV_INT("MRHIP_OPAIR_BLK_LANES", 0);
     if (max_lanes < 64 || max_lanes > 448) max_lanes = tk.r_f64 ? 320 : 448;
     int nblocks = static_cast<int>((Sout / 2 + max_lanes - 1) / max_lanes);
     if (nblocks < 2) nblocks = 2;
@@ -234,7 +234,7 @@ bool plan_rational_opair_blocks(const TypeKey &tk, bool fused, const PolyArgs &a
     const int ns = wg_per_cu == 1 ? 3 : 2;
     const long long budget = ((wg_per_cu <= 3 ? 150 : 160) * 1024 / wg_per_cu - 64) / ns;
     long long J = budget / (lds_step * es);
-    if (const int env_j = opair_env_int("MRHIP_OPAIR_J", 0); env_j > 0) J = env_j;
+    if (const int env_j = MRHIP_ENV_INT("MRHIP_OPAIR_J", 0); env_j > 0) J = env_j;
     if (J > 64) J = 64;
     if (J < 1) return false;
     const long long max_slots = 60 / (ns > 2 ? ns - 2 : 1);
@@ -289,6 +289,57 @@ bool opair_ring_available(const TypeKey &tk, bool fused, const PolyArgs &a)
 #else
     return a.T == 24 || a.T == 32;
 #endif
+}
+
+#ifdef MRHIP_OPAIR_PROBE
+// developer build only (make PROBE=1): per-wave records of the launch are written to the file $MRHIP_PROBE_OUT
+static unsigned long long *opair_probe_buf(long long g)
+{
+    static unsigned long long *buf = nullptr;
+    static long long cap = 0;
+    if (!std::getenv("MRHIP_PROBE_OUT")) return nullptr;
+    if (g > cap) { if (buf) (void)hipFree(buf); (void)hipMalloc(&buf, static_cast<size_t>(g) * 8 * 4 * 8); cap = g; }
+    (void)hipMemset(buf, 0, static_cast<size_t>(g) * 8 * 4 * 8);
+    (void)hipDeviceSynchronize();
+    return buf;
+}
+static void opair_probe_dump(unsigned long long *buf, long long g, hipStream_t s)
+{
+    if (!buf) return;
+    (void)hipStreamSynchronize(s);
+    std::vector<unsigned long long> h(static_cast<size_t>(g) * 8 * 4);
+    (void)hipMemcpy(h.data(), buf, h.size() * 8, hipMemcpyDeviceToHost);
+    if (FILE *f = std::fopen(std::getenv("MRHIP_PROBE_OUT"), "wb")) { std::fwrite(h.data(), 8, h.size(), f); std::fclose(f); }
+}
+#define MRHIP_PROBE_PRE(g) pa.probe = opair_probe_buf(g);
+#define MRHIP_PROBE_POST(g) opair_probe_dump(pa.probe, g, s);
+#else
+#define MRHIP_PROBE_PRE(g)
+#define MRHIP_PROBE_POST(g)
+#endif
+
+// The launch of every rational_opair_kernel instantiation (opair_kernel.inc: launch_opair_T selects kfn; NULL: not built for this launch)
+hipError_t launch_opair_kernel(PairKernelFn kfn, const void *key, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, PairArgs pa, int num_cus)
+{
+    if (!kfn) return hipErrorNotSupported;
+    int per_cu = 0;
+    hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), block.x, lds, &per_cu);
+    if (eo != hipSuccess) return eo;
+    per_cu = opair_six_wave_cap(per_cu, num_cus, pa.total_steps, pa.J, block.x);
+    if (const int bpc = MRHIP_ENV_INT("MRHIP_OPAIR_BPC", 0); bpc > 0) per_cu = bpc;
+    const PairGrid pg = pair_grid(per_cu, num_cus, pa.total_steps, pa.J, kPairGroups, a.multi ? a.multi_n : 0, a.ring_dev != nullptr, pa.grid_cap);
+    pa.ngroups = pg.ngroups;
+    if (!a.ring_dev) pa.steps_per_group = pg.steps_per_group;   // (ring: steps per grab, set by ring_api.inc)
+    pa.static_grabs = pg.static_grabs;
+    const long long g = pg.grid;
+    if (int regs; debug_first_launch(key, reinterpret_cast<const void *>(kfn), &regs))
+        std::fprintf(stderr, "[mrhip] rational_opair T=%d smin=%d in=%zuB arith=%zuB grid=%lld block=%u lds=%zu occ/CU=%d regs=%d c=%d P=%d cM=%d J=%d ns=%d\n",
+                     a.T, static_cast<int>(a.M / a.L), static_cast<size_t>(pa.x_f64 ? 8 : 4) * pa.nc, static_cast<size_t>(pa.r_f64 ? 8 : 4), g, block.x, lds, per_cu,
+                     regs, pa.c, pa.P, pa.cM, pa.J, pa.ns);
+    MRHIP_PROBE_PRE(g)
+    launch_kernel(kfn, dim3(static_cast<unsigned>(g)), block, lds, s, a, pa);
+    MRHIP_PROBE_POST(g)
+    return hipGetLastError();
 }
 
 hipError_t launch_rational_opair(bool fused, const PolyArgs &a, const PairArgs &pa_in, dim3 block, size_t lds, hipStream_t s,

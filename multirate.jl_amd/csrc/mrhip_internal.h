@@ -56,6 +56,13 @@ struct CallPlan {
 };
 CallPlan plan_rational(int kind, int64_t L, int64_t M, int64_t phiIdx, int64_t inputDeficit, int64_t xLen);
 
+// Grid arithmetic of the launchers (host_logic.cpp has the rules; tests/test_launch_grid.py checks them against recorded cases)
+long long persistent_grid_size(int *per_cu, int num_cus, long long total_tiles, int bpc, bool bpc_replaces);
+int opair_six_wave_cap(int per_cu, int num_cus, unsigned total_steps, int J, unsigned block_x);
+struct PairGrid { long long grid; int ngroups; unsigned steps_per_group; int static_grabs; };
+PairGrid pair_grid(int per_cu, int num_cus, unsigned total_steps, int J, int max_groups, int multi_n, bool ring = false, int grid_cap = 0);
+constexpr int kPairGroups = 32;   // scheduling groups of a pair kernel's launch at most (kCounterBytes)
+
 // FIRArbitrary phase recurrence (src/Filters.jl:663-673, 715-734) run on the host.
 struct ArbState {
     double acc = 1.0;   // 𝜙Accumulator
@@ -553,6 +560,21 @@ inline bool env_dynamic()
 #define MRHIP_ENV_INT(name, dflt) ([]() -> int { static const int v_ = ::mrhip::env_int_read(name, dflt); \
                                                  return ::mrhip::env_dynamic() ? ::mrhip::env_int_read(name, dflt) : v_; }())
 
+// Persistent grid of a kernel from its occupancy (persistent_grid_size, host_logic.cpp)
+struct PersistentGrid { hipError_t err; long long grid; int per_cu; };
+inline PersistentGrid persistent_grid(const void *kfn, unsigned threads, size_t lds, int num_cus, long long total_tiles, int bpc = 0,
+                                      bool bpc_replaces = false)
+{
+    PersistentGrid g{hipSuccess, 1, 0};
+    g.err = occupancy_cached(kfn, threads, lds, &g.per_cu);
+    if (g.err == hipSuccess) g.grid = persistent_grid_size(&g.per_cu, num_cus, total_tiles, bpc, bpc_replaces);
+    return g;
+}
+
+// MRHIP_DEBUG=1: a launcher reports the geometry of each entry of its selection switch once, at that entry's first launch.
+// `key` names the entry (its base instantiation, whatever variant `kfn` is launched); true: the line is due, *regs = kfn's VGPRs.
+bool debug_first_launch(const void *key, const void *kfn, int *regs);   // kernels_generic.hip
+
 // dtype combination a kernel is instantiated for
 struct TypeKey {
     bool x_f64;      // Tx scalar is double
@@ -582,6 +604,12 @@ hipError_t launch_rational_opair(bool fused, const PolyArgs &a, const PairArgs &
 // the opt-in FUSED numerics for M/L < 2 and tapsPerPhi a multiple of 4 only (other FUSED shapes run on poly_phase_stationary_kernel /
 // poly_tiled_kernel): the FUSED half of the matrix was 18 MB of code objects.
 constexpr bool opair_instantiated(bool fused, int smin, int T) { return !fused || (smin <= 1 && T % 4 == 0); }
+// The launch path of every pair-kernel instantiation: the units' selection switches choose `kfn` and hand it over.  key: the entry
+// of the switch for the MRHIP_DEBUG line (debug_first_launch).  launch_opair_kernel: kernels_rational_opair.hip; launch_stream_kernel
+// (fir_stream_kernel and fir_stream_rt_kernel): kernels_fir_stream.hip.
+using PairKernelFn = void (*)(PolyArgs, PairArgs);
+hipError_t launch_opair_kernel(PairKernelFn kfn, const void *key, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, PairArgs pa, int num_cus);
+hipError_t launch_stream_kernel(PairKernelFn kfn, const void *key, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, PairArgs pa, int num_cus);
 bool plan_fir_stream(const TypeKey &tk, const PolyArgs &a, int num_cus, PairArgs *out, dim3 *block, size_t *lds);
 hipError_t launch_fir_stream(bool fused, const PolyArgs &a, const PairArgs &pa, dim3 block, size_t lds, hipStream_t s,
                              const char **kname, int num_cus, unsigned *counters);   // FIRStandard / FIRDecimator, streaming form; also performs shiftin!

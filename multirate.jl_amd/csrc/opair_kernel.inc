@@ -22,9 +22,6 @@ namespace mrhip {
 namespace {
 
 constexpr int kOMaxThreads = 512;
-constexpr int kOGroups = 32;
-
-#define opair_env_int(name, dflt) MRHIP_ENV_INT(name, dflt)   // cached per call site (mrhip_internal.h)
 
 using namespace dev;
 
@@ -438,93 +435,35 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
 #endif
 }
 
-#ifdef MRHIP_OPAIR_PROBE
-// developer build only (make PROBE=1): per-wave records of the launch are written to the file $MRHIP_PROBE_OUT
-inline unsigned long long *opair_probe_buf(long long g)
-{
-    static unsigned long long *buf = nullptr;
-    static long long cap = 0;
-    if (!std::getenv("MRHIP_PROBE_OUT")) return nullptr;
-    if (g > cap) { if (buf) (void)hipFree(buf); (void)hipMalloc(&buf, static_cast<size_t>(g) * 8 * 4 * 8); cap = g; }
-    (void)hipMemset(buf, 0, static_cast<size_t>(g) * 8 * 4 * 8);
-    (void)hipDeviceSynchronize();
-    return buf;
-}
-inline void opair_probe_dump(unsigned long long *buf, long long g, hipStream_t s)
-{
-    if (!buf) return;
-    (void)hipStreamSynchronize(s);
-    std::vector<unsigned long long> h(static_cast<size_t>(g) * 8 * 4);
-    (void)hipMemcpy(h.data(), buf, h.size() * 8, hipMemcpyDeviceToHost);
-    if (FILE *f = std::fopen(std::getenv("MRHIP_PROBE_OUT"), "wb")) { std::fwrite(h.data(), 8, h.size(), f); std::fclose(f); }
-}
-#define MRHIP_PROBE_PRE(g) pa.probe = opair_probe_buf(g);
-#define MRHIP_PROBE_POST(g) opair_probe_dump(pa.probe, g, s);
-#else
-#define MRHIP_PROBE_PRE(g)
-#define MRHIP_PROBE_POST(g)
-#endif
-
 // (opair_instantiated(fused, smin, T), mrhip_internal.h: which (numerics, M/L class, tapsPerPhi) combinations exist)
 template <typename TXS, typename R>
 constexpr bool opair_plain_instantiated(bool fused, int nc, int smin, int T)
 {
     return !fused && smin <= 1 && (T == 24 || T == 32) && (nc >= 1) && sizeof(TXS) >= 4 && sizeof(R) >= 4;   // (every sample / tap type)
 }
+// the instantiation of one entry for a launch's mode (0: arguments overridable at entry; NULL: the ring's consumer is not built for it)
+template <int T, bool FUSED, int NC, int SMIN, typename TXS, typename R>
+PairKernelFn opair_select(int mode)
+{
+    if constexpr (opair_plain_instantiated<TXS, R>(FUSED, NC, SMIN, T)) {
+        if (mode == 1) return rational_opair_kernel<T, FUSED, NC, SMIN, TXS, R, 1>;
+        if (mode == 2) return rational_opair_kernel<T, FUSED, NC, SMIN, TXS, R, 2>;
+        if (mode == 3) return rational_opair_kernel<T, FUSED, NC, SMIN, TXS, R, 3>;
+    } else if (mode == 2) return nullptr;
+    return rational_opair_kernel<T, FUSED, NC, SMIN, TXS, R>;
+}
 template <bool FUSED, int NC, int SMIN, typename TXS, typename R>
 hipError_t launch_opair_T(int T, dim3 block, size_t lds, hipStream_t s, const PolyArgs &a, PairArgs pa, int num_cus)
 {
-#define MRHIP_CASE(TT)                                                                              \
-    case TT: if constexpr (opair_instantiated(FUSED, SMIN, TT)) {                                   \
-        auto kfn = rational_opair_kernel<TT, FUSED, NC, SMIN, TXS, R>;                                       \
-        if constexpr (opair_plain_instantiated<TXS, R>(FUSED, NC, SMIN, TT)) {                      \
-            if (a.ring_dev) kfn = rational_opair_kernel<TT, FUSED, NC, SMIN, TXS, R, 2>;            \
-            /* PLAIN (the arguments stay in the kernarg segment): MODE 1 for big launches (seam tiles element by element: the DMA variant's \
-               loader code costs the headline 1.3 %), MODE 3 for small ones -- a 1e6-sample chunk of one channel -- whose seam tiles are a \
-               good part of the launch and go by LDS-DMA */                                                                                 \
-            else if (!a.dyn && !a.multi && opair_env_int("MRHIP_OPAIR_PLAIN", 1))                                                           \
-                kfn = a.n_out * a.nch >= (1LL << 22) ? rational_opair_kernel<TT, FUSED, NC, SMIN, TXS, R, 1> : rational_opair_kernel<TT, FUSED, NC, SMIN, TXS, R, 3>; \
-        } else if (a.ring_dev) return hipErrorNotSupported;                                         \
-        int per_cu = 0;                                                                             \
-        hipError_t eo = occupancy_cached(reinterpret_cast<const void *>(kfn), block.x, lds, &per_cu); \
-        if (eo != hipSuccess) return eo;                                                            \
-        if (per_cu < 1) per_cu = 1;                                                                 \
-        {   /* six-wave workgroups: the fourth never fits next to three running ones (see kernels_rational_pair.hip) */ \
-            const long long tiles = (static_cast<long long>(pa.total_steps) + pa.J - 1) / pa.J;     \
-            if (block.x == 6 * 64 && per_cu > 3 && tiles > 3LL * num_cus * per_cu) per_cu = 3;      \
-        }                                                                                           \
-        const int bpc = opair_env_int("MRHIP_OPAIR_BPC", 0);                                 \
-        if (bpc > 0) per_cu = bpc;                                                                  \
-        long long g = static_cast<long long>(num_cus) * per_cu;                                     \
-        if (g > static_cast<long long>(pa.total_steps)) g = pa.total_steps;                         \
-        if (g < 1) g = 1;                                                                           \
-        if (a.ring_dev) { g = static_cast<long long>(num_cus) * per_cu;   /* the ring's consumer: every workgroup the chip holds at once (workgroup 0: the feeder) */ \
-            if (pa.grid_cap > 1 && g > pa.grid_cap) g = pa.grid_cap; }                                  \
-        pa.ngroups = static_cast<int>(g < kOGroups ? g : kOGroups);                                 \
-        if (!a.ring_dev) pa.steps_per_group = static_cast<unsigned>((pa.total_steps + pa.ngroups - 1) / pa.ngroups);   /* (ring: steps per grab, set by ring_api.inc) */ \
-        pa.static_grabs = (static_cast<long long>(pa.total_steps) + pa.J - 1) / pa.J <= 3 * g;      \
-        if (a.multi) {   /* independent streams: group = stream, its workgroups deal its tiles round-robin (pa.total_steps: the longest) */ \
-            long long w = static_cast<long long>(num_cus) * per_cu / a.multi_n;                     \
-            const long long tiles = (static_cast<long long>(pa.total_steps) + pa.J - 1) / pa.J;     \
-            if (w > tiles) w = tiles;                                                               \
-            if (w < 1) w = 1;                                                                       \
-            g = w * a.multi_n;                                                                      \
-            pa.ngroups = a.multi_n;                                                                 \
-            pa.static_grabs = 1;                                                                    \
-        }                                                                                           \
-        static int dbg = opair_env_int("MRHIP_DEBUG", 0);                                           \
-        if (dbg == 1) {                                                                             \
-            dbg = 0;                                                                                \
-            hipFuncAttributes fa;                                                                   \
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kfn));                   \
-            std::fprintf(stderr, "[mrhip] rational_opair T=%d smin=%d in=%zuB arith=%zuB grid=%lld block=%u lds=%zu occ/CU=%d regs=%d c=%d P=%d cM=%d J=%d ns=%d\n", \
-                         TT, SMIN, sizeof(TXS) * NC, sizeof(R), g, block.x, lds, per_cu, fa.numRegs, pa.c, pa.P, pa.cM, pa.J, pa.ns); \
-        }                                                                                           \
-        MRHIP_PROBE_PRE(g)                                                                          \
-        launch_kernel(kfn, dim3(static_cast<unsigned>(g)), block, lds, s, a, pa);                   \
-        MRHIP_PROBE_POST(g)                                                                         \
-        return hipGetLastError();                                                                   \
-    } else break;
+    // each entry only selects the instantiation; sizing, debug line and launch: launch_opair_kernel (kernels_rational_opair.hip).
+    // PLAIN (the arguments stay in the kernarg segment): MODE 1 for big launches (seam tiles element by element: the DMA variant's
+    // loader code costs the headline 1.3 %), MODE 3 for small ones -- a 1e6-sample chunk of one channel -- whose seam tiles are a
+    // good part of the launch and go by LDS-DMA; MODE 2: the ring's consumer
+    const bool plain = !a.ring_dev && !a.dyn && !a.multi && MRHIP_ENV_INT("MRHIP_OPAIR_PLAIN", 1);
+    const int mode = a.ring_dev ? 2 : !plain ? 0 : a.n_out * a.nch >= (1LL << 22) ? 1 : 3;
+#define MRHIP_CASE(TT) \
+    case TT: if constexpr (opair_instantiated(FUSED, SMIN, TT)) return launch_opair_kernel(opair_select<TT, FUSED, NC, SMIN, TXS, R>(mode), \
+        reinterpret_cast<const void *>(rational_opair_kernel<TT, FUSED, NC, SMIN, TXS, R>), block, lds, s, a, pa, num_cus); else break;
 #ifdef MRHIP_OPAIR_LONG      // the units that hold 49..64 taps per phase (Float32 samples)
     switch (T) {
 #ifdef MRHIP_PS_FAST_BUILD

@@ -1,7 +1,7 @@
 // pipe_stage.h -- what the arbitrary-rate kernels share: the multiply-add of all of them (kernels_arbitrary.hip,
 // kernels_arb_pipe.hip, kernels_farrow_pipe.hip), the hand-out of tiles of arb_tiled_kernel and farrow_tiled_kernel, and for the
 // two hand-scheduled pipe kernels the scalar-base pointers, the synchronous take-over of the schedule's first index and the
-// planning of their sample buffers and grids on the host.  (The pipe kernels' staging lambdas and their own hand-out code are
+// planning of their sample buffers on the host (their grids: persistent_grid, mrhip_internal.h).  (The pipe kernels' staging lambdas and their own hand-out code are
 // still written out in each of them.)
 #pragma once
 
@@ -138,21 +138,6 @@ inline PipeStagePlan pipe_stage_plan(size_t sb, int cpl, long long max_span, lon
         p.buf_bytes = (static_cast<size_t>(max_span) * cpl * copies + p.copyb_pad) * sb;
     }
     return p;
-}
-
-// Persistent grid of a pipe kernel: as many workgroups as the chip holds (at most `bpc` per CU where bpc > 0), at most one per tile
-struct PipeGrid { hipError_t err; long long grid; int per_cu; };
-inline PipeGrid pipe_grid(const void *kfn, unsigned threads, size_t lds, int num_cus, long long total_tiles, int bpc)
-{
-    PipeGrid g{hipSuccess, 1, 0};
-    g.err = occupancy_cached(kfn, threads, lds, &g.per_cu);
-    if (g.err != hipSuccess) return g;
-    if (g.per_cu < 1) g.per_cu = 1;
-    if (bpc > 0 && bpc < g.per_cu) g.per_cu = bpc;
-    g.grid = static_cast<long long>(num_cus) * g.per_cu;
-    if (g.grid > total_tiles) g.grid = total_tiles;
-    if (g.grid < 1) g.grid = 1;
-    return g;
 }
 
 }  // namespace mrhip

@@ -147,7 +147,7 @@ def plan(L, M, T, th, tx, n_out, nch, num_cus=NUM_CUS):
     if slots(J) > max_slots or ns * slots(J) * 1024 > 156 * 1024:
         return None
     # the workgroups a CU can hold at once, whatever the kernel's registers allow: by the LDS of the stages as planned (160 KiB per
-    # CU) and by its 32 wave slots -- an upper bound of the occupancy launch_opair_T sizes the grid with (a tile that stops at the
+    # CU) and by its 32 wave slots -- an upper bound of the occupancy launch_opair_kernel sizes the grid with (a tile that stops at the
     # 60-slot or the J <= 64 cap leaves LDS for more workgroups than the wgpc the stages were budgeted for)
     lds = ns * slots(J) * 1024 + 8 * ns
     wg_bound = max(1, min(160 * 1024 // lds, 32 // (nwaves + 1)))
@@ -157,7 +157,7 @@ def plan(L, M, T, th, tx, n_out, nch, num_cus=NUM_CUS):
 
 def many_outputs(L, M, T, th, tx):
     """outputs per channel of the many-tiles shape's large chunk: the fewest (in steps of 10 %) at which the call's tiles outnumber
-    three times the workgroups the chip can hold (plan(): wg_bound per CU) -- launch_opair_T then hands tiles out by dynamic grabs"""
+    three times the workgroups the chip can hold (plan(): wg_bound per CU) -- pair_grid then hands tiles out by dynamic grabs"""
     n_out = 25_000
     while True:
         pl = plan(L, M, T, th, tx, n_out, MANY_CHANNELS)

@@ -13,7 +13,7 @@ Per instantiation one ratio of opair_cases.RATIOS[SMIN], rotated by T + index(ty
 * many tiles: 64 channels built from 4 distinct rows, chunks [p, 1, 13, rest] with p prime; runs of -0.0 longer than a lane's run of
   samples (one of them across the short chunks' boundaries), +Inf / -Inf in row 0, a 3-sample NaN run in row 3; the signal is
   uploaded afresh for every case, so the first call reads cold lines.  `rest` gives opair_cases.many_outputs() outputs per
-  channel, sized per instantiation: workgroups take tiles by dynamic grabs only when tiles > 3 x grid (launch_opair_T:
+  channel, sized per instantiation: workgroups take tiles by dynamic grabs only when tiles > 3 x grid (pair_grid:
   static_grabs false), the grid is as many workgroups as the 256 CUs hold at once -- the 1 to 4 per CU the plan sizes its LDS stages
   for, up to 6 where a tile stops short of its stage (opair_cases.plan: wg_bound, an upper bound by LDS and wave slots) -- and a
   tile is as many steps as fit a stage (the plan shortens tiles only until a call has 1 024 of them, which is below 3 x grid
@@ -271,7 +271,7 @@ _LINE = re.compile(r"\[mrhip\] rational_opair T=(\d+) smin=(\d+) .* grid=(\d+) b
 
 
 def test_many_tiles_shape_takes_dynamic_grabs():
-    """item 4, the sweep's own premise: in the many-tiles shape workgroups take several tiles each, by dynamic grabs (launch_opair_T:
+    """item 4, the sweep's own premise: in the many-tiles shape workgroups take several tiles each, by dynamic grabs (pair_grid, host_logic.cpp:
     static_grabs is false when tiles > 3 x grid), and the short shape has at least two tiles per channel.  The geometry cannot be
     seen from Python, so a child process (a fresh interpreter with MRHIP_DEBUG=1: the library then prints one line per instantiation,
     at its first launch) issues, for every (type, SMIN) and one T per ratio of the table, the many-tiles shape's large chunk and
