@@ -19,13 +19,22 @@
 // instruction stream.  So the run starts at R = qA rounded down to even, window A starts offA = qA - R in {0, 1}
 // samples into it and window B offB = qB - R in {SMIN .. SMIN+2}.  Sample j of the run meets "slot" j of each
 // output; a lane's tap registers hold its column SHIFTED by its offset (slot j of A holds tap j - offA), and the
-// slots at the two ends that are inside the window for some lanes and outside for others (2 for A, 4 for B) are
-// made exact no-ops for the lanes that must skip them: the product is replaced by -0.0 (one v_cndmask with a
-// wave-level lane mask held in SGPRs), and x + (-0.0) == x bit for bit for every x (also -0.0, NaN, Inf), even as
-// the very first term ("first product initialises the accumulator": -0.0 + p == p).  Multiplying by a zero tap
-// instead would not be exact (0 * Inf = NaN, and the sign of an all-zero sum).  Every lane therefore performs
-// exactly the reference's operations in the reference's order (support.jl:5-31) => bit-identical to the generic
-// kernel; the price is 12 extra VALU instructions per 2 outputs (94 -> 106 for 24 taps).
+// slots at the two ends that are inside the window for some lanes and outside for others (2 for A, 4 for B) run with
+// EXEC narrowed to the lanes they belong to: the lane masks (offA == 0, dB <= 1, ...) are wave-level SGPR pairs, a
+// masked group is `s_and_saveexec_b64`, the slot's multiply and add, `s_mov_b64 exec` (pair_device.h: masked_mac and
+// its kin), and the scalar unit is idle in this loop.  A lane outside the mask never sees the slot, which is the
+// reference's operation sequence for it.  At the front the slot that is inside EVERY lane's window (slot 1 of A, slot 2
+// of B) initialises the accumulator on all lanes and the slots before it are added in front of it under their masks --
+// dB = 0: (p0 + p1) + p2, dB = 1: p1 + p2, dB = 2: p2 -- so "the first product initialises the accumulator" holds for
+// every lane.  Every lane therefore performs exactly the reference's operations in the reference's order
+// (support.jl:5-31) => bit-identical to the generic kernel, and the end slots cost their own multiply and add and
+// nothing else: 6 extra VALU instructions per 2 outputs (94 -> 100 for 24 taps; + 1 address add per step).
+// tapsPerPhi <= 2, where no slot is inside every lane's window, and the heads of FUSED (where masking removes no
+// instruction) keep the earlier form: the product, or the fma's result, is replaced for the lanes that skip the slot
+// by a `v_cndmask` on the same lane mask -- -0.0 as a product, since x + (-0.0) == x bit for bit for every x (also
+// -0.0, NaN, Inf), even as the very first term (-0.0 + p == p).  Multiplying by a zero tap instead would not be exact
+// (0 * Inf = NaN, and the sign of an all-zero sum).  Until the masks the selects were everywhere: 12 extra
+// instructions per 2 outputs (94 -> 106).
 //
 // Everything else is the pair kernel's machinery (pair_loader.h): a loader wave stages tiles HBM -> LDS by LDS-DMA
 // ahead of the compute waves, steps are handed out dynamically in XCD-local groups, window reads go through a

@@ -84,6 +84,8 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
     constexpr int W = T + SMIN + 2;             // samples of the run a lane may touch
     constexpr int NPR = (W + SPRD - 1) / SPRD;  // aligned reads per lane per step
     constexpr int NA = T + 1, NB = T + 2;       // slots of the two outputs (B's slot j' meets run sample SMIN + j')
+    constexpr bool TAILM = T >= 3;              // the slots past a window's end run under a lane mask in EXEC ...
+    constexpr bool HEADM = T >= 3 && !FUSED;    // ... and so do the slots in front of its start (otherwise: selects, slot_mac)
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>(smem));
@@ -120,15 +122,19 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
         R colA[T], colB[T];
 #pragma unroll
         for (int i = 0; i < T; ++i) { colA[i] = ca[i]; colB[i] = cb[i]; }
+        // from the last slot down, each pinned: slot j is the last reader of column element j, whose register is free from there on
+        // (in any other order the shifted columns live beside the loaded ones: eight VGPRs more than the step loop needs)
 #pragma unroll
-        for (int j = 0; j < NA; ++j) {
+        for (int j = NA - 1; j >= 0; --j) {
             const R t0 = j < T ? colA[j] : R(0), t1 = j >= 1 ? colA[j - 1] : R(0);
             tapA[j] = act ? (offA == 0 ? t0 : t1) : R(0);
+            pin(tapA[j]);
         }
 #pragma unroll
-        for (int j = 0; j < NB; ++j) {
+        for (int j = NB - 1; j >= 0; --j) {
             const R t0 = j < T ? colB[j] : R(0), t1 = (j >= 1 && j - 1 < T) ? colB[j - 1] : R(0), t2 = j >= 2 ? colB[j - 2] : R(0);
             tapB[j] = act ? (dB == 0 ? t0 : dB == 1 ? t1 : t2) : R(0);
+            pin(tapB[j]);
         }
     };
     if constexpr (RING) {
@@ -167,26 +173,17 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
         for (int j = 0; j < NA; ++j) pin(tapA[j]);
 #pragma unroll
         for (int j = 0; j < NB; ++j) pin(tapB[j]);
-    } else {
-        const R *__restrict__ ca = static_cast<const R *>(a.taps) + static_cast<long long>(phA) * T;
-        const R *__restrict__ cb = static_cast<const R *>(a.taps) + static_cast<long long>(phB) * T;
-        R colA[T], colB[T];
-#pragma unroll
-        for (int i = 0; i < T; ++i) { colA[i] = ca[i]; colB[i] = cb[i]; }
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-            const R t0 = j < T ? colA[j] : R(0), t1 = j >= 1 ? colA[j - 1] : R(0);
-            tapA[j] = act ? (offA == 0 ? t0 : t1) : R(0);
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const R t0 = j < T ? colB[j] : R(0), t1 = (j >= 1 && j - 1 < T) ? colB[j - 1] : R(0), t2 = j >= 2 ? colB[j - 2] : R(0);
-            tapB[j] = act ? (dB == 0 ? t0 : dB == 1 ? t1 : t2) : R(0);
-        }
-    }
+    } else gather_taps();
     // which lanes have the end slots inside their window (lane masks; wave-uniform SGPR pairs in the loop)
     bool useA0 = offA == 0, useAT = offA == 1;
     bool useB0 = dB == 0, useB1 = dB <= 1, useBT = dB >= 1, useBT1 = dB == 2;
+    // T >= 3: the end slots run under these masks as EXEC (pair_device.h: masked_mac and its kin) -- the lanes a slot is outside of never
+    // see it, which is the reference's operation sequence for them; slot 1 of A and slot 2 of B, inside every lane's window, initialise
+    // the accumulators, and the slots in front of them are added in front: dB = 0: (p0 + p1) + p2, dB = 1: p1 + p2, dB = 2: p2.
+    // FUSED keeps the select form for the heads (masking removes no instruction there).  T <= 2: slots 1 / 2 are not inside every window.
+    auto lanes_of = [](bool b) { return static_cast<unsigned long long>(__builtin_amdgcn_ballot_w64(b)); };
+    unsigned long long mA0 = lanes_of(useA0), mAT = lanes_of(useAT);
+    unsigned long long mB0 = lanes_of(useB0), mB1 = lanes_of(useB1), mBT = lanes_of(useBT), mBT1 = lanes_of(useBT1);
 
     const int n_out = static_cast<int>(a.n_out);
 #ifdef MRHIP_OPAIR_PROBE
@@ -254,6 +251,8 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
                 gather_taps();
                 useA0 = offA == 0; useAT = offA == 1;
                 useB0 = dB == 0; useB1 = dB <= 1; useBT = dB >= 1; useBT1 = dB == 2;
+                mA0 = lanes_of(useA0); mAT = lanes_of(useAT);
+                mB0 = lanes_of(useB0); mB1 = lanes_of(useB1); mBT = lanes_of(useBT); mBT1 = lanes_of(useBT1);
             }
         } else {
             const unsigned tg = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(tile_flag[2 * s])));
@@ -294,6 +293,7 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
                 const unsigned wcur = wbase + static_cast<unsigned>(j) * pa.lds_step * ES;
                 const unsigned wnext = wbase + static_cast<unsigned>(jn) * pa.lds_step * ES;
                 R accA[NC] = {}, accB[NC] = {};
+                R headA[NC], headB[NC], sumB[NC];                 // masked heads: slot 0's product, B's sum of slots 0 and 1
                 static_for<0, NPRV>([&](auto I) {
                     constexpr int r = decltype(I)::value;
                     constexpr int slot = r % KP;
@@ -323,21 +323,46 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
                             // lower bound matters for the first slots (j < max offset), the upper one for the last (j > T - 1)
                             constexpr bool a_lo = js < 1, a_hi = js > T - 1;             // A: offsets 0..1
                             constexpr bool b_lo = jb < 2, b_hi = jb > T - 1;             // B: offsets 0..2 (relative to SMIN)
+                            constexpr int h = decltype(H)::value;
+                            if constexpr (js < NA) {
+                                if constexpr (HEADM && js == 0) {
+                                    if constexpr (SPRD == 1) masked_mul(headA, tapA[0], wv[h], mA0);   // (else: with slot 1, whose sample came by the same read)
+                                } else if constexpr (HEADM && js == 1) {
 #pragma unroll
-                            for (int cc = 0; cc < NC; ++cc) {
-                                const R w = wv[decltype(H)::value][cc];
-                                if constexpr (js < NA) {
+                                    for (int cc = 0; cc < NC; ++cc) accA[cc] = tapA[1] * wv[h][cc];
+                                    if constexpr (SPRD == 1) masked_add(accA, headA, mA0);
+                                    else masked_mul_add(accA, tapA[0], wv[0], mA0);
+                                } else if constexpr (TAILM && a_hi) masked_mac<FUSED>(accA, tapA[js], wv[h], mAT);
+                                else {
                                     const bool used = (a_lo ? useA0 : true) && (a_hi ? useAT : true);
-                                    accA[cc] = slot_mac<FUSED, js == 0, a_lo || a_hi, R>(tapA[js], w, accA[cc], used);
+#pragma unroll
+                                    for (int cc = 0; cc < NC; ++cc) accA[cc] = slot_mac<FUSED, js == 0, a_lo || a_hi, R>(tapA[js], wv[h][cc], accA[cc], used);
                                 }
-                                if constexpr (jb >= 0 && jb < NB) {
+                            }
+                            if constexpr (jb >= 0 && jb < NB) {
+                                if constexpr (HEADM && jb == 0) masked_mul(headB, tapB[0], wv[h], mB0);
+                                else if constexpr (HEADM && jb == 1) masked_mul_then_add(sumB, headB, tapB[1], wv[h], mB1, mB0);
+                                else if constexpr (HEADM && jb == 2) {
+#pragma unroll
+                                    for (int cc = 0; cc < NC; ++cc) accB[cc] = tapB[2] * wv[h][cc];
+                                    masked_add(accB, sumB, mB1);
+                                } else if constexpr (TAILM && b_hi) masked_mac<FUSED>(accB, tapB[jb], wv[h], jb == T ? mBT : mBT1);
+                                else {
                                     const bool used = (b_lo ? (jb == 0 ? useB0 : useB1) : true) && (b_hi ? (jb == T ? useBT : useBT1) : true);
-                                    accB[cc] = slot_mac<FUSED, jb == 0, b_lo || b_hi, R>(tapB[jb], w, accB[cc], used);
+#pragma unroll
+                                    for (int cc = 0; cc < NC; ++cc) accB[cc] = slot_mac<FUSED, jb == 0, b_lo || b_hi, R>(tapB[jb], wv[h][cc], accB[cc], used);
                                 }
                             }
                         });
+                        // pair r is consumed before its slot is re-targeted: whatever holds its products so far is pinned here
+                        constexpr int js_l = SPRD * r + SPRD - 1, jb_l = js_l - SMIN;        // the unit's last sample as a slot of A, of B
 #pragma unroll
-                        for (int cc = 0; cc < NC; ++cc) { pin(accA[cc]); pin(accB[cc]); }   // pair r is consumed before its slot is re-targeted
+                        for (int cc = 0; cc < NC; ++cc) {
+                            if constexpr (HEADM && js_l == 0) pin(headA[cc]); else pin(accA[cc]);
+                            if constexpr (HEADM && jb_l == 0) pin(headB[cc]);
+                            else if constexpr (HEADM && jb_l == 1) pin(sumB[cc]);
+                            else if constexpr (!HEADM || jb_l >= 2) pin(accB[cc]);
+                        }
                     }
                     if constexpr (r + KP < NPR) pring[slot] = read_pair(std::integral_constant<int, r + KP>{}, wcur);
                     else if constexpr (r + KP >= NPRV) pring[slot] = read_pair(std::integral_constant<int, r + KP - NPRV>{}, wnext);

@@ -225,6 +225,112 @@ __device__ __forceinline__ float macf(float t, float x, float acc)
     else { const float p = t * x; return acc + p; }
 }
 
+// ---- EXEC-masked slots (opair_kernel.inc): a slot that is inside the window of some lanes only runs under their lane mask ----
+// One statement each: EXEC &= mask (an SGPR pair, e.g. a ballot), the group's VALU instructions, EXEC put back to what it was (never
+// assumed all ones).  Lanes outside the mask never see the group: their accumulators ("+v") keep their value bit for bit, and what
+// a pure output holds for them is unspecified (its readers run under a mask inside the writer's).  One group covers both components
+// of a complex sample.  An all-zero mask makes the group a no-op.
+#define MRHIP_MASKED_SLOT_OPS(R, SFX)                                                                                                     \
+    /* acc = acc + tap * w (FUSED: fma(tap, w, acc)) */                                                                                   \
+    template <bool FUSED>                                                                                                                 \
+    __device__ __forceinline__ void masked_mac(R (&acc)[1], R tap, const R (&w)[1], unsigned long long m)                                 \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        if constexpr (FUSED)                                                                                                              \
+            asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_fma_" SFX " %[a0], %[t], %[w0], %[a0]\n\ts_mov_b64 exec, %[sv]"                      \
+                : [a0] "+v"(acc[0]), [sv] "=&s"(sv) : [t] "v"(tap), [w0] "v"(w[0]), [m] "s"(m) : "scc");                                  \
+        else {                                                                                                                            \
+            R p0;                                                                                                                         \
+            asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_mul_" SFX " %[p0], %[t], %[w0]\n\tv_add_" SFX " %[a0], %[a0], %[p0]\n\t"             \
+                "s_mov_b64 exec, %[sv]"                                                                                                   \
+                : [a0] "+v"(acc[0]), [p0] "=&v"(p0), [sv] "=&s"(sv) : [t] "v"(tap), [w0] "v"(w[0]), [m] "s"(m) : "scc");                  \
+        }                                                                                                                                 \
+    }                                                                                                                                     \
+    template <bool FUSED>                                                                                                                 \
+    __device__ __forceinline__ void masked_mac(R (&acc)[2], R tap, const R (&w)[2], unsigned long long m)                                 \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        if constexpr (FUSED)                                                                                                              \
+            asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_fma_" SFX " %[a0], %[t], %[w0], %[a0]\n\tv_fma_" SFX " %[a1], %[t], %[w1], %[a1]\n\t" \
+                "s_mov_b64 exec, %[sv]"                                                                                                   \
+                : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [sv] "=&s"(sv) : [t] "v"(tap), [w0] "v"(w[0]), [w1] "v"(w[1]), [m] "s"(m) : "scc"); \
+        else {                                                                                                                            \
+            R p0, p1;                                                                                                                     \
+            asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_mul_" SFX " %[p0], %[t], %[w0]\n\tv_mul_" SFX " %[p1], %[t], %[w1]\n\t"              \
+                "v_add_" SFX " %[a0], %[a0], %[p0]\n\tv_add_" SFX " %[a1], %[a1], %[p1]\n\ts_mov_b64 exec, %[sv]"                         \
+                : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [p0] "=&v"(p0), [p1] "=&v"(p1), [sv] "=&s"(sv)                                    \
+                : [t] "v"(tap), [w0] "v"(w[0]), [w1] "v"(w[1]), [m] "s"(m) : "scc");                                                      \
+        }                                                                                                                                 \
+    }                                                                                                                                     \
+    /* s = tap * w; acc = s + acc: the slot in front of the one that initialised acc */                                                   \
+    __device__ __forceinline__ void masked_mul_add(R (&acc)[1], R tap, const R (&w)[1], unsigned long long m)                             \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        R p0;                                                                                                                             \
+        asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_mul_" SFX " %[p0], %[t], %[w0]\n\tv_add_" SFX " %[a0], %[p0], %[a0]\n\t"                 \
+            "s_mov_b64 exec, %[sv]"                                                                                                       \
+            : [a0] "+v"(acc[0]), [p0] "=&v"(p0), [sv] "=&s"(sv) : [t] "v"(tap), [w0] "v"(w[0]), [m] "s"(m) : "scc");                      \
+    }                                                                                                                                     \
+    __device__ __forceinline__ void masked_mul_add(R (&acc)[2], R tap, const R (&w)[2], unsigned long long m)                             \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        R p0, p1;                                                                                                                         \
+        asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_mul_" SFX " %[p0], %[t], %[w0]\n\tv_mul_" SFX " %[p1], %[t], %[w1]\n\t"                  \
+            "v_add_" SFX " %[a0], %[p0], %[a0]\n\tv_add_" SFX " %[a1], %[p1], %[a1]\n\ts_mov_b64 exec, %[sv]"                             \
+            : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [p0] "=&v"(p0), [p1] "=&v"(p1), [sv] "=&s"(sv)                                        \
+            : [t] "v"(tap), [w0] "v"(w[0]), [w1] "v"(w[1]), [m] "s"(m) : "scc");                                                          \
+    }                                                                                                                                     \
+    /* s = tap * w for the lanes of m (a product that a later masked group adds in front of its sum) */                                   \
+    __device__ __forceinline__ void masked_mul(R (&s)[1], R tap, const R (&w)[1], unsigned long long m)                                   \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_mul_" SFX " %[s0], %[t], %[w0]\n\ts_mov_b64 exec, %[sv]"                                 \
+            : [s0] "=&v"(s[0]), [sv] "=&s"(sv) : [t] "v"(tap), [w0] "v"(w[0]), [m] "s"(m) : "scc");                                       \
+    }                                                                                                                                     \
+    __device__ __forceinline__ void masked_mul(R (&s)[2], R tap, const R (&w)[2], unsigned long long m)                                   \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_mul_" SFX " %[s0], %[t], %[w0]\n\tv_mul_" SFX " %[s1], %[t], %[w1]\n\t"                  \
+            "s_mov_b64 exec, %[sv]"                                                                                                       \
+            : [s0] "=&v"(s[0]), [s1] "=&v"(s[1]), [sv] "=&s"(sv) : [t] "v"(tap), [w0] "v"(w[0]), [w1] "v"(w[1]), [m] "s"(m) : "scc");     \
+    }                                                                                                                                     \
+    /* acc = s + acc */                                                                                                                   \
+    __device__ __forceinline__ void masked_add(R (&acc)[1], const R (&s)[1], unsigned long long m)                                        \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_add_" SFX " %[a0], %[s0], %[a0]\n\ts_mov_b64 exec, %[sv]"                                \
+            : [a0] "+v"(acc[0]), [sv] "=&s"(sv) : [s0] "v"(s[0]), [m] "s"(m) : "scc");                                                    \
+    }                                                                                                                                     \
+    __device__ __forceinline__ void masked_add(R (&acc)[2], const R (&s)[2], unsigned long long m)                                        \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        asm("s_and_saveexec_b64 %[sv], %[m]\n\tv_add_" SFX " %[a0], %[s0], %[a0]\n\tv_add_" SFX " %[a1], %[s1], %[a1]\n\t"                \
+            "s_mov_b64 exec, %[sv]"                                                                                                       \
+            : [a0] "+v"(acc[0]), [a1] "+v"(acc[1]), [sv] "=&s"(sv) : [s0] "v"(s[0]), [s1] "v"(s[1]), [m] "s"(m) : "scc");                 \
+    }                                                                                                                                     \
+    /* under m1: r = tap * w; under m0 (a subset of m1): r = s + r */                                                                      \
+    __device__ __forceinline__ void masked_mul_then_add(R (&r)[1], const R (&s)[1], R tap, const R (&w)[1], unsigned long long m1,        \
+                                                        unsigned long long m0)                                                            \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        asm("s_and_saveexec_b64 %[sv], %[m1]\n\tv_mul_" SFX " %[r0], %[t], %[w0]\n\ts_and_b64 exec, exec, %[m0]\n\t"                      \
+            "v_add_" SFX " %[r0], %[s0], %[r0]\n\ts_mov_b64 exec, %[sv]"                                                                  \
+            : [r0] "=&v"(r[0]), [sv] "=&s"(sv) : [s0] "v"(s[0]), [t] "v"(tap), [w0] "v"(w[0]), [m1] "s"(m1), [m0] "s"(m0) : "scc");       \
+    }                                                                                                                                     \
+    __device__ __forceinline__ void masked_mul_then_add(R (&r)[2], const R (&s)[2], R tap, const R (&w)[2], unsigned long long m1,        \
+                                                        unsigned long long m0)                                                            \
+    {                                                                                                                                     \
+        unsigned long long sv;                                                                                                            \
+        asm("s_and_saveexec_b64 %[sv], %[m1]\n\tv_mul_" SFX " %[r0], %[t], %[w0]\n\tv_mul_" SFX " %[r1], %[t], %[w1]\n\t"                 \
+            "s_and_b64 exec, exec, %[m0]\n\tv_add_" SFX " %[r0], %[s0], %[r0]\n\tv_add_" SFX " %[r1], %[s1], %[r1]\n\t"                   \
+            "s_mov_b64 exec, %[sv]"                                                                                                       \
+            : [r0] "=&v"(r[0]), [r1] "=&v"(r[1]), [sv] "=&s"(sv)                                                                          \
+            : [s0] "v"(s[0]), [s1] "v"(s[1]), [t] "v"(tap), [w0] "v"(w[0]), [w1] "v"(w[1]), [m1] "s"(m1), [m0] "s"(m0) : "scc");          \
+    }
+MRHIP_MASKED_SLOT_OPS(float, "f32")
+MRHIP_MASKED_SLOT_OPS(double, "f64")
+#undef MRHIP_MASKED_SLOT_OPS
+
 // ---- compile-time bookkeeping of the ring pipeline (see run_steps in the kernel) ----
 // virtual group p of a step issues a read iff p + K names a pair of this step (< NPR) or of the next one (>= NPRV)
 constexpr int ring_nprv(int npr, int k) { return (npr + k - 1) / k * k; }
