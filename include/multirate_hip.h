@@ -45,10 +45,11 @@ typedef enum {
     MRHIP_ERR_BUFFER_TOO_SMALL = 2, /* reference: error("buffer is too small"), Filters.jl:460,503,550 */
     MRHIP_ERR_HIP = 3,              /* a HIP runtime call failed; message holds hipGetErrorString */
     MRHIP_ERR_NO_DEVICE = 4,        /* no gfx950 device visible: the engine has no CPU fallback */
-    MRHIP_ERR_UNSUPPORTED = 5       /* e.g. complex taps on FIRArbitrary / FIRFarrow, FUSED numerics with complex taps */
+    MRHIP_ERR_UNSUPPORTED = 5       /* e.g. complex taps on FIRFarrow (and on mrhip_create_arbitrary), FUSED numerics with complex taps */
 } mrhip_status;
 
-/* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational);
+/* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational) and
+ * FIRArbitrary (mrhip_create_arbitrary_ctaps);
  * Tx in {F32,F64,C64,C128}; Tb = promote_type(Th,Tx) -- complex as soon as either side is */
 typedef enum { MRHIP_F32 = 0, MRHIP_F64 = 1, MRHIP_C64 = 2, MRHIP_C128 = 3 } mrhip_dtype;
 
@@ -69,7 +70,7 @@ typedef enum {
  *   FUSED : same order, each step one fused multiply-add.  Faster where the kernel is
  *           VALU-bound; differs from STRICT by <= 1 rounding per tap. */
 typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numerics;
-/* Complex taps (Th in {C64,C128}; the rational family).  The reference is generic over the tap type: the unsafedot
+/* Complex taps (Th in {C64,C128}; the rational family, and FIRArbitrary through mrhip_create_arbitrary_ctaps).  The reference is generic over the tap type: the unsafedot
  * methods (src/support.jl:5-55) only multiply and add, so the contract is the one above with Julia's complex products
  * written out.  Let R be the promoted real scalar (Float64 if either side is 64-bit, else Float32); every multiply, add
  * and subtract is rounded separately in R, a narrower operand is widened exactly before use:
@@ -80,7 +81,18 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - acc = acc + p, component-wise.
  * The output is always complex (C128 if either side is 64-bit, else C64); the history stays in Tx (real for real
  * samples).  No FUSED form is defined: mrhip_set_numerics(f, FUSED) returns MRHIP_ERR_UNSUPPORTED on such a filter.
- * mrhip_create_arbitrary / mrhip_create_farrow with complex taps return MRHIP_ERR_UNSUPPORTED. */
+ * mrhip_create_arbitrary / mrhip_create_farrow with complex taps return MRHIP_ERR_UNSUPPORTED.
+ * FIRArbitrary with complex taps (mrhip_create_arbitrary_ctaps; FIRArbitrary(h, rate, Nphi), src/Filters.jl:105-117, update,
+ * tapsforphase! and filt!, :663-742, only take differences, multiply and add):
+ *   - dh = [diff(h), 0] is taken per component in the tap type; pfb and dpfb are taps2pfb of h and dh;
+ *   - yLower and yUpper are two complex dot products over ONE window, with pfb[:, phiIdx] and dpfb[:, phiIdx], each computed
+ *     exactly as stated above (FIRArbitrary has no start-from-zero seam: its seam method is the Matrix one, support.jl:16-31);
+ *   - buffer[k] = yLower + yUpper * alpha with alpha::Float64: both sides promote to Complex{Float64} and the store rounds to
+ *     Complex{R}; per component c: y_c = R(double(lo_c) + double(up_c) * alpha), the product and the sum each rounded once in
+ *     Float64 -- what the real-tap kernels do per real component;
+ *   - the phase schedule, outputlength, set_state / reset and the mod form do not depend on the tap type;
+ *   - no FUSED form either; the ring is not resident, mrhip_filt_device_multi issues single calls, mrhip_sharded_create refuses
+ *     complex taps, and a cascade takes such a filter as a stage like any FIRArbitrary (the per-stage calls). */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -169,6 +181,11 @@ int mrhip_create_rational(const void *h, int64_t hLen, int tap_dtype, int64_t nu
  * MRHIP_ERR_INVALID_ARG ("rate must be greater than 0", :184). */
 int mrhip_create_arbitrary(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
                            int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* the same constructor for COMPLEX taps (tap_dtype C64 | C128, interleaved (re, im) pairs; see "Complex taps" above): the
+ * filter's kind is MRHIP_FIR_ARBITRARY and its output is complex for every sample type.  A real tap_dtype is
+ * MRHIP_ERR_INVALID_ARG: real taps use mrhip_create_arbitrary (which keeps refusing complex ones). */
+int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
+                                 int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer, polyorder::Integer),
  * src/Filters.jl:192-198 (+ FIRFarrow(h, rate, Nphi, polyorder), :138-147, pfb2pnfb :311-321 and
  * polyfit, src/support.jl:85-88): every ROW of the tapsPerPhi x Nphi filter bank is replaced by its
@@ -190,8 +207,9 @@ int mrhip_get_pnfb(const mrhip_filter *f, double *host_out);
 int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_out);
 /* replaces tapsforphase(kernel::FIRArbitrary, phase), src/Filters.jl:677-690: (alpha, phiIdx) = modf(phase);
  * taps[i] = pfb[i, phiIdx] + alpha * dpfb[i, phiIdx], evaluated in Float64 (alpha is a Float64 there) and stored in
- * tap_dtype.  phase outside [0, Nphi+1] is MRHIP_ERR_INVALID_ARG (:678); so is a phase whose integer part is not a
- * column of the bank (0 or Nphi+1: a BoundsError in the reference). */
+ * tap_dtype (complex taps: tapsPerPhi complex taps, the statement per component).  phase outside [0, Nphi+1] is
+ * MRHIP_ERR_INVALID_ARG (:678); so is a phase whose integer part is not a column of the bank (0 or Nphi+1: a BoundsError in
+ * the reference). */
 int mrhip_arbitrary_tapsforphase(const mrhip_filter *f, double phase, void *host_out);
 void mrhip_destroy(mrhip_filter *f);
 

@@ -427,10 +427,12 @@ int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int6
     return MRHIP_OK;
 }
 
-int mrhip_create_arbitrary(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                           int device, mrhip_filter **out)
+// FIRArbitrary(h, rate, N𝜙), src/Filters.jl:105-117, behind both constructors: real taps (mrhip_create_arbitrary) and complex
+// ones (mrhip_create_arbitrary_ctaps).  The banks are held in the tap type on the host; upload_taps widens them exactly to R
+// (complex taps: as interleaved (re, im) scalars, the [Nphi][T] layout of pairs that kernels_ctaps_arb.hip reads).
+static int create_arbitrary_common(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
+                                   int device, mrhip_filter **out)
 {
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
     if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
     if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
 
@@ -444,19 +446,11 @@ int mrhip_create_arbitrary(const void *h, int64_t hLen, int th, double rate, int
     f->nch = nch; f->hLen = hLen; f->L = Nphi; f->M = 1; f->Nphi = Nphi; f->device = device;
     f->rate = rate;
     f->delta = static_cast<double>(Nphi) / rate;   // Δ = N𝜙/rate, Filters.jl:113
-    const size_t es = dtype_scalar_size(th);
+    const size_t es = dtype_size(th);
 
     // dh = [diff(h), 0] in the tap type (Filters.jl:106)
     std::vector<unsigned char> dh(static_cast<size_t>(hLen) * es, 0);
-    if (th == MRHIP_F32) {
-        const float *s = static_cast<const float *>(h);
-        float *d = reinterpret_cast<float *>(dh.data());
-        for (int64_t i = 0; i + 1 < hLen; ++i) d[i] = s[i + 1] - s[i];
-    } else {
-        const double *s = static_cast<const double *>(h);
-        double *d = reinterpret_cast<double *>(dh.data());
-        for (int64_t i = 0; i + 1 < hLen; ++i) d[i] = s[i + 1] - s[i];
-    }
+    arbitrary_dh(h, hLen, th, dh.data());
     f->T = taps2pfb(h, hLen, th, Nphi, nullptr);
     f->H = f->T - 1;
     f->h_taps.resize(static_cast<size_t>(f->T) * Nphi * es);
@@ -471,6 +465,23 @@ int mrhip_create_arbitrary(const void *h, int64_t hLen, int th, double rate, int
     sched_configure(f);
     *out = f;
     return MRHIP_OK;
+}
+
+int mrhip_create_arbitrary(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
+                           int device, mrhip_filter **out)
+{
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, out);
+}
+
+int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
+                                 int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_F32 || th == MRHIP_F64)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_arbitrary_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_arbitrary");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
+    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, out);
 }
 
 static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen, int th, double rate, int64_t Nphi,
@@ -1277,7 +1288,7 @@ static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_
         sf.hist_new = f->d_hist[in_place ? f->hist_cur : c.hist_next];
         sf.done = in_place ? f->d_counters + 128 : nullptr;
     }
-    const size_t yelt = dtype_scalar_size(f->ty) * static_cast<size_t>(f->nc);
+    const size_t yelt = y_elt(f);                  // (the OUTPUT element: complex taps give real samples a complex output)
     void *yk = static_cast<unsigned char *>(c.y) + static_cast<size_t>(k0) * yelt;
     // the tiled kernels' tiles are handed out from a counter of the filter (its launches are stream-ordered: one at a time);
     // MRHIP_PIPE_DYNAMIC=0: every workgroup takes every gridDim-th tile
@@ -1322,7 +1333,14 @@ static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_
         ArbTileArgs ta;
         size_t lds = 0;
         ArbLaneArgs la;
-        if (arb_lane_ok(r, cnt) && plan_arb_lane(tk, a, f->rate, &la, &lds)) {
+        if (tk.complex_h) {               // complex taps (kernels_ctaps_arb.hip): no plan_* below ever sees such a call
+            a.fold = sf;                  // (both kernels write the next call's history themselves)
+            if (!f->force_generic && plan_ctaps_arb_tiled(tk, a, f->rate, f->num_cus, &ta, &lds))
+                MRHIP_CHECK_HIP(launch_arb_ctaps_tiled(tk, a, ta, lds, stream, &f->last_kernel, f->num_cus));
+            else
+                MRHIP_CHECK_HIP(launch_arb_ctaps_generic(tk, a, stream, &f->last_kernel));
+        }
+        else if (arb_lane_ok(r, cnt) && plan_arb_lane(tk, a, f->rate, &la, &lds)) {
             // (64 channels or more, Float64, a rate >= 1: a lane per channel, the taps in scalar registers -- kernels_arb_lane.hip)
             la.counters = f->d_counters;
             a.fold = sf;
@@ -1365,7 +1383,7 @@ static int arb_call_device_sched(ArbRange &r, int64_t est, CallOut &out, ArbStat
     //  them in, both run much longer -- config 4 on a continuing stream read 3.9 or 4.5-5.1 ms per call.  Behind it, on the caller's
     //  stream: 3.93 + 0.2 ms, every call.  profiles/r06/experiments.md I; MRHIP_SCHED_BESIDE_LANE=1: as before)
     //  (the call launches est outputs: launch_range below)
-    const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && arb_lane_ok(r, est) &&
+    const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && !c.tk.complex_h && arb_lane_ok(r, est) &&
                             arb_lane_eligible(c.tk, static_cast<int>(f->T), static_cast<int>(f->H), f->nch, f->rate, c.x_len, c.x_stride, c.y_stride) &&
                             MRHIP_ENV_INT("MRHIP_SCHED_BESIDE_LANE", 0) == 0;
     const bool inline_sched = est <= MRHIP_ENV_INT("MRHIP_SCHED_INLINE_MAX", 65536) || lane_shape;

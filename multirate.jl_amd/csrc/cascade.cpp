@@ -216,9 +216,12 @@ int mrhip_arbitrary_tapsforphase(const mrhip_filter *f, double phase, void *host
     const double alpha = std::modf(phase, &ip);                                                 // :681
     const int64_t col = static_cast<int64_t>(ip);                                               // :682
     if (col < 1 || col > f->Nphi) return fail(MRHIP_ERR_INVALID_ARG, "phase selects column 0 or Nphi+1 of the filter bank (BoundsError in the reference)");
-    const size_t base = static_cast<size_t>(col - 1) * static_cast<size_t>(f->T);             // column-major T x Nphi
-    for (int64_t i = 0; i < f->T; ++i) {                                                        // :684-686, Float64 arithmetic, stored as T
-        if (f->th == MRHIP_F32) {
+    // complex taps: the same statement per component (Julia: Complex{T} + Float64 * Complex{T} promotes both components to
+    // Float64) -- the column is 2T interleaved scalars
+    const size_t nc = dtype_is_complex(f->th) ? 2 : 1;
+    const size_t base = static_cast<size_t>(col - 1) * static_cast<size_t>(f->T) * nc;        // column-major T x Nphi
+    for (int64_t i = 0; i < f->T * static_cast<int64_t>(nc); ++i) {                             // :684-686, Float64 arithmetic, stored as T
+        if (!dtype_is_f64(f->th)) {
             const double p = static_cast<double>(reinterpret_cast<const float *>(f->h_taps.data())[base + i]);
             const double d = static_cast<double>(reinterpret_cast<const float *>(f->h_dtaps.data())[base + i]);
             const double t = alpha * d;

@@ -36,6 +36,19 @@ int64_t taps2pfb(const void *h, int64_t hLen, int th, int64_t Nphi, void *out)
     return T;
 }
 
+// dh = [diff(h), 0] (src/Filters.jl:106), in the tap type: one subtraction per scalar, the components of a complex tap each on
+// their own (Julia's Complex - Complex).  `dh` receives hLen elements of `th`.
+void arbitrary_dh(const void *h, int64_t hLen, int th, void *dh)
+{
+    const int64_t nc = dtype_is_complex(th) ? 2 : 1;        // scalars per tap: h[i + 1] is nc scalars behind h[i]
+    const int64_t n = hLen * nc;
+    auto diff = [&](auto *d, const auto *s) {
+        for (int64_t j = 0; j < n; ++j) d[j] = j + nc < n ? s[j + nc] - s[j] : 0;
+    };
+    if (dtype_is_f64(th)) diff(static_cast<double *>(dh), static_cast<const double *>(h));
+    else diff(static_cast<float *>(dh), static_cast<const float *>(h));
+}
+
 // src/Filters.jl:433-439
 int64_t nextphase(int64_t phase, int64_t L, int64_t M)
 {

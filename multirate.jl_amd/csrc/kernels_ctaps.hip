@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "ctaps_device.h"
 #include "mrhip_internal.h"
 
 #pragma clang fp contract(off)
@@ -32,45 +33,7 @@ namespace {
 
 constexpr int kCtapsThreads = 256;
 
-template <typename R> struct alignas(2 * sizeof(R)) CPair { R re, im; };
-template <typename TX, int NCX> struct alignas(sizeof(TX) * NCX) CSample { TX c[NCX]; };
-
-// the ONE set of arithmetic statements both kernels execute
-template <typename TX, typename R, int NCX>
-__device__ __forceinline__ CPair<R> ctap_product(const CPair<R> h, const CSample<TX, NCX> v)
-{
-    CPair<R> p;
-    if constexpr (NCX == 1) {
-        const R x = static_cast<R>(v.c[0]);
-        p.re = h.re * x;
-        p.im = h.im * x;
-    } else {
-        const R xr = static_cast<R>(v.c[0]), xi = static_cast<R>(v.c[1]);
-        const R rr = h.re * xr;
-        const R ii = h.im * xi;
-        p.re = rr - ii;
-        const R ri = h.re * xi;
-        const R ir = h.im * xr;
-        p.im = ri + ir;
-    }
-    return p;
-}
-template <typename R>
-__device__ __forceinline__ CPair<R> ctap_zero_start(const CPair<R> p)      // support.jl:46
-{
-    CPair<R> a;
-    a.re = static_cast<R>(0) + p.re;
-    a.im = static_cast<R>(0) + p.im;
-    return a;
-}
-template <typename R>
-__device__ __forceinline__ CPair<R> ctap_add(const CPair<R> acc, const CPair<R> p)
-{
-    CPair<R> a;
-    a.re = acc.re + p.re;
-    a.im = acc.im + p.im;
-    return a;
-}
+// (CPair, CSample, ctap_product, ctap_zero_start, ctap_add, dispatch_ctaps: ctaps_device.h, shared with kernels_ctaps_arb.hip)
 
 // One thread per output, any (L, M, T, hLen): poly_generic_kernel with complex taps.  Serves host-planned calls (files the end
 // state in the record) and device-planned ones (a.dyn: mrhip_filt_device_async, calls under HIP-graph capture).
@@ -197,15 +160,6 @@ __global__ __launch_bounds__(kCtapsThreads) void poly_ctaps_tiled_kernel(PolyArg
             }
         }
     }
-}
-
-template <typename F>
-hipError_t dispatch_ctaps(const TypeKey &tk, F &&f)
-{
-    if (!tk.x_f64 && !tk.r_f64) return tk.complex_x ? f.template operator()<float, float, 2>() : f.template operator()<float, float, 1>();
-    if (!tk.x_f64 && tk.r_f64) return tk.complex_x ? f.template operator()<float, double, 2>() : f.template operator()<float, double, 1>();
-    if (tk.x_f64 && tk.r_f64) return tk.complex_x ? f.template operator()<double, double, 2>() : f.template operator()<double, double, 1>();
-    return hipErrorInvalidValue;
 }
 
 }  // namespace

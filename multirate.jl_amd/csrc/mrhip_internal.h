@@ -580,7 +580,7 @@ struct TypeKey {
     bool x_f64;      // Tx scalar is double
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
-    bool complex_h = false;   // complex taps (rational family): R-typed (re, im) pairs, complex output; kernels_ctaps.hip only
+    bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family) and kernels_ctaps_arb.hip (FIRArbitrary) only
 };
 
 // ---------------------------------------------------------------------------------------
@@ -640,6 +640,14 @@ hipError_t launch_poly_ctaps_generic(const TypeKey &tk, const PolyArgs &a, hipSt
 bool plan_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
 hipError_t launch_poly_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                    const char **kname, int num_cus);
+// complex taps, FIRArbitrary (kernels_ctaps_arb.hip): the universal kernel and the LDS-tiled one; both serve host- and device-planned
+// calls and take the ShiftFold epilogue
+hipError_t launch_arb_ctaps_generic(const TypeKey &tk, const ArbArgs &a, hipStream_t s, const char **kname);
+bool plan_ctaps_arb_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+hipError_t launch_arb_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
+                                  const char **kname, int num_cus);
+// dh = [diff(h), 0] in the tap type, per component for complex taps (src/Filters.jl:106); host_logic.cpp
+void arbitrary_dh(const void *h, int64_t hLen, int th, void *dh);
 bool plan_phase_stationary(const TypeKey &tk, const PolyArgs &a, int num_cus, TileArgs *out, dim3 *grid, dim3 *block,
                            size_t *lds);
 hipError_t launch_poly_phase_stationary(const TypeKey &tk, bool fused, const PolyArgs &a, const TileArgs &ta, dim3 grid,

@@ -77,6 +77,7 @@ ABI = [
     ("mrhip_firdes_kaiser", _i64, [_vp, _i, _d, _d, _i, _d, _vp]),
     ("mrhip_create_rational", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
@@ -299,11 +300,25 @@ class FIRFilter:
         FIRRational); the output is always complex (Complex128 if either side is 64-bit).  Real ``h`` is promoted to
         complex.  STRICT numerics only (include/multirate_hip.h: complex taps)."""
         if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "complex taps: the rational family only (FIRArbitrary / FIRFarrow take Float32/Float64 taps)")
+            raise MultirateHIPError(5, "complex_taps builds the rational family only (a float rate: FIRFilter.complex_taps_arbitrary; FIRFarrow takes Float32/Float64 taps)")
         h = np.ascontiguousarray(h)
         if h.dtype != np.complex64 and h.dtype != np.complex128:
             h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
         return cls(h, ratio, device=device, _complex_taps=True)
+
+    @classmethod
+    def complex_taps_arbitrary(cls, h, rate, Nphi: int = 32, *, device: int = 0):
+        """FIRFilter(h::Vector{Complex64 / Complex128}, rate::Float, N𝜙 = 32): FIRArbitrary with complex taps
+        (FIRArbitrary(h, rate, N𝜙), src/Filters.jl:105-117, is generic over the tap type: dh = [diff(h), 0], both filter banks
+        and tapsforphase are complex).  The output is always complex (Complex128 if either side is 64-bit); real ``h`` is
+        promoted to complex.  STRICT numerics only (include/multirate_hip.h: complex taps).  The device object is created by
+        ``mrhip_create_arbitrary_ctaps``."""
+        if not isinstance(rate, (float, np.floating)):
+            raise MultirateHIPError(1, "complex_taps_arbitrary takes a floating-point rate (a Rational ratio: FIRFilter.complex_taps)")
+        h = np.ascontiguousarray(h)
+        if h.dtype != np.complex64 and h.dtype != np.complex128:
+            h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
+        return cls(h, float(rate), int(Nphi), device=device, _complex_taps=True)
 
     # -- lifetime
     def _ensure(self, tx: np.dtype, nch: int):
@@ -322,6 +337,9 @@ class FIRFilter:
         elif self.kind == FARROW:
             rc = self._lib.mrhip_create_farrow(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate, self.Nphi,
                                                self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self.kind == ARBITRARY and self.h.dtype.kind == "c":
+            rc = self._lib.mrhip_create_arbitrary_ctaps(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate,
+                                                        self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
         elif self.kind == ARBITRARY:
             rc = self._lib.mrhip_create_arbitrary(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate,
                                                   self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))

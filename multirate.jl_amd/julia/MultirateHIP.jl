@@ -81,6 +81,13 @@ function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer = 32; devic
     f = FIRFilter{FIRArbitrary{Th}}(copy(h), nothing, Float64(rate), Nphi, -1, device, C_NULL, nothing, 0)
     finalizer(destroy!, f)
 end
+# the same constructor with complex taps (the reference is generic over Th; dh = [diff(h), 0] per component): bind! creates the
+# device object through mrhip_create_arbitrary_ctaps; the output is complex for every sample type
+function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{ComplexF32,ComplexF64}}
+    rate > 0.0 || error("rate must be greater than 0")
+    f = FIRFilter{FIRArbitrary{Th}}(copy(h), nothing, Float64(rate), Nphi, -1, device, C_NULL, nothing, 0)
+    finalizer(destroy!, f)
+end
 # FIRFilter(h, rate::AbstractFloat, Nphi, polyorder)      src/Filters.jl:192-198  (FIRFarrow)
 function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     rate > 0.0 || error("rate must be greater than 0")
@@ -105,6 +112,10 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
         check(ccall((:mrhip_create_farrow, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
                     f.h, length(f.h), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
+    elseif f.ratio === nothing && Th <: Complex
+        check(ccall((:mrhip_create_arbitrary_ctaps, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, length(f.h), dtypecode(Th), f.rate, f.Nphi, dtypecode(Tx), nch, f.device, out))
     elseif f.ratio === nothing
         check(ccall((:mrhip_create_arbitrary, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),

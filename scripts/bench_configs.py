@@ -41,7 +41,9 @@ def rand(shape, dtype):
 def run(name, h, ratio, nphi, nch, n, dtype, bytes_per_in, flops_per_in, reps=5, chunk=None, polyorder=None, per_call=False, note=None):
     """bytes_per_in / flops_per_in: algorithmic bytes and flops (2 per tap per real component) per input sample per channel"""
     x = rand((nch, n), dtype)
-    if np.iscomplexobj(h):                     # complex taps: the rational family, STRICT only (FIRFilter.complex_taps)
+    if np.iscomplexobj(h) and isinstance(ratio, float):   # complex taps, FIRArbitrary (FIRFilter.complex_taps_arbitrary), STRICT only
+        f = pkg.FIRFilter.complex_taps_arbitrary(h, ratio, nphi, device=dev.index or 0)
+    elif np.iscomplexobj(h):                   # complex taps: the rational family, STRICT only (FIRFilter.complex_taps)
         f = pkg.FIRFilter.complex_taps(h, ratio, device=dev.index or 0)
     else:
         f = pkg.FIRFilter(h, ratio, nphi, polyorder, device=dev.index or 0, numerics=pkg.NUMERICS_FUSED if FUSED else pkg.NUMERICS_STRICT)
@@ -318,6 +320,21 @@ def rows(which):
             else:
                 os.environ["MRHIP_FORCE_GENERIC"] = was
 
+    def _xcta():
+        # complex taps on FIRArbitrary (kernels_ctaps_arb.hip): config 4's filter (pi/3, N𝜙 = 32, 32 taps per phase) rotated to a band
+        # centre, on complex and on real samples, 64 ch x 1e6.  The kernel is the one the process's MRHIP_CTAPS_TILED selects (read once
+        # per process: run this row once with =1 for arb_ctaps_tiled_kernel and once with =0 for arb_ctaps_generic_kernel); the real-tap
+        # row of the same shape stands beside them for scale.  Flops per output: two dots of 32 taps, 8 per tap for Complex*Complex
+        # and 4 for Complex*Real, plus 4 for the combine.  MRHIP_BENCH_XCTA_SIZES="nch:n,..." measures other call sizes (the plan's threshold).
+        rot = (harb * np.exp(2j * np.pi * 0.05 * np.arange(len(harb)))).astype(np.complex64)
+        tag = f" (MRHIP_CTAPS_TILED={os.environ.get('MRHIP_CTAPS_TILED', 'unset')})"
+        sizes = [tuple(int(v) for v in s_.split(":")) for s_ in os.environ.get("MRHIP_BENCH_XCTA_SIZES", "64:1000000").split(",")]
+        rate = float(math.pi / 3)
+        for nch, n in sizes:
+            run(f"X complex taps: arbitrary pi/3 32x32 c64 taps x c64 {nch}ch x {n}{tag}", rot, rate, 32, nch, n, torch.complex64, 8 + 8 * rate, (2 * 8 * 32 + 4) * rate, reps=10)
+            run(f"X complex taps: arbitrary pi/3 32x32 c64 taps x f32 {nch}ch x {n}{tag}", rot, rate, 32, nch, n, torch.float32, 4 + 8 * rate, (2 * 4 * 32 + 4) * rate, reps=10)
+            run(f"X real taps for scale: arbitrary pi/3 32x32 f32 taps x c64 {nch}ch x {n}", harb.astype(np.float32), rate, 32, nch, n, torch.complex64, 8 + 8 * rate, (2 * 4 * 32 + 4) * rate, reps=10)
+
     def _ms():
         # the north star's "one-channel-per-stream": 64 INDEPENDENT single-channel FIRFilters (README.md:87-141: one object per
         # signal), chunks of about 1e6 samples of UNEQUAL lengths arriving round after round, one launch per round
@@ -367,7 +384,7 @@ def rows(which):
         for f in fs:
             f.close()
 
-    table = {"ms": _ms, "c1": _c1, "c2": _c2, "c2s": _c2s, "c2r": _c2r, "c3a": _c3a, "c3b": _c3b, "c4": _c4, "c4f": _c4f, "c5": _c5, "x160": _x160, "xf64": _xf64, "xmix": _xmix, "xstd": _xstd, "x32": _x32, "xc32": _xc32, "xarb": _xarb, "xmix64": _xmix64, "af": _af, "xdec": _xdec, "xlarge": _xlarge, "xct": _xct}
+    table = {"ms": _ms, "c1": _c1, "c2": _c2, "c2s": _c2s, "c2r": _c2r, "c3a": _c3a, "c3b": _c3b, "c4": _c4, "c4f": _c4f, "c5": _c5, "x160": _x160, "xf64": _xf64, "xmix": _xmix, "xstd": _xstd, "x32": _x32, "xc32": _xc32, "xarb": _xarb, "xmix64": _xmix64, "af": _af, "xdec": _xdec, "xlarge": _xlarge, "xct": _xct, "xcta": _xcta}
     for name in which:                # in the order asked for (bench.py wants the BASELINE rows last)
         table[name]()
 
