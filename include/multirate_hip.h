@@ -45,11 +45,11 @@ typedef enum {
     MRHIP_ERR_BUFFER_TOO_SMALL = 2, /* reference: error("buffer is too small"), Filters.jl:460,503,550 */
     MRHIP_ERR_HIP = 3,              /* a HIP runtime call failed; message holds hipGetErrorString */
     MRHIP_ERR_NO_DEVICE = 4,        /* no gfx950 device visible: the engine has no CPU fallback */
-    MRHIP_ERR_UNSUPPORTED = 5       /* e.g. complex taps on FIRFarrow (and on mrhip_create_arbitrary), FUSED numerics with complex taps */
+    MRHIP_ERR_UNSUPPORTED = 5       /* e.g. complex taps on mrhip_create_arbitrary / mrhip_create_farrow, FUSED numerics with complex taps */
 } mrhip_status;
 
 /* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational) and
- * FIRArbitrary (mrhip_create_arbitrary_ctaps);
+ * FIRArbitrary (mrhip_create_arbitrary_ctaps) and FIRFarrow (mrhip_create_farrow_ctaps, mrhip_create_farrow_pnfb_ctaps);
  * Tx in {F32,F64,C64,C128}; Tb = promote_type(Th,Tx) -- complex as soon as either side is */
 typedef enum { MRHIP_F32 = 0, MRHIP_F64 = 1, MRHIP_C64 = 2, MRHIP_C128 = 3 } mrhip_dtype;
 
@@ -70,7 +70,8 @@ typedef enum {
  *   FUSED : same order, each step one fused multiply-add.  Faster where the kernel is
  *           VALU-bound; differs from STRICT by <= 1 rounding per tap. */
 typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numerics;
-/* Complex taps (Th in {C64,C128}; the rational family, and FIRArbitrary through mrhip_create_arbitrary_ctaps).  The reference is generic over the tap type: the unsafedot
+/* Complex taps (Th in {C64,C128}; the rational family, FIRArbitrary through mrhip_create_arbitrary_ctaps and FIRFarrow through
+ * mrhip_create_farrow_ctaps).  The reference is generic over the tap type: the unsafedot
  * methods (src/support.jl:5-55) only multiply and add, so the contract is the one above with Julia's complex products
  * written out.  Let R be the promoted real scalar (Float64 if either side is 64-bit, else Float32); every multiply, add
  * and subtract is rounded separately in R, a narrower operand is widened exactly before use:
@@ -92,7 +93,26 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     Float64 -- what the real-tap kernels do per real component;
  *   - the phase schedule, outputlength, set_state / reset and the mod form do not depend on the tap type;
  *   - no FUSED form either; the ring is not resident, mrhip_filt_device_multi issues single calls, mrhip_sharded_create refuses
- *     complex taps, and a cascade takes such a filter as a stage like any FIRArbitrary (the per-stage calls). */
+ *     complex taps, and a cascade takes such a filter as a stage like any FIRArbitrary (the per-stage calls).
+ * FIRFarrow with complex taps (mrhip_create_farrow_ctaps, mrhip_create_farrow_pnfb_ctaps; FIRFarrow(h, rate, Nphi, polyorder),
+ * src/Filters.jl:138-147, pfb2pnfb :311-321, tapsforphase!, update and filt!, :764-839):
+ *   - pnfb is one polynomial per ROW of taps2pfb(h, Nphi).  The least-squares fit is taken per component: polyfit on the real
+ *     parts and on the imaginary parts of a row (the Vandermonde matrix is real, so a complex fit is these two; the reference
+ *     pins no bits of the fit).  Coefficients are stored in the tap type per component -- for C64 each is rounded to Float32,
+ *     as for F32 -- and held as Float64;
+ *   - the taps of an output with the Float64 phase phi: for tap i and component c exactly the statement
+ *     mrhip_farrow_tapsforphase makes for real taps -- Horner in Float64 from the highest power, t = phi*v; v = coef + t, the
+ *     product and the sum each rounded once; the result rounded once to the tap's real scalar and widened exactly to R.  This is
+ *     polyval(Poly{Complex{T}}, ::Float64) written out (y = p[i] + x*y; Real*Complex and Complex+Complex are by components),
+ *     stored into currentTaps::Vector{Complex{T}} (:764-792).  (Polynomials.jl is not part of the reference tree this was
+ *     written against; the statement is its documented Horner loop, as for real taps);
+ *   - the dot is the Vector unsafedot (support.jl:33-55) with the products and sums stated above: oldest sample first, the
+ *     first product initialises the accumulator; outputs with xIdx < tapsPerPhi that are not a continuation piece of a split
+ *     call take the start-from-zero seam (support.jl:46) per component: acc_c = 0 + p_c;
+ *   - the output is complex (C128 if either side is 64-bit, else C64), the history stays in Tx; the phase schedule,
+ *     outputlength, set_state / reset and the mod form do not depend on the tap type;
+ *   - no FUSED form; mrhip_sharded_create keeps refusing complex taps, mrhip_filt_device_multi issues single calls, a cascade
+ *     takes such a filter as a stage through its per-stage calls. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -200,10 +220,21 @@ int mrhip_create_farrow(const void *h, int64_t hLen, int tap_dtype, double rate,
  * reference pins no bits of the fit) and lets tests hand oracle and GPU the same coefficients. */
 int mrhip_create_farrow_pnfb(const double *pnfb, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
                              int64_t polyorder, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
-/* the polynomial filter bank in use, [tapsPerPhi][polyorder+1] Float64 (pfb2pnfb's result) */
+/* the two FIRFarrow constructors for COMPLEX taps (tap_dtype C64 | C128; see "Complex taps" above): the filter's kind is
+ * MRHIP_FIR_FARROW and its output is complex for every sample type.  `h`: interleaved (re, im) pairs, the fit is taken per
+ * component; `pnfb`: [tapsPerPhi][polyorder+1] (re, im) pairs of Float64, ascending powers.  A real tap_dtype is
+ * MRHIP_ERR_INVALID_ARG: real taps use the two constructors above (which keep refusing complex ones); the other argument
+ * checks are theirs. */
+int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi, int64_t polyorder,
+                              int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
+                                   int64_t polyorder, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* the polynomial filter bank in use, [tapsPerPhi][polyorder+1] Float64 (pfb2pnfb's result); complex taps: (re, im) pairs of
+ * Float64, twice as many values */
 int mrhip_get_pnfb(const mrhip_filter *f, double *host_out);
 /* replaces tapsforphase(kernel::FIRFarrow, phase), src/Filters.jl:764-775: tapsPerPhi taps of tap_dtype
- * for a phase in [0, Nphi+1] (host evaluation; MRHIP_ERR_INVALID_ARG outside the range like :765) */
+ * for a phase in [0, Nphi+1] (host evaluation; MRHIP_ERR_INVALID_ARG outside the range like :765); complex taps: tapsPerPhi
+ * complex taps, the statement per component */
 int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_out);
 /* replaces tapsforphase(kernel::FIRArbitrary, phase), src/Filters.jl:677-690: (alpha, phiIdx) = modf(phase);
  * taps[i] = pfb[i, phiIdx] + alpha * dpfb[i, phiIdx], evaluated in Float64 (alpha is a Float64 there) and stored in

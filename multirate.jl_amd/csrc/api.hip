@@ -484,6 +484,8 @@ int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int th, double rat
     return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, out);
 }
 
+// FIRFarrow(h, rate, N𝜙, polyorder), src/Filters.jl:138-147, behind all four constructors.  pnfb_in: [T][polyorder+1] coefficients,
+// ascending powers -- scalars for real taps, (re, im) pairs for complex ones (the layout kernels_ctaps_farrow.hip reads).
 static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen, int th, double rate, int64_t Nphi,
                                 int64_t polyorder, int tx, int64_t nch, int device, mrhip_filter **out)
 {
@@ -501,13 +503,13 @@ static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen
     f->T = (hLen + Nphi - 1) / Nphi;
     f->H = f->T - 1;
     f->h_pnfb = pnfb_in;
-    // Poly{T} storage: coefficients live in the tap type (Filters.jl:313 Array(Poly{T}, ...))
-    if (th == MRHIP_F32) for (double &c : f->h_pnfb) c = static_cast<double>(static_cast<float>(c));
+    // Poly{T} storage: coefficients live in the tap type (Filters.jl:313 Array(Poly{T}, ...)), complex ones per component
+    if (!dtype_is_f64(th)) for (double &c : f->h_pnfb) c = static_cast<double>(static_cast<float>(c));
     int rc = MRHIP_OK;
     if (hipMalloc(reinterpret_cast<void **>(&f->d_pnfb), f->h_pnfb.size() * sizeof(double)) != hipSuccess ||
         hipMemcpy(f->d_pnfb, f->h_pnfb.data(), f->h_pnfb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(MRHIP_ERR_HIP, "uploading the polynomial filter bank failed");
-    if (!rc && f->T <= 32) {        // the same bank degree-major, padded to 32 taps with zeros (kernels_farrow_wave.hip)
+    if (!rc && f->T <= 32 && !dtype_is_complex(th)) {   // the same bank degree-major, padded to 32 taps with zeros (kernels_farrow_wave.hip)
         std::vector<double> t(static_cast<size_t>(polyorder + 1) * 32, 0.0);
         for (int64_t i = 0; i < f->T; ++i)
             for (int64_t j = 0; j <= polyorder; ++j) t[static_cast<size_t>(j) * 32 + i] = f->h_pnfb[static_cast<size_t>(i) * (polyorder + 1) + j];
@@ -558,6 +560,54 @@ int mrhip_create_farrow_pnfb(const double *pnfb, int64_t hLen, int th, double ra
     return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, out);
 }
 
+// The same two constructors for COMPLEX taps (include/multirate_hip.h, "Complex taps", FIRFarrow part).  The Vandermonde matrix of
+// the fit is real, so the least-squares fit of a complex row is the fit of its real parts and the fit of its imaginary parts.
+int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
+                              int64_t nch, int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_F32 || th == MRHIP_F64)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_farrow_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_farrow");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
+    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
+    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
+    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
+        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
+    const size_t es = dtype_size(th);
+    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
+    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
+    taps2pfb(h, hLen, th, Nphi, pfb.data());                // column-major T x Nphi of (re, im) pairs
+    const size_t np = static_cast<size_t>(polyorder + 1);
+    std::vector<double> pn(static_cast<size_t>(T) * np * 2), row(static_cast<size_t>(Nphi)), fit(np);
+    for (int64_t i = 0; i < T; ++i)
+        for (int comp = 0; comp < 2; ++comp) {
+            for (int64_t c = 0; c < Nphi; ++c) {
+                const size_t e = static_cast<size_t>(c * T + i) * 2 + comp;
+                row[static_cast<size_t>(c)] = dtype_is_f64(th) ? reinterpret_cast<const double *>(pfb.data())[e]
+                                                               : static_cast<double>(reinterpret_cast<const float *>(pfb.data())[e]);
+            }
+            if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), fit.data()))
+                return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
+            for (size_t j = 0; j < np; ++j) pn[(static_cast<size_t>(i) * np + j) * 2 + comp] = fit[j];
+        }
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, out);
+}
+
+int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder,
+                                   int tx, int64_t nch, int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_F32 || th == MRHIP_F64)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_farrow_pnfb_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_farrow_pnfb");
+    if (int rc = check_create_args(pnfb, hLen, th, tx, nch, device, out, true)) return rc;
+    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
+    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
+    if (polyorder < 0 || polyorder > 32) return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32");
+    const int64_t T = (hLen + Nphi - 1) / Nphi;
+    std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1) * 2);
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, out);
+}
+
 int mrhip_polyfit(const double *y, int64_t n, int64_t polyorder, double *coef)
 {
     if (!y || !coef || polyorder < 0 || polyorder > 64) return fail(MRHIP_ERR_INVALID_ARG, "bad polyfit arguments");
@@ -580,11 +630,14 @@ int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_ou
     if (!(phase >= 0.0 && phase <= static_cast<double>(f->Nphi) + 1.0))
         return fail(MRHIP_ERR_INVALID_ARG, "phase must be >= 0 and <= Nphi+1");      // Filters.jl:765
     const int64_t P = f->polyorder;
-    for (int64_t i = 0; i < f->T; ++i) {
-        const double *c = &f->h_pnfb[static_cast<size_t>(i) * (P + 1)];
-        double yv = c[P];
-        for (int64_t j = P - 1; j >= 0; --j) { const double t = phase * yv; yv = c[j] + t; }
-        if (f->th == MRHIP_F32) static_cast<float *>(host_out)[i] = static_cast<float>(yv);
+    // complex taps: the same statement per component (Real*Complex and Complex+Complex are by components) -- a polynomial is
+    // P+1 (re, im) pairs, the result T interleaved pairs
+    const int64_t nc = dtype_is_complex(f->th) ? 2 : 1;
+    for (int64_t i = 0; i < f->T * nc; ++i) {
+        const double *c = &f->h_pnfb[static_cast<size_t>(i / nc) * (P + 1) * nc + i % nc];
+        double yv = c[P * nc];
+        for (int64_t j = P - 1; j >= 0; --j) { const double t = phase * yv; yv = c[j * nc] + t; }
+        if (!dtype_is_f64(f->th)) static_cast<float *>(host_out)[i] = static_cast<float>(yv);
         else static_cast<double *>(host_out)[i] = yv;
     }
     return MRHIP_OK;
@@ -1300,13 +1353,20 @@ static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_
         fa.n_idx = static_cast<const int *>(r.sched_dn) + k0; fa.acc = static_cast<const double *>(r.sched_dacc) + k0;
         fa.x_stride = c.x_stride; fa.y_stride = c.y_stride; fa.x_len = c.x_len; fa.n_out = cnt;
         fa.T = static_cast<int>(f->T); fa.H = static_cast<int>(f->H); fa.polyorder = static_cast<int>(f->polyorder);
-        fa.tap_f32 = f->th == MRHIP_F32; fa.nch = static_cast<int>(f->nch);
+        fa.tap_f32 = !dtype_is_f64(f->th); fa.nch = static_cast<int>(f->nch);
         fa.seam_below = c.continuation ? 0 : static_cast<int>(f->T);
         fa.dyn = dyn;
         if (int rc = timing_mark(f, stream)) return rc;
         ArbTileArgs fta;
         size_t flds = 0;
-        if (!f->force_generic && f->d_pnfb_t && plan_farrow_wave(fa)) {
+        if (tk.complex_h) {               // complex taps (kernels_ctaps_farrow.hip): no plan_* below ever sees such a call
+            fa.fold = sf;                 // (both kernels write the next call's history themselves)
+            if (!f->force_generic && plan_ctaps_farrow_tiled(tk, fa, f->rate, f->num_cus, &fta, &flds))
+                MRHIP_CHECK_HIP(launch_farrow_ctaps_tiled(tk, fa, fta, flds, stream, &f->last_kernel, f->num_cus));
+            else
+                MRHIP_CHECK_HIP(launch_farrow_ctaps_generic(tk, fa, stream, &f->last_kernel));
+        }
+        else if (!f->force_generic && f->d_pnfb_t && plan_farrow_wave(fa)) {
             FarrowArgs fw = fa;
             fw.pnfb = f->d_pnfb_t;                              // degree-major, padded: [polyorder+1][32]
             fw.fold = sf;

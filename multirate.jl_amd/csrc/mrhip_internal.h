@@ -408,19 +408,19 @@ struct FarrowArgs {          // FIRFarrow
     const void *x;
     void *y;
     const void *hist;
-    const double *pnfb;      // device, [T][polyorder+1] ascending powers (values representable in Th)
+    const double *pnfb;      // device, [T][polyorder+1] ascending powers (values representable in Th); complex taps: (re, im) pairs
     const int *n_idx;        // device, per output: 1-based input index
     const double *acc;       // device, per output: the Float64 phase 𝜙Idx
     long long x_stride, y_stride;
     long long x_len;
     long long n_out;
     int T, H, polyorder;
-    int tap_f32;             // currentTaps is a Vector{Float32}: round every evaluated tap to Float32
+    int tap_f32;             // currentTaps is a Vector{Float32} (or Complex64): round every evaluated tap (component) to Float32
     int nch;
     int seam_below;          // outputs whose 1-based input index n < this start from +0 (support.jl:46): T, or 0 for a
                              // piece that continues a call (mrhip_filt_device splits long calls)
     const DevCall *dyn;      // != NULL: n_out is read from it
-    ShiftFold fold;          // farrow_wave_kernel, farrow_pipe_kernel, farrow_tiled_kernel
+    ShiftFold fold;          // farrow_wave_kernel, farrow_pipe_kernel, farrow_tiled_kernel, farrow_ctaps_*_kernel
 };
 
 struct HistArgs {            // shiftin! (src/support.jl:61-80) for every channel
@@ -580,7 +580,7 @@ struct TypeKey {
     bool x_f64;      // Tx scalar is double
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
-    bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family) and kernels_ctaps_arb.hip (FIRArbitrary) only
+    bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family), kernels_ctaps_arb.hip (FIRArbitrary) and kernels_ctaps_farrow.hip (FIRFarrow) only
 };
 
 // ---------------------------------------------------------------------------------------
@@ -646,6 +646,12 @@ hipError_t launch_arb_ctaps_generic(const TypeKey &tk, const ArbArgs &a, hipStre
 bool plan_ctaps_arb_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
 hipError_t launch_arb_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                   const char **kname, int num_cus);
+// complex taps, FIRFarrow (kernels_ctaps_farrow.hip): the universal kernel and the LDS-tiled one; both serve host- and device-planned
+// calls and take the ShiftFold epilogue.  a.pnfb: [T][polyorder+1] (re, im) pairs of Float64
+hipError_t launch_farrow_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, hipStream_t s, const char **kname);
+bool plan_ctaps_farrow_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+hipError_t launch_farrow_ctaps_tiled(const TypeKey &tk, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
+                                     const char **kname, int num_cus);
 // dh = [diff(h), 0] in the tap type, per component for complex taps (src/Filters.jl:106); host_logic.cpp
 void arbitrary_dh(const void *h, int64_t hLen, int th, void *dh);
 bool plan_phase_stationary(const TypeKey &tk, const PolyArgs &a, int num_cus, TileArgs *out, dim3 *grid, dim3 *block,

@@ -80,6 +80,8 @@ ABI = [
     ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_farrow_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_farrow_pnfb_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -267,7 +269,8 @@ class FIRFilter:
             self.kind = ARBITRARY if polyorder is None else FARROW
             self.polyorder = None if polyorder is None else int(polyorder)
             # optional caller-fitted polynomial bank (tapsPerPhi x (polyorder+1), ascending powers)
-            self._pnfb_in = None if pnfb is None else np.ascontiguousarray(pnfb, dtype=np.float64)
+            # (complex taps, FIRFilter.complex_taps_farrow: complex coefficients, handed over as (re, im) pairs of Float64)
+            self._pnfb_in = None if pnfb is None else np.ascontiguousarray(pnfb, dtype=np.complex128 if self.h.dtype.kind == "c" else np.float64)
             self.interpolation, self.decimation = self.Nphi, 1
             self.tapsPerPhi = -(-len(self.h) // self.Nphi)
             self.historyLen = self.tapsPerPhi - 1
@@ -320,6 +323,26 @@ class FIRFilter:
             h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
         return cls(h, float(rate), int(Nphi), device=device, _complex_taps=True)
 
+    @classmethod
+    def complex_taps_farrow(cls, h, rate, Nphi, polyorder, *, pnfb=None, device: int = 0):
+        """FIRFilter(h::Vector{Complex64 / Complex128}, rate::Float, N𝜙, polyorder): FIRFarrow with complex taps
+        (FIRFarrow(h, rate, N𝜙, polyorder), src/Filters.jl:138-147, is generic over the tap type: one Poly{Complex{T}} per row of
+        the filter bank, fitted per component; tapsforphase and pnfb() are complex).  ``pnfb``: a caller-fitted bank, complex, shape
+        (tapsPer𝜙, polyorder+1), ascending powers.  The output is always complex (Complex128 if either side is 64-bit); real
+        ``h`` is promoted to complex.  STRICT numerics only (include/multirate_hip.h: complex taps).  The device object is created
+        by ``mrhip_create_farrow_ctaps`` / ``mrhip_create_farrow_pnfb_ctaps``."""
+        if not isinstance(rate, (float, np.floating)):
+            raise MultirateHIPError(1, "complex_taps_farrow takes a floating-point rate (a Rational ratio: FIRFilter.complex_taps)")
+        if polyorder is None:
+            raise MultirateHIPError(1, "complex_taps_farrow takes a polyorder (without one: FIRFilter.complex_taps_arbitrary)")
+        h = np.ascontiguousarray(h)
+        if h.dtype != np.complex64 and h.dtype != np.complex128:
+            h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
+        f = cls(h, float(rate), int(Nphi), int(polyorder), device=device, pnfb=pnfb, _complex_taps=True)
+        if f._pnfb_in is not None and f._pnfb_in.shape != (f.tapsPerPhi, f.polyorder + 1):
+            raise MultirateHIPError(1, f"pnfb must have shape (tapsPerPhi, polyorder+1) = {(f.tapsPerPhi, f.polyorder + 1)}")
+        return f
+
     # -- lifetime
     def _ensure(self, tx: np.dtype, nch: int):
         tx = np.dtype(tx)
@@ -331,7 +354,14 @@ class FIRFilter:
         if tx not in _NP2DT:
             raise MultirateHIPError(1, f"unsupported sample dtype {tx}")
         out = C.c_void_p()
-        if self.kind == FARROW and self._pnfb_in is not None:
+        if self.kind == FARROW and self.h.dtype.kind == "c":
+            if self._pnfb_in is not None:
+                rc = self._lib.mrhip_create_farrow_pnfb_ctaps(_ptr(self._pnfb_in), len(self.h), _NP2DT[self.h.dtype], self.rate,
+                                                              self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
+            else:
+                rc = self._lib.mrhip_create_farrow_ctaps(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate, self.Nphi,
+                                                         self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self.kind == FARROW and self._pnfb_in is not None:
             rc = self._lib.mrhip_create_farrow_pnfb(_ptr(self._pnfb_in), len(self.h), _NP2DT[self.h.dtype], self.rate,
                                                     self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
         elif self.kind == FARROW:
@@ -424,7 +454,7 @@ class FIRFilter:
         """FIRFarrow.pnfb (src/Filters.jl:126): tapsPer𝜙 polynomials, ascending powers, shape (tapsPer𝜙, polyorder+1)."""
         if self._handle is None or self.kind != FARROW:
             raise MultirateHIPError(1, "pnfb() needs a bound FIRFarrow filter")
-        out = np.zeros((self.tapsPerPhi, self.polyorder + 1), dtype=np.float64)
+        out = np.zeros((self.tapsPerPhi, self.polyorder + 1), dtype=np.complex128 if self.h.dtype.kind == "c" else np.float64)
         _check(self._lib.mrhip_get_pnfb(self._handle, _ptr(out)))
         return out
 

@@ -94,6 +94,13 @@ function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer, polyorder:
     f = FIRFilter{FIRFarrow{Th}}(copy(h), nothing, Float64(rate), Nphi, polyorder, device, C_NULL, nothing, 0)
     finalizer(destroy!, f)
 end
+# the same constructor with complex taps (the reference is generic over Th: pnfb is one Poly{Complex{T}} per row of the bank, fitted
+# per component): bind! creates the device object through mrhip_create_farrow_ctaps; the output is complex for every sample type
+function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{ComplexF32,ComplexF64}}
+    rate > 0.0 || error("rate must be greater than 0")
+    f = FIRFilter{FIRFarrow{Th}}(copy(h), nothing, Float64(rate), Nphi, polyorder, device, C_NULL, nothing, 0)
+    finalizer(destroy!, f)
+end
 
 function destroy!(f::FIRFilter)
     f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle)
@@ -108,7 +115,11 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
     end
     out = Ref{Ptr{Cvoid}}(C_NULL)
     Th = eltype(f.h)
-    if f.ratio === nothing && f.polyorder >= 0
+    if f.ratio === nothing && f.polyorder >= 0 && Th <: Complex
+        check(ccall((:mrhip_create_farrow_ctaps, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, length(f.h), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
+    elseif f.ratio === nothing && f.polyorder >= 0
         check(ccall((:mrhip_create_farrow, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
                     f.h, length(f.h), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
@@ -126,6 +137,20 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
                     f.h, length(f.h), dtypecode(Th), numerator(f.ratio), denominator(f.ratio), dtypecode(Tx), nch,
                     f.device, out))
     end
+    f.handle, f.Tx, f.nchannels = out[], Tx, nch
+    f
+end
+
+# FIRFarrow with complex taps and a polynomial filter bank the CALLER fitted (the reference pins no bits of the fit): pnfb is
+# tapsPer𝜙 x (polyorder + 1), ascending powers; the device object is created here instead of by the first filt call
+function bind!(f::FIRFilter{FIRFarrow{Th}}, pnfb::AbstractMatrix{<:Complex}, ::Type{Tx}, nch::Integer) where {Th<:Union{ComplexF32,ComplexF64},Tx}
+    f.handle == C_NULL || error("filter is bound to $(f.nchannels) channel(s) of $(f.Tx)")
+    size(pnfb) == (cld(length(f.h), f.Nphi), f.polyorder + 1) || error("pnfb must be tapsPerPhi x (polyorder + 1)")
+    rows = Matrix{ComplexF64}(permutedims(pnfb))          # [tapsPerPhi][polyorder+1] (re, im) pairs, as the C ABI reads them
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mrhip_create_farrow_pnfb_ctaps, libmr), Cint,
+                (Ptr{Cdouble}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                rows, length(f.h), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
     f.handle, f.Tx, f.nchannels = out[], Tx, nch
     f
 end

@@ -335,6 +335,108 @@ def rows(which):
             run(f"X complex taps: arbitrary pi/3 32x32 c64 taps x f32 {nch}ch x {n}{tag}", rot, rate, 32, nch, n, torch.float32, 4 + 8 * rate, (2 * 4 * 32 + 4) * rate, reps=10)
             run(f"X real taps for scale: arbitrary pi/3 32x32 f32 taps x c64 {nch}ch x {n}", harb.astype(np.float32), rate, 32, nch, n, torch.complex64, 8 + 8 * rate, (2 * 4 * 32 + 4) * rate, reps=10)
 
+    def _xctf():
+        # complex taps on FIRFarrow (kernels_ctaps_farrow.hip), as KERNEL time (the library's HIP events round the filter launch), per call
+        # of a continuing stream: N𝜙 = 32, 1024 taps (32 per phase) rotated to a band centre, polyorder 4, Complex64 taps on Float32 and on
+        # Complex64 samples.  Shapes "nch:n:u|d" (u: rate 2.123, d: rate 1/2.123) from MRHIP_BENCH_XCTF_SIZES; default: 64 ch x 1e6 up and
+        # the reference's own benchmark shape, 1 ch x 1e7 down.  Three ways (MRHIP_BENCH_XCTF_MODES):
+        #   a  what a user did before the constructor existed: two real-tap FIRFarrow calls with real(h) and imag(h) plus the combine
+        #      into a complex tensor (torch; timed with events of its own)
+        #   b  farrow_ctaps_generic_kernel (MRHIP_CTAPS_TILED=0)        c  farrow_ctaps_tiled_kernel (MRHIP_CTAPS_TILED=1)
+        #   d  whatever the default rule selects (MRHIP_CTAPS_TILED unset)
+        # alternating, MRHIP_BENCH_XCTF_ROUNDS (3) times; every figure is the median of 20 calls behind SETTLE_MS of the same calls.
+        # Run it in a process of its own: the switch is re-read per call only under MRHIP_ENV_DYNAMIC=1, latched at the first launch.
+        os.environ["MRHIP_ENV_DYNAMIC"] = "1"
+        # MRHIP_BENCH_XCTF_BANK="Nphi:hLen:polyorder" and MRHIP_BENCH_XCTF_TAPS=c128 measure another bank / Complex128 taps (the plan's rule).
+        nphi, hlen, po = (int(v) for v in os.environ.get("MRHIP_BENCH_XCTF_BANK", "32:1024:4").split(":"))
+        th = np.complex128 if os.environ.get("MRHIP_BENCH_XCTF_TAPS", "c64") == "c128" else np.complex64
+        hb = harb if (nphi, hlen) == (32, 1024) else pkg.firdes(hlen, 0.45 / nphi, beta=7.8562) * nphi
+        rot = (hb * np.exp(2j * np.pi * 0.05 * np.arange(len(hb)))).astype(th)
+        rt = np.float64 if th == np.complex128 else np.float32
+        hre, him = np.ascontiguousarray(rot.real).astype(rt), np.ascontiguousarray(rot.imag).astype(rt)
+        ydt = torch.complex128 if th == np.complex128 else torch.complex64
+        sizes = [s_.split(":") for s_ in os.environ.get("MRHIP_BENCH_XCTF_SIZES", "64:1000000:u,1:10000000:d").split(",")]
+        modes = os.environ.get("MRHIP_BENCH_XCTF_MODES", "a,b,c,d").split(",")
+        rounds, calls = int(os.environ.get("MRHIP_BENCH_XCTF_ROUNDS", "3")), 20
+        want_kernel = {"b": "farrow_ctaps_generic_kernel", "c": "farrow_ctaps_tiled_kernel"}
+
+        def switch(mode):
+            os.environ.pop("MRHIP_CTAPS_TILED", None)
+            if mode in ("b", "c"):
+                os.environ["MRHIP_CTAPS_TILED"] = "1" if mode == "c" else "0"
+
+        for nch_s, n_s, ud in sizes:
+            nch, n, rate = int(nch_s), int(n_s), (2.123 if ud == "u" else 1 / 2.123)
+            for dtype in (torch.float32, torch.complex64):
+                x = rand((nch, n), dtype)
+                cplx = dtype.is_complex
+                fs, ys = {}, {}
+                for mode in modes:
+                    switch(mode)
+                    if mode == "a":
+                        fs[mode] = [pkg.FIRFilter(hre, rate, nphi, po, device=dev.index or 0), pkg.FIRFilter(him, rate, nphi, po, device=dev.index or 0)]
+                    else:
+                        fs[mode] = [pkg.FIRFilter.complex_taps_farrow(rot, rate, nphi, po, device=dev.index or 0)]
+                    for f in fs[mode]:
+                        f.bind(np.complex64 if cplx else np.float32, nch)
+                    bound = max(fs[mode][0].outputlength_bound(n), 1)
+                    adt = {(False, False): torch.float32, (False, True): torch.float64, (True, False): torch.complex64, (True, True): torch.complex128}[cplx, th == np.complex128]
+                    ys[mode] = [torch.zeros((nch, bound), dtype=adt if mode == "a" else ydt, device=dev) for _ in fs[mode]]
+                    if mode == "a":
+                        ys[mode].append(torch.zeros((nch, bound), dtype=ydt, device=dev))
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+                def call(mode):
+                    """one call of the stream; its kernel time in ms"""
+                    switch(mode)
+                    for f, y in zip(fs[mode], ys[mode]):
+                        f.filt_into(y, x)
+                    if mode == "a":
+                        ev0.record()
+                        if cplx:
+                            torch.add(ys[mode][0], ys[mode][1], alpha=1j, out=ys[mode][2])
+                        else:
+                            torch.complex(ys[mode][0], ys[mode][1], out=ys[mode][2])
+                        ev1.record()
+                    torch.cuda.synchronize()
+                    ms = sum(f.timing_read()[1] for f in fs[mode])
+                    return ms + (ev0.elapsed_time(ev1) if mode == "a" else 0.0)
+
+                # the same first call everywhere: b == c bit for bit, a to rounding (Complex*Complex sums its products in another order)
+                first = {}
+                for mode in modes:
+                    for f in fs[mode]:
+                        f.set_timing(True)
+                    call(mode)
+                    first[mode] = ys[mode][-1].clone()
+                same = {m: bool(torch.equal(first[m], first["b"])) for m in modes if m in ("c", "d") and "b" in first}
+                if "a" in first and "b" in first:
+                    same["a_max_abs_diff"] = float((first["a"] - first["b"]).abs().max())
+                del first
+                med = {m: [] for m in modes}
+                for _ in range(rounds):
+                    for mode in modes:
+                        t0 = time.perf_counter()
+                        for i_settle in range(200):
+                            call(mode)
+                            if i_settle >= 1 and (time.perf_counter() - t0) * 1e3 >= SETTLE_MS:
+                                break
+                        med[mode].append(float(np.median([call(mode) for _ in range(calls)])))
+                for mode in modes:
+                    kern = fs[mode][0].last_kernel_name()
+                    if mode in want_kernel and kern != want_kernel[mode]:
+                        raise RuntimeError(f"xctf: mode {mode} ran {kern}: MRHIP_CTAPS_TILED is not re-read (run this row in a process of its own)")
+                    EMIT(json.dumps({"config": f"X complex taps: farrow {'2.123' if ud == 'u' else '1/2.123'} {nphi}x{-(-hlen // nphi)} polyorder {po}, {'c128' if th == np.complex128 else 'c64'} taps x {'c64' if cplx else 'f32'} {nch}ch x {n}",
+                                     "mode": mode, "kernel": kern, "channels": nch, "samples_per_channel": n,
+                                     "kernel_ms_per_call_median_of_20": [round(v, 4) for v in med[mode]], "rounds": rounds,
+                                     **({"first_call_vs_generic": same} if mode == "b" else {})}))
+                for mode in modes:
+                    for f in fs[mode]:
+                        f.close()
+                del x, ys, fs
+                torch.cuda.empty_cache()
+        os.environ.pop("MRHIP_CTAPS_TILED", None)
+
     def _ms():
         # the north star's "one-channel-per-stream": 64 INDEPENDENT single-channel FIRFilters (README.md:87-141: one object per
         # signal), chunks of about 1e6 samples of UNEQUAL lengths arriving round after round, one launch per round
@@ -384,7 +486,7 @@ def rows(which):
         for f in fs:
             f.close()
 
-    table = {"ms": _ms, "c1": _c1, "c2": _c2, "c2s": _c2s, "c2r": _c2r, "c3a": _c3a, "c3b": _c3b, "c4": _c4, "c4f": _c4f, "c5": _c5, "x160": _x160, "xf64": _xf64, "xmix": _xmix, "xstd": _xstd, "x32": _x32, "xc32": _xc32, "xarb": _xarb, "xmix64": _xmix64, "af": _af, "xdec": _xdec, "xlarge": _xlarge, "xct": _xct, "xcta": _xcta}
+    table = {"ms": _ms, "c1": _c1, "c2": _c2, "c2s": _c2s, "c2r": _c2r, "c3a": _c3a, "c3b": _c3b, "c4": _c4, "c4f": _c4f, "c5": _c5, "x160": _x160, "xf64": _xf64, "xmix": _xmix, "xstd": _xstd, "x32": _x32, "xc32": _xc32, "xarb": _xarb, "xmix64": _xmix64, "af": _af, "xdec": _xdec, "xlarge": _xlarge, "xct": _xct, "xcta": _xcta, "xctf": _xctf}
     for name in which:                # in the order asked for (bench.py wants the BASELINE rows last)
         table[name]()
 
