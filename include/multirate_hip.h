@@ -113,6 +113,21 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     outputlength, set_state / reset and the mod form do not depend on the tap type;
  *   - no FUSED form; mrhip_sharded_create keeps refusing complex taps, mrhip_filt_device_multi issues single calls, a cascade
  *     takes such a filter as a stage through its per-stage calls. */
+/* Per-channel taps (mrhip_create_rational_bank; the rational family, Th in {F32,F64}).  In the reference N channels are N
+ * FIRFilter(h_c, ratio) objects and every h_c may differ; a filter built by mrhip_create_rational shares one h among its
+ * channels.  A bank filter shares everything but the taps: ratio, state (phiIdx, inputDeficit) and call length.
+ *   - for every channel c the outputs, the per-call counts, the end state and the history are bit for bit those of
+ *     mrhip_create_rational(h_c, ..., nchannels = 1) fed x_c: every row goes through taps2pfb on its own, and the dot product
+ *     is the one stated above (oldest sample first, first product initialises, the start-from-zero seam of support.jl:46);
+ *   - STRICT is the default; under mrhip_set_numerics(f, FUSED) the results are those of that one-channel filter under FUSED;
+ *   - everything that does not depend on the taps is unchanged: outputlength, inputlength, set_state, reset, set_history*,
+ *     next_output_count, outputlength_bound; the mrhip_state layout is the same;
+ *   - mrhip_get_taps(f, 0, out) returns the nchannels filter banks one after the other, each tapsPerPhi*Nphi elements laid
+ *     out as mrhip_taps2pfb does;
+ *   - complex taps in a bank return MRHIP_ERR_UNSUPPORTED; FIRArbitrary and FIRFarrow have no bank constructor;
+ *   - mrhip_filt_device_multi with a bank filter among its streams issues single calls; a ring on a bank filter is not
+ *     resident (stream-ordered launches); mrhip_sharded_create has no bank constructor; a cascade takes a bank filter as a
+ *     stage through its per-stage calls. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -196,6 +211,11 @@ int64_t mrhip_firdes_kaiser(const double *cutoff, int ncutoff, double transition
  * pairs and make the output complex: see "Complex taps" above).  `device` is a HIP ordinal. */
 int mrhip_create_rational(const void *h, int64_t hLen, int tap_dtype, int64_t num, int64_t den,
                           int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* one FIRFilter(h_c, resampleRatio) per channel behind one handle (see "Per-channel taps" above): `h` holds nchannels rows of
+ * hLen taps, row-major, row c is channel c's h.  tap_dtype F32 | F64 (complex: MRHIP_ERR_UNSUPPORTED).  Kind selection, L, M,
+ * tapsPerPhi, historyLen and every error are those of mrhip_create_rational. */
+int mrhip_create_rational_bank(const void *h, int64_t hLen, int tap_dtype, int64_t num, int64_t den,
+                               int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer = 32), src/Filters.jl:183-189
  * (+ FIRArbitrary(h, rate, Nphi), :105-117: dh = [diff(h), 0], two PFBs).  rate <= 0 is
  * MRHIP_ERR_INVALID_ARG ("rate must be greater than 0", :184). */

@@ -84,7 +84,7 @@ bool device_is_gfx950(int dev)
 
 TypeKey type_key(const mrhip_filter *f)
 {
-    return TypeKey{dtype_is_f64(f->tx), f->r_f64, f->nc == 2, dtype_is_complex(f->th)};
+    return TypeKey{dtype_is_f64(f->tx), f->r_f64, f->nc == 2, dtype_is_complex(f->th), f->bank};
 }
 
 size_t r_size(const mrhip_filter *f) { return f->r_f64 ? 8 : 4; }
@@ -298,6 +298,14 @@ hipError_t launch_poly(const mrhip_filter *f, const TypeKey &tk, bool fused, con
 {
     *did_shiftin = false;
     *rec_written = false;             // the pair kernels and the universal kernel file the call's end state in the device record
+    if (tk.bank) {                    // per-channel taps (kernels_bank.hip): no plan_* below ever sees such a call
+        *rec_written = true;
+        ArbTileArgs bt;
+        size_t bl = 0;
+        if (!f->force_generic && plan_bank_tiled(tk, a, f->num_cus, &bt, &bl))
+            return launch_poly_bank_tiled(tk, fused, a, bt, bl, s, kname, f->num_cus);
+        return launch_poly_bank_generic(tk, fused, a, s, kname);
+    }
     if (tk.complex_h) {               // complex taps (kernels_ctaps.hip): no plan_* below ever sees such a call
         *rec_written = true;
         ArbTileArgs ct;
@@ -388,10 +396,11 @@ int mrhip_output_dtype(int th, int tx)
     return f64 ? MRHIP_F64 : MRHIP_F32;
 }
 
-int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
-                          int device, mrhip_filter **out)
+// FIRFilter(h, ratio), src/Filters.jl:158-180, behind both constructors.  bank: `h` holds nch rows, every row goes through taps2pfb on
+// its own and the banks sit one after the other, [nch][Nphi][T] (upload_taps widens them exactly to R).
+static int create_rational_common(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
+                                  int device, bool bank, mrhip_filter **out)
 {
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
     if (num < 1 || den < 1) return fail(MRHIP_ERR_INVALID_ARG, "ratio must be positive");
     const int64_t g = std::gcd(num, den);
     const int64_t L = num / g, M = den / g;
@@ -405,26 +414,48 @@ int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int6
     f->nc = dtype_is_complex(tx) ? 2 : 1;
     f->r_f64 = dtype_is_f64(f->ty);
     f->nch = nch; f->hLen = hLen; f->L = L; f->M = M; f->device = device;
+    f->bank = bank;
     const size_t es = dtype_size(th);
+    const size_t rows = bank ? static_cast<size_t>(nch) : 1;      // tap vectors in `h`, each hLen long
 
     if (L == 1) {            // STANDARD (Filters.jl:163-165) / DECIMATOR (:166-168): h = flipud(h)
         f->kind = M == 1 ? MRHIP_FIR_STANDARD : MRHIP_FIR_DECIMATOR;
         f->Nphi = 1; f->T = hLen; f->H = hLen - 1;
-        f->h_taps.resize(static_cast<size_t>(hLen) * es);
-        taps2pfb(h, hLen, th, 1, f->h_taps.data());   // one column, reversed == flipud
     } else {                 // INTERPOLATOR (:169-171) / RATIONAL (:172-174)
         f->kind = M == 1 ? MRHIP_FIR_INTERPOLATOR : MRHIP_FIR_RATIONAL;
         f->Nphi = L;
         f->T = taps2pfb(h, hLen, th, L, nullptr);
         f->H = f->T - 1;
-        f->h_taps.resize(static_cast<size_t>(f->T) * L * es);
-        taps2pfb(h, hLen, th, L, f->h_taps.data());
+    }
+    {
+        const size_t bank_bytes = static_cast<size_t>(f->T) * static_cast<size_t>(f->Nphi) * es;
+        f->h_taps.resize(bank_bytes * rows);
+        for (size_t r = 0; r < rows; ++r)           // (L == 1: one column, reversed == flipud)
+            taps2pfb(static_cast<const unsigned char *>(h) + r * static_cast<size_t>(hLen) * es, hLen, th, f->Nphi, f->h_taps.data() + r * bank_bytes);
     }
     int rc = upload_taps(f, f->h_taps, &f->d_taps, &f->d_taps_alloc);
     if (!rc) rc = alloc_common(f);
     if (rc) { mrhip_destroy(f); return rc; }
     *out = f;
     return MRHIP_OK;
+}
+
+int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
+                          int device, mrhip_filter **out)
+{
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
+    return create_rational_common(h, hLen, th, num, den, tx, nch, device, false, out);
+}
+
+// One FIRFilter(h_c, ratio) per channel behind one handle (include/multirate_hip.h, "Per-channel taps"): `h` holds nch rows of hLen taps.
+int mrhip_create_rational_bank(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
+                               int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_C64 || th == MRHIP_C128)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_rational_bank takes Float32 / Float64 taps (complex taps in a bank are not supported)");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    return create_rational_common(h, hLen, th, num, den, tx, nch, device, true, out);
 }
 
 // FIRArbitrary(h, rate, N𝜙), src/Filters.jl:105-117, behind both constructors: real taps (mrhip_create_arbitrary) and complex
@@ -1169,6 +1200,11 @@ static hipError_t launch_poly_dyn(mrhip_filter *f, const TypeKey &tk, bool fused
                                   long long *count_dev, hipStream_t s, const char **kname, bool *did_shiftin, const DevCall *x_from = nullptr)
 {
     *did_shiftin = false;
+    if (tk.bank) {                    // per-channel taps: the universal bank kernel reads the call record
+        hipError_t e = launch_poly_plan(f, x_len, 1, y_capacity, count_dev, s, x_from);
+        if (e != hipSuccess) return e;
+        return launch_poly_bank_generic(tk, fused, a, s, kname);
+    }
     if (tk.complex_h) {               // complex taps: the universal complex-tap kernel reads the call record
         hipError_t e = launch_poly_plan(f, x_len, 1, y_capacity, count_dev, s, x_from);
         if (e != hipSuccess) return e;
@@ -1865,7 +1901,8 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
         for (int j = 0; j < i; ++j)
             if (filters[j] == f) return fail(MRHIP_ERR_INVALID_ARG, "the same filter twice in one multi-stream call");
         same = f->kind == f0->kind && f->L == f0->L && f->M == f0->M && f->T == f0->T && f->tx == f0->tx && f->th == f0->th &&
-               f->numerics == f0->numerics && f->device == f0->device && x_len[i] > 0 && x_len[i] < 0x7fffffffLL && x[i] && y[i];
+               f->numerics == f0->numerics && f->device == f0->device && x_len[i] > 0 && x_len[i] < 0x7fffffffLL && x[i] && y[i] &&
+               !f->bank;                                   // (per-channel taps: kernels_bank.hip only -- single calls)
     }
     if (!same || stream_is_capturing(stream)) return single_calls();
     DeviceGuard guard(f0->device);

@@ -240,7 +240,7 @@ int mrhip_ring_open(mrhip_filter *f, mrhip_ring **out)
     if (int rc = adopt_stream(f, r->stream)) return bail(rc);            // behind whatever the filter enqueued before
     const TypeKey tk = type_key(f);
     // the resident kernel: FIRRational / FIRInterpolator shapes the output-pair kernel has a RING instantiation for
-    bool resident = (f->kind == MRHIP_FIR_RATIONAL || f->kind == MRHIP_FIR_INTERPOLATOR) && !f->force_generic && !tk.complex_h &&
+    bool resident = (f->kind == MRHIP_FIR_RATIONAL || f->kind == MRHIP_FIR_INTERPOLATOR) && !f->force_generic && !tk.complex_h && !tk.bank &&
                     f->numerics == MRHIP_NUMERICS_STRICT && MRHIP_ENV_INT("MRHIP_RING_RESIDENT", 1) != 0 && f->device >= 0 && f->device < 64;
     if (resident) {
         std::lock_guard<std::mutex> g(g_ring_mutex);

@@ -76,6 +76,7 @@ ABI = [
     ("mrhip_firdes", _i64, [_i64, _vp, _i, _i, _d, _d, _vp, _vp]),
     ("mrhip_firdes_kaiser", _i64, [_vp, _i, _d, _d, _i, _d, _vp]),
     ("mrhip_create_rational", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_rational_bank", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -260,6 +261,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
+        self._bank = None                 # per-channel taps (FIRFilter.per_channel): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
                 raise MultirateHIPError(1, "rate must be greater than 0")  # Filters.jl:184
@@ -343,6 +345,26 @@ class FIRFilter:
             raise MultirateHIPError(1, f"pnfb must have shape (tapsPerPhi, polyorder+1) = {(f.tapsPerPhi, f.polyorder + 1)}")
         return f
 
+    @classmethod
+    def per_channel(cls, H, ratio=1, *, device: int = 0, numerics: int = NUMERICS_STRICT):
+        """One FIRFilter(H[c], ratio) per channel behind one filter object: in the reference N channels are N FIRFilter objects and
+        every ``h`` may differ (per-antenna equalisers, matched-filter banks, calibration filters in front of a common resampler).
+        ``H``: shape (nchannels, hLen), Float32 or Float64.  Ratio, state and call length are shared, only the taps differ; channel
+        c is bit for bit ``FIRFilter(H[c], ratio)`` fed ``x[c]`` (include/multirate_hip.h: per-channel taps).  Rational family
+        only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape (nchannels, tapsPer𝜙, N𝜙).  The device
+        object is created by ``mrhip_create_rational_bank``."""
+        if isinstance(ratio, (float, np.floating)):
+            raise MultirateHIPError(5, "per_channel builds the rational family only (FIRArbitrary / FIRFarrow have no per-channel taps)")
+        H = np.asarray(H)
+        if H.dtype.kind == "c":
+            raise MultirateHIPError(5, "per_channel takes Float32/Float64 taps (complex taps in a bank are not supported)")
+        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+            raise MultirateHIPError(1, f"per_channel takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
+        H = np.ascontiguousarray(_as_taps(H))
+        f = cls(H[0], ratio, device=device, numerics=numerics)
+        f._bank = H.copy()
+        return f
+
     # -- lifetime
     def _ensure(self, tx: np.dtype, nch: int):
         tx = np.dtype(tx)
@@ -354,7 +376,13 @@ class FIRFilter:
         if tx not in _NP2DT:
             raise MultirateHIPError(1, f"unsupported sample dtype {tx}")
         out = C.c_void_p()
-        if self.kind == FARROW and self.h.dtype.kind == "c":
+        if self._bank is not None and nch != self._bank.shape[0]:
+            raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
+        if self._bank is not None:
+            rc = self._lib.mrhip_create_rational_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype],
+                                                      self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
+                                                      self.device, C.byref(out))
+        elif self.kind == FARROW and self.h.dtype.kind == "c":
             if self._pnfb_in is not None:
                 rc = self._lib.mrhip_create_farrow_pnfb_ctaps(_ptr(self._pnfb_in), len(self.h), _NP2DT[self.h.dtype], self.rate,
                                                               self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
@@ -443,9 +471,14 @@ class FIRFilter:
         _check(self._lib.mrhip_set_history(self._handle, _ptr(hist)))
 
     def taps(self, which: int = 0) -> np.ndarray:
-        """kernel.h (flipped) / kernel.pfb (which=0) or kernel.dpfb (which=1) as stored."""
+        """kernel.h (flipped) / kernel.pfb (which=0) or kernel.dpfb (which=1) as stored.  A per-channel filter: one bank per channel,
+        shape (nchannels, tapsPer𝜙, N𝜙)."""
         if self._handle is None:
             raise MultirateHIPError(1, "taps() needs a bound filter")
+        if self._bank is not None:
+            out = np.zeros((self._nch, self.Nphi, self.tapsPerPhi), dtype=self.h.dtype)
+            _check(self._lib.mrhip_get_taps(self._handle, which, _ptr(out)))
+            return out.transpose(0, 2, 1).copy()
         out = np.zeros(self.tapsPerPhi * self.Nphi, dtype=self.h.dtype)
         _check(self._lib.mrhip_get_taps(self._handle, which, _ptr(out)))
         return out.reshape(self.Nphi, self.tapsPerPhi).T.copy()

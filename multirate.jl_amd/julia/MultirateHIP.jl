@@ -61,7 +61,10 @@ mutable struct FIRFilter{Tk<:FIRKernel}
     handle::Ptr{Cvoid}
     Tx::Union{DataType,Nothing}
     nchannels::Int
+    nbank::Int                        # per-channel taps (FIRFilter(H::Matrix, ratio)): the number of tap vectors in h, 0 otherwise
 end
+FIRFilter{Tk}(h, ratio, rate, Nphi, polyorder, device, handle, Tx, nchannels) where {Tk<:FIRKernel} =
+    FIRFilter{Tk}(h, ratio, rate, Nphi, polyorder, device, handle, Tx, nchannels, 0)
 
 function kindof(ratio::Rational)
     L, M = numerator(ratio), denominator(ratio)
@@ -73,6 +76,14 @@ end
 function FIRFilter(h::Vector{Th}, ratio::Rational = 1//1; device::Integer = 0) where {Th<:Union{Float32,Float64,ComplexF32,ComplexF64}}
     r = Rational{Int}(ratio)
     f = FIRFilter{kindof(r){Th}}(copy(h), r, 0.0, 0, -1, device, C_NULL, nothing, 0)
+    finalizer(destroy!, f)
+end
+# One FIRFilter(H[:, c], ratio) per channel behind one filter object (include/multirate_hip.h: per-channel taps): in the reference N
+# channels are N FIRFilter objects and every h may differ.  One COLUMN holds one channel's taps: a column-major hLen x nch matrix is
+# the row-major [nch][hLen] layout mrhip_create_rational_bank reads.  The filter binds to exactly size(H, 2) channels.
+function FIRFilter(H::Matrix{Th}, ratio::Rational; device::Integer = 0) where {Th<:Union{Float32,Float64}}
+    r = Rational{Int}(ratio)
+    f = FIRFilter{kindof(r){Th}}(vec(copy(H)), r, 0.0, 0, -1, device, C_NULL, nothing, 0, size(H, 2))
     finalizer(destroy!, f)
 end
 # FIRFilter(h, rate::AbstractFloat, Nphi = 32)            src/Filters.jl:183-189
@@ -115,7 +126,13 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
     end
     out = Ref{Ptr{Cvoid}}(C_NULL)
     Th = eltype(f.h)
-    if f.ratio === nothing && f.polyorder >= 0 && Th <: Complex
+    if f.nbank > 0
+        nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
+        check(ccall((:mrhip_create_rational_bank, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, div(length(f.h), f.nbank), dtypecode(Th), numerator(f.ratio), denominator(f.ratio), dtypecode(Tx), nch,
+                    f.device, out))
+    elseif f.ratio === nothing && f.polyorder >= 0 && Th <: Complex
         check(ccall((:mrhip_create_farrow_ctaps, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
                     f.h, length(f.h), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
