@@ -48,7 +48,7 @@ typedef enum {
     MRHIP_ERR_UNSUPPORTED = 5       /* e.g. complex taps on mrhip_create_arbitrary / mrhip_create_farrow, FUSED numerics with complex taps */
 } mrhip_status;
 
-/* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational) and
+/* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational, mrhip_create_rational_bank_ctaps) and
  * FIRArbitrary (mrhip_create_arbitrary_ctaps) and FIRFarrow (mrhip_create_farrow_ctaps, mrhip_create_farrow_pnfb_ctaps);
  * Tx in {F32,F64,C64,C128}; Tb = promote_type(Th,Tx) -- complex as soon as either side is */
 typedef enum { MRHIP_F32 = 0, MRHIP_F64 = 1, MRHIP_C64 = 2, MRHIP_C128 = 3 } mrhip_dtype;
@@ -124,9 +124,28 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     next_output_count, outputlength_bound; the mrhip_state layout is the same;
  *   - mrhip_get_taps(f, 0, out) returns the nchannels filter banks one after the other, each tapsPerPhi*Nphi elements laid
  *     out as mrhip_taps2pfb does;
- *   - complex taps in a bank return MRHIP_ERR_UNSUPPORTED; FIRArbitrary and FIRFarrow have no bank constructor;
+ *   - complex taps return MRHIP_ERR_UNSUPPORTED here (they have a constructor of their own: "Per-channel complex taps" below); FIRArbitrary and FIRFarrow have no bank constructor;
  *   - mrhip_filt_device_multi with a bank filter among its streams issues single calls; a ring on a bank filter is not
  *     resident (stream-ordered launches); mrhip_sharded_create has no bank constructor; a cascade takes a bank filter as a
+ *     stage through its per-stage calls. */
+/* Per-channel complex taps (mrhip_create_rational_bank_ctaps; the rational family, Th in {C64,C128}): one
+ * FIRFilter(h_c::Vector{Complex}, ratio) per channel behind one handle -- a prototype rotated to every channel's own centre
+ * frequency, per-channel Hilbert filters, per-antenna complex equalisers.  The contract is the conjunction of the two above:
+ *   - for every channel c the outputs, the per-call counts, the end state and the history are bit for bit those of
+ *     mrhip_create_rational(h_c complex, ..., nchannels = 1) fed x_c: the "Complex taps" arithmetic on bank c;
+ *   - that arithmetic: every multiply, add and subtract is rounded separately in R; the window is visited oldest sample first,
+ *     the first product initialises the accumulator, the start-from-zero seam of support.jl:46 applies as 0 + p per component,
+ *     and the Complex*Real and Complex*Complex products are written out in the operand order stated under "Complex taps";
+ *   - the output is always complex (C128 if either side is 64-bit, else C64); the history stays in Tx;
+ *   - no FUSED form is defined: mrhip_set_numerics(f, FUSED) returns MRHIP_ERR_UNSUPPORTED;
+ *   - mrhip_get_taps(f, 0, out) returns the nchannels filter banks one after the other, each tapsPerPhi*Nphi (re, im) pairs
+ *     laid out as mrhip_taps2pfb does;
+ *   - everything that does not depend on the taps is unchanged: outputlength, inputlength, set_state, reset, set_history*,
+ *     next_output_count, outputlength_bound; the mrhip_state layout is the same and its tap_dtype reads 2 or 3;
+ *   - mrhip_create_rational_bank keeps returning MRHIP_ERR_UNSUPPORTED for complex taps; a real tap_dtype here is
+ *     MRHIP_ERR_INVALID_ARG;
+ *   - as for both parents: mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is
+ *     not resident (stream-ordered launches); mrhip_sharded_create has no such constructor; a cascade takes the filter as a
  *     stage through its per-stage calls. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
@@ -216,6 +235,12 @@ int mrhip_create_rational(const void *h, int64_t hLen, int tap_dtype, int64_t nu
  * tapsPerPhi, historyLen and every error are those of mrhip_create_rational. */
 int mrhip_create_rational_bank(const void *h, int64_t hLen, int tap_dtype, int64_t num, int64_t den,
                                int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* the same for COMPLEX taps (see "Per-channel complex taps" above): `h` holds nchannels rows of hLen interleaved (re, im) pairs,
+ * row-major, row c is channel c's h.  tap_dtype C64 | C128; a real tap_dtype is MRHIP_ERR_INVALID_ARG: real taps use
+ * mrhip_create_rational_bank (which keeps refusing complex ones).  Kind selection, L, M, tapsPerPhi, historyLen and every other
+ * error are those of mrhip_create_rational. */
+int mrhip_create_rational_bank_ctaps(const void *h, int64_t hLen, int tap_dtype, int64_t num, int64_t den,
+                                     int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer = 32), src/Filters.jl:183-189
  * (+ FIRArbitrary(h, rate, Nphi), :105-117: dh = [diff(h), 0], two PFBs).  rate <= 0 is
  * MRHIP_ERR_INVALID_ARG ("rate must be greater than 0", :184). */

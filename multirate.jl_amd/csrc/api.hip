@@ -298,7 +298,15 @@ hipError_t launch_poly(const mrhip_filter *f, const TypeKey &tk, bool fused, con
 {
     *did_shiftin = false;
     *rec_written = false;             // the pair kernels and the universal kernel file the call's end state in the device record
-    if (tk.bank) {                    // per-channel taps (kernels_bank.hip): no plan_* below ever sees such a call
+    if (tk.bank && tk.complex_h) {    // per-channel complex taps (kernels_bank_ctaps.hip): no branch or plan_* below ever sees such a call
+        *rec_written = true;
+        ArbTileArgs bt;
+        size_t bl = 0;
+        if (!f->force_generic && plan_bank_ctaps_tiled(tk, a, f->num_cus, &bt, &bl))
+            return launch_poly_bank_ctaps_tiled(tk, a, bt, bl, s, kname, f->num_cus);
+        return launch_poly_bank_ctaps_generic(tk, a, s, kname);
+    }
+    if (tk.bank) {                  // per-channel taps (kernels_bank.hip): no plan_* below ever sees such a call
         *rec_written = true;
         ArbTileArgs bt;
         size_t bl = 0;
@@ -396,8 +404,9 @@ int mrhip_output_dtype(int th, int tx)
     return f64 ? MRHIP_F64 : MRHIP_F32;
 }
 
-// FIRFilter(h, ratio), src/Filters.jl:158-180, behind both constructors.  bank: `h` holds nch rows, every row goes through taps2pfb on
-// its own and the banks sit one after the other, [nch][Nphi][T] (upload_taps widens them exactly to R).
+// FIRFilter(h, ratio), src/Filters.jl:158-180, behind its three constructors.  bank: `h` holds nch rows, every row goes through taps2pfb on
+// its own and the banks sit one after the other, [nch][Nphi][T] (upload_taps widens them exactly to R; complex taps: [nch][Nphi][T]
+// (re, im) pairs, widened as the interleaved scalars they are).
 static int create_rational_common(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
                                   int device, bool bank, mrhip_filter **out)
 {
@@ -455,6 +464,19 @@ int mrhip_create_rational_bank(const void *h, int64_t hLen, int th, int64_t num,
     if (th == MRHIP_C64 || th == MRHIP_C128)
         return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_rational_bank takes Float32 / Float64 taps (complex taps in a bank are not supported)");
     if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    return create_rational_common(h, hLen, th, num, den, tx, nch, device, true, out);
+}
+
+// One FIRFilter(h_c::Vector{Complex}, ratio) per channel behind one handle (include/multirate_hip.h, "Per-channel complex taps"): `h`
+// holds nch rows of hLen (re, im) pairs.  taps2pfb moves whole elements of the tap type, upload_taps widens the interleaved scalars of
+// all rows exactly to R: the device holds [nch][Nphi][T] pairs of R, what kernels_bank_ctaps.hip reads.
+int mrhip_create_rational_bank_ctaps(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
+                                     int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_F32 || th == MRHIP_F64)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_rational_bank_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_rational_bank");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
     return create_rational_common(h, hLen, th, num, den, tx, nch, device, true, out);
 }
 
@@ -1200,6 +1222,11 @@ static hipError_t launch_poly_dyn(mrhip_filter *f, const TypeKey &tk, bool fused
                                   long long *count_dev, hipStream_t s, const char **kname, bool *did_shiftin, const DevCall *x_from = nullptr)
 {
     *did_shiftin = false;
+    if (tk.bank && tk.complex_h) {    // per-channel complex taps: the universal bank-ctaps kernel reads the call record
+        hipError_t e = launch_poly_plan(f, x_len, 1, y_capacity, count_dev, s, x_from);
+        if (e != hipSuccess) return e;
+        return launch_poly_bank_ctaps_generic(tk, a, s, kname);
+    }
     if (tk.bank) {                    // per-channel taps: the universal bank kernel reads the call record
         hipError_t e = launch_poly_plan(f, x_len, 1, y_capacity, count_dev, s, x_from);
         if (e != hipSuccess) return e;

@@ -581,7 +581,7 @@ struct TypeKey {
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
     bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family), kernels_ctaps_arb.hip (FIRArbitrary) and kernels_ctaps_farrow.hip (FIRFarrow) only
-    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only
+    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -647,6 +647,12 @@ hipError_t launch_poly_bank_generic(const TypeKey &tk, bool fused, const PolyArg
 bool plan_bank_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
 hipError_t launch_poly_bank_tiled(const TypeKey &tk, bool fused, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                   const char **kname, int num_cus);
+// per-channel COMPLEX taps (kernels_bank_ctaps.hip; a.taps is [nch][Nphi][T] (re, im) pairs; TypeKey::bank && TypeKey::complex_h): the
+// universal kernel (host- and device-planned calls) and the LDS-tiled one (host-planned calls only)
+hipError_t launch_poly_bank_ctaps_generic(const TypeKey &tk, const PolyArgs &a, hipStream_t s, const char **kname);
+bool plan_bank_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
+hipError_t launch_poly_bank_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
+                                        const char **kname, int num_cus);
 // complex taps, FIRArbitrary (kernels_ctaps_arb.hip): the universal kernel and the LDS-tiled one; both serve host- and device-planned
 // calls and take the ShiftFold epilogue
 hipError_t launch_arb_ctaps_generic(const TypeKey &tk, const ArbArgs &a, hipStream_t s, const char **kname);

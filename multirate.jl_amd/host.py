@@ -77,6 +77,7 @@ ABI = [
     ("mrhip_firdes_kaiser", _i64, [_vp, _i, _d, _d, _i, _d, _vp]),
     ("mrhip_create_rational", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_rational_bank", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_rational_bank_ctaps", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -261,7 +262,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
-        self._bank = None                 # per-channel taps (FIRFilter.per_channel): the (nchannels, hLen) matrix; self.h is its row 0
+        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
                 raise MultirateHIPError(1, "rate must be greater than 0")  # Filters.jl:184
@@ -365,6 +366,27 @@ class FIRFilter:
         f._bank = H.copy()
         return f
 
+    @classmethod
+    def per_channel_complex_taps(cls, H, ratio=1, *, device: int = 0):
+        """One FIRFilter(H[c]::Vector{Complex64 / Complex128}, ratio) per channel behind one filter object: one low-pass prototype
+        rotated to every channel's own centre frequency in front of a common resampler, per-channel Hilbert or single-sideband
+        filters, per-antenna complex equalisers.  ``H``: shape (nchannels, hLen); real ``H`` is promoted to complex, as
+        ``complex_taps`` does.  Channel c is bit for bit ``FIRFilter.complex_taps(H[c], ratio)`` fed ``x[c]``
+        (include/multirate_hip.h: per-channel complex taps).  Rational family only; the output is always complex (Complex128 if
+        either side is 64-bit); STRICT numerics only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape
+        (nchannels, tapsPer𝜙, N𝜙), complex.  The device object is created by ``mrhip_create_rational_bank_ctaps``."""
+        if isinstance(ratio, (float, np.floating)):
+            raise MultirateHIPError(5, "per_channel_complex_taps builds the rational family only (FIRArbitrary / FIRFarrow have no per-channel taps)")
+        H = np.asarray(H)
+        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+            raise MultirateHIPError(1, f"per_channel_complex_taps takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
+        if H.dtype != np.complex64 and H.dtype != np.complex128:
+            H = H.astype(np.complex64 if H.dtype == np.float32 else np.complex128)
+        H = np.ascontiguousarray(H)
+        f = cls(H[0], ratio, device=device, _complex_taps=True)
+        f._bank = H.copy()
+        return f
+
     # -- lifetime
     def _ensure(self, tx: np.dtype, nch: int):
         tx = np.dtype(tx)
@@ -378,7 +400,11 @@ class FIRFilter:
         out = C.c_void_p()
         if self._bank is not None and nch != self._bank.shape[0]:
             raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
-        if self._bank is not None:
+        if self._bank is not None and self._bank.dtype.kind == "c":
+            rc = self._lib.mrhip_create_rational_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype],
+                                                            self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
+                                                            self.device, C.byref(out))
+        elif self._bank is not None:
             rc = self._lib.mrhip_create_rational_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype],
                                                       self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
                                                       self.device, C.byref(out))

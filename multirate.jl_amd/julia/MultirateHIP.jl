@@ -86,6 +86,15 @@ function FIRFilter(H::Matrix{Th}, ratio::Rational; device::Integer = 0) where {T
     f = FIRFilter{kindof(r){Th}}(vec(copy(H)), r, 0.0, 0, -1, device, C_NULL, nothing, 0, size(H, 2))
     finalizer(destroy!, f)
 end
+# The same with COMPLEX taps (include/multirate_hip.h: per-channel complex taps): one FIRFilter(H[:, c]::Vector{Complex}, ratio) per
+# channel -- a prototype rotated to every channel's own centre frequency in front of a common resampler.  The same transposition: one
+# column per channel; bind! creates the device object through mrhip_create_rational_bank_ctaps; the output is complex for every sample
+# type.  (Like the rest of this file, never executed where the library is built and tested: no Julia there.)
+function FIRFilter(H::Matrix{Th}, ratio::Rational; device::Integer = 0) where {Th<:Union{ComplexF32,ComplexF64}}
+    r = Rational{Int}(ratio)
+    f = FIRFilter{kindof(r){Th}}(vec(copy(H)), r, 0.0, 0, -1, device, C_NULL, nothing, 0, size(H, 2))
+    finalizer(destroy!, f)
+end
 # FIRFilter(h, rate::AbstractFloat, Nphi = 32)            src/Filters.jl:183-189
 function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     rate > 0.0 || error("rate must be greater than 0")
@@ -126,7 +135,13 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
     end
     out = Ref{Ptr{Cvoid}}(C_NULL)
     Th = eltype(f.h)
-    if f.nbank > 0
+    if f.nbank > 0 && Th <: Complex
+        nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
+        check(ccall((:mrhip_create_rational_bank_ctaps, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, div(length(f.h), f.nbank), dtypecode(Th), numerator(f.ratio), denominator(f.ratio), dtypecode(Tx), nch,
+                    f.device, out))
+    elseif f.nbank > 0
         nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
         check(ccall((:mrhip_create_rational_bank, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
