@@ -124,7 +124,8 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     next_output_count, outputlength_bound; the mrhip_state layout is the same;
  *   - mrhip_get_taps(f, 0, out) returns the nchannels filter banks one after the other, each tapsPerPhi*Nphi elements laid
  *     out as mrhip_taps2pfb does;
- *   - complex taps return MRHIP_ERR_UNSUPPORTED here (they have a constructor of their own: "Per-channel complex taps" below); FIRArbitrary and FIRFarrow have no bank constructor;
+ *   - complex taps return MRHIP_ERR_UNSUPPORTED here (they have a constructor of their own: "Per-channel complex taps" below); FIRArbitrary has a
+ *     bank constructor of its own ("Per-channel taps for FIRArbitrary" below), FIRFarrow has none;
  *   - mrhip_filt_device_multi with a bank filter among its streams issues single calls; a ring on a bank filter is not
  *     resident (stream-ordered launches); mrhip_sharded_create has no bank constructor; a cascade takes a bank filter as a
  *     stage through its per-stage calls. */
@@ -147,6 +148,31 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - as for both parents: mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is
  *     not resident (stream-ordered launches); mrhip_sharded_create has no such constructor; a cascade takes the filter as a
  *     stage through its per-stage calls. */
+
+/* Per-channel taps for FIRArbitrary (mrhip_create_arbitrary_bank; Th in {F32,F64}): one FIRFilter(h_c, rate, Nphi) per channel
+ * behind one handle -- per-antenna equalisers folded into the prototype of a clock-trim resampler, per-channel matched pulse
+ * shapes, per-sensor calibration filters.  The phase schedule (update(), src/Filters.jl:663-673) does not depend on the taps, so
+ * the channels share rate, Nphi, state and call length; only the two filter banks differ.
+ *   - for every channel c the outputs, the per-call counts, the end state (inputDeficit, phiAccumulator, phiIdx, alpha, xIdx)
+ *     and the history are bit for bit those of mrhip_create_arbitrary(h_c, ..., nchannels = 1) fed x_c;
+ *   - every row gets its own dh_c = [diff(h_c), 0] in the tap type, and both taps2pfb calls are made per row;
+ *   - both dots are taken over ONE window, oldest sample first, the first product initialises the accumulator, no
+ *     start-from-zero seam (FIRArbitrary's seam method is the Matrix one, support.jl:16-31); STRICT rounds every multiply and add
+ *     separately in R, FUSED is one fma per tap; y = R(double(lo) + double(up) * alpha), the product and the sum each rounded
+ *     once in Float64;
+ *   - STRICT is the default; under mrhip_set_numerics(f, FUSED) the results are those of that one-channel filter under FUSED;
+ *   - everything that does not depend on the taps is the shared code, unchanged: the phase schedule, mrhip_set_mod_form,
+ *     outputlength, next_output_count, outputlength_bound, advance_state, set_state, reset, set_history*; the mrhip_state
+ *     layout is the same;
+ *   - mrhip_get_taps(f, 0, out) returns the nchannels pfb banks one after the other, which = 1 the dpfb banks; each bank is
+ *     tapsPerPhi*Nphi elements laid out as mrhip_taps2pfb does;
+ *   - mrhip_arbitrary_tapsforphase returns nchannels rows of tapsPerPhi taps, row c is the statement for real taps on bank c;
+ *     the range errors are unchanged;
+ *   - mrhip_create_arbitrary and mrhip_create_rational_bank* answer exactly as before; mrhip_filt_device_multi with such a
+ *     filter among its streams issues single calls; a ring on it is not resident; mrhip_sharded_create has no such
+ *     constructor; a cascade takes the filter as a stage through its per-stage calls;
+ *   - left out on purpose: FIRFarrow banks, complex-tap FIRArbitrary banks (complex taps return MRHIP_ERR_UNSUPPORTED here),
+ *     sharded banks, and the hand-scheduled shared-taps FIRArbitrary kernels (such a filter runs on its own two kernels). */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -251,6 +277,11 @@ int mrhip_create_arbitrary(const void *h, int64_t hLen, int tap_dtype, double ra
  * MRHIP_ERR_INVALID_ARG: real taps use mrhip_create_arbitrary (which keeps refusing complex ones). */
 int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
                                  int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* one FIRFilter(h_c, rate, Nphi) per channel behind one handle (see "Per-channel taps for FIRArbitrary" above): `h` holds nchannels
+ * rows of hLen taps, row-major, row c is channel c's h.  tap_dtype F32 | F64 (complex: MRHIP_ERR_UNSUPPORTED, left out).  rate, Nphi
+ * and every other argument check are those of mrhip_create_arbitrary; the filter's kind is MRHIP_FIR_ARBITRARY. */
+int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
+                                int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer, polyorder::Integer),
  * src/Filters.jl:192-198 (+ FIRFarrow(h, rate, Nphi, polyorder), :138-147, pfb2pnfb :311-321 and
  * polyfit, src/support.jl:85-88): every ROW of the tapsPerPhi x Nphi filter bank is replaced by its

@@ -482,9 +482,11 @@ int mrhip_create_rational_bank_ctaps(const void *h, int64_t hLen, int th, int64_
 
 // FIRArbitrary(h, rate, N𝜙), src/Filters.jl:105-117, behind both constructors: real taps (mrhip_create_arbitrary) and complex
 // ones (mrhip_create_arbitrary_ctaps).  The banks are held in the tap type on the host; upload_taps widens them exactly to R
-// (complex taps: as interleaved (re, im) scalars, the [Nphi][T] layout of pairs that kernels_ctaps_arb.hip reads).
+// (complex taps: as interleaved (re, im) scalars, the [Nphi][T] layout of pairs that kernels_ctaps_arb.hip reads).  bank: `h` holds
+// nch rows; every row gets its own dh and both its taps2pfb calls, and the banks sit one after the other, [nch][Nphi][T]
+// (mrhip_create_arbitrary_bank; kernels_bank_arb.hip).
 static int create_arbitrary_common(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                                   int device, mrhip_filter **out)
+                                   int device, bool bank, mrhip_filter **out)
 {
     if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
     if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
@@ -499,17 +501,24 @@ static int create_arbitrary_common(const void *h, int64_t hLen, int th, double r
     f->nch = nch; f->hLen = hLen; f->L = Nphi; f->M = 1; f->Nphi = Nphi; f->device = device;
     f->rate = rate;
     f->delta = static_cast<double>(Nphi) / rate;   // Δ = N𝜙/rate, Filters.jl:113
+    f->bank = bank;
     const size_t es = dtype_size(th);
+    const size_t rows = bank ? static_cast<size_t>(nch) : 1;      // tap vectors in `h`, each hLen long
 
-    // dh = [diff(h), 0] in the tap type (Filters.jl:106)
-    std::vector<unsigned char> dh(static_cast<size_t>(hLen) * es, 0);
-    arbitrary_dh(h, hLen, th, dh.data());
     f->T = taps2pfb(h, hLen, th, Nphi, nullptr);
     f->H = f->T - 1;
-    f->h_taps.resize(static_cast<size_t>(f->T) * Nphi * es);
-    f->h_dtaps.resize(static_cast<size_t>(f->T) * Nphi * es);
-    taps2pfb(h, hLen, th, Nphi, f->h_taps.data());
-    taps2pfb(dh.data(), hLen, th, Nphi, f->h_dtaps.data());
+    const size_t bank_bytes = static_cast<size_t>(f->T) * Nphi * es;
+    f->h_taps.resize(bank_bytes * rows);
+    f->h_dtaps.resize(bank_bytes * rows);
+    std::vector<unsigned char> dh(static_cast<size_t>(hLen) * es);
+    for (size_t r = 0; r < rows; ++r) {
+        const unsigned char *hr = static_cast<const unsigned char *>(h) + r * static_cast<size_t>(hLen) * es;
+        // dh = [diff(h), 0] in the tap type (Filters.jl:106)
+        std::fill(dh.begin(), dh.end(), static_cast<unsigned char>(0));
+        arbitrary_dh(hr, hLen, th, dh.data());
+        taps2pfb(hr, hLen, th, Nphi, f->h_taps.data() + r * bank_bytes);
+        taps2pfb(dh.data(), hLen, th, Nphi, f->h_dtaps.data() + r * bank_bytes);
+    }
 
     int rc = upload_taps(f, f->h_taps, &f->d_taps, &f->d_taps_alloc);
     if (!rc) rc = upload_taps(f, f->h_dtaps, &f->d_dtaps, &f->d_dtaps_alloc);
@@ -524,7 +533,7 @@ int mrhip_create_arbitrary(const void *h, int64_t hLen, int th, double rate, int
                            int device, mrhip_filter **out)
 {
     if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, out);
+    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, false, out);
 }
 
 int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
@@ -534,7 +543,19 @@ int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int th, double rat
     if (th == MRHIP_F32 || th == MRHIP_F64)
         return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_arbitrary_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_arbitrary");
     if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
-    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, out);
+    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, false, out);
+}
+
+// One FIRFilter(h_c, rate, N𝜙) per channel behind one handle (include/multirate_hip.h, "Per-channel taps for FIRArbitrary"): `h`
+// holds nch rows of hLen taps.
+int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
+                                int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_C64 || th == MRHIP_C128)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_arbitrary_bank takes Float32 / Float64 taps (complex taps in a FIRArbitrary bank are left out)");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, true, out);
 }
 
 // FIRFarrow(h, rate, N𝜙, polyorder), src/Filters.jl:138-147, behind all four constructors.  pnfb_in: [T][polyorder+1] coefficients,
@@ -1456,7 +1477,14 @@ static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_
         ArbTileArgs ta;
         size_t lds = 0;
         ArbLaneArgs la;
-        if (tk.complex_h) {               // complex taps (kernels_ctaps_arb.hip): no plan_* below ever sees such a call
+        if (tk.bank) {                    // per-channel taps (kernels_bank_arb.hip): no plan_* below ever sees such a call
+            a.fold = sf;                  // (both kernels write the next call's history themselves)
+            if (!f->force_generic && plan_arb_bank_tiled(tk, a, f->rate, f->num_cus, &ta, &lds))
+                MRHIP_CHECK_HIP(launch_arb_bank_tiled(tk, fused, a, ta, lds, stream, &f->last_kernel, f->num_cus));
+            else
+                MRHIP_CHECK_HIP(launch_arb_bank_generic(tk, fused, a, stream, &f->last_kernel));
+        }
+        else if (tk.complex_h) {          // complex taps (kernels_ctaps_arb.hip): no plan_* below ever sees such a call
             a.fold = sf;                  // (both kernels write the next call's history themselves)
             if (!f->force_generic && plan_ctaps_arb_tiled(tk, a, f->rate, f->num_cus, &ta, &lds))
                 MRHIP_CHECK_HIP(launch_arb_ctaps_tiled(tk, a, ta, lds, stream, &f->last_kernel, f->num_cus));
@@ -1506,7 +1534,7 @@ static int arb_call_device_sched(ArbRange &r, int64_t est, CallOut &out, ArbStat
     //  them in, both run much longer -- config 4 on a continuing stream read 3.9 or 4.5-5.1 ms per call.  Behind it, on the caller's
     //  stream: 3.93 + 0.2 ms, every call.  profiles/r06/experiments.md I; MRHIP_SCHED_BESIDE_LANE=1: as before)
     //  (the call launches est outputs: launch_range below)
-    const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && !c.tk.complex_h && arb_lane_ok(r, est) &&
+    const bool lane_shape = f->kind == MRHIP_FIR_ARBITRARY && !c.tk.complex_h && !c.tk.bank && arb_lane_ok(r, est) &&
                             arb_lane_eligible(c.tk, static_cast<int>(f->T), static_cast<int>(f->H), f->nch, f->rate, c.x_len, c.x_stride, c.y_stride) &&
                             MRHIP_ENV_INT("MRHIP_SCHED_BESIDE_LANE", 0) == 0;
     const bool inline_sched = est <= MRHIP_ENV_INT("MRHIP_SCHED_INLINE_MAX", 65536) || lane_shape;

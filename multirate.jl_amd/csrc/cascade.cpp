@@ -219,18 +219,23 @@ int mrhip_arbitrary_tapsforphase(const mrhip_filter *f, double phase, void *host
     // complex taps: the same statement per component (Julia: Complex{T} + Float64 * Complex{T} promotes both components to
     // Float64) -- the column is 2T interleaved scalars
     const size_t nc = dtype_is_complex(f->th) ? 2 : 1;
-    const size_t base = static_cast<size_t>(col - 1) * static_cast<size_t>(f->T) * nc;        // column-major T x Nphi
-    for (int64_t i = 0; i < f->T * static_cast<int64_t>(nc); ++i) {                             // :684-686, Float64 arithmetic, stored as T
-        if (!dtype_is_f64(f->th)) {
-            const double p = static_cast<double>(reinterpret_cast<const float *>(f->h_taps.data())[base + i]);
-            const double d = static_cast<double>(reinterpret_cast<const float *>(f->h_dtaps.data())[base + i]);
-            const double t = alpha * d;
-            static_cast<float *>(host_out)[i] = static_cast<float>(p + t);
-        } else {
-            const double p = reinterpret_cast<const double *>(f->h_taps.data())[base + i];
-            const double d = reinterpret_cast<const double *>(f->h_dtaps.data())[base + i];
-            const double t = alpha * d;
-            static_cast<double *>(host_out)[i] = p + t;
+    // per-channel taps (mrhip_create_arbitrary_bank): nch banks one after the other, the same statement on each; row c of the result is bank c's
+    const size_t rows = f->bank ? static_cast<size_t>(f->nch) : 1;
+    const size_t col_elems = static_cast<size_t>(f->T) * nc, bank_elems = col_elems * static_cast<size_t>(f->Nphi);
+    for (size_t r = 0; r < rows; ++r) {
+        const size_t base = r * bank_elems + static_cast<size_t>(col - 1) * col_elems;        // column-major T x Nphi
+        for (size_t i = 0; i < col_elems; ++i) {                                                // :684-686, Float64 arithmetic, stored as T
+            if (!dtype_is_f64(f->th)) {
+                const double p = static_cast<double>(reinterpret_cast<const float *>(f->h_taps.data())[base + i]);
+                const double d = static_cast<double>(reinterpret_cast<const float *>(f->h_dtaps.data())[base + i]);
+                const double t = alpha * d;
+                static_cast<float *>(host_out)[r * col_elems + i] = static_cast<float>(p + t);
+            } else {
+                const double p = reinterpret_cast<const double *>(f->h_taps.data())[base + i];
+                const double d = reinterpret_cast<const double *>(f->h_dtaps.data())[base + i];
+                const double t = alpha * d;
+                static_cast<double *>(host_out)[r * col_elems + i] = p + t;
+            }
         }
     }
     return MRHIP_OK;

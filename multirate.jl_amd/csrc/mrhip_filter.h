@@ -23,6 +23,7 @@ struct mrhip_filter {
     int numerics = MRHIP_NUMERICS_STRICT;
     int force_generic = 0;   // MRHIP_FORCE_GENERIC=1 in the environment: always use the universal kernels
     bool bank = false;       // per-channel taps (mrhip_create_rational_bank): d_taps / h_taps hold nch banks, [nch][Nphi][T]; kernels_bank.hip only
+                             // (FIRArbitrary, mrhip_create_arbitrary_bank: d_dtaps / h_dtaps as well; kernels_bank_arb.hip only)
 
     // device memory
     void *d_taps = nullptr, *d_dtaps = nullptr;            // (inside d_taps_alloc / d_dtaps_alloc: kTapPad zero elements either side)

@@ -391,8 +391,8 @@ struct ArbArgs {             // FIRArbitrary
     const void *x;
     void *y;
     const void *hist;
-    const void *taps;        // pfb  [Nphi][T]
-    const void *dtaps;       // dpfb [Nphi][T]
+    const void *taps;        // pfb  [Nphi][T]  (per-channel taps: [nch][Nphi][T])
+    const void *dtaps;       // dpfb [Nphi][T]  (per-channel taps: [nch][Nphi][T])
     const int *n_idx;        // device, per output: 1-based input index
     const double *acc;       // device, per output: phase accumulator
     long long x_stride, y_stride;
@@ -401,7 +401,7 @@ struct ArbArgs {             // FIRArbitrary
     int T, H, Nphi;
     int nch;
     const DevCall *dyn;      // != NULL: n_out is read from it (a device-planned call; the value above is an upper bound)
-    ShiftFold fold;          // arb_pipe_kernel, arb_tiled_kernel, arb_generic_kernel
+    ShiftFold fold;          // arb_pipe_kernel, arb_tiled_kernel, arb_generic_kernel, arb_ctaps_*_kernel, arb_bank_*_kernel
 };
 
 struct FarrowArgs {          // FIRFarrow
@@ -581,7 +581,7 @@ struct TypeKey {
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
     bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family), kernels_ctaps_arb.hip (FIRArbitrary) and kernels_ctaps_farrow.hip (FIRFarrow) only
-    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only)
+    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only; FIRArbitrary, mrhip_create_arbitrary_bank: ArbArgs::taps / dtaps are [nch][Nphi][T], kernels_bank_arb.hip only)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -659,6 +659,12 @@ hipError_t launch_arb_ctaps_generic(const TypeKey &tk, const ArbArgs &a, hipStre
 bool plan_ctaps_arb_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
 hipError_t launch_arb_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                   const char **kname, int num_cus);
+// per-channel taps, FIRArbitrary (kernels_bank_arb.hip; a.taps and a.dtaps are [nch][Nphi][T]; TypeKey::bank on a FIRArbitrary filter):
+// the universal kernel and the LDS-tiled one; both serve host- and device-planned calls and take the ShiftFold epilogue
+hipError_t launch_arb_bank_generic(const TypeKey &tk, bool fused, const ArbArgs &a, hipStream_t s, const char **kname);
+bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+hipError_t launch_arb_bank_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
+                                 const char **kname, int num_cus);
 // complex taps, FIRFarrow (kernels_ctaps_farrow.hip): the universal kernel and the LDS-tiled one; both serve host- and device-planned
 // calls and take the ShiftFold epilogue.  a.pnfb: [T][polyorder+1] (re, im) pairs of Float64
 hipError_t launch_farrow_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, hipStream_t s, const char **kname);

@@ -158,8 +158,13 @@ int ring_end_epoch(mrhip_ring *r, bool relaunch)
     MRHIP_CHECK_HIP(hipMemcpy(&fetched, &r->dev->head, sizeof(fetched), hipMemcpyDeviceToHost));
     // everything fetched has been filtered (the workers leave only when no fetched chunk holds a ticket of theirs)
     const uint64_t left = r->pushed - fetched;
-    if (fetched % mrhip::kRingDepth != 0 && r->slot_bytes)
-        MRHIP_CHECK_HIP(hipMemcpy(r->hist, static_cast<unsigned char *>(r->hist) + (fetched % mrhip::kRingDepth) * r->slot_bytes, r->slot_bytes, hipMemcpyDeviceToDevice));
+    // (on the ring's own stream, and waited for: a device-to-device hipMemcpy goes down the null stream, which r->stream -- non-blocking -- is
+    //  not ordered with, and may return before the copy has run; mrhip_ring_close's copy of slot 0 back into the filter then read a slot 0
+    //  that was only partly rewritten: the first 8 KiB pieces new, the rest chunk 0's call-start history)
+    if (fetched % mrhip::kRingDepth != 0 && r->slot_bytes) {
+        MRHIP_CHECK_HIP(hipMemcpyAsync(r->hist, static_cast<unsigned char *>(r->hist) + (fetched % mrhip::kRingDepth) * r->slot_bytes, r->slot_bytes, hipMemcpyDeviceToDevice, r->stream));
+        MRHIP_CHECK_HIP(hipStreamSynchronize(r->stream));
+    }
     std::vector<mrhip::RingDesc> keep(static_cast<size_t>(left));
     for (uint64_t i = 0; i < left; ++i) keep[i] = r->host->desc[(fetched + i) % mrhip::kRingDepth];
     const uint64_t tb0 = left ? keep[0].tile_base : r->tile_base;

@@ -80,6 +80,7 @@ ABI = [
     ("mrhip_create_rational_bank_ctaps", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_arbitrary_bank", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -262,7 +263,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
-        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps): the (nchannels, hLen) matrix; self.h is its row 0
+        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
                 raise MultirateHIPError(1, "rate must be greater than 0")  # Filters.jl:184
@@ -355,7 +356,7 @@ class FIRFilter:
         only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape (nchannels, tapsPer𝜙, N𝜙).  The device
         object is created by ``mrhip_create_rational_bank``."""
         if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "per_channel builds the rational family only (FIRArbitrary / FIRFarrow have no per-channel taps)")
+            raise MultirateHIPError(5, "per_channel builds the rational family only (a float rate: FIRFilter.per_channel_arbitrary; FIRFarrow has no per-channel taps)")
         H = np.asarray(H)
         if H.dtype.kind == "c":
             raise MultirateHIPError(5, "per_channel takes Float32/Float64 taps (complex taps in a bank are not supported)")
@@ -387,6 +388,27 @@ class FIRFilter:
         f._bank = H.copy()
         return f
 
+    @classmethod
+    def per_channel_arbitrary(cls, H, rate, Nphi: int = 32, *, device: int = 0, numerics: int = NUMERICS_STRICT):
+        """One FIRFilter(H[c], rate::Float, N𝜙) per channel behind one filter object: FIRArbitrary with per-channel taps (per-antenna
+        equalisers folded into the prototype of a clock-trim resampler, per-channel matched pulse shapes in front of a common
+        symbol-rate change, per-sensor calibration filters).  ``H``: shape (nchannels, hLen), Float32 or Float64.  The phase schedule
+        does not depend on the taps: rate, N𝜙, state and call length are shared, only the two filter banks differ; channel c is bit
+        for bit ``FIRFilter(H[c], rate, Nphi)`` fed ``x[c]``, under STRICT and FUSED (include/multirate_hip.h: per-channel taps for
+        FIRArbitrary).  The filter binds to exactly ``H.shape[0]`` channels; ``taps(which)`` has shape (nchannels, tapsPer𝜙, N𝜙) and
+        ``tapsforphase`` (nchannels, tapsPer𝜙).  The device object is created by ``mrhip_create_arbitrary_bank``."""
+        if not isinstance(rate, (float, np.floating)):
+            raise MultirateHIPError(1, "per_channel_arbitrary takes a floating-point rate (a Rational ratio: FIRFilter.per_channel)")
+        H = np.asarray(H)
+        if H.dtype.kind == "c":
+            raise MultirateHIPError(5, "per_channel_arbitrary takes Float32/Float64 taps (complex taps in a FIRArbitrary bank are not supported)")
+        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+            raise MultirateHIPError(1, f"per_channel_arbitrary takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
+        H = np.ascontiguousarray(_as_taps(H))
+        f = cls(H[0], float(rate), int(Nphi), device=device, numerics=numerics)
+        f._bank = H.copy()
+        return f
+
     # -- lifetime
     def _ensure(self, tx: np.dtype, nch: int):
         tx = np.dtype(tx)
@@ -400,7 +422,10 @@ class FIRFilter:
         out = C.c_void_p()
         if self._bank is not None and nch != self._bank.shape[0]:
             raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
-        if self._bank is not None and self._bank.dtype.kind == "c":
+        if self._bank is not None and self.kind == ARBITRARY:
+            rc = self._lib.mrhip_create_arbitrary_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
+                                                       self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self._bank is not None and self._bank.dtype.kind == "c":
             rc = self._lib.mrhip_create_rational_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype],
                                                             self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
                                                             self.device, C.byref(out))
@@ -522,7 +547,8 @@ class FIRFilter:
         tapsforphase(kernel::FIRFarrow, phase), src/Filters.jl:764-775."""
         if self._handle is None or self.kind not in (ARBITRARY, FARROW):
             raise MultirateHIPError(1, "tapsforphase() needs a bound FIRArbitrary or FIRFarrow filter")
-        out = np.zeros(self.tapsPerPhi, dtype=self.h.dtype)
+        rows = (self._nch, self.tapsPerPhi) if self._bank is not None else self.tapsPerPhi   # (a per-channel filter: one row per channel)
+        out = np.zeros(rows, dtype=self.h.dtype)
         fn = self._lib.mrhip_farrow_tapsforphase if self.kind == FARROW else self._lib.mrhip_arbitrary_tapsforphase
         _check(fn(self._handle, float(phase), _ptr(out)))
         return out
