@@ -125,7 +125,7 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - mrhip_get_taps(f, 0, out) returns the nchannels filter banks one after the other, each tapsPerPhi*Nphi elements laid
  *     out as mrhip_taps2pfb does;
  *   - complex taps return MRHIP_ERR_UNSUPPORTED here (they have a constructor of their own: "Per-channel complex taps" below); FIRArbitrary has a
- *     bank constructor of its own ("Per-channel taps for FIRArbitrary" below), FIRFarrow has none;
+ *     bank constructor of its own ("Per-channel taps for FIRArbitrary" below), and so has FIRFarrow ("Per-channel taps for FIRFarrow");
  *   - mrhip_filt_device_multi with a bank filter among its streams issues single calls; a ring on a bank filter is not
  *     resident (stream-ordered launches); mrhip_sharded_create has no bank constructor; a cascade takes a bank filter as a
  *     stage through its per-stage calls. */
@@ -171,8 +171,36 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - mrhip_create_arbitrary and mrhip_create_rational_bank* answer exactly as before; mrhip_filt_device_multi with such a
  *     filter among its streams issues single calls; a ring on it is not resident; mrhip_sharded_create has no such
  *     constructor; a cascade takes the filter as a stage through its per-stage calls;
- *   - left out on purpose: FIRFarrow banks, complex-tap FIRArbitrary banks (complex taps return MRHIP_ERR_UNSUPPORTED here),
- *     sharded banks, and the hand-scheduled shared-taps FIRArbitrary kernels (such a filter runs on its own two kernels). */
+ *   - left out on purpose: complex-tap FIRArbitrary banks (complex taps return MRHIP_ERR_UNSUPPORTED here), sharded banks, and
+ *     the hand-scheduled shared-taps FIRArbitrary kernels (such a filter runs on its own two kernels).  FIRFarrow banks have a
+ *     constructor of their own (next). */
+
+/* Per-channel taps for FIRFarrow (mrhip_create_farrow_bank; Th in {F32,F64}): one FIRFilter(h_c, rate, Nphi, polyorder) per
+ * channel behind one handle -- a per-antenna equaliser or a per-sensor calibration filter in front of a common, continuously
+ * variable rate change.  The phase schedule (update(), src/Filters.jl:780-792) does not depend on the taps, so the channels
+ * share rate, Nphi, polyorder, state and call length; only the polynomial banks differ.
+ *   - for every channel c the outputs, the per-call counts, the end state (inputDeficit, phiAccumulator, phiIdx) and the history
+ *     are bit for bit those of mrhip_create_farrow(h_c, ..., nchannels = 1) fed x_c;
+ *   - every row goes through taps2pfb and the per-row polynomial fit on its own, exactly as mrhip_create_farrow treats one h;
+ *     the coefficients are stored in the tap type;
+ *   - per tap: Horner in Float64 from the highest power, t = phi*v; v = coef + t, the product and the sum each rounded once
+ *     (never fused, under FUSED neither), the result rounded once to the tap type and widened exactly to R;
+ *   - the dot: oldest sample first, the first product initialises the accumulator, outputs on the start-from-zero seam of
+ *     support.jl:46 then take 0 + acc per component; the remaining taps are a separately rounded multiply and add under STRICT
+ *     and one fma under FUSED;
+ *   - STRICT is the default; under mrhip_set_numerics(f, FUSED) the results are those of that one-channel filter under FUSED;
+ *   - everything that does not depend on the taps is the shared code, unchanged: the phase schedule, mrhip_set_mod_form,
+ *     outputlength, next_output_count, outputlength_bound, advance_state, set_state, reset, set_history*; the mrhip_state
+ *     layout is the same;
+ *   - mrhip_get_pnfb returns the nchannels banks one after the other, [nchannels][tapsPerPhi][polyorder+1] Float64;
+ *   - mrhip_farrow_tapsforphase returns nchannels rows of tapsPerPhi taps, row c is the statement for real taps on bank c; the
+ *     range error is unchanged;
+ *   - mrhip_create_farrow*, mrhip_create_arbitrary_bank and mrhip_create_rational_bank* answer exactly as before;
+ *     mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is not resident;
+ *     mrhip_sharded_create has no such constructor; a cascade takes the filter as a stage through its per-stage calls;
+ *   - left out on purpose: complex-tap FIRFarrow banks (complex taps return MRHIP_ERR_UNSUPPORTED here), complex-tap FIRArbitrary
+ *     banks, a caller-fitted pnfb for banks, sharded banks, a resident ring for banks, and the shared-taps FIRFarrow kernels
+ *     farrow_pipe_kernel / farrow_wave_kernel (such a filter runs on its own two kernels). */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -290,6 +318,10 @@ int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int tap_dtype, doub
  * done on the host in Float64 by a Householder QR. */
 int mrhip_create_farrow(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi, int64_t polyorder,
                         int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* one FIRFilter(h_c, rate, Nphi, polyorder) per channel behind one handle (see "Per-channel taps for FIRFarrow" above): `h` holds
+ * nchannels rows of hLen taps, row-major, row c is channel c's h.  tap_dtype F32 | F64 (complex: MRHIP_ERR_UNSUPPORTED, left out).
+ * rate, Nphi, polyorder and every other argument check are those of mrhip_create_farrow; the filter's kind is MRHIP_FIR_FARROW. */
+int mrhip_create_farrow_bank(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi, int64_t polyorder, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* same, with the polynomial filter bank supplied by the caller: pnfb[tapsPerPhi][polyorder+1] Float64,
  * ascending powers (the layout of Poly.a), tapsPerPhi = ceil(hLen/Nphi); values are rounded to the tap type
  * as the reference's Poly{T} storage does.  Lets a caller fit with its own least-squares routine (the
@@ -306,11 +338,11 @@ int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int tap_dtype, double
 int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
                                    int64_t polyorder, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* the polynomial filter bank in use, [tapsPerPhi][polyorder+1] Float64 (pfb2pnfb's result); complex taps: (re, im) pairs of
- * Float64, twice as many values */
+ * Float64, twice as many values; per-channel taps (mrhip_create_farrow_bank): the nchannels banks one after the other */
 int mrhip_get_pnfb(const mrhip_filter *f, double *host_out);
 /* replaces tapsforphase(kernel::FIRFarrow, phase), src/Filters.jl:764-775: tapsPerPhi taps of tap_dtype
  * for a phase in [0, Nphi+1] (host evaluation; MRHIP_ERR_INVALID_ARG outside the range like :765); complex taps: tapsPerPhi
- * complex taps, the statement per component */
+ * complex taps, the statement per component; per-channel taps (mrhip_create_farrow_bank): nchannels rows of tapsPerPhi taps */
 int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_out);
 /* replaces tapsforphase(kernel::FIRArbitrary, phase), src/Filters.jl:677-690: (alpha, phiIdx) = modf(phase);
  * taps[i] = pfb[i, phiIdx] + alpha * dpfb[i, phiIdx], evaluated in Float64 (alpha is a Float64 there) and stored in

@@ -559,9 +559,11 @@ int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int th, double rate
 }
 
 // FIRFarrow(h, rate, N𝜙, polyorder), src/Filters.jl:138-147, behind all four constructors.  pnfb_in: [T][polyorder+1] coefficients,
-// ascending powers -- scalars for real taps, (re, im) pairs for complex ones (the layout kernels_ctaps_farrow.hip reads).
+// ascending powers -- scalars for real taps, (re, im) pairs for complex ones (the layout kernels_ctaps_farrow.hip reads).  bank: pnfb_in
+// holds nch such banks one after the other, [nch][T][polyorder+1] (mrhip_create_farrow_bank; kernels_bank_farrow.hip), and the degree-major
+// copy for farrow_wave_kernel is never built.
 static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen, int th, double rate, int64_t Nphi,
-                                int64_t polyorder, int tx, int64_t nch, int device, mrhip_filter **out)
+                                int64_t polyorder, int tx, int64_t nch, int device, bool bank, mrhip_filter **out)
 {
     DeviceGuard guard(device);
     if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
@@ -574,6 +576,7 @@ static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen
     f->rate = rate;
     f->delta = static_cast<double>(Nphi) / rate;   // Δ = N𝜙/rate, Filters.jl:143
     f->polyorder = polyorder;
+    f->bank = bank;
     f->T = (hLen + Nphi - 1) / Nphi;
     f->H = f->T - 1;
     f->h_pnfb = pnfb_in;
@@ -583,7 +586,7 @@ static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen
     if (hipMalloc(reinterpret_cast<void **>(&f->d_pnfb), f->h_pnfb.size() * sizeof(double)) != hipSuccess ||
         hipMemcpy(f->d_pnfb, f->h_pnfb.data(), f->h_pnfb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(MRHIP_ERR_HIP, "uploading the polynomial filter bank failed");
-    if (!rc && f->T <= 32 && !dtype_is_complex(th)) {   // the same bank degree-major, padded to 32 taps with zeros (kernels_farrow_wave.hip)
+    if (!rc && f->T <= 32 && !dtype_is_complex(th) && !bank) {   // the same bank degree-major, padded to 32 taps with zeros (kernels_farrow_wave.hip)
         std::vector<double> t(static_cast<size_t>(polyorder + 1) * 32, 0.0);
         for (int64_t i = 0; i < f->T; ++i)
             for (int64_t j = 0; j <= polyorder; ++j) t[static_cast<size_t>(j) * 32 + i] = f->h_pnfb[static_cast<size_t>(i) * (polyorder + 1) + j];
@@ -598,6 +601,24 @@ static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen
     return MRHIP_OK;
 }
 
+// pfb = taps2pfb(h, Nphi); one polynomial per ROW (Filters.jl:139-140, :315-318): the fit of one tap vector `h` into pn, [T][polyorder+1].
+// false: the fit is rank deficient.
+static bool farrow_fit(const void *h, int64_t hLen, int th, int64_t Nphi, int64_t polyorder, double *pn)
+{
+    const size_t es = dtype_scalar_size(th);
+    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
+    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
+    taps2pfb(h, hLen, th, Nphi, pfb.data());
+    std::vector<double> row(static_cast<size_t>(Nphi));
+    for (int64_t i = 0; i < T; ++i) {
+        for (int64_t c = 0; c < Nphi; ++c)          // element (row i, column c) of the column-major bank
+            row[static_cast<size_t>(c)] = th == MRHIP_F32 ? static_cast<double>(reinterpret_cast<const float *>(pfb.data())[c * T + i])
+                                                          : reinterpret_cast<const double *>(pfb.data())[c * T + i];
+        if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), &pn[static_cast<size_t>(i) * (polyorder + 1)])) return false;
+    }
+    return true;
+}
+
 int mrhip_create_farrow(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
                         int64_t nch, int device, mrhip_filter **out)
 {
@@ -606,20 +627,32 @@ int mrhip_create_farrow(const void *h, int64_t hLen, int th, double rate, int64_
     if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
     if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
         return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
-    // pfb = taps2pfb(h, Nphi); one polynomial per ROW (Filters.jl:139-140, :315-318)
-    const size_t es = dtype_scalar_size(th);
-    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
-    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
-    taps2pfb(h, hLen, th, Nphi, pfb.data());
-    std::vector<double> pn(static_cast<size_t>(T) * (polyorder + 1)), row(static_cast<size_t>(Nphi));
-    for (int64_t i = 0; i < T; ++i) {
-        for (int64_t c = 0; c < Nphi; ++c)          // element (row i, column c) of the column-major bank
-            row[static_cast<size_t>(c)] = th == MRHIP_F32 ? static_cast<double>(reinterpret_cast<const float *>(pfb.data())[c * T + i])
-                                                          : reinterpret_cast<const double *>(pfb.data())[c * T + i];
-        if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), &pn[static_cast<size_t>(i) * (polyorder + 1)]))
+    const int64_t T = (hLen + Nphi - 1) / Nphi;
+    std::vector<double> pn(static_cast<size_t>(T) * (polyorder + 1));
+    if (!farrow_fit(h, hLen, th, Nphi, polyorder, pn.data())) return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
+}
+
+// One FIRFilter(h_c, rate, N𝜙, polyorder) per channel behind one handle (include/multirate_hip.h, "Per-channel taps for FIRFarrow"): `h`
+// holds nch rows of hLen taps; every row goes through taps2pfb and the per-row fit on its own.
+int mrhip_create_farrow_bank(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
+                             int64_t nch, int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_C64 || th == MRHIP_C128)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_bank takes Float32 / Float64 taps (complex taps in a FIRFarrow bank are left out)");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
+    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
+    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
+        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
+    const int64_t T = (hLen + Nphi - 1) / Nphi;
+    const size_t bank_elems = static_cast<size_t>(T) * (polyorder + 1), es = dtype_scalar_size(th);
+    std::vector<double> pn(bank_elems * static_cast<size_t>(nch));
+    for (int64_t r = 0; r < nch; ++r)
+        if (!farrow_fit(static_cast<const unsigned char *>(h) + static_cast<size_t>(r) * hLen * es, hLen, th, Nphi, polyorder, &pn[r * bank_elems]))
             return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
-    }
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, out);
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, true, out);
 }
 
 int mrhip_create_farrow_pnfb(const double *pnfb, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder,
@@ -631,7 +664,7 @@ int mrhip_create_farrow_pnfb(const double *pnfb, int64_t hLen, int th, double ra
     if (polyorder < 0 || polyorder > 32) return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32");
     const int64_t T = (hLen + Nphi - 1) / Nphi;
     std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1));
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, out);
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
 }
 
 // The same two constructors for COMPLEX taps (include/multirate_hip.h, "Complex taps", FIRFarrow part).  The Vandermonde matrix of
@@ -664,7 +697,7 @@ int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int th, double rate, 
                 return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
             for (size_t j = 0; j < np; ++j) pn[(static_cast<size_t>(i) * np + j) * 2 + comp] = fit[j];
         }
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, out);
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
 }
 
 int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder,
@@ -679,7 +712,7 @@ int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int th, dou
     if (polyorder < 0 || polyorder > 32) return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32");
     const int64_t T = (hLen + Nphi - 1) / Nphi;
     std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1) * 2);
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, out);
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
 }
 
 int mrhip_polyfit(const double *y, int64_t n, int64_t polyorder, double *coef)
@@ -707,13 +740,16 @@ int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_ou
     // complex taps: the same statement per component (Real*Complex and Complex+Complex are by components) -- a polynomial is
     // P+1 (re, im) pairs, the result T interleaved pairs
     const int64_t nc = dtype_is_complex(f->th) ? 2 : 1;
-    for (int64_t i = 0; i < f->T * nc; ++i) {
-        const double *c = &f->h_pnfb[static_cast<size_t>(i / nc) * (P + 1) * nc + i % nc];
-        double yv = c[P * nc];
-        for (int64_t j = P - 1; j >= 0; --j) { const double t = phase * yv; yv = c[j * nc] + t; }
-        if (!dtype_is_f64(f->th)) static_cast<float *>(host_out)[i] = static_cast<float>(yv);
-        else static_cast<double *>(host_out)[i] = yv;
-    }
+    // per-channel taps (mrhip_create_farrow_bank): nch banks one after the other, the same statement on each; row c of the result is bank c's
+    const int64_t rows = f->bank ? f->nch : 1, row_elems = f->T * nc;
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t i = 0; i < row_elems; ++i) {
+            const double *c = &f->h_pnfb[(static_cast<size_t>(r) * f->T + static_cast<size_t>(i / nc)) * (P + 1) * nc + i % nc];
+            double yv = c[P * nc];
+            for (int64_t j = P - 1; j >= 0; --j) { const double t = phase * yv; yv = c[j * nc] + t; }
+            if (!dtype_is_f64(f->th)) static_cast<float *>(host_out)[r * row_elems + i] = static_cast<float>(yv);
+            else static_cast<double *>(host_out)[r * row_elems + i] = yv;
+        }
     return MRHIP_OK;
 }
 
@@ -1443,7 +1479,14 @@ static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_
         if (int rc = timing_mark(f, stream)) return rc;
         ArbTileArgs fta;
         size_t flds = 0;
-        if (tk.complex_h) {               // complex taps (kernels_ctaps_farrow.hip): no plan_* below ever sees such a call
+        if (tk.bank) {                    // per-channel taps (kernels_bank_farrow.hip): no plan_* below ever sees such a call
+            fa.fold = sf;                 // (both kernels write the next call's history themselves)
+            if (!f->force_generic && plan_farrow_bank_tiled(tk, fa, f->rate, f->num_cus, &fta, &flds))
+                MRHIP_CHECK_HIP(launch_farrow_bank_tiled(tk, fused, fa, fta, flds, stream, &f->last_kernel, f->num_cus));
+            else
+                MRHIP_CHECK_HIP(launch_farrow_bank_generic(tk, fused, fa, stream, &f->last_kernel));
+        }
+        else if (tk.complex_h) {          // complex taps (kernels_ctaps_farrow.hip): no plan_* below ever sees such a call
             fa.fold = sf;                 // (both kernels write the next call's history themselves)
             if (!f->force_generic && plan_ctaps_farrow_tiled(tk, fa, f->rate, f->num_cus, &fta, &flds))
                 MRHIP_CHECK_HIP(launch_farrow_ctaps_tiled(tk, fa, fta, flds, stream, &f->last_kernel, f->num_cus));

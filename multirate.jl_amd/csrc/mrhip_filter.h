@@ -24,13 +24,15 @@ struct mrhip_filter {
     int force_generic = 0;   // MRHIP_FORCE_GENERIC=1 in the environment: always use the universal kernels
     bool bank = false;       // per-channel taps (mrhip_create_rational_bank): d_taps / h_taps hold nch banks, [nch][Nphi][T]; kernels_bank.hip only
                              // (FIRArbitrary, mrhip_create_arbitrary_bank: d_dtaps / h_dtaps as well; kernels_bank_arb.hip only)
+                             // (FIRFarrow, mrhip_create_farrow_bank: d_pnfb / h_pnfb hold nch banks, [nch][T][polyorder+1], no d_pnfb_t;
+                             //  kernels_bank_farrow.hip only)
 
     // device memory
     void *d_taps = nullptr, *d_dtaps = nullptr;            // (inside d_taps_alloc / d_dtaps_alloc: kTapPad zero elements either side)
     void *d_taps_alloc = nullptr, *d_dtaps_alloc = nullptr;
     double *d_pnfb = nullptr;              // FIRFarrow: polynomial filter bank on the device
     double *d_pnfb_t = nullptr;            // ... degree-major and padded to 32 taps, [polyorder+1][32] (farrow_wave_kernel; tapsPerPhi <= 32)
-    std::vector<double> h_pnfb;            // ... and on the host, [T][polyorder+1]
+    std::vector<double> h_pnfb;            // ... and on the host, [T][polyorder+1] (per-channel taps: [nch][T][polyorder+1])
     int64_t polyorder = 0;
     void *d_hist[3] = {nullptr, nullptr, nullptr};   // [0], [1]: ping-pong; [2]: zeros(historyLen), read-only -- what a reset() makes current (hist_other)
     unsigned *d_counters = nullptr;   // pair kernel's dynamic scheduling: 33 counters, 256 bytes apart, zero between launches

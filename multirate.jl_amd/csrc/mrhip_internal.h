@@ -408,7 +408,8 @@ struct FarrowArgs {          // FIRFarrow
     const void *x;
     void *y;
     const void *hist;
-    const double *pnfb;      // device, [T][polyorder+1] ascending powers (values representable in Th); complex taps: (re, im) pairs
+    const double *pnfb;      // device, [T][polyorder+1] ascending powers (values representable in Th); complex taps: (re, im) pairs;
+                             // per-channel taps (mrhip_create_farrow_bank): [nch][T][polyorder+1]
     const int *n_idx;        // device, per output: 1-based input index
     const double *acc;       // device, per output: the Float64 phase 𝜙Idx
     long long x_stride, y_stride;
@@ -420,7 +421,7 @@ struct FarrowArgs {          // FIRFarrow
     int seam_below;          // outputs whose 1-based input index n < this start from +0 (support.jl:46): T, or 0 for a
                              // piece that continues a call (mrhip_filt_device splits long calls)
     const DevCall *dyn;      // != NULL: n_out is read from it
-    ShiftFold fold;          // farrow_wave_kernel, farrow_pipe_kernel, farrow_tiled_kernel, farrow_ctaps_*_kernel
+    ShiftFold fold;          // farrow_wave_kernel, farrow_pipe_kernel, farrow_tiled_kernel, farrow_ctaps_*_kernel, farrow_bank_*_kernel
 };
 
 struct HistArgs {            // shiftin! (src/support.jl:61-80) for every channel
@@ -581,7 +582,7 @@ struct TypeKey {
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
     bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family), kernels_ctaps_arb.hip (FIRArbitrary) and kernels_ctaps_farrow.hip (FIRFarrow) only
-    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only; FIRArbitrary, mrhip_create_arbitrary_bank: ArbArgs::taps / dtaps are [nch][Nphi][T], kernels_bank_arb.hip only)
+    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only; FIRArbitrary, mrhip_create_arbitrary_bank: ArbArgs::taps / dtaps are [nch][Nphi][T], kernels_bank_arb.hip only; FIRFarrow, mrhip_create_farrow_bank: FarrowArgs::pnfb is [nch][T][polyorder+1], kernels_bank_farrow.hip only)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -665,6 +666,12 @@ hipError_t launch_arb_bank_generic(const TypeKey &tk, bool fused, const ArbArgs 
 bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
 hipError_t launch_arb_bank_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                  const char **kname, int num_cus);
+// per-channel taps, FIRFarrow (kernels_bank_farrow.hip; a.pnfb is [nch][T][polyorder+1]; TypeKey::bank on a FIRFarrow filter): the
+// universal kernel and the LDS-tiled one; both serve host- and device-planned calls and take the ShiftFold epilogue
+hipError_t launch_farrow_bank_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, hipStream_t s, const char **kname);
+bool plan_farrow_bank_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+hipError_t launch_farrow_bank_tiled(const TypeKey &tk, bool fused, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
+                                    const char **kname, int num_cus);
 // complex taps, FIRFarrow (kernels_ctaps_farrow.hip): the universal kernel and the LDS-tiled one; both serve host- and device-planned
 // calls and take the ShiftFold epilogue.  a.pnfb: [T][polyorder+1] (re, im) pairs of Float64
 hipError_t launch_farrow_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, hipStream_t s, const char **kname);

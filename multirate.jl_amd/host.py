@@ -82,6 +82,7 @@ ABI = [
     ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_bank", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_farrow_bank", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -263,7 +264,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
-        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary): the (nchannels, hLen) matrix; self.h is its row 0
+        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
                 raise MultirateHIPError(1, "rate must be greater than 0")  # Filters.jl:184
@@ -356,7 +357,7 @@ class FIRFilter:
         only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape (nchannels, tapsPer𝜙, N𝜙).  The device
         object is created by ``mrhip_create_rational_bank``."""
         if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "per_channel builds the rational family only (a float rate: FIRFilter.per_channel_arbitrary; FIRFarrow has no per-channel taps)")
+            raise MultirateHIPError(5, "per_channel builds the rational family only (a float rate: FIRFilter.per_channel_arbitrary, FIRFilter.per_channel_farrow)")
         H = np.asarray(H)
         if H.dtype.kind == "c":
             raise MultirateHIPError(5, "per_channel takes Float32/Float64 taps (complex taps in a bank are not supported)")
@@ -409,6 +410,30 @@ class FIRFilter:
         f._bank = H.copy()
         return f
 
+    @classmethod
+    def per_channel_farrow(cls, H, rate, Nphi: int = 32, polyorder=4, *, device: int = 0, numerics: int = NUMERICS_STRICT):
+        """One FIRFilter(H[c], rate::Float, N𝜙, polyorder) per channel behind one filter object: FIRFarrow with per-channel taps (a
+        per-antenna equaliser or per-sensor calibration filter in front of a common, continuously variable rate change).  ``H``: shape
+        (nchannels, hLen), Float32 or Float64.  The phase schedule does not depend on the taps: rate, N𝜙, polyorder, state and call
+        length are shared, only the polynomial banks differ (every row is fitted on its own); channel c is bit for bit
+        ``FIRFilter(H[c], rate, Nphi, polyorder)`` fed ``x[c]``, under STRICT and FUSED (include/multirate_hip.h: per-channel taps
+        for FIRFarrow).  The filter binds to exactly ``H.shape[0]`` channels; ``pnfb()`` has shape (nchannels, tapsPer𝜙, polyorder+1)
+        and ``tapsforphase`` (nchannels, tapsPer𝜙).  A caller-fitted ``pnfb`` is not accepted here.  The device object is created by
+        ``mrhip_create_farrow_bank``."""
+        if not isinstance(rate, (float, np.floating)):
+            raise MultirateHIPError(1, "per_channel_farrow takes a floating-point rate (a Rational ratio: FIRFilter.per_channel)")
+        if polyorder is None:
+            raise MultirateHIPError(1, "per_channel_farrow takes a polyorder (without one: FIRFilter.per_channel_arbitrary)")
+        H = np.asarray(H)
+        if H.dtype.kind == "c":
+            raise MultirateHIPError(5, "per_channel_farrow takes Float32/Float64 taps (complex taps in a FIRFarrow bank are not supported)")
+        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+            raise MultirateHIPError(1, f"per_channel_farrow takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
+        H = np.ascontiguousarray(_as_taps(H))
+        f = cls(H[0], float(rate), int(Nphi), int(polyorder), device=device, numerics=numerics)
+        f._bank = H.copy()
+        return f
+
     # -- lifetime
     def _ensure(self, tx: np.dtype, nch: int):
         tx = np.dtype(tx)
@@ -425,6 +450,9 @@ class FIRFilter:
         if self._bank is not None and self.kind == ARBITRARY:
             rc = self._lib.mrhip_create_arbitrary_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
                                                        self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self._bank is not None and self.kind == FARROW:
+            rc = self._lib.mrhip_create_farrow_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
+                                                    self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
         elif self._bank is not None and self._bank.dtype.kind == "c":
             rc = self._lib.mrhip_create_rational_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype],
                                                             self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
@@ -535,10 +563,12 @@ class FIRFilter:
         return out.reshape(self.Nphi, self.tapsPerPhi).T.copy()
 
     def pnfb(self) -> np.ndarray:
-        """FIRFarrow.pnfb (src/Filters.jl:126): tapsPer𝜙 polynomials, ascending powers, shape (tapsPer𝜙, polyorder+1)."""
+        """FIRFarrow.pnfb (src/Filters.jl:126): tapsPer𝜙 polynomials, ascending powers, shape (tapsPer𝜙, polyorder+1); a per-channel
+        filter (FIRFilter.per_channel_farrow): (nchannels, tapsPer𝜙, polyorder+1)."""
         if self._handle is None or self.kind != FARROW:
             raise MultirateHIPError(1, "pnfb() needs a bound FIRFarrow filter")
-        out = np.zeros((self.tapsPerPhi, self.polyorder + 1), dtype=np.complex128 if self.h.dtype.kind == "c" else np.float64)
+        shape = (self.tapsPerPhi, self.polyorder + 1)
+        out = np.zeros((self._nch,) + shape if self._bank is not None else shape, dtype=np.complex128 if self.h.dtype.kind == "c" else np.float64)
         _check(self._lib.mrhip_get_pnfb(self._handle, _ptr(out)))
         return out
 

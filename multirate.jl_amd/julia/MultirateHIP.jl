@@ -131,6 +131,17 @@ function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer, polyorder:
     finalizer(destroy!, f)
 end
 
+# One FIRFilter(H[:, c], rate, Nphi, polyorder) per channel behind one filter object (include/multirate_hip.h: per-channel taps for
+# FIRFarrow): the phase schedule does not depend on the taps, so the channels share rate, Nphi, polyorder, state and call length; every
+# column is fitted on its own.  One COLUMN holds one channel's taps (the row-major [nch][hLen] layout mrhip_create_farrow_bank reads);
+# the filter binds to exactly size(H, 2) channels.  (Like the rest of this file, never executed where the library is built and tested:
+# no Julia there.)
+function FIRFilter(H::Matrix{Th}, rate::AbstractFloat, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{Float32,Float64}}
+    rate > 0.0 || error("rate must be greater than 0")
+    f = FIRFilter{FIRFarrow{Th}}(vec(copy(H)), nothing, Float64(rate), Nphi, polyorder, device, C_NULL, nothing, 0, size(H, 2))
+    finalizer(destroy!, f)
+end
+
 function destroy!(f::FIRFilter)
     f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle)
     f.handle = C_NULL
@@ -144,7 +155,12 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
     end
     out = Ref{Ptr{Cvoid}}(C_NULL)
     Th = eltype(f.h)
-    if f.nbank > 0 && f.ratio === nothing
+    if f.nbank > 0 && f.ratio === nothing && f.polyorder >= 0
+        nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
+        check(ccall((:mrhip_create_farrow_bank, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, div(length(f.h), f.nbank), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
+    elseif f.nbank > 0 && f.ratio === nothing
         nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
         check(ccall((:mrhip_create_arbitrary_bank, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),

@@ -1,0 +1,103 @@
+"""CPU-only checks of per-channel taps for FIRFarrow (FIRFilter.per_channel_farrow, mrhip_create_farrow_bank,
+csrc/kernels_bank_farrow.hip): the argument errors of the Python constructor, the description of the unbound filter, the exported symbol
+and its declaration, the build conditions of the kernel unit and the instantiations in the object the build made: both kernels for
+(Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED = 12 each, none with scratch memory or
+AccVGPRs."""
+import os
+import re
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from test_build_properties import CSRC, LLVM, _kernel_scratch
+
+
+def test_argument_errors_of_the_python_constructor(pkg):
+    H = np.ones((3, 8), dtype=np.float32)
+    for bad in (H[0], np.ones((2, 3, 4), dtype=np.float32), np.ones((0, 4), dtype=np.float32), np.ones((2, 0), dtype=np.float32)):
+        with pytest.raises(pkg.MultirateHIPError) as e:
+            pkg.FIRFilter.per_channel_farrow(bad, 1.5, 4, 2)            # not a (nchannels >= 1, hLen >= 1) matrix
+        assert e.value.code == 1
+    for ct in (np.complex64, np.complex128):
+        with pytest.raises(pkg.MultirateHIPError) as e:
+            pkg.FIRFilter.per_channel_farrow(H.astype(ct), 1.5, 4, 2)   # complex taps in a FIRFarrow bank: left out
+        assert e.value.code == 5
+    for rate in (Fraction(3, 2), 2, (3, 2)):
+        with pytest.raises(pkg.MultirateHIPError) as e:
+            pkg.FIRFilter.per_channel_farrow(H, rate, 4, 2)             # a ratio: FIRFilter.per_channel
+        assert e.value.code == 1
+    for rate in (-1.5, 0.0):
+        with pytest.raises(pkg.MultirateHIPError) as e:
+            pkg.FIRFilter.per_channel_farrow(H, rate, 4, 2)             # "rate must be greater than 0", Filters.jl:193
+        assert e.value.code == 1
+    with pytest.raises(pkg.MultirateHIPError) as e:
+        pkg.FIRFilter.per_channel_farrow(H, 1.5, 4, None)               # no polyorder: that is FIRArbitrary
+    assert e.value.code == 1 and "per_channel_arbitrary" in str(e.value)
+    with pytest.raises(TypeError):
+        pkg.FIRFilter.per_channel_farrow(H, 1.5, 4, 2, pnfb=np.zeros((2, 3)))   # a caller-fitted bank is not accepted here
+
+
+def test_the_other_per_channel_constructors_keep_their_errors(pkg):
+    H = np.ones((3, 8), dtype=np.float32)
+    with pytest.raises(pkg.MultirateHIPError) as e:
+        pkg.FIRFilter.per_channel(H, 1.5)                                # a float rate: not the rational family
+    assert e.value.code == 5
+    with pytest.raises(pkg.MultirateHIPError) as e:
+        pkg.FIRFilter.per_channel_arbitrary(H, Fraction(3, 2))
+    assert e.value.code == 1
+    with pytest.raises(pkg.MultirateHIPError) as e:
+        pkg.FIRFilter.per_channel_arbitrary(H.astype(np.complex64), 1.5)
+    assert e.value.code == 5
+    with pytest.raises(pkg.MultirateHIPError) as e:
+        pkg.FIRFilter.per_channel_arbitrary(H, -1.5)
+    assert e.value.code == 1
+
+
+def test_the_unbound_filter_describes_one_channels_filter(pkg):
+    H = np.arange(3 * 30, dtype=np.float64).reshape(3, 30)
+    f = pkg.FIRFilter.per_channel_farrow(H, 2.123, 4, 3, numerics=pkg.NUMERICS_FUSED)
+    one = pkg.FIRFilter(H[0], 2.123, 4, 3)
+    st = f.state
+    assert f.kind == one.kind == pkg.host.FARROW and f.kernel_name == one.kernel_name
+    assert (st.kind, st.Nphi, st.hLen, st.tapsPerPhi, st.historyLen) == (5, 4, 30, 8, 7)             # tapsPerPhi = ceil(hLen / Nphi)
+    assert (st.rate, st.delta, st.phiAccumulator, st.inputDeficit) == (2.123, 4 / 2.123, 1.0, 1)
+    assert f.polyorder == one.polyorder == 3
+    assert f.numerics == pkg.NUMERICS_FUSED
+    d = pkg.FIRFilter.per_channel_farrow(H.astype(np.float32), 0.47)
+    assert (d.Nphi, d.polyorder) == (32, 4)                                                          # the defaults
+    assert np.array_equal(f._bank, H) and f._bank is not H
+
+
+def test_the_library_exports_the_constructor_and_the_header_declares_it(pkg):
+    lib = pkg.load_library()
+    assert hasattr(lib, "mrhip_create_farrow_bank")
+    assert any(name == "mrhip_create_farrow_bank" for name, *_ in pkg.host.ABI)
+    hdr = open(os.path.join(os.path.dirname(CSRC), "..", "include", "multirate_hip.h")).read()
+    assert re.search(r"int mrhip_create_farrow_bank\(const void \*h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,\s*"
+                     r"int64_t polyorder,\s*int sample_dtype, int64_t nchannels, int device, mrhip_filter \*\*out\);", hdr)
+    assert "FIRFarrow has none" not in hdr
+
+
+def test_the_unit_is_in_the_makefile_with_separately_rounded_arithmetic():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"^SRCS\s*=.*\bkernels_bank_farrow\.hip\b", mk, flags=re.M)
+    assert re.search(r"^CXXFLAGS\s*=.*-ffp-contract=off", mk, flags=re.M)
+    src = open(os.path.join(CSRC, "kernels_bank_farrow.hip")).read()
+    assert "#pragma clang fp contract(off)" in src
+    assert "__builtin_fmaf" in src and "__builtin_fma(" in src      # FUSED is an explicit fma
+
+
+def test_farrow_bank_kernels_use_no_scratch(pkg):
+    src = "kernels_bank_farrow.hip"
+    obj = os.path.join(CSRC, "build", src + ".o")
+    if not os.path.exists(obj) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
+        pytest.skip("no built object (the library came prebuilt) or no llvm tools")
+    if os.path.getmtime(obj) < os.path.getmtime(os.path.join(CSRC, src)):
+        pytest.skip("object older than its source")
+    sizes = _kernel_scratch(obj)
+    for kernel, count in (("farrow_bank_generic_kernel", 12), ("farrow_bank_tiled_kernel", 12)):
+        mine = {k: v for k, v in sizes.items() if kernel in k}
+        assert len(mine) == count, f"expected {count} instantiations of {kernel} in the object, found {len(mine)}"
+        spilling = {k: v for k, v in mine.items() if v != 0}
+        assert not spilling, f"{kernel}: instantiations with scratch or AccVGPRs: {list(spilling.items())[:6]}"
