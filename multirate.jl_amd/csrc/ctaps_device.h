@@ -1,5 +1,6 @@
-// ctaps_device.h -- the arithmetic of the complex-tap kernels (kernels_ctaps.hip: the rational family; kernels_ctaps_arb.hip:
-// FIRArbitrary), stated ONCE.  Contract: include/multirate_hip.h, "Complex taps".  R = the promoted real scalar; every multiply,
+// ctaps_device.h -- the arithmetic of the complex-tap kernels (kernels_ctaps.hip, kernels_bank_ctaps.hip: the rational family;
+// kernels_ctaps_arb.hip: FIRArbitrary; kernels_ctaps_farrow.hip: FIRFarrow), stated ONCE, and the sample struct of every variant
+// kernel (variant_device.h wraps the arithmetic as the complex tap algebra).  Contract: include/multirate_hip.h, "Complex taps".  R = the promoted real scalar; every multiply,
 // add and subtract below is rounded separately in R: the including translation units are compiled with -ffp-contract=off.
 #pragma once
 
@@ -61,16 +62,6 @@ __device__ __forceinline__ CPair<R> ctap_arb_combine(const CPair<R> lo, const CP
     const double si = static_cast<double>(lo.im) + pi;
     y.im = static_cast<R>(si);
     return y;
-}
-
-// (Tx scalar, R, components of a sample) of a complex-tap filter -> the kernel instantiation
-template <typename F>
-hipError_t dispatch_ctaps(const TypeKey &tk, F &&f)
-{
-    if (!tk.x_f64 && !tk.r_f64) return tk.complex_x ? f.template operator()<float, float, 2>() : f.template operator()<float, float, 1>();
-    if (!tk.x_f64 && tk.r_f64) return tk.complex_x ? f.template operator()<float, double, 2>() : f.template operator()<float, double, 1>();
-    if (tk.x_f64 && tk.r_f64) return tk.complex_x ? f.template operator()<double, double, 2>() : f.template operator()<double, double, 1>();
-    return hipErrorInvalidValue;
 }
 
 }  // namespace mrhip

@@ -158,6 +158,198 @@ PairGrid pair_grid(int per_cu, int num_cus, unsigned total_steps, int J, int max
     return p;
 }
 
+// ---- plans of the LDS-tiled variant kernels (complex taps, per-channel taps) ----------------------------------------------------
+// Two shapes (plan_variant_poly_tiled, plan_variant_arb_tiled) and under each the families' own eligibility with the value of
+// the family's switch passed in (the kernel units read it: MRHIP_*_TILED = 0 never, 1 wherever the LDS plan fits -- tests,
+// measurements -- unset (-1) the family's measured default rule).
+
+namespace {
+size_t variant_sample_bytes(const TypeKey &tk) { return (tk.x_f64 ? 8 : 4) * (tk.complex_x ? 2 : 1); }
+size_t variant_tap_bytes(const TypeKey &tk) { return (tk.r_f64 ? 8 : 4) * (tk.complex_h ? 2 : 1); }     // complex taps: an (re, im) pair
+}  // namespace
+
+// Rational shape: ONE tap bank (the shared one, or one channel's) with a column pitch of T + 1 taps, at most 96 KB, plus the sample
+// window of a tile of cpl channels fit the LDS budget (at most 150 KB); the tile shrinks from 256 outputs to 64 -- and, where
+// channels per lane are searched (search_cpl: the shared complex bank; 4 from 32 channels, 2 from 8), cpl first -- until they do.
+// By default (not forced) the call must give every CU a tile: below that the universal kernel's one-lane-per-output grid spreads
+// wider than the tiles do.
+bool plan_variant_poly_tiled(size_t tap_bytes, bool search_cpl, int L, int M, int T, long long n_out, int nch, size_t sample_bytes,
+                             int num_cus, bool forced, ArbTileArgs *out, size_t *lds)
+{
+    const int TP = T + 1;
+    const size_t bank_elems = static_cast<size_t>(L) * TP;
+    const size_t bank_bytes = (bank_elems * tap_bytes + 15) / 16 * 16;
+    if (bank_bytes > 96 * 1024) return false;
+    int cpl = !search_cpl ? 1 : nch >= 32 ? 4 : (nch >= 8 ? 2 : 1);
+    long long tile_out = kVariantThreads;
+    // samples a tile of `t` outputs can touch: floor((u_first + (t-1)*M)/L) - floor(u_first/L) + T
+    auto span_of = [&](long long t) { return ((t - 1) * M + L - 1) / L + T + 1; };
+    const size_t budget = std::max<size_t>(64 * 1024, std::min<size_t>(bank_bytes + 40 * 1024, 150 * 1024));
+    for (;;) {
+        const long long max_span = span_of(tile_out);
+        const size_t total = bank_bytes + static_cast<size_t>(max_span) * sample_bytes * cpl;
+        if (total <= budget || (cpl == 1 && tile_out == 64)) {
+            if (total > 150 * 1024 || max_span > (1 << 30)) return false;
+            const long long groups = (nch + cpl - 1) / cpl;
+            ArbTileArgs ta{};
+            ta.tap_pitch = TP;
+            ta.bank_elems = static_cast<int>(bank_elems);
+            ta.x_offset_bytes = static_cast<int>(bank_bytes);
+            ta.max_span = static_cast<int>(max_span);
+            ta.tile_out = tile_out;
+            ta.tiles_per_channel = (n_out + tile_out - 1) / tile_out;
+            ta.total_tiles = ta.tiles_per_channel * groups;
+            ta.cpl = cpl;
+            if (!forced && ta.total_tiles < static_cast<long long>(num_cus)) return false;
+            *out = ta;
+            *lds = total;
+            return true;
+        }
+        if (cpl > 1) cpl /= 2;
+        else tile_out /= 2;
+    }
+}
+
+// poly_ctaps_tiled_kernel: the shared bank of pairs, CPL channels a lane
+bool plan_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.complex_h || a.dyn || a.n_out < 1 || a.T < 1) return false;
+    return plan_variant_poly_tiled(variant_tap_bytes(tk), true, a.L, a.M, a.T, a.n_out, a.nch, variant_sample_bytes(tk), num_cus, mode == 1, out, lds);
+}
+// poly_bank_tiled_kernel: ONE channel's bank.  The default rule is the measured plan: with at least one tile per CU the tiled kernel
+// was 1.12 ... 3.6 times faster in every row measured (profiles/r07/bank.txt); smaller calls are unmeasured
+// and stay on the universal kernel.
+bool plan_bank_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.bank || tk.complex_h || a.dyn || a.n_out < 1 || a.T < 1) return false;
+    return plan_variant_poly_tiled(variant_tap_bytes(tk), false, a.L, a.M, a.T, a.n_out, a.nch, variant_sample_bytes(tk), num_cus, mode == 1, out, lds);
+}
+// poly_bank_ctaps_tiled_kernel: ONE channel's bank of pairs; with at least one tile per CU 1.48 ... 4.1 times faster in every row
+// measured (profiles/r07/bank_ctaps.txt)
+bool plan_bank_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.bank || !tk.complex_h || a.dyn || a.n_out < 1 || a.T < 1) return false;
+    return plan_variant_poly_tiled(variant_tap_bytes(tk), false, a.L, a.M, a.T, a.n_out, a.nch, variant_sample_bytes(tk), num_cus, mode == 1, out, lds);
+}
+
+// Arbitrary-rate shape (FIRArbitrary, FIRFarrow).  A tile is 256 outputs (a lane each) of cpl channels; beside what the kernel
+// keeps in LDS anyway (v.fixed_bytes, at most v.fixed_max) the samples may take 40 KiB or what v.total_max leaves.  The planned span
+// follows from the rate -- consecutive outputs are 1/rate samples apart -- and is CUT to that room: tiles with a longer run read global
+// memory, so a rate that makes EVERY full tile such a tile is left to the universal kernel unless the kernel is forced.
+bool plan_variant_arb_tiled(const ArbVariantShape &v, int T, long long n_out, int nch, size_t sample_bytes, double rate, bool forced,
+                            ArbTileArgs *out, size_t *lds)
+{
+    if (v.fixed_bytes > v.fixed_max) return false;
+    constexpr size_t kSampleBytesMax = 40 * 1024;
+    const size_t room = std::min(kSampleBytesMax, v.total_max - v.fixed_bytes) / 16 * 16;
+    const long long tile_out = kVariantThreads;
+    // samples the run of a tile can hold: n advances by at most ceil(1/rate) + 1 per output (update(), Filters.jl:663-673, 780-788)
+    const double per_tile = std::ceil(static_cast<double>(tile_out - 1) / rate) + static_cast<double>(T) + 2.0;
+    int cpl = v.cpl_start;
+    while (cpl > 1 && per_tile * static_cast<double>(sample_bytes * cpl) > static_cast<double>(room)) cpl /= 2;
+    long long max_span = static_cast<long long>(room / (sample_bytes * cpl));
+    const bool cut = per_tile > static_cast<double>(max_span);
+    if (!cut) max_span = static_cast<long long>(per_tile);
+    if (max_span < T + 1) return false;                                               // not even one window
+    if (cut && !forced) return false;
+    ArbTileArgs ta{};
+    ta.cpl = cpl;
+    ta.tap_pitch = v.tap_pitch;
+    ta.bank_elems = v.bank_elems;
+    ta.x_offset_bytes = static_cast<int>(v.fixed_bytes);
+    ta.max_span = static_cast<int>(max_span);
+    ta.tile_out = tile_out;
+    ta.tiles_per_channel = (n_out + tile_out - 1) / tile_out;
+    ta.total_tiles = v.tile_all_channels ? ta.tiles_per_channel : ta.tiles_per_channel * ((nch + cpl - 1) / cpl);
+    *out = ta;
+    *lds = v.fixed_bytes + static_cast<size_t>(max_span) * sample_bytes * cpl;
+    return true;
+}
+
+// arb_ctaps_tiled_kernel: both banks of pairs (column pitch T + 1, at most 96 KiB) beside 40 KiB of samples.  CPL = 1 or 2: with
+// four channels a lane -- lo and up of four complex sums beside both banks' pairs -- the compiler spills to scratch in every type
+// combination.  The default rule: a tile per CU at least, and min_work (MRHIP_CTAPS_ARB_TILED_MIN) outputs x channels -- by default
+// never (negative): profiles/r07/ctaps_arb.txt has the measurements that comes from.
+bool plan_ctaps_arb_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, int min_work, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.complex_h || a.n_out < 1 || a.T < 1 || !(rate > 0.0)) return false;
+    const int TP = a.T + 1;
+    const size_t bank_pairs = static_cast<size_t>(a.Nphi) * TP;
+    const size_t banks_bytes = (2 * bank_pairs * variant_tap_bytes(tk) + 15) / 16 * 16;
+    const ArbVariantShape v{banks_bytes, 96 * 1024, (96 + 40) * 1024, TP, static_cast<int>(bank_pairs), a.nch >= 8 ? 2 : 1, false};
+    ArbTileArgs ta;
+    size_t bytes;
+    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate, mode == 1, &ta, &bytes)) return false;
+    if (mode != 1) {
+        if (ta.total_tiles < static_cast<long long>(num_cus)) return false;
+        if (min_work < 0 || a.n_out * static_cast<long long>(a.nch) < min_work) return false;
+    }
+    *out = ta;
+    *lds = bytes;
+    return true;
+}
+
+// arb_bank_tiled_kernel: both banks of ONE channel plus the sample tile fit LDS at two workgroups a CU (160 KiB a CU: 78 KiB a
+// workgroup, which leaves room for the epilogue's own word).  The default rule: the tiled kernel was faster than the universal one by
+// far more than the spread of the repeats in every measured call of 5312 tiles or more (1.4 ... 10 times: DESIGN.md 9 item 12,
+// profiles/r07/arb_bank.txt) and was not at 664 and 166 tiles (calls bound by their launches).  So: from kArbBankTiledTilesPerCu tiles
+// per CU (5120 tiles on 256 CUs; 5312 is the smallest measured call it won); everything smaller stays on the universal kernel.
+constexpr long long kArbBankTiledTilesPerCu = 20;
+bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate > 0.0)) return false;
+    const int TP = a.T + 1;
+    const size_t bank_elems = static_cast<size_t>(a.Nphi) * TP;
+    const size_t banks_bytes = (2 * bank_elems * variant_tap_bytes(tk) + 15) / 16 * 16;
+    const ArbVariantShape v{banks_bytes, 78 * 1024, 78 * 1024, TP, static_cast<int>(bank_elems), 1, false};
+    ArbTileArgs ta;
+    size_t bytes;
+    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate, mode == 1, &ta, &bytes)) return false;
+    if (mode != 1 && ta.total_tiles < kArbBankTiledTilesPerCu * static_cast<long long>(num_cus)) return false;
+    *out = ta;
+    *lds = bytes;
+    return true;
+}
+
+// farrow_bank_tiled_kernel: LDS holds the sample run only (a tap feeds one product; the coefficients are scalar loads), at most 40 KiB:
+// two workgroups a CU.  The default rule is NEVER: the tiled kernel beat the universal one nowhere by more than the spread of the
+// repeats (profiles/r07/farrow_bank.txt: 0.76 ... 0.98 times its speed at Float32 samples, 166 ... 530 752 tiles;
+// at 64 ch x 1e7 Float64, 2 618 048 tiles, 16.27 against 16.67 ms in one run and 16.68 against 16.80 with a spread of 0.46 in the
+// next), so it stays behind its switch.
+bool plan_farrow_bank_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int /*num_cus*/, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode != 1 || !tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || !(rate > 0.0)) return false;
+    const ArbVariantShape v{0, 0, 40 * 1024, 0, 0, 1, false};
+    return plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate, true, out, lds);
+}
+
+// farrow_ctaps_tiled_kernel: the coefficient bank of pairs of Float64, 256 tap columns of pairs of R and the samples fit the 160 KiB
+// of a CU less the kernel's static words (159 KiB); a tile is every channel of its 256 outputs, CPL (1 or 2, as in
+// arb_ctaps_tiled_kernel) channels at a time.  The default rule: only where the tiled kernel was measured, and faster than the
+// universal one in every run (profiles/r07/ctaps_farrow.txt): Float32 arithmetic, 32 taps per phase, 1 to 64 channels, 21 230
+// outputs a channel and more (83 tiles: fewer than the chip has CUs, and still ahead) -- min_out (MRHIP_CTAPS_FARROW_TILED_MIN;
+// negative: never) is the smallest call measured.  Float64 arithmetic and other banks are not measured yet and stay on the
+// universal kernel.
+constexpr int kCtapsFarrowMeasuredT = 32;
+bool plan_ctaps_farrow_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int /*num_cus*/, int mode, int min_out, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || !(rate > 0.0)) return false;
+    const size_t bank_pairs = static_cast<size_t>(a.T) * (a.polyorder + 1);
+    const size_t bank_bytes = bank_pairs * 2 * sizeof(double);                          // (whole 16-byte units)
+    const size_t col_bytes = static_cast<size_t>(a.T) * kVariantThreads * variant_tap_bytes(tk);
+    const ArbVariantShape v{bank_bytes + col_bytes, 159 * 1024, 159 * 1024, 0, static_cast<int>(bank_pairs), a.nch >= 2 ? 2 : 1, true};
+    ArbTileArgs ta;
+    size_t bytes;
+    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate, mode == 1, &ta, &bytes)) return false;
+    if (mode != 1) {
+        if (tk.r_f64 || a.T != kCtapsFarrowMeasuredT) return false;
+        if (min_out < 0 || a.n_out < min_out) return false;
+    }
+    *out = ta;
+    *lds = bytes;
+    return true;
+}
+
 // FIRArbitrary / FIRFarrow: the phase accumulator is a serial Float64 recurrence whose roundings the reference's
 // outputs depend on (src/Filters.jl:663-673), so it is evaluated here, in order, once per call; every channel shares
 // the result.  One step of update():  acc += delta; if acc > N: xIdx += ifloor((acc-1)/N); acc = mod(acc-1, N) + 1.

@@ -18,28 +18,13 @@
 // The coefficient bank is [T][polyorder+1] (re, im) pairs of Float64 on the device, ascending powers, values representable in
 // the tap type; the history is Tx (real for real samples); the output is (re, im) pairs of R.  Both kernels take the ShiftFold
 // epilogue (shiftin! by the workgroup that leaves last) exactly as arb_ctaps_generic_kernel does.
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
-
-#include "ctaps_device.h"
-#include "mrhip_internal.h"
-#include "pair_device.h"
+// Shared with the other variant units: variant_device.h (staging, launch shapes); the tiled plan: host_logic.cpp.
+#include "variant_device.h"
 
 #pragma clang fp contract(off)
 
 namespace mrhip {
 namespace {
-
-constexpr int kCtapsFarrowThreads = 256;
-// outputs a channel from which plan_ctaps_farrow_tiled takes a call by default: the smallest call measured, at which -- as at every
-// larger one -- the tiled kernel beat the universal one in every run (profiles/r07/ctaps_farrow.txt); negative: only when
-// MRHIP_CTAPS_TILED=1 asks for it
-constexpr int kCtapsFarrowTiledMinDefault = 21000;
-constexpr int kCtapsFarrowMeasuredT = 32;                  // the tapsPer𝜙 those measurements were taken at
-// LDS a workgroup of the tiled kernel may take: the 160 KiB of a CU less the kernel's static words
-constexpr size_t kCtapsFarrowLdsBudget = 159 * 1024;
-constexpr size_t kCtapsFarrowSampleBytes = 40 * 1024;
 
 // One complex tap of one output: polyval(Poly{Complex{T}}, 𝜙::Float64) written out (y = p[i] + x*y; Real*Complex and
 // Complex+Complex are by components), stored into a Vector{Complex{T}} (one rounding to T per component), widened exactly to R.
@@ -66,7 +51,7 @@ __device__ __forceinline__ CPair<R> farrow_ctap(const double *c, const int P, co
 // the output, not on the channel) and reuses them for every channel it visits; 0: the columns do not fit, the taps are
 // evaluated per channel.
 template <typename TX, typename R, int NCX>
-__global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_generic_kernel(FarrowArgs a, int cache)
+__global__ __launch_bounds__(kVariantThreads) void farrow_ctaps_generic_kernel(FarrowArgs a, int cache)
 {
     using Sample = CSample<TX, NCX>;
     extern __shared__ __attribute__((aligned(16))) unsigned char ctaps_farrow_smem[];
@@ -99,19 +84,16 @@ __global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_generic_kern
     dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }
 
-// Persistent workgroups, modelled on arb_ctaps_tiled_kernel and on the way farrow_pipe_kernel treats taps.  A tile is 256
+// Persistent workgroups, as arb_ctaps_tiled_kernel, with taps treated as in farrow_pipe_kernel.  A tile is 256
 // consecutive outputs (a lane each) of EVERY channel: the lane evaluates its output's T complex taps ONCE per tile -- 2 T
 // polyorder Float64 multiply-adds, the cost that sets this kind apart -- from the coefficient bank (copied to LDS once per
 // workgroup; every lane reads the same coefficient: a broadcast) into an LDS column of its own (tap i of lane l at i*256 + l: a
-// wave's reads are consecutive), then walks the channel groups, CPL channels at a time: the contiguous [history ; x] run between
-// the tile's first and last n_idx (the schedule is non-decreasing in k) is staged per group, and one tap read serves CPL
-// products.  The span of a tile is read from the schedule HERE, so the kernel serves device-planned calls too (a.dyn); a tile
-// whose run is longer than the planned span (ta.max_span: a heavily decimating rate, rate << 1) reads its windows from global
-// memory.  Tiles are assigned statically (tile += gridDim.x): no tile counter, no waiting between workgroups beyond the
-// shiftin_by_last_workgroup epilogue.
+// wave's reads are consecutive), then walks the channel groups, CPL channels at a time: the tile's run of samples (tile_span) is
+// staged per group, and one tap read serves CPL products.  Tiles are assigned statically (tile += gridDim.x): no tile counter, no
+// waiting between workgroups beyond the shiftin_by_last_workgroup epilogue.
 // LDS: [T][polyorder+1] pairs of Float64 | [T][256] pairs of R | [CPL][max_span] samples.
 template <typename TX, typename R, int NCX, int CPL>
-__global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_tiled_kernel(FarrowArgs a, ArbTileArgs ta)
+__global__ __launch_bounds__(kVariantThreads) void farrow_ctaps_tiled_kernel(FarrowArgs a, ArbTileArgs ta)
 {
     using Sample = CSample<TX, NCX>;
     extern __shared__ __attribute__((aligned(16))) unsigned char ctaps_farrow_smem[];
@@ -122,7 +104,7 @@ __global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_tiled_kernel
     const int tid = threadIdx.x;
     const int T = a.T, P = a.polyorder;
     const bool tap_f32 = a.tap_f32 != 0;
-    for (int e = tid; e < ta.bank_elems * 2; e += kCtapsFarrowThreads) lcoef[e] = a.pnfb[e];
+    for (int e = tid; e < ta.bank_elems * 2; e += kVariantThreads) lcoef[e] = a.pnfb[e];
     long long ngroups;                                              // (1: a tile is every channel of its outputs)
     tiles_take_dyn(a.n_out, ta, ngroups, a.dyn);                    // (a device-planned call: the count from the call record)
     const int ncg = (a.nch + CPL - 1) / CPL;
@@ -131,20 +113,17 @@ __global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_tiled_kernel
     for (long long tile = blockIdx.x; tile < ta.total_tiles; tile += gridDim.x) {
         const long long k0 = tile * ta.tile_out;
         const long long klast = (k0 + ta.tile_out < a.n_out ? k0 + ta.tile_out : a.n_out) - 1;
-        const long long n_lo = a.n_idx[k0], n_hi = a.n_idx[klast];
-        const long long o = n_lo - T;                                                   // 0-based x index of LDS sample 0 (>= -H)
-        const long long span = n_hi - n_lo + T;
-        const bool staged = span <= ta.max_span;                                        // (uniform over the workgroup)
+        const TileSpan w = tile_span(a.n_idx, k0, klast, T, ta.max_span);
         const long long k = k0 + tid;
         const bool active = k <= klast;
-        long long n = n_lo;
+        long long n = w.n_lo;
         bool seam = false;
         if (active) {
             n = a.n_idx[k];
             seam = n < a.seam_below;
             const double phase = a.acc[k];
             for (int i = 0; i < T; ++i)                  // (the column is this lane's alone: no barrier between tiles or before the reads)
-                tl[i * kCtapsFarrowThreads + tid] = farrow_ctap<R>(lcoef + i * (P + 1) * 2, P, phase, tap_f32);
+                tl[i * kVariantThreads + tid] = farrow_ctap<R>(lcoef + i * (P + 1) * 2, P, phase, tap_f32);
         }
         const CPair<R> *const tcol = tl + tid;
 
@@ -153,29 +132,18 @@ __global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_tiled_kernel
             const int ch0 = cg * CPL;
             const int nchl = a.nch - ch0 < CPL ? a.nch - ch0 : CPL;
             __syncthreads();   // the previous group's (and tile's) reads of the samples are done
-            if (staged) {
+            if (w.staged) {
 #pragma unroll 1
-                for (int cc = 0; cc < nchl; ++cc) {
-                    const Sample *__restrict__ xc = static_cast<const Sample *>(a.x) + static_cast<long long>(ch0 + cc) * a.x_stride;
-                    const Sample *__restrict__ hc = static_cast<const Sample *>(a.hist) + static_cast<long long>(ch0 + cc) * a.H;
-                    Sample *const lxc = lx + static_cast<size_t>(cc) * ta.max_span;
-                    for (int s = tid; s < static_cast<int>(span); s += kCtapsFarrowThreads) {
-                        const long long gi = o + s;
-                        Sample v;
-#pragma unroll
-                        for (int c = 0; c < NCX; ++c) v.c[c] = static_cast<TX>(0);
-                        if (gi >= 0) { if (gi < a.x_len) v = xc[gi]; }
-                        else if (gi >= -static_cast<long long>(a.H)) v = hc[a.H + gi];
-                        lxc[s] = v;
-                    }
-                }
+                for (int cc = 0; cc < nchl; ++cc)
+                    stage_window(lx + static_cast<size_t>(cc) * ta.max_span, static_cast<const Sample *>(a.x) + static_cast<long long>(ch0 + cc) * a.x_stride,
+                                 static_cast<const Sample *>(a.hist) + static_cast<long long>(ch0 + cc) * a.H, w.o, static_cast<int>(w.span), a.x_len, a.H, tid);
             }
             __syncthreads();
             if (!active) continue;                       // (no barrier below)
 
             CPair<R> acc[CPL];
-            if (staged) {
-                const Sample *wp = lx + (n - n_lo);      // oldest sample of this output's window (channel 0 of the group)
+            if (w.staged) {
+                const Sample *wp = lx + (n - w.n_lo);      // oldest sample of this output's window (channel 0 of the group)
                 {
                     const CPair<R> t = tcol[0];
 #pragma unroll
@@ -186,7 +154,7 @@ __global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_tiled_kernel
                 }
 #pragma unroll 2
                 for (int i = 1; i < T; ++i) {
-                    const CPair<R> t = tcol[i * kCtapsFarrowThreads];
+                    const CPair<R> t = tcol[i * kVariantThreads];
 #pragma unroll
                     for (int cc = 0; cc < CPL; ++cc)
                         acc[cc] = ctap_add<R>(acc[cc], ctap_product<TX, R, NCX>(t, wp[static_cast<size_t>(cc) * ta.max_span + i]));
@@ -203,7 +171,7 @@ __global__ __launch_bounds__(kCtapsFarrowThreads) void farrow_ctaps_tiled_kernel
                         if (seam) l = ctap_zero_start<R>(l);
                         for (int i = 1; i < T; ++i) {
                             const long long xi = base + i;
-                            l = ctap_add<R>(l, ctap_product<TX, R, NCX>(tcol[i * kCtapsFarrowThreads], xi >= 0 ? xc[xi] : hc[xi]));
+                            l = ctap_add<R>(l, ctap_product<TX, R, NCX>(tcol[i * kVariantThreads], xi >= 0 ? xc[xi] : hc[xi]));
                         }
                         acc[cc] = l;
                     }
@@ -228,12 +196,12 @@ hipError_t launch_farrow_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, h
     if (!tk.complex_h) return hipErrorInvalidValue;
     if (a.n_out <= 0 && !a.dyn) return hipSuccess;
     *kname = "farrow_ctaps_generic_kernel";
-    return dispatch_ctaps(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
+    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
         // block size: as many outputs as keep one LDS column of T tap pairs per thread within 64 KiB (launch_farrow's rule)
         const long long per_thread = static_cast<long long>(a.T) * static_cast<long long>(sizeof(CPair<R>));
         int bs = static_cast<int>(65536 / per_thread) / 64 * 64;
         const bool cache = bs >= 64;
-        if (bs > kCtapsFarrowThreads || !cache) bs = kCtapsFarrowThreads;
+        if (bs > kVariantThreads || !cache) bs = kVariantThreads;
         const size_t lds = cache ? static_cast<size_t>(per_thread) * bs : 0;
         const long long bx = std::max<long long>((a.n_out + bs - 1) / bs, 1);
         if (bx > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -248,54 +216,11 @@ hipError_t launch_farrow_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, h
     });
 }
 
-// Eligibility of farrow_ctaps_tiled_kernel (beside plan_ctaps_arb_tiled, kernels_ctaps_arb.hip): the coefficient bank of pairs,
-// 256 tap columns and a tile of samples fit the 160 KiB of LDS of a CU.  A tile is 256 outputs (a lane each) of every channel,
-// CPL channels at a time; its planned span follows from the rate -- consecutive outputs are 1/rate samples apart -- and is
-// cut to what the samples may take (40 KiB, or what the bank and the columns leave): tiles with a longer run read global
-// memory, so a rate that makes EVERY full tile such a tile is left to the universal kernel unless the kernel is forced.
-// MRHIP_CTAPS_TILED=0: never; =1: whenever LDS allows (tests, measurements); unset: the measured rule at the end.
-bool plan_ctaps_farrow_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int /*num_cus*/, ArbTileArgs *out, size_t *lds)
+// (MRHIP_CTAPS_FARROW_TILED_MIN: the threshold of the default rule, outputs a channel)
+bool plan_ctaps_farrow_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds)
 {
-    const int mode = MRHIP_ENV_INT("MRHIP_CTAPS_TILED", -1);
-    if (mode == 0 || !tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || !(rate > 0.0)) return false;
-    const size_t ps = (tk.r_f64 ? 8 : 4) * 2;                                           // one tap pair
-    const size_t sb = (tk.x_f64 ? 8 : 4) * (tk.complex_x ? 2 : 1);                      // one sample
-    const size_t bank_pairs = static_cast<size_t>(a.T) * (a.polyorder + 1);
-    const size_t bank_bytes = bank_pairs * 2 * sizeof(double);                          // (whole 16-byte units)
-    const size_t col_bytes = static_cast<size_t>(a.T) * kCtapsFarrowThreads * ps;
-    if (bank_bytes + col_bytes >= kCtapsFarrowLdsBudget) return false;
-    const size_t sample_bytes = std::min(kCtapsFarrowSampleBytes, kCtapsFarrowLdsBudget - bank_bytes - col_bytes) / 16 * 16;
-    const long long tile_out = kCtapsFarrowThreads;
-    // samples the run of a tile can hold: n advances by at most ceil(1/rate) + 1 per output (update(), Filters.jl:780-788)
-    const double per_tile = std::ceil(static_cast<double>(tile_out - 1) / rate) + static_cast<double>(a.T) + 2.0;
-    // (CPL = 1 or 2, as in arb_ctaps_tiled_kernel)
-    int cpl = a.nch >= 2 ? 2 : 1;
-    while (cpl > 1 && per_tile * static_cast<double>(sb * cpl) > static_cast<double>(sample_bytes)) cpl /= 2;
-    long long max_span = static_cast<long long>(sample_bytes / (sb * cpl));
-    const bool cut = per_tile > static_cast<double>(max_span);
-    if (!cut) max_span = static_cast<long long>(per_tile);
-    if (max_span < a.T + 1) return false;                                               // not even one window
-    if (cut && mode != 1) return false;
-    ArbTileArgs ta{};
-    ta.cpl = cpl;
-    ta.bank_elems = static_cast<int>(bank_pairs);
-    ta.x_offset_bytes = static_cast<int>(bank_bytes + col_bytes);
-    ta.max_span = static_cast<int>(max_span);
-    ta.tile_out = tile_out;
-    ta.tiles_per_channel = (a.n_out + tile_out - 1) / tile_out;
-    ta.total_tiles = ta.tiles_per_channel;                                              // a tile covers every channel
-    if (mode != 1) {
-        // The default rule: only where the tiled kernel was measured, and faster than the universal one in every run
-        // (profiles/r07/ctaps_farrow.txt): Float32 arithmetic, 32 taps per phase, 1 to 64 channels, 21 230 outputs a channel and more
-        // (83 tiles: fewer than the chip has CUs, and still ahead).  Float64 arithmetic and other banks are not measured yet and stay
-        // on the universal kernel.  MRHIP_CTAPS_FARROW_TILED_MIN: another threshold, in outputs a channel.
-        if (tk.r_f64 || a.T != kCtapsFarrowMeasuredT) return false;
-        const long long min_out = MRHIP_ENV_INT("MRHIP_CTAPS_FARROW_TILED_MIN", kCtapsFarrowTiledMinDefault);
-        if (min_out < 0 || a.n_out < min_out) return false;
-    }
-    *out = ta;
-    *lds = bank_bytes + col_bytes + static_cast<size_t>(max_span) * sb * cpl;
-    return true;
+    return plan_ctaps_farrow_tiled(tk, a, rate, num_cus, MRHIP_ENV_INT("MRHIP_CTAPS_TILED", -1),
+                                   MRHIP_ENV_INT("MRHIP_CTAPS_FARROW_TILED_MIN", kCtapsFarrowTiledMinDefault), out, lds);
 }
 
 hipError_t launch_farrow_ctaps_tiled(const TypeKey &tk, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
@@ -303,14 +228,9 @@ hipError_t launch_farrow_ctaps_tiled(const TypeKey &tk, const FarrowArgs &a, con
 {
     if (!tk.complex_h) return hipErrorInvalidValue;
     *kname = "farrow_ctaps_tiled_kernel";
-    return dispatch_ctaps(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
-        auto go = [&](auto kfn) -> hipError_t {
-            const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kCtapsFarrowThreads, lds, num_cus, ta.total_tiles);
-            if (pg.err != hipSuccess) return pg.err;
-            launch_kernel(kfn, dim3(static_cast<unsigned>(pg.grid)), dim3(kCtapsFarrowThreads), lds, s, a, ta);
-            return hipGetLastError();
-        };
-        return ta.cpl == 2 ? go(farrow_ctaps_tiled_kernel<TX, R, NCX, 2>) : go(farrow_ctaps_tiled_kernel<TX, R, NCX, 1>);
+    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
+        return ta.cpl == 2 ? launch_persistent(farrow_ctaps_tiled_kernel<TX, R, NCX, 2>, a, ta, lds, s, num_cus)
+                           : launch_persistent(farrow_ctaps_tiled_kernel<TX, R, NCX, 1>, a, ta, lds, s, num_cus);
     });
 }
 

@@ -63,6 +63,22 @@ struct PairGrid { long long grid; int ngroups; unsigned steps_per_group; int sta
 PairGrid pair_grid(int per_cu, int num_cus, unsigned total_steps, int J, int max_groups, int multi_n, bool ring = false, int grid_cap = 0);
 constexpr int kPairGroups = 32;   // scheduling groups of a pair kernel's launch at most (kCounterBytes)
 
+// Plans of the LDS-tiled "variant" kernels (complex taps, per-channel taps; variant_device.h), one per shape (host_logic.cpp has
+// the rules; tests/test_variant_plans.py checks them against recorded cases).  forced: the kernel's switch is 1.
+struct ArbTileArgs;
+constexpr int kVariantThreads = 256;   // lanes of a workgroup of the variant kernels = outputs of a full tile
+bool plan_variant_poly_tiled(size_t tap_bytes, bool search_cpl, int L, int M, int T, long long n_out, int nch, size_t sample_bytes,
+                             int num_cus, bool forced, ArbTileArgs *out, size_t *lds);
+struct ArbVariantShape {                 // what differs between the arbitrary-rate variant kernels
+    size_t fixed_bytes;                  // LDS beside the samples (tap banks; coefficient bank and tap columns): the sample tile starts there
+    size_t fixed_max, total_max;         // byte budgets of `fixed_bytes` and of the workgroup
+    int tap_pitch, bank_elems;           // -> ArbTileArgs
+    int cpl_start;                       // channels per lane the plan starts from (halved while the planned span does not fit)
+    bool tile_all_channels;              // a tile covers every channel (else: one group of cpl channels)
+};
+bool plan_variant_arb_tiled(const ArbVariantShape &v, int T, long long n_out, int nch, size_t sample_bytes, double rate, bool forced,
+                            ArbTileArgs *out, size_t *lds);
+
 // FIRArbitrary phase recurrence (src/Filters.jl:663-673, 715-734) run on the host.
 struct ArbState {
     double acc = 1.0;   // 𝜙Accumulator
@@ -640,42 +656,54 @@ hipError_t launch_poly_tiled(const TypeKey &tk, bool fused, const PolyArgs &a, c
 // complex taps (kernels_ctaps.hip): the universal kernel (host- and device-planned calls) and the LDS-tiled one
 hipError_t launch_poly_ctaps_generic(const TypeKey &tk, const PolyArgs &a, hipStream_t s, const char **kname);
 bool plan_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
 hipError_t launch_poly_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                    const char **kname, int num_cus);
 // per-channel taps (kernels_bank.hip; a.taps is [nch][Nphi][T]): the universal kernel (host- and device-planned calls) and the
 // LDS-tiled one (host-planned calls only)
 hipError_t launch_poly_bank_generic(const TypeKey &tk, bool fused, const PolyArgs &a, hipStream_t s, const char **kname);
 bool plan_bank_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_bank_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
 hipError_t launch_poly_bank_tiled(const TypeKey &tk, bool fused, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                   const char **kname, int num_cus);
 // per-channel COMPLEX taps (kernels_bank_ctaps.hip; a.taps is [nch][Nphi][T] (re, im) pairs; TypeKey::bank && TypeKey::complex_h): the
 // universal kernel (host- and device-planned calls) and the LDS-tiled one (host-planned calls only)
 hipError_t launch_poly_bank_ctaps_generic(const TypeKey &tk, const PolyArgs &a, hipStream_t s, const char **kname);
 bool plan_bank_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_bank_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
 hipError_t launch_poly_bank_ctaps_tiled(const TypeKey &tk, const PolyArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                         const char **kname, int num_cus);
 // complex taps, FIRArbitrary (kernels_ctaps_arb.hip): the universal kernel and the LDS-tiled one; both serve host- and device-planned
 // calls and take the ShiftFold epilogue
 hipError_t launch_arb_ctaps_generic(const TypeKey &tk, const ArbArgs &a, hipStream_t s, const char **kname);
 bool plan_ctaps_arb_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_ctaps_arb_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, int min_work, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
+// (min_work: outputs x channels from which the default rule takes a call; negative: only when MRHIP_CTAPS_TILED=1 asks for it)
+constexpr int kCtapsArbTiledMinDefault = -1;
 hipError_t launch_arb_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                   const char **kname, int num_cus);
 // per-channel taps, FIRArbitrary (kernels_bank_arb.hip; a.taps and a.dtaps are [nch][Nphi][T]; TypeKey::bank on a FIRArbitrary filter):
 // the universal kernel and the LDS-tiled one; both serve host- and device-planned calls and take the ShiftFold epilogue
 hipError_t launch_arb_bank_generic(const TypeKey &tk, bool fused, const ArbArgs &a, hipStream_t s, const char **kname);
 bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
 hipError_t launch_arb_bank_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                  const char **kname, int num_cus);
 // per-channel taps, FIRFarrow (kernels_bank_farrow.hip; a.pnfb is [nch][T][polyorder+1]; TypeKey::bank on a FIRFarrow filter): the
 // universal kernel and the LDS-tiled one; both serve host- and device-planned calls and take the ShiftFold epilogue
 hipError_t launch_farrow_bank_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, hipStream_t s, const char **kname);
 bool plan_farrow_bank_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_farrow_bank_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
 hipError_t launch_farrow_bank_tiled(const TypeKey &tk, bool fused, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                     const char **kname, int num_cus);
 // complex taps, FIRFarrow (kernels_ctaps_farrow.hip): the universal kernel and the LDS-tiled one; both serve host- and device-planned
 // calls and take the ShiftFold epilogue.  a.pnfb: [T][polyorder+1] (re, im) pairs of Float64
 hipError_t launch_farrow_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, hipStream_t s, const char **kname);
 bool plan_ctaps_farrow_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_ctaps_farrow_tiled(const TypeKey &tk, const FarrowArgs &a, double rate, int num_cus, int mode, int min_out, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
+// (min_out: outputs a channel from which the default rule takes a call: the smallest call measured, at which -- as at every larger
+// one -- the tiled kernel beat the universal one in every run (profiles/r07/ctaps_farrow.txt); negative: only when MRHIP_CTAPS_TILED=1 asks)
+constexpr int kCtapsFarrowTiledMinDefault = 21000;
 hipError_t launch_farrow_ctaps_tiled(const TypeKey &tk, const FarrowArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                      const char **kname, int num_cus);
 // dh = [diff(h), 0] in the tap type, per component for complex taps (src/Filters.jl:106); host_logic.cpp

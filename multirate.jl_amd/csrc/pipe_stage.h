@@ -1,5 +1,7 @@
-// pipe_stage.h -- what the arbitrary-rate kernels share: the multiply-add of all of them (kernels_arbitrary.hip,
-// kernels_arb_pipe.hip, kernels_farrow_pipe.hip), the hand-out of tiles of arb_tiled_kernel and farrow_tiled_kernel, and for the
+// pipe_stage.h -- what the arbitrary-rate kernels share: the multiply-add (mac) of all of them (kernels_arbitrary.hip,
+// kernels_arb_pipe.hip, kernels_farrow_pipe.hip) and, through the real-tap algebra of variant_device.h, of the per-channel-taps
+// kernels of all three families (kernels_bank.hip, kernels_bank_arb.hip, kernels_bank_farrow.hip); the hand-out of tiles of
+// arb_tiled_kernel and farrow_tiled_kernel, and for the
 // two hand-scheduled pipe kernels the scalar-base pointers, the synchronous take-over of the schedule's first index and the
 // planning of their sample buffers on the host (their grids: persistent_grid, mrhip_internal.h).  (The pipe kernels' staging lambdas and their own hand-out code are
 // still written out in each of them.)

@@ -66,7 +66,12 @@ def test_the_unit_is_in_the_makefile_with_separately_rounded_arithmetic():
     assert re.search(r"^CXXFLAGS\s*=.*-ffp-contract=off", mk, flags=re.M)
     src = open(os.path.join(CSRC, "kernels_bank_arb.hip")).read()
     assert "#pragma clang fp contract(off)" in src
-    assert "__builtin_fmaf" in src and "__builtin_fma(" in src      # FUSED is an explicit fma
+    # FUSED is an explicit fma: the unit's multiply-add is RealTaps::step of variant_device.h, which calls mac of pipe_stage.h
+    shared = open(os.path.join(CSRC, "variant_device.h")).read()
+    assert '#include "variant_device.h"' in src and "RealTaps<TX, R, NCX, FUSED>" in src
+    assert '#include "pipe_stage.h"' in shared and "#pragma clang fp contract(off)" in shared and "mac<FUSED, R>(" in shared
+    mac = open(os.path.join(CSRC, "pipe_stage.h")).read()
+    assert "__builtin_fmaf" in mac and "__builtin_fma(" in mac
 
 
 def test_arb_bank_kernels_use_no_scratch(pkg):
