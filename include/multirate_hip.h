@@ -49,7 +49,7 @@ typedef enum {
 } mrhip_status;
 
 /* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational, mrhip_create_rational_bank_ctaps) and
- * FIRArbitrary (mrhip_create_arbitrary_ctaps) and FIRFarrow (mrhip_create_farrow_ctaps, mrhip_create_farrow_pnfb_ctaps);
+ * FIRArbitrary (mrhip_create_arbitrary_ctaps, mrhip_create_arbitrary_bank_ctaps) and FIRFarrow (mrhip_create_farrow_ctaps, mrhip_create_farrow_pnfb_ctaps);
  * Tx in {F32,F64,C64,C128}; Tb = promote_type(Th,Tx) -- complex as soon as either side is */
 typedef enum { MRHIP_F32 = 0, MRHIP_F64 = 1, MRHIP_C64 = 2, MRHIP_C128 = 3 } mrhip_dtype;
 
@@ -171,9 +171,37 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - mrhip_create_arbitrary and mrhip_create_rational_bank* answer exactly as before; mrhip_filt_device_multi with such a
  *     filter among its streams issues single calls; a ring on it is not resident; mrhip_sharded_create has no such
  *     constructor; a cascade takes the filter as a stage through its per-stage calls;
- *   - left out on purpose: complex-tap FIRArbitrary banks (complex taps return MRHIP_ERR_UNSUPPORTED here), sharded banks, and
- *     the hand-scheduled shared-taps FIRArbitrary kernels (such a filter runs on its own two kernels).  FIRFarrow banks have a
- *     constructor of their own (next). */
+ *   - complex taps return MRHIP_ERR_UNSUPPORTED here (left out of THIS constructor: they have one of their own, "Per-channel complex
+ *     taps for FIRArbitrary" below); left out on purpose: sharded banks, and the hand-scheduled shared-taps FIRArbitrary kernels (such
+ *     a filter runs on its own two kernels).  FIRFarrow banks have a constructor of their own (below). */
+
+/* Per-channel complex taps for FIRArbitrary (mrhip_create_arbitrary_bank_ctaps; Th in {C64,C128}): one
+ * FIRFilter(h_c::Vector{Complex}, rate, Nphi) per channel behind one handle -- a prototype rotated to every channel's own centre
+ * frequency in front of a common clock-trim or arbitrary-rate change, per-antenna complex equalisers folded into the resampler's
+ * prototype, per-channel Hilbert or single-sideband filters in front of a symbol-rate change.  The contract is the conjunction of
+ * "Complex taps" (FIRArbitrary) and "Per-channel taps for FIRArbitrary":
+ *   - for every channel c the outputs, the per-call counts, the end state (inputDeficit, phiAccumulator, phiIdx, alpha, xIdx)
+ *     and the history are bit for bit those of mrhip_create_arbitrary_ctaps(h_c, ..., nchannels = 1) fed x_c;
+ *   - every row gets its own dh_c = [diff(h_c), 0], taken per component in the tap type, and both taps2pfb calls are made per row;
+ *   - both dots are taken over ONE window, oldest sample first, the first product initialises the accumulator, no
+ *     start-from-zero seam; Complex*Real and Complex*Complex are written out in the operand order stated under "Complex taps",
+ *     every multiply, add and subtract rounded separately in R; per component y_c = R(double(lo_c) + double(up_c) * alpha), the
+ *     product and the sum each rounded once in Float64;
+ *   - the output is always complex (C128 if either side is 64-bit, else C64); the history stays in Tx;
+ *   - no FUSED form is defined: mrhip_set_numerics(f, FUSED) returns MRHIP_ERR_UNSUPPORTED;
+ *   - everything that does not depend on the taps is the shared code, unchanged: the phase schedule, mrhip_set_mod_form,
+ *     outputlength, next_output_count, outputlength_bound, advance_state, set_state, reset, set_history*; the mrhip_state
+ *     layout is the same and its tap_dtype reads 2 or 3;
+ *   - mrhip_get_taps(f, 0, out) returns the nchannels pfb banks one after the other, which = 1 the dpfb banks; each bank is
+ *     tapsPerPhi*Nphi (re, im) pairs laid out as mrhip_taps2pfb does;
+ *   - mrhip_arbitrary_tapsforphase returns nchannels rows of tapsPerPhi pairs, row c is the statement for complex taps (per
+ *     component) on bank c; the range errors are unchanged;
+ *   - mrhip_create_arbitrary_bank keeps returning MRHIP_ERR_UNSUPPORTED for complex taps; a real tap_dtype here is
+ *     MRHIP_ERR_INVALID_ARG; mrhip_create_arbitrary_ctaps and mrhip_create_arbitrary answer exactly as before;
+ *   - as for both parents: mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is
+ *     not resident; mrhip_sharded_create has no such constructor; a cascade takes the filter as a stage through its per-stage
+ *     calls;
+ *   - left out on purpose: FIRFarrow banks with complex taps, a FUSED form, sharded banks, a resident ring for banks. */
 
 /* Per-channel taps for FIRFarrow (mrhip_create_farrow_bank; Th in {F32,F64}): one FIRFilter(h_c, rate, Nphi, polyorder) per
  * channel behind one handle -- a per-antenna equaliser or a per-sensor calibration filter in front of a common, continuously
@@ -198,8 +226,7 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - mrhip_create_farrow*, mrhip_create_arbitrary_bank and mrhip_create_rational_bank* answer exactly as before;
  *     mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is not resident;
  *     mrhip_sharded_create has no such constructor; a cascade takes the filter as a stage through its per-stage calls;
- *   - left out on purpose: complex-tap FIRFarrow banks (complex taps return MRHIP_ERR_UNSUPPORTED here), complex-tap FIRArbitrary
- *     banks, a caller-fitted pnfb for banks, sharded banks, a resident ring for banks, and the shared-taps FIRFarrow kernels
+ *   - left out on purpose: complex-tap FIRFarrow banks (complex taps return MRHIP_ERR_UNSUPPORTED here), a caller-fitted pnfb for banks, sharded banks, a resident ring for banks, and the shared-taps FIRFarrow kernels
  *     farrow_pipe_kernel / farrow_wave_kernel (such a filter runs on its own two kernels). */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
@@ -310,6 +337,12 @@ int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int tap_dtype, dou
  * and every other argument check are those of mrhip_create_arbitrary; the filter's kind is MRHIP_FIR_ARBITRARY. */
 int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
                                 int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* the same for COMPLEX taps (see "Per-channel complex taps for FIRArbitrary" above): `h` holds nchannels rows of hLen interleaved
+ * (re, im) pairs, row-major, row c is channel c's h.  tap_dtype C64 | C128; a real tap_dtype is MRHIP_ERR_INVALID_ARG: real taps use
+ * mrhip_create_arbitrary_bank (which keeps refusing complex ones).  rate, Nphi and every other argument check are those of
+ * mrhip_create_arbitrary; the filter's kind is MRHIP_FIR_ARBITRARY and its output is complex for every sample type. */
+int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
+                                      int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer, polyorder::Integer),
  * src/Filters.jl:192-198 (+ FIRFarrow(h, rate, Nphi, polyorder), :138-147, pfb2pnfb :311-321 and
  * polyfit, src/support.jl:85-88): every ROW of the tapsPerPhi x Nphi filter bank is replaced by its

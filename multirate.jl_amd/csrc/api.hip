@@ -484,7 +484,8 @@ int mrhip_create_rational_bank_ctaps(const void *h, int64_t hLen, int th, int64_
 // ones (mrhip_create_arbitrary_ctaps).  The banks are held in the tap type on the host; upload_taps widens them exactly to R
 // (complex taps: as interleaved (re, im) scalars, the [Nphi][T] layout of pairs that kernels_ctaps_arb.hip reads).  bank: `h` holds
 // nch rows; every row gets its own dh and both its taps2pfb calls, and the banks sit one after the other, [nch][Nphi][T]
-// (mrhip_create_arbitrary_bank; kernels_bank_arb.hip).
+// (mrhip_create_arbitrary_bank; kernels_bank_arb.hip -- with complex taps mrhip_create_arbitrary_bank_ctaps: [nch][Nphi][T] pairs,
+// kernels_bank_arb_ctaps.hip).
 static int create_arbitrary_common(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
                                    int device, bool bank, mrhip_filter **out)
 {
@@ -555,6 +556,19 @@ int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int th, double rate
     if (th == MRHIP_C64 || th == MRHIP_C128)
         return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_arbitrary_bank takes Float32 / Float64 taps (complex taps in a FIRArbitrary bank are left out)");
     if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, true, out);
+}
+
+// The same with COMPLEX taps (include/multirate_hip.h, "Per-channel complex taps for FIRArbitrary"): `h` holds nch rows of hLen
+// interleaved (re, im) pairs; every row gets its own dh per component and both its taps2pfb calls, upload_taps widens the scalars
+// exactly to R: the device holds pfb and dpfb as [nch][Nphi][T] pairs of R, what kernels_bank_arb_ctaps.hip reads.
+int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
+                                      int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_F32 || th == MRHIP_F64)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_arbitrary_bank_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_arbitrary_bank");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
     return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, true, out);
 }
 
@@ -1520,7 +1534,14 @@ static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_
         ArbTileArgs ta;
         size_t lds = 0;
         ArbLaneArgs la;
-        if (tk.bank) {                    // per-channel taps (kernels_bank_arb.hip): no plan_* below ever sees such a call
+        if (tk.bank && tk.complex_h) {    // per-channel complex taps (kernels_bank_arb_ctaps.hip): no branch or plan_* below ever sees such a call
+            a.fold = sf;                  // (both kernels write the next call's history themselves)
+            if (!f->force_generic && plan_arb_bank_ctaps_tiled(tk, a, f->rate, f->num_cus, &ta, &lds))
+                MRHIP_CHECK_HIP(launch_arb_bank_ctaps_tiled(tk, a, ta, lds, stream, &f->last_kernel, f->num_cus));
+            else
+                MRHIP_CHECK_HIP(launch_arb_bank_ctaps_generic(tk, a, stream, &f->last_kernel));
+        }
+        else if (tk.bank) {               // per-channel taps (kernels_bank_arb.hip): no plan_* below ever sees such a call
             a.fold = sf;                  // (both kernels write the next call's history themselves)
             if (!f->force_generic && plan_arb_bank_tiled(tk, a, f->rate, f->num_cus, &ta, &lds))
                 MRHIP_CHECK_HIP(launch_arb_bank_tiled(tk, fused, a, ta, lds, stream, &f->last_kernel, f->num_cus));

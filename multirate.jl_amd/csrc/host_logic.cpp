@@ -311,6 +311,31 @@ bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int n
     return true;
 }
 
+// arb_bank_ctaps_tiled_kernel: both banks of ONE channel as (re, im) pairs of R (column pitch T + 1) plus the sample tile fit LDS at
+// two workgroups a CU (78 KiB a workgroup, as for plan_arb_bank_tiled); one channel a lane (cpl = 1); the span follows from the rate
+// and is cut only when the kernel is forced.  The default rule: the tiled kernel was faster than the universal one by far more than
+// the spread of the repeats in every measured call of 5312 tiles or more (profiles/r08/arb_bank_ctaps.txt:
+// 6.6, 5.1 and 6.0 times at 64 ch x 1e6 -- 2.27 against 14.92 ms, 0.71 against 3.65, 2.73 against 16.26, spreads <= 0.16 ms -- 2.1
+// times at 4096 ch x 1e4, 1.29 times at 64 ch x 1e4 = 5312 tiles: 0.052 against 0.068 ms, spread 0.001) and was not at 664 tiles
+// (0.050 against 0.048 ms: a call bound by its launches).  So: from kArbBankCtapsTiledTilesPerCu tiles per CU (5120 tiles on 256
+// CUs; 5312 is the smallest measured call it won); everything smaller stays on the universal kernel.
+constexpr long long kArbBankCtapsTiledTilesPerCu = 20;
+bool plan_arb_bank_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.bank || !tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate > 0.0)) return false;
+    const int TP = a.T + 1;
+    const size_t bank_pairs = static_cast<size_t>(a.Nphi) * TP;
+    const size_t banks_bytes = (2 * bank_pairs * variant_tap_bytes(tk) + 15) / 16 * 16;
+    const ArbVariantShape v{banks_bytes, 78 * 1024, 78 * 1024, TP, static_cast<int>(bank_pairs), 1, false};
+    ArbTileArgs ta;
+    size_t bytes;
+    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate, mode == 1, &ta, &bytes)) return false;
+    if (mode != 1 && ta.total_tiles < kArbBankCtapsTiledTilesPerCu * static_cast<long long>(num_cus)) return false;
+    *out = ta;
+    *lds = bytes;
+    return true;
+}
+
 // farrow_bank_tiled_kernel: LDS holds the sample run only (a tap feeds one product; the coefficients are scalar loads), at most 40 KiB:
 // two workgroups a CU.  The default rule is NEVER: the tiled kernel beat the universal one nowhere by more than the spread of the
 // repeats (profiles/r07/farrow_bank.txt: 0.76 ... 0.98 times its speed at Float32 samples, 166 ... 530 752 tiles;

@@ -598,7 +598,7 @@ struct TypeKey {
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
     bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family), kernels_ctaps_arb.hip (FIRArbitrary) and kernels_ctaps_farrow.hip (FIRFarrow) only
-    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only; FIRArbitrary, mrhip_create_arbitrary_bank: ArbArgs::taps / dtaps are [nch][Nphi][T], kernels_bank_arb.hip only; FIRFarrow, mrhip_create_farrow_bank: FarrowArgs::pnfb is [nch][T][polyorder+1], kernels_bank_farrow.hip only)
+    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only; FIRArbitrary, mrhip_create_arbitrary_bank: ArbArgs::taps / dtaps are [nch][Nphi][T], kernels_bank_arb.hip only -- with complex_h, mrhip_create_arbitrary_bank_ctaps: pairs, kernels_bank_arb_ctaps.hip only; FIRFarrow, mrhip_create_farrow_bank: FarrowArgs::pnfb is [nch][T][polyorder+1], kernels_bank_farrow.hip only)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -689,6 +689,14 @@ bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int n
 bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
 hipError_t launch_arb_bank_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                  const char **kname, int num_cus);
+// per-channel COMPLEX taps, FIRArbitrary (kernels_bank_arb_ctaps.hip; a.taps and a.dtaps are [nch][Nphi][T] (re, im) pairs;
+// TypeKey::bank && TypeKey::complex_h on a FIRArbitrary filter): the universal kernel and the LDS-tiled one; both serve host- and
+// device-planned calls and take the ShiftFold epilogue
+hipError_t launch_arb_bank_ctaps_generic(const TypeKey &tk, const ArbArgs &a, hipStream_t s, const char **kname);
+bool plan_arb_bank_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, ArbTileArgs *out, size_t *lds);
+bool plan_arb_bank_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
+hipError_t launch_arb_bank_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
+                                       const char **kname, int num_cus);
 // per-channel taps, FIRFarrow (kernels_bank_farrow.hip; a.pnfb is [nch][T][polyorder+1]; TypeKey::bank on a FIRFarrow filter): the
 // universal kernel and the LDS-tiled one; both serve host- and device-planned calls and take the ShiftFold epilogue
 hipError_t launch_farrow_bank_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, hipStream_t s, const char **kname);

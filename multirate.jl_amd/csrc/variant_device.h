@@ -1,4 +1,4 @@
-// variant_device.h -- what the seven "variant" units (complex taps: kernels_ctaps*.hip; per-channel taps: kernels_bank*.hip) share,
+// variant_device.h -- what the eight "variant" units (complex taps: kernels_ctaps*.hip; per-channel taps: kernels_bank*.hip) share,
 // stated ONCE: the dispatch over (Tx scalar, R, components), the staging of a [history ; x] window into LDS, the hand-out of the
 // channel-major tile order, the small statements of the rational and FIRArbitrary kernels, the TAP ALGEBRA -- the only thing in which a
 // real-tap and a complex-tap body differ -- the bodies that are one kernel under two algebras, and the two launch shapes.  The plans of
@@ -314,6 +314,82 @@ __device__ __forceinline__ void arb_variant_generic_body(ArbArgs a, const long l
                 lo = A::step(lo, tp[i], v);
                 up = A::step(up, dp[i], v);
             }
+            A::store(yc, k, A::arb_combine(lo, up, alpha));
+        }
+    }
+    dev::shiftin_by_last_workgroup<typename A::Tx, A::NC>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+}
+
+// FIRArbitrary, per-channel taps, persistent workgroups in the channel-major tile order (tile_run): arb_bank_tiled_kernel's body under
+// algebra A.  arb_bank_ctaps_tiled_kernel (complex taps) is a wrapper of it; arb_bank_tiled_kernel (real taps) keeps its own copy in
+// kernels_bank_arb.hip: as a wrapper of this body it measured 0.1 % slower than the parent's two runs at 64 ch x 1e7 Float64 in both of
+// its runs (profiles/r08/arb_bank_ctaps.txt), which is the condition under which it was to stay as it is.  A tile is (channel, run of tile_out = 256 outputs); the workgroup
+// holds one channel's pfb and dpfb in LDS as A::Tap (column pitch T + 1: lanes of different phases read different LDS banks; a pair
+// is aligned to its size, so a tap is one LDS read) and reloads them only when its run crosses into the next channel.  The tile's run
+// of samples is staged through LDS (tile_span); a tile whose run exceeds the planned span reads its windows from global memory.  The
+// count and the tiling follow the call record when a.dyn is set (tiles_take_dyn with nch groups), so every workgroup's run is computed
+// from the device-side count.  No workgroup communicates with or waits for another; ends with the ShiftFold epilogue.
+template <typename A>
+__device__ __forceinline__ void arb_variant_bank_tiled_body(ArbArgs a, ArbTileArgs ta)
+{
+    using Sample = typename A::Sample;
+    using Tap = typename A::Tap;
+    extern __shared__ __attribute__((aligned(16))) unsigned char variant_smem[];
+    Tap *const lpfb = reinterpret_cast<Tap *>(variant_smem);
+    Tap *const ldpfb = lpfb + ta.bank_elems;
+    Sample *const lx = reinterpret_cast<Sample *>(variant_smem + ta.x_offset_bytes);
+
+    const int tid = threadIdx.x;
+    const int T = a.T, TP = ta.tap_pitch;
+    long long ngroups;                                              // (== nch: a tile covers one channel)
+    tiles_take_dyn(a.n_out, ta, ngroups, a.dyn);                    // (a device-planned call: the count from the call record)
+    const TileRun run = tile_run(ta.total_tiles);
+    const int bank_elems = a.Nphi * T;
+    int ch_in_lds = -1;
+
+    for (long long tile = run.begin; tile < run.end; ++tile) {
+        const BankTile t = bank_tile(tile, ta, a.n_out);
+        const int ch = t.ch;
+        const TileSpan w = tile_span(a.n_idx, t.k0, t.klast, T, ta.max_span);
+        const Sample *__restrict__ xc = static_cast<const Sample *>(a.x) + static_cast<long long>(ch) * a.x_stride;
+        const Sample *__restrict__ hc = static_cast<const Sample *>(a.hist) + static_cast<long long>(ch) * a.H;
+
+        __syncthreads();   // the previous tile's reads of banks and window are done
+        if (ch != ch_in_lds) {   // (uniform over the workgroup) channel ch's banks -> LDS: element (phi, i) at phi*TP + i
+            const Tap *__restrict__ g0 = static_cast<const Tap *>(a.taps) + static_cast<long long>(ch) * bank_elems;
+            const Tap *__restrict__ g1 = static_cast<const Tap *>(a.dtaps) + static_cast<long long>(ch) * bank_elems;
+            for (int e = tid; e < bank_elems; e += kVariantThreads) {
+                const int phi = e / T, i = e - phi * T;
+                lpfb[phi * TP + i] = g0[e];
+                ldpfb[phi * TP + i] = g1[e];
+            }
+            ch_in_lds = ch;
+        }
+        if (w.staged) stage_window(lx, xc, hc, w.o, static_cast<int>(w.span), a.x_len, a.H, tid);
+        __syncthreads();
+
+        typename A::Out *__restrict__ yc = A::channel_out(a.y, ch, a.y_stride);
+        for (long long k = t.k0 + tid; k <= t.klast; k += kVariantThreads) {
+            const long long n = a.n_idx[k];
+            double alpha;
+            const int phi = arb_phase(a.acc[k], &alpha);
+            const Tap *tp = lpfb + phi * TP;
+            const Tap *dp = ldpfb + phi * TP;
+            typename A::Sum lo, up;
+            if (w.staged) {
+                const Sample *wp = lx + (n - w.n_lo);             // oldest sample of this output's window
+                const Tap t0 = tp[0], d0 = dp[0];
+                const Sample v0 = wp[0];
+                lo = A::first(t0, v0);
+                up = A::first(d0, v0);
+#pragma unroll 4
+                for (int i = 1; i < T; ++i) {
+                    const Tap ti = tp[i], di = dp[i];
+                    const Sample v = wp[i];
+                    lo = A::step(lo, ti, v);
+                    up = A::step(up, di, v);
+                }
+            } else arb_dots_global<A>(tp, dp, xc, hc + a.H, n - T, T, lo, up);
             A::store(yc, k, A::arb_combine(lo, up, alpha));
         }
     }

@@ -81,6 +81,7 @@ ABI = [
     ("mrhip_create_arbitrary", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_bank", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_arbitrary_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_bank", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -264,7 +265,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
-        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_farrow): the (nchannels, hLen) matrix; self.h is its row 0
+        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
                 raise MultirateHIPError(1, "rate must be greater than 0")  # Filters.jl:184
@@ -378,7 +379,7 @@ class FIRFilter:
         either side is 64-bit); STRICT numerics only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape
         (nchannels, tapsPer𝜙, N𝜙), complex.  The device object is created by ``mrhip_create_rational_bank_ctaps``."""
         if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "per_channel_complex_taps builds the rational family only (FIRArbitrary / FIRFarrow have no per-channel taps)")
+            raise MultirateHIPError(5, "per_channel_complex_taps builds the rational family only (a float rate: FIRFilter.per_channel_complex_taps_arbitrary; FIRFarrow has no per-channel complex taps)")
         H = np.asarray(H)
         if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
             raise MultirateHIPError(1, f"per_channel_complex_taps takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
@@ -402,11 +403,35 @@ class FIRFilter:
             raise MultirateHIPError(1, "per_channel_arbitrary takes a floating-point rate (a Rational ratio: FIRFilter.per_channel)")
         H = np.asarray(H)
         if H.dtype.kind == "c":
-            raise MultirateHIPError(5, "per_channel_arbitrary takes Float32/Float64 taps (complex taps in a FIRArbitrary bank are not supported)")
+            raise MultirateHIPError(5, "per_channel_arbitrary takes Float32/Float64 taps (complex taps: FIRFilter.per_channel_complex_taps_arbitrary)")
         if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
             raise MultirateHIPError(1, f"per_channel_arbitrary takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
         H = np.ascontiguousarray(_as_taps(H))
         f = cls(H[0], float(rate), int(Nphi), device=device, numerics=numerics)
+        f._bank = H.copy()
+        return f
+
+    @classmethod
+    def per_channel_complex_taps_arbitrary(cls, H, rate, Nphi: int = 32, *, device: int = 0):
+        """One FIRFilter(H[c]::Vector{Complex64 / Complex128}, rate::Float, N𝜙) per channel behind one filter object: FIRArbitrary
+        with per-channel complex taps (a prototype rotated to every channel's own centre frequency in front of a common clock-trim or
+        arbitrary-rate change, per-antenna complex equalisers folded into the resampler's prototype, per-channel Hilbert or
+        single-sideband filters in front of a symbol-rate change).  ``H``: shape (nchannels, hLen), Complex64 or Complex128; real
+        taps belong to ``per_channel_arbitrary``.  Rate, N𝜙, state and call length are shared, only the two filter banks differ;
+        channel c is bit for bit ``FIRFilter.complex_taps_arbitrary(H[c], rate, Nphi)`` fed ``x[c]`` (include/multirate_hip.h:
+        per-channel complex taps for FIRArbitrary).  The output is always complex (Complex128 if either side is 64-bit); STRICT
+        numerics only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps(which)`` has shape (nchannels, tapsPer𝜙, N𝜙)
+        and ``tapsforphase`` (nchannels, tapsPer𝜙), both complex.  The device object is created by
+        ``mrhip_create_arbitrary_bank_ctaps``."""
+        if not isinstance(rate, (float, np.floating)):
+            raise MultirateHIPError(1, "per_channel_complex_taps_arbitrary takes a floating-point rate (a Rational ratio: FIRFilter.per_channel_complex_taps)")
+        H = np.asarray(H)
+        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+            raise MultirateHIPError(1, f"per_channel_complex_taps_arbitrary takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
+        if H.dtype != np.complex64 and H.dtype != np.complex128:
+            raise MultirateHIPError(1, f"per_channel_complex_taps_arbitrary takes Complex64/Complex128 taps, got {H.dtype} (real taps: FIRFilter.per_channel_arbitrary)")
+        H = np.ascontiguousarray(H)
+        f = cls(H[0], float(rate), int(Nphi), device=device, _complex_taps=True)
         f._bank = H.copy()
         return f
 
@@ -447,7 +472,10 @@ class FIRFilter:
         out = C.c_void_p()
         if self._bank is not None and nch != self._bank.shape[0]:
             raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
-        if self._bank is not None and self.kind == ARBITRARY:
+        if self._bank is not None and self.kind == ARBITRARY and self._bank.dtype.kind == "c":
+            rc = self._lib.mrhip_create_arbitrary_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
+                                                             self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self._bank is not None and self.kind == ARBITRARY:
             rc = self._lib.mrhip_create_arbitrary_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
                                                        self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
         elif self._bank is not None and self.kind == FARROW:

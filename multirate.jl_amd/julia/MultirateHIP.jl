@@ -117,6 +117,16 @@ function FIRFilter(H::Matrix{Th}, rate::AbstractFloat, Nphi::Integer = 32; devic
     f = FIRFilter{FIRArbitrary{Th}}(vec(copy(H)), nothing, Float64(rate), Nphi, -1, device, C_NULL, nothing, 0, size(H, 2))
     finalizer(destroy!, f)
 end
+# The same with COMPLEX taps (include/multirate_hip.h: per-channel complex taps for FIRArbitrary): one
+# FIRFilter(H[:, c]::Vector{Complex}, rate, Nphi) per channel -- a prototype rotated to every channel's own centre frequency in front
+# of a common arbitrary-rate change.  The same transposition: one column per channel; bind! creates the device object through
+# mrhip_create_arbitrary_bank_ctaps; the output is complex for every sample type.  (Like the rest of this file, never executed where the
+# library is built and tested: no Julia there.)
+function FIRFilter(H::Matrix{Th}, rate::AbstractFloat, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{ComplexF32,ComplexF64}}
+    rate > 0.0 || error("rate must be greater than 0")
+    f = FIRFilter{FIRArbitrary{Th}}(vec(copy(H)), nothing, Float64(rate), Nphi, -1, device, C_NULL, nothing, 0, size(H, 2))
+    finalizer(destroy!, f)
+end
 # FIRFilter(h, rate::AbstractFloat, Nphi, polyorder)      src/Filters.jl:192-198  (FIRFarrow)
 function FIRFilter(h::Vector{Th}, rate::AbstractFloat, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     rate > 0.0 || error("rate must be greater than 0")
@@ -160,6 +170,11 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
         check(ccall((:mrhip_create_farrow_bank, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
                     f.h, div(length(f.h), f.nbank), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
+    elseif f.nbank > 0 && f.ratio === nothing && Th <: Complex
+        nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
+        check(ccall((:mrhip_create_arbitrary_bank_ctaps, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, div(length(f.h), f.nbank), dtypecode(Th), f.rate, f.Nphi, dtypecode(Tx), nch, f.device, out))
     elseif f.nbank > 0 && f.ratio === nothing
         nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
         check(ccall((:mrhip_create_arbitrary_bank, libmr), Cint,
