@@ -49,7 +49,7 @@ typedef enum {
 } mrhip_status;
 
 /* element types: Th in {F32,F64} for every kind, and {C64,C128} for the rational family (mrhip_create_rational, mrhip_create_rational_bank_ctaps) and
- * FIRArbitrary (mrhip_create_arbitrary_ctaps, mrhip_create_arbitrary_bank_ctaps) and FIRFarrow (mrhip_create_farrow_ctaps, mrhip_create_farrow_pnfb_ctaps);
+ * FIRArbitrary (mrhip_create_arbitrary_ctaps, mrhip_create_arbitrary_bank_ctaps) and FIRFarrow (mrhip_create_farrow_ctaps, mrhip_create_farrow_pnfb_ctaps, mrhip_create_farrow_bank_ctaps);
  * Tx in {F32,F64,C64,C128}; Tb = promote_type(Th,Tx) -- complex as soon as either side is */
 typedef enum { MRHIP_F32 = 0, MRHIP_F64 = 1, MRHIP_C64 = 2, MRHIP_C128 = 3 } mrhip_dtype;
 
@@ -201,7 +201,8 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - as for both parents: mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is
  *     not resident; mrhip_sharded_create has no such constructor; a cascade takes the filter as a stage through its per-stage
  *     calls;
- *   - left out on purpose: FIRFarrow banks with complex taps, a FUSED form, sharded banks, a resident ring for banks. */
+ *   - left out on purpose: a FUSED form, sharded banks, a resident ring for banks.  FIRFarrow banks with complex taps have a
+ *     constructor of their own ("Per-channel complex taps for FIRFarrow" below). */
 
 /* Per-channel taps for FIRFarrow (mrhip_create_farrow_bank; Th in {F32,F64}): one FIRFilter(h_c, rate, Nphi, polyorder) per
  * channel behind one handle -- a per-antenna equaliser or a per-sensor calibration filter in front of a common, continuously
@@ -226,8 +227,40 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - mrhip_create_farrow*, mrhip_create_arbitrary_bank and mrhip_create_rational_bank* answer exactly as before;
  *     mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is not resident;
  *     mrhip_sharded_create has no such constructor; a cascade takes the filter as a stage through its per-stage calls;
- *   - left out on purpose: complex-tap FIRFarrow banks (complex taps return MRHIP_ERR_UNSUPPORTED here), a caller-fitted pnfb for banks, sharded banks, a resident ring for banks, and the shared-taps FIRFarrow kernels
- *     farrow_pipe_kernel / farrow_wave_kernel (such a filter runs on its own two kernels). */
+ *   - complex taps return MRHIP_ERR_UNSUPPORTED here (left out of THIS constructor: they have one of their own, "Per-channel complex
+ *     taps for FIRFarrow" below); left out on purpose: a caller-fitted pnfb for banks, sharded banks, a resident ring for banks, and
+ *     the shared-taps FIRFarrow kernels farrow_pipe_kernel / farrow_wave_kernel (such a filter runs on its own two kernels). */
+
+/* Per-channel complex taps for FIRFarrow (mrhip_create_farrow_bank_ctaps; Th in {C64,C128}): one
+ * FIRFilter(h_c::Vector{Complex}, rate, Nphi, polyorder) per channel behind one handle -- a prototype rotated to every channel's own
+ * centre frequency, or a per-antenna complex equaliser, in front of a common, continuously variable rate change.  The contract is
+ * the conjunction of "Complex taps" (FIRFarrow) and "Per-channel taps for FIRFarrow":
+ *   - for every channel c the outputs, the per-call counts, the end state (inputDeficit, phiAccumulator, phiIdx) and the history
+ *     are bit for bit those of mrhip_create_farrow_ctaps(h_c, ..., nchannels = 1) fed x_c;
+ *   - every row goes through taps2pfb and the per-component polynomial fit on its own, exactly as mrhip_create_farrow_ctaps
+ *     treats one h; the coefficients are stored in the tap type, per component;
+ *   - per tap and component: Horner in Float64 from the highest power, t = phi*v; v = coef + t, the product and the sum each
+ *     rounded once (never fused), the result rounded once to the tap's real scalar and widened exactly to R;
+ *   - the dot: oldest sample first, the first product initialises the accumulator, Complex*Real and Complex*Complex written out
+ *     in the operand order stated under "Complex taps", every multiply, add and subtract rounded separately in R; outputs on the
+ *     start-from-zero seam of support.jl:46 then take 0 + acc per component;
+ *   - the output is always complex (C128 if either side is 64-bit, else C64); the history stays in Tx;
+ *   - STRICT only, no FUSED form is defined: mrhip_set_numerics(f, FUSED) returns MRHIP_ERR_UNSUPPORTED;
+ *   - everything that does not depend on the taps is the shared code, unchanged: the phase schedule, mrhip_set_mod_form,
+ *     outputlength, next_output_count, outputlength_bound, advance_state, set_state, reset, set_history*; the mrhip_state
+ *     layout is the same and its tap_dtype reads 2 or 3;
+ *   - mrhip_get_pnfb returns the nchannels banks one after the other, [nchannels][tapsPerPhi][polyorder+1] (re, im) pairs of
+ *     Float64;
+ *   - mrhip_farrow_tapsforphase returns nchannels rows of tapsPerPhi pairs, row c is the statement for complex taps (per
+ *     component) on bank c; the range error is unchanged;
+ *   - mrhip_create_farrow_bank keeps returning MRHIP_ERR_UNSUPPORTED for complex taps; a real tap_dtype here is
+ *     MRHIP_ERR_INVALID_ARG; mrhip_create_farrow*, mrhip_create_arbitrary_bank* and mrhip_create_rational_bank* answer exactly as
+ *     before;
+ *   - as for both parents: mrhip_filt_device_multi with such a filter among its streams issues single calls; a ring on it is
+ *     not resident; mrhip_sharded_create has no such constructor; a cascade takes the filter as a stage through its per-stage
+ *     calls;
+ *   - such a filter runs on ONE kernel (farrow_bank_ctaps_generic_kernel); MRHIP_FORCE_GENERIC has no effect on it;
+ *   - left out on purpose: a caller-fitted pnfb for banks, a FUSED form, sharded banks, a resident ring for banks. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -352,9 +385,15 @@ int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int tap_dtype
 int mrhip_create_farrow(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi, int64_t polyorder,
                         int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* one FIRFilter(h_c, rate, Nphi, polyorder) per channel behind one handle (see "Per-channel taps for FIRFarrow" above): `h` holds
- * nchannels rows of hLen taps, row-major, row c is channel c's h.  tap_dtype F32 | F64 (complex: MRHIP_ERR_UNSUPPORTED, left out).
+ * nchannels rows of hLen taps, row-major, row c is channel c's h.  tap_dtype F32 | F64 (complex: MRHIP_ERR_UNSUPPORTED, left out of
+ * this entry point: mrhip_create_farrow_bank_ctaps).
  * rate, Nphi, polyorder and every other argument check are those of mrhip_create_farrow; the filter's kind is MRHIP_FIR_FARROW. */
 int mrhip_create_farrow_bank(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi, int64_t polyorder, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* the same with COMPLEX taps (see "Per-channel complex taps for FIRFarrow" above): `h` holds nchannels rows of hLen interleaved
+ * (re, im) taps, row-major.  tap_dtype C64 | C128 (real: MRHIP_ERR_INVALID_ARG, mrhip_create_farrow_bank takes those); every other
+ * argument check is that of mrhip_create_farrow_ctaps; the output is complex for every sample type. */
+int mrhip_create_farrow_bank_ctaps(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi, int64_t polyorder,
+                                   int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* same, with the polynomial filter bank supplied by the caller: pnfb[tapsPerPhi][polyorder+1] Float64,
  * ascending powers (the layout of Poly.a), tapsPerPhi = ceil(hLen/Nphi); values are rounded to the tap type
  * as the reference's Poly{T} storage does.  Lets a caller fit with its own least-squares routine (the
@@ -371,11 +410,13 @@ int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int tap_dtype, double
 int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
                                    int64_t polyorder, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* the polynomial filter bank in use, [tapsPerPhi][polyorder+1] Float64 (pfb2pnfb's result); complex taps: (re, im) pairs of
- * Float64, twice as many values; per-channel taps (mrhip_create_farrow_bank): the nchannels banks one after the other */
+ * Float64, twice as many values; per-channel taps (mrhip_create_farrow_bank, mrhip_create_farrow_bank_ctaps): the nchannels banks
+ * one after the other */
 int mrhip_get_pnfb(const mrhip_filter *f, double *host_out);
 /* replaces tapsforphase(kernel::FIRFarrow, phase), src/Filters.jl:764-775: tapsPerPhi taps of tap_dtype
  * for a phase in [0, Nphi+1] (host evaluation; MRHIP_ERR_INVALID_ARG outside the range like :765); complex taps: tapsPerPhi
- * complex taps, the statement per component; per-channel taps (mrhip_create_farrow_bank): nchannels rows of tapsPerPhi taps */
+ * complex taps, the statement per component; per-channel taps (mrhip_create_farrow_bank, mrhip_create_farrow_bank_ctaps): nchannels
+ * rows of tapsPerPhi taps */
 int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_out);
 /* replaces tapsforphase(kernel::FIRArbitrary, phase), src/Filters.jl:677-690: (alpha, phiIdx) = modf(phase);
  * taps[i] = pfb[i, phiIdx] + alpha * dpfb[i, phiIdx], evaluated in Float64 (alpha is a Float64 there) and stored in

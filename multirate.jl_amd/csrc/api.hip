@@ -574,8 +574,8 @@ int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int th, doubl
 
 // FIRFarrow(h, rate, N𝜙, polyorder), src/Filters.jl:138-147, behind all four constructors.  pnfb_in: [T][polyorder+1] coefficients,
 // ascending powers -- scalars for real taps, (re, im) pairs for complex ones (the layout kernels_ctaps_farrow.hip reads).  bank: pnfb_in
-// holds nch such banks one after the other, [nch][T][polyorder+1] (mrhip_create_farrow_bank; kernels_bank_farrow.hip), and the degree-major
-// copy for farrow_wave_kernel is never built.
+// holds nch such banks one after the other, [nch][T][polyorder+1] (mrhip_create_farrow_bank; kernels_bank_farrow.hip -- with complex taps
+// mrhip_create_farrow_bank_ctaps: pairs, kernels_bank_farrow_ctaps.hip), and the degree-major copy for farrow_wave_kernel is never built.
 static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen, int th, double rate, int64_t Nphi,
                                 int64_t polyorder, int tx, int64_t nch, int device, bool bank, mrhip_filter **out)
 {
@@ -633,6 +633,29 @@ static bool farrow_fit(const void *h, int64_t hLen, int th, int64_t Nphi, int64_
     return true;
 }
 
+// The same for one COMPLEX tap vector `h` (hLen (re, im) pairs) into pn, [T][polyorder+1] pairs.  The Vandermonde matrix of the fit is
+// real, so the least-squares fit of a complex row is the fit of its real parts and the fit of its imaginary parts.
+static bool farrow_fit_ctaps(const void *h, int64_t hLen, int th, int64_t Nphi, int64_t polyorder, double *pn)
+{
+    const size_t es = dtype_size(th);
+    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
+    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
+    taps2pfb(h, hLen, th, Nphi, pfb.data());                // column-major T x Nphi of (re, im) pairs
+    const size_t np = static_cast<size_t>(polyorder + 1);
+    std::vector<double> row(static_cast<size_t>(Nphi)), fit(np);
+    for (int64_t i = 0; i < T; ++i)
+        for (int comp = 0; comp < 2; ++comp) {
+            for (int64_t c = 0; c < Nphi; ++c) {
+                const size_t e = static_cast<size_t>(c * T + i) * 2 + comp;
+                row[static_cast<size_t>(c)] = dtype_is_f64(th) ? reinterpret_cast<const double *>(pfb.data())[e]
+                                                               : static_cast<double>(reinterpret_cast<const float *>(pfb.data())[e]);
+            }
+            if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), fit.data())) return false;
+            for (size_t j = 0; j < np; ++j) pn[(static_cast<size_t>(i) * np + j) * 2 + comp] = fit[j];
+        }
+    return true;
+}
+
 int mrhip_create_farrow(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
                         int64_t nch, int device, mrhip_filter **out)
 {
@@ -654,7 +677,8 @@ int mrhip_create_farrow_bank(const void *h, int64_t hLen, int th, double rate, i
 {
     if (out) *out = nullptr;
     if (th == MRHIP_C64 || th == MRHIP_C128)
-        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_bank takes Float32 / Float64 taps (complex taps in a FIRFarrow bank are left out)");
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_bank takes Float32 / Float64 taps (complex taps in a FIRFarrow bank are left out of "
+                                           "this entry point: mrhip_create_farrow_bank_ctaps)");
     if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
     if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
     if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
@@ -681,8 +705,7 @@ int mrhip_create_farrow_pnfb(const double *pnfb, int64_t hLen, int th, double ra
     return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
 }
 
-// The same two constructors for COMPLEX taps (include/multirate_hip.h, "Complex taps", FIRFarrow part).  The Vandermonde matrix of
-// the fit is real, so the least-squares fit of a complex row is the fit of its real parts and the fit of its imaginary parts.
+// The same two constructors for COMPLEX taps (include/multirate_hip.h, "Complex taps", FIRFarrow part); the fit: farrow_fit_ctaps.
 int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
                               int64_t nch, int device, mrhip_filter **out)
 {
@@ -694,24 +717,32 @@ int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int th, double rate, 
     if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
     if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
         return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
-    const size_t es = dtype_size(th);
-    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
-    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
-    taps2pfb(h, hLen, th, Nphi, pfb.data());                // column-major T x Nphi of (re, im) pairs
-    const size_t np = static_cast<size_t>(polyorder + 1);
-    std::vector<double> pn(static_cast<size_t>(T) * np * 2), row(static_cast<size_t>(Nphi)), fit(np);
-    for (int64_t i = 0; i < T; ++i)
-        for (int comp = 0; comp < 2; ++comp) {
-            for (int64_t c = 0; c < Nphi; ++c) {
-                const size_t e = static_cast<size_t>(c * T + i) * 2 + comp;
-                row[static_cast<size_t>(c)] = dtype_is_f64(th) ? reinterpret_cast<const double *>(pfb.data())[e]
-                                                               : static_cast<double>(reinterpret_cast<const float *>(pfb.data())[e]);
-            }
-            if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), fit.data()))
-                return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
-            for (size_t j = 0; j < np; ++j) pn[(static_cast<size_t>(i) * np + j) * 2 + comp] = fit[j];
-        }
+    const int64_t T = (hLen + Nphi - 1) / Nphi;
+    std::vector<double> pn(static_cast<size_t>(T) * (polyorder + 1) * 2);
+    if (!farrow_fit_ctaps(h, hLen, th, Nphi, polyorder, pn.data())) return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
     return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
+}
+
+// One FIRFilter(h_c::Vector{Complex}, rate, N𝜙, polyorder) per channel behind one handle (include/multirate_hip.h, "Per-channel complex
+// taps for FIRFarrow"): `h` holds nch rows of hLen (re, im) pairs; every row goes through taps2pfb and the per-component fit on its own.
+int mrhip_create_farrow_bank_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
+                                   int64_t nch, int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_F32 || th == MRHIP_F64)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_farrow_bank_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_farrow_bank");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
+    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
+    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
+    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
+        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
+    const int64_t T = (hLen + Nphi - 1) / Nphi;
+    const size_t bank_scalars = static_cast<size_t>(T) * (polyorder + 1) * 2, es = dtype_size(th);
+    std::vector<double> pn(bank_scalars * static_cast<size_t>(nch));
+    for (int64_t r = 0; r < nch; ++r)
+        if (!farrow_fit_ctaps(static_cast<const unsigned char *>(h) + static_cast<size_t>(r) * hLen * es, hLen, th, Nphi, polyorder, &pn[r * bank_scalars]))
+            return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
+    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, true, out);
 }
 
 int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder,
@@ -754,7 +785,7 @@ int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_ou
     // complex taps: the same statement per component (Real*Complex and Complex+Complex are by components) -- a polynomial is
     // P+1 (re, im) pairs, the result T interleaved pairs
     const int64_t nc = dtype_is_complex(f->th) ? 2 : 1;
-    // per-channel taps (mrhip_create_farrow_bank): nch banks one after the other, the same statement on each; row c of the result is bank c's
+    // per-channel taps (mrhip_create_farrow_bank, mrhip_create_farrow_bank_ctaps): nch banks one after the other, the same statement on each; row c of the result is bank c's
     const int64_t rows = f->bank ? f->nch : 1, row_elems = f->T * nc;
     for (int64_t r = 0; r < rows; ++r)
         for (int64_t i = 0; i < row_elems; ++i) {
@@ -1493,7 +1524,11 @@ static int launch_range(const ArbRange &r, int64_t k0, int64_t cnt, const int32_
         if (int rc = timing_mark(f, stream)) return rc;
         ArbTileArgs fta;
         size_t flds = 0;
-        if (tk.bank) {                    // per-channel taps (kernels_bank_farrow.hip): no plan_* below ever sees such a call
+        if (tk.bank && tk.complex_h) {    // per-channel complex taps (kernels_bank_farrow_ctaps.hip): one kernel; no branch or plan_* below ever sees such a call
+            fa.fold = sf;                 // (the kernel writes the next call's history itself)
+            MRHIP_CHECK_HIP(launch_farrow_bank_ctaps_generic(tk, fa, stream, &f->last_kernel));
+        }
+        else if (tk.bank) {               // per-channel taps (kernels_bank_farrow.hip): no plan_* below ever sees such a call
             fa.fold = sf;                 // (both kernels write the next call's history themselves)
             if (!f->force_generic && plan_farrow_bank_tiled(tk, fa, f->rate, f->num_cus, &fta, &flds))
                 MRHIP_CHECK_HIP(launch_farrow_bank_tiled(tk, fused, fa, fta, flds, stream, &f->last_kernel, f->num_cus));

@@ -425,7 +425,7 @@ struct FarrowArgs {          // FIRFarrow
     void *y;
     const void *hist;
     const double *pnfb;      // device, [T][polyorder+1] ascending powers (values representable in Th); complex taps: (re, im) pairs;
-                             // per-channel taps (mrhip_create_farrow_bank): [nch][T][polyorder+1]
+                             // per-channel taps (mrhip_create_farrow_bank; pairs: mrhip_create_farrow_bank_ctaps): [nch][T][polyorder+1]
     const int *n_idx;        // device, per output: 1-based input index
     const double *acc;       // device, per output: the Float64 phase 𝜙Idx
     long long x_stride, y_stride;
@@ -598,7 +598,7 @@ struct TypeKey {
     bool r_f64;      // compute/output scalar is double
     bool complex_x;  // NC == 2
     bool complex_h = false;   // complex taps: R-typed (re, im) pairs, complex output; kernels_ctaps.hip (rational family), kernels_ctaps_arb.hip (FIRArbitrary) and kernels_ctaps_farrow.hip (FIRFarrow) only
-    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only; FIRArbitrary, mrhip_create_arbitrary_bank: ArbArgs::taps / dtaps are [nch][Nphi][T], kernels_bank_arb.hip only -- with complex_h, mrhip_create_arbitrary_bank_ctaps: pairs, kernels_bank_arb_ctaps.hip only; FIRFarrow, mrhip_create_farrow_bank: FarrowArgs::pnfb is [nch][T][polyorder+1], kernels_bank_farrow.hip only)
+    bool bank = false;        // per-channel taps (mrhip_create_rational_bank): PolyArgs::taps is [nch][Nphi][T]; kernels_bank.hip only (with complex_h, mrhip_create_rational_bank_ctaps: kernels_bank_ctaps.hip only; FIRArbitrary, mrhip_create_arbitrary_bank: ArbArgs::taps / dtaps are [nch][Nphi][T], kernels_bank_arb.hip only -- with complex_h, mrhip_create_arbitrary_bank_ctaps: pairs, kernels_bank_arb_ctaps.hip only; FIRFarrow, mrhip_create_farrow_bank: FarrowArgs::pnfb is [nch][T][polyorder+1], kernels_bank_farrow.hip only -- with complex_h, mrhip_create_farrow_bank_ctaps: pairs, kernels_bank_farrow_ctaps.hip only)
 };
 
 // ---------------------------------------------------------------------------------------
@@ -697,6 +697,9 @@ bool plan_arb_bank_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate,
 bool plan_arb_bank_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int num_cus, int mode, ArbTileArgs *out, size_t *lds);   // host_logic.cpp: the switch value passed in
 hipError_t launch_arb_bank_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, const ArbTileArgs &ta, size_t lds, hipStream_t s,
                                        const char **kname, int num_cus);
+// per-channel COMPLEX taps, FIRFarrow (kernels_bank_farrow_ctaps.hip; a.pnfb is [nch][T][polyorder+1] (re, im) pairs; TypeKey::bank &&
+// TypeKey::complex_h on a FIRFarrow filter): the one kernel of such a filter -- host- and device-planned calls, the ShiftFold epilogue
+hipError_t launch_farrow_bank_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, hipStream_t s, const char **kname);
 // per-channel taps, FIRFarrow (kernels_bank_farrow.hip; a.pnfb is [nch][T][polyorder+1]; TypeKey::bank on a FIRFarrow filter): the
 // universal kernel and the LDS-tiled one; both serve host- and device-planned calls and take the ShiftFold epilogue
 hipError_t launch_farrow_bank_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, hipStream_t s, const char **kname);

@@ -1,4 +1,4 @@
-// variant_device.h -- what the eight "variant" units (complex taps: kernels_ctaps*.hip; per-channel taps: kernels_bank*.hip) share,
+// variant_device.h -- what the nine "variant" units (complex taps: kernels_ctaps*.hip; per-channel taps: kernels_bank*.hip) share,
 // stated ONCE: the dispatch over (Tx scalar, R, components), the staging of a [history ; x] window into LDS, the hand-out of the
 // channel-major tile order, the small statements of the rational and FIRArbitrary kernels, the TAP ALGEBRA -- the only thing in which a
 // real-tap and a complex-tap body differ -- the bodies that are one kernel under two algebras, and the two launch shapes.  The plans of
@@ -27,9 +27,55 @@ hipError_t dispatch_variant(const TypeKey &tk, F &&f)
     return hipErrorInvalidValue;
 }
 
+// ---- FIRFarrow with per-channel taps: the coefficient reads and the Horner chains ------------------------------------------------
+// The polynomial bank is never written while a filter exists: through the constant address space the compiler uses scalar loads for
+// the wave-uniform coefficient indices (it cannot prove that for a global pointer next to the y stores).
+typedef const __attribute__((address_space(4))) double *farrow_coef_t;
+
+// polyorder 4 is the default of every constructor above this library and the one every measurement was taken at: its Horner chains are
+// unrolled (kFarrowBankUnrolledP); every other polyorder takes the runtime loop.  The branch is on a kernel argument: uniform.
+constexpr int kFarrowBankUnrolledP = 4;
+
+// polyval(pnfb_c[i], 𝜙) by Horner in Float64 (Polynomials.jl: y = p[end]; y = p[i] + x*y), NC chains side by side: 1 for a real
+// polynomial, 2 for a Poly{Complex} (Real*Complex and Complex+Complex are by components; the coefficients are (re, im) pairs).
+// `c`: the polynomial's (P+1)*NC scalars, ascending powers, wave-uniform.  Per step and component t = 𝜙*v; v = coef + t, the product and
+// the sum each rounded once, never fused.  PP >= 0: the polyorder at compile time -- the (P+1)*NC scalar loads of a tap are issued
+// together and waited for once; PP < 0: any polyorder, the loads inside the loop.  The arithmetic is the same statement either way.
+template <int PP, int NC>
+__device__ __forceinline__ void farrow_bank_horner(farrow_coef_t c, const int P, const double phase, double (&v)[NC])
+{
+    if constexpr (PP >= 0) {
+        double cj[(PP + 1) * NC];
+#pragma unroll
+        for (int e = 0; e < (PP + 1) * NC; ++e) cj[e] = c[e];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) v[q] = cj[PP * NC + q];
+#pragma unroll
+        for (int j = PP - 1; j >= 0; --j) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+                const double t = phase * v[q];
+                v[q] = cj[j * NC + q] + t;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < NC; ++q) v[q] = c[P * NC + q];
+        for (int j = P - 1; j >= 0; --j) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+                const double t = phase * v[q];
+                v[q] = c[j * NC + q] + t;
+            }
+        }
+    }
+}
+
 // ---- the tap algebras --------------------------------------------------------------------------------------------------------
 // Tap: one tap in global memory and LDS; Sum: the running sum(s) of one output; first / zero_start (support.jl:46) / step / the
-// FIRArbitrary combine (yLower + yUpper * α in Float64: src/Filters.jl:724-730) / the store of one output.
+// FIRArbitrary combine (yLower + yUpper * α in Float64: src/Filters.jl:724-730) / the store of one output; ComplexTaps also the FIRFarrow
+// tap of one (channel, output) from its polynomial (stored into currentTaps::Vector{Th}: one rounding to the tap's real scalar, widened
+// exactly to R) -- RealTaps would evaluate one chain to an R (farrow_bank_horner<PP, 1>) once farrow_bank_generic_kernel joins the body.
 
 // real taps: NCX independent real dot products
 template <typename TX, typename R, int NCX, bool FUSED>
@@ -92,6 +138,17 @@ struct ComplexTaps {
     static __device__ __forceinline__ Sum zero_start(const Sum s) { return ctap_zero_start<R>(s); }
     static __device__ __forceinline__ Sum step(const Sum s, const Tap t, const Sample v) { return ctap_add<R>(s, ctap_product<TX, R, NCX>(t, v)); }
     static __device__ __forceinline__ Sum arb_combine(const Sum lo, const Sum up, const double alpha) { return ctap_arb_combine<R>(lo, up, alpha); }
+    static constexpr int kCoefScalars = 2;       // an (re, im) pair of Float64 per polynomial coefficient
+    template <int PP>
+    static __device__ __forceinline__ Tap farrow_tap(farrow_coef_t c, const int P, const double phase, const bool tap_f32)
+    {
+        double v[2];
+        farrow_bank_horner<PP, 2>(c, P, phase, v);
+        Tap t;
+        t.re = tap_f32 ? static_cast<R>(static_cast<float>(v[0])) : static_cast<R>(v[0]);
+        t.im = tap_f32 ? static_cast<R>(static_cast<float>(v[1])) : static_cast<R>(v[1]);
+        return t;
+    }
     static __device__ __forceinline__ Out *channel_out(void *y, long long ch, long long y_stride) { return static_cast<Out *>(y) + ch * y_stride; }
     static __device__ __forceinline__ void store(Out *yc, long long k, const Sum s) { yc[k] = s; }
 };
@@ -392,6 +449,52 @@ __device__ __forceinline__ void arb_variant_bank_tiled_body(ArbArgs a, ArbTileAr
             } else arb_dots_global<A>(tp, dp, xc, hc + a.H, n - T, T, lo, up);
             A::store(yc, k, A::arb_combine(lo, up, alpha));
         }
+    }
+    dev::shiftin_by_last_workgroup<typename A::Tx, A::NC>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+}
+
+// FIRFarrow, per-channel taps, one thread per output, any (T, polyorder, rate): farrow_kernel with bank ch of a.pnfb,
+// [nch][T][polyorder+1] coefficients of A::kCoefScalars Float64 each.  A tap belongs to one (channel, output) and feeds exactly one
+// product: it is evaluated in the inner loop (A::farrow_tap), used and dropped.  The coefficient address is the same for every lane of a
+// wave (the channel is uniform per block, i and j are loop counters): scalar loads, the coefficients reach the Float64 adds as scalar
+// operands.  blockIdx.y strides the channels.  Serves every path: device-planned calls (a.dyn), host-scheduled calls, the pieces of a
+// split call (seam_below == 0 on continuation pieces) and captured calls.  No dynamic LDS; ends with the ShiftFold epilogue.
+// farrow_bank_ctaps_generic_kernel (complex taps) is a wrapper of it; farrow_bank_generic_kernel (real taps) keeps its own copy in
+// kernels_bank_farrow.hip, with farrow_coef_t and kFarrowBankUnrolledP restated in its anonymous namespace: as a wrapper of this body its
+// twelve code objects did not keep their instructions, which (or a timing run that was not made) was the condition for merging them
+// (DESIGN.md 5.16).  k: the lane's output, computed in the kernel (there blockDim.x is one scalar load).
+template <typename A>
+__device__ __forceinline__ void farrow_variant_bank_generic_body(FarrowArgs a, const long long k)
+{
+    using Sample = typename A::Sample;
+    if (a.dyn) a.n_out = a.dyn->n_out;              // a device-planned call: the count the schedule's FINISH kernel left
+    if (k < a.n_out) {                               // (no early return: every thread takes part in the history epilogue below)
+        const long long n = a.n_idx[k];
+        const double phase = a.acc[k];
+        const int P = a.polyorder, T = a.T;
+        const bool tap_f32 = a.tap_f32 != 0;
+        const long long base = n - T;               // 0-based index of the oldest sample (>= -H: n >= 1)
+        const bool seam = n < a.seam_below;         // kernel.xIdx < kernel.tapsPer𝜙, Filters.jl:818 (never in a piece that continues a call)
+        const int poly = (P + 1) * A::kCoefScalars;  // Float64 scalars of one tap's polynomial
+        auto channels = [&]<int PP>() {
+            for (int ch = blockIdx.y; ch < a.nch; ch += gridDim.y) {
+                farrow_coef_t pc = reinterpret_cast<farrow_coef_t>(reinterpret_cast<uintptr_t>(a.pnfb)) + static_cast<long long>(ch) * T * poly;
+                const Sample *__restrict__ xc = static_cast<const Sample *>(a.x) + static_cast<long long>(ch) * a.x_stride;
+                const Sample *__restrict__ hc = static_cast<const Sample *>(a.hist) + static_cast<long long>(ch) * a.H;
+                typename A::Out *__restrict__ yc = A::channel_out(a.y, ch, a.y_stride);
+                auto sample = [&](long long xi) -> Sample { return xi >= 0 ? xc[xi] : hc[static_cast<long long>(a.H) + xi]; };
+                const Sample v0 = sample(base);
+                typename A::Sum acc = A::first(A::template farrow_tap<PP>(pc, P, phase, tap_f32), v0);
+                if (seam) acc = A::zero_start(acc);
+                for (int i = 1; i < T; ++i) {
+                    const Sample v = sample(base + i);
+                    acc = A::step(acc, A::template farrow_tap<PP>(pc + i * poly, P, phase, tap_f32), v);
+                }
+                A::store(yc, k, acc);
+            }
+        };
+        if (P == kFarrowBankUnrolledP) channels.template operator()<kFarrowBankUnrolledP>();
+        else channels.template operator()<-1>();
     }
     dev::shiftin_by_last_workgroup<typename A::Tx, A::NC>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }

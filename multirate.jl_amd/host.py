@@ -84,6 +84,7 @@ ABI = [
     ("mrhip_create_arbitrary_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_bank", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_farrow_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_pnfb_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -265,7 +266,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
-        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow): the (nchannels, hLen) matrix; self.h is its row 0
+        self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow, .per_channel_complex_taps_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
                 raise MultirateHIPError(1, "rate must be greater than 0")  # Filters.jl:184
@@ -379,7 +380,7 @@ class FIRFilter:
         either side is 64-bit); STRICT numerics only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape
         (nchannels, tapsPer𝜙, N𝜙), complex.  The device object is created by ``mrhip_create_rational_bank_ctaps``."""
         if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "per_channel_complex_taps builds the rational family only (a float rate: FIRFilter.per_channel_complex_taps_arbitrary; FIRFarrow has no per-channel complex taps)")
+            raise MultirateHIPError(5, "per_channel_complex_taps builds the rational family only (a float rate: FIRFilter.per_channel_complex_taps_arbitrary, FIRFilter.per_channel_complex_taps_farrow)")
         H = np.asarray(H)
         if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
             raise MultirateHIPError(1, f"per_channel_complex_taps takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
@@ -451,11 +452,37 @@ class FIRFilter:
             raise MultirateHIPError(1, "per_channel_farrow takes a polyorder (without one: FIRFilter.per_channel_arbitrary)")
         H = np.asarray(H)
         if H.dtype.kind == "c":
-            raise MultirateHIPError(5, "per_channel_farrow takes Float32/Float64 taps (complex taps in a FIRFarrow bank are not supported)")
+            raise MultirateHIPError(5, "per_channel_farrow takes Float32/Float64 taps (complex taps: FIRFilter.per_channel_complex_taps_farrow)")
         if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
             raise MultirateHIPError(1, f"per_channel_farrow takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
         H = np.ascontiguousarray(_as_taps(H))
         f = cls(H[0], float(rate), int(Nphi), int(polyorder), device=device, numerics=numerics)
+        f._bank = H.copy()
+        return f
+
+    @classmethod
+    def per_channel_complex_taps_farrow(cls, H, rate, Nphi: int = 32, polyorder=4, *, device: int = 0):
+        """One FIRFilter(H[c]::Vector{Complex64 / Complex128}, rate::Float, N𝜙, polyorder) per channel behind one filter object:
+        FIRFarrow with per-channel complex taps (a prototype rotated to every channel's own centre frequency, or a per-antenna complex
+        equaliser, in front of a common, continuously variable rate change).  ``H``: shape (nchannels, hLen), Complex64 or
+        Complex128; real taps belong to ``per_channel_farrow``.  Rate, N𝜙, polyorder, state and call length are shared, only the
+        polynomial banks differ (every row is fitted on its own, per component); channel c is bit for bit
+        ``FIRFilter.complex_taps_farrow(H[c], rate, Nphi, polyorder)`` fed ``x[c]`` (include/multirate_hip.h: per-channel complex taps
+        for FIRFarrow).  The output is always complex (Complex128 if either side is 64-bit); STRICT numerics only.  The filter binds
+        to exactly ``H.shape[0]`` channels; ``pnfb()`` has shape (nchannels, tapsPer𝜙, polyorder+1) and ``tapsforphase``
+        (nchannels, tapsPer𝜙), both complex.  A caller-fitted ``pnfb`` is not accepted here.  The device object is created by
+        ``mrhip_create_farrow_bank_ctaps``."""
+        if not isinstance(rate, (float, np.floating)):
+            raise MultirateHIPError(1, "per_channel_complex_taps_farrow takes a floating-point rate (a Rational ratio: FIRFilter.per_channel_complex_taps)")
+        if polyorder is None:
+            raise MultirateHIPError(1, "per_channel_complex_taps_farrow takes a polyorder (without one: FIRFilter.per_channel_complex_taps_arbitrary)")
+        H = np.asarray(H)
+        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+            raise MultirateHIPError(1, f"per_channel_complex_taps_farrow takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
+        if H.dtype != np.complex64 and H.dtype != np.complex128:
+            raise MultirateHIPError(1, f"per_channel_complex_taps_farrow takes Complex64/Complex128 taps, got {H.dtype} (real taps: FIRFilter.per_channel_farrow)")
+        H = np.ascontiguousarray(H)
+        f = cls(H[0], float(rate), int(Nphi), int(polyorder), device=device, _complex_taps=True)
         f._bank = H.copy()
         return f
 
@@ -478,6 +505,9 @@ class FIRFilter:
         elif self._bank is not None and self.kind == ARBITRARY:
             rc = self._lib.mrhip_create_arbitrary_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
                                                        self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self._bank is not None and self.kind == FARROW and self._bank.dtype.kind == "c":
+            rc = self._lib.mrhip_create_farrow_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
+                                                          self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
         elif self._bank is not None and self.kind == FARROW:
             rc = self._lib.mrhip_create_farrow_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
                                                     self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
@@ -592,7 +622,7 @@ class FIRFilter:
 
     def pnfb(self) -> np.ndarray:
         """FIRFarrow.pnfb (src/Filters.jl:126): tapsPer𝜙 polynomials, ascending powers, shape (tapsPer𝜙, polyorder+1); a per-channel
-        filter (FIRFilter.per_channel_farrow): (nchannels, tapsPer𝜙, polyorder+1)."""
+        filter (FIRFilter.per_channel_farrow; complex: FIRFilter.per_channel_complex_taps_farrow): (nchannels, tapsPer𝜙, polyorder+1)."""
         if self._handle is None or self.kind != FARROW:
             raise MultirateHIPError(1, "pnfb() needs a bound FIRFarrow filter")
         shape = (self.tapsPerPhi, self.polyorder + 1)

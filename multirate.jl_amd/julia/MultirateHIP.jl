@@ -151,6 +151,15 @@ function FIRFilter(H::Matrix{Th}, rate::AbstractFloat, Nphi::Integer, polyorder:
     f = FIRFilter{FIRFarrow{Th}}(vec(copy(H)), nothing, Float64(rate), Nphi, polyorder, device, C_NULL, nothing, 0, size(H, 2))
     finalizer(destroy!, f)
 end
+# The same with COMPLEX taps (include/multirate_hip.h: per-channel complex taps for FIRFarrow): one
+# FIRFilter(H[:, c]::Vector{Complex}, rate, Nphi, polyorder) per channel -- a prototype rotated to every channel's own centre frequency,
+# or a per-antenna complex equaliser, in front of a common, continuously variable rate change.  The same transposition: one column per
+# channel; bind! creates the device object through mrhip_create_farrow_bank_ctaps; the output is complex for every sample type.
+function FIRFilter(H::Matrix{Th}, rate::AbstractFloat, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{ComplexF32,ComplexF64}}
+    rate > 0.0 || error("rate must be greater than 0")
+    f = FIRFilter{FIRFarrow{Th}}(vec(copy(H)), nothing, Float64(rate), Nphi, polyorder, device, C_NULL, nothing, 0, size(H, 2))
+    finalizer(destroy!, f)
+end
 
 function destroy!(f::FIRFilter)
     f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle)
@@ -165,7 +174,12 @@ function bind!(f::FIRFilter, ::Type{Tx}, nch::Integer) where {Tx}
     end
     out = Ref{Ptr{Cvoid}}(C_NULL)
     Th = eltype(f.h)
-    if f.nbank > 0 && f.ratio === nothing && f.polyorder >= 0
+    if f.nbank > 0 && f.ratio === nothing && f.polyorder >= 0 && Th <: Complex
+        nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
+        check(ccall((:mrhip_create_farrow_bank_ctaps, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, div(length(f.h), f.nbank), dtypecode(Th), f.rate, f.Nphi, f.polyorder, dtypecode(Tx), nch, f.device, out))
+    elseif f.nbank > 0 && f.ratio === nothing && f.polyorder >= 0
         nch == f.nbank || error("a per-channel filter of $(f.nbank) tap vectors binds to exactly that many channels")
         check(ccall((:mrhip_create_farrow_bank, libmr), Cint,
                     (Ptr{Cvoid}, Int64, Cint, Cdouble, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
