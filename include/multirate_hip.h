@@ -484,6 +484,12 @@ int mrhip_get_taps(mrhip_filter *f, int which, void *host_out);
  * enqueued: the call is asynchronous on `stream` (a hipStream_t, NULL = default stream).
  * A short input (x_len < inputDeficit) is not an error: history is shifted, inputDeficit
  * reduced, *n_written = 0 (:543-547, :638-643, :705-709).
+ * Only the outputs are written: like the reference's filt!, which writes buffer[1:n] and nothing else, every entry point
+ * (mrhip_filt_device, _async, _chained, _chunked, _multi, mrhip_ring_push*, mrhip_cascade_filt_device*) leaves the elements of y
+ * outside [0, count) of each channel row untouched -- whatever the alignment of y, whatever y_stride >= the required minimum
+ * (count; mrhip_outputlength_bound(x_len) for a device-planned call), also between count and y_capacity, also where the launch is
+ * sized for an estimate or a bound of the count, and also when the call fails with MRHIP_ERR_BUFFER_TOO_SMALL.  A caller may
+ * filter into a slice of a larger buffer and lay the outputs of consecutive calls end to end (tests/test_gpu_output_bounds.py).
  * On a stream that is being captured into a HIP graph the call takes the device-planned path of mrhip_filt_device_async
  * (same buffer rule); *n_written then is the count of the FIRST replay (rational family) or -1 (FIRArbitrary / FIRFarrow:
  * read it with mrhip_sync_state after a replay). */
