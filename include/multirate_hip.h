@@ -262,6 +262,37 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - such a filter runs on ONE kernel (farrow_bank_ctaps_generic_kernel); MRHIP_FORCE_GENERIC has no effect on it;
  *   - left out on purpose: a caller-fitted pnfb for banks, a FUSED form, sharded banks, a resident ring for banks. */
 
+/* Per-channel rates for FIRArbitrary (mrhip_create_arbitrary_rates; Th in {F32,F64}): one FIRFilter(h, rates[c], Nphi) per channel
+ * behind one handle -- receivers or ADCs each off its own clock trimmed to a common rate, per-satellite or per-emitter Doppler
+ * time-scale correction, and (with a per-channel start phase, mrhip_set_channel_states) per-channel fractional delay.  The channels
+ * share h (so pfb and dpfb), Nphi, the call length and the history length; each channel has its own rate, delta, phiAccumulator,
+ * phiIdx, alpha, xIdx, inputDeficit and per-call output count (mrhip_channel_state).
+ *   - parity: for every channel c the outputs, the count of every call, the end state (inputDeficit, phiAccumulator, phiIdx, alpha,
+ *     xIdx) and the history are bit for bit those of mrhip_create_arbitrary(h, rates[c], Nphi, nchannels = 1) fed x_c, under STRICT
+ *     and under FUSED.  That includes the short-input path of filt! (src/Filters.jl:705-709): a channel whose inputDeficit exceeds
+ *     x_len writes nothing and only has its deficit reduced, while its neighbours produce outputs in the same call;
+ *   - arithmetic: that of "Per-channel taps for FIRArbitrary" -- two dot products over ONE window, oldest sample first, the first
+ *     product initialises the accumulator, no start-from-zero seam, y = R(double(lo) + double(up) * alpha);
+ *   - tap types F32 and F64 (complex taps: MRHIP_ERR_UNSUPPORTED, left out); all four sample types;
+ *   - any rate <= 0 (or not finite) is MRHIP_ERR_INVALID_ARG; a rate below 2^-30 is MRHIP_ERR_UNSUPPORTED;
+ *   - mrhip_set_mod_form(f, 1) is accepted when Nphi is a power of two, where the two forms agree in every bit; otherwise it
+ *     returns MRHIP_ERR_UNSUPPORTED;
+ *   - device-planned calls only: the host never learns a count before the kernels have run.  mrhip_filt_device_rates enqueues a
+ *     schedule kernel (one lane per channel walks update() serially) and one filter kernel on the caller's stream and nothing else;
+ *     the filter has no schedule stream and uses no stream of its own in a call;
+ *   - these work on such a filter: mrhip_destroy, mrhip_reset, mrhip_set_numerics, mrhip_get_history, mrhip_set_history,
+ *     mrhip_set_history_device, mrhip_get_taps, mrhip_arbitrary_tapsforphase, mrhip_outputlength_bound (the largest of the channels'
+ *     bounds), mrhip_synchronize, mrhip_set_timing, mrhip_timing_read, mrhip_last_kernel_name;
+ *   - every entry point that carries ONE state or ONE count returns MRHIP_ERR_UNSUPPORTED (-1 from the counting functions) with a
+ *     message that names the calls below: mrhip_filt_device, _async, _chained, _chunked, mrhip_filt_host, mrhip_filt_device_multi,
+ *     mrhip_ring_open, mrhip_cascade_create, mrhip_get_state, mrhip_set_state, mrhip_sync_state, mrhip_outputlength,
+ *     mrhip_inputlength, mrhip_next_output_count, mrhip_advance_state; mrhip_sharded_create has no such constructor;
+ *   - every other constructor and filter answers exactly as before;
+ *   - left out on purpose: FIRFarrow with per-channel rates; complex or per-channel taps combined with per-channel rates; evaluating
+ *     a long channel's schedule with the parallel tables / chain / emit machinery instead of the serial walk (the next speed step
+ *     for few long channels); graph capture, rings, cascades and sharding of such a filter; a mrhip_filt_device_multi that serves
+ *     FIRArbitrary streams in one launch. */
+
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
 /* Snapshot of the kernel fields of the reference structs (src/Filters.jl:15-117,151-155).
@@ -286,6 +317,11 @@ typedef struct {
     double alpha;            /* α :99 */
     double delta;            /* Δ :100 */
 } mrhip_state;
+
+/* One channel of a filter with per-channel rates (mrhip_create_arbitrary_rates): the FIRArbitrary fields that differ from channel to
+ * channel (src/Filters.jl:91-117), and the output count of the channel's latest call. */
+typedef struct { double rate, delta, phiAccumulator, alpha;
+                 int64_t phiIdx, inputDeficit, xIdx, last_count; } mrhip_channel_state;
 
 /* ---- library ------------------------------------------------------------------------- */
 int mrhip_abi_version(void);
@@ -376,6 +412,12 @@ int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int tap_dtype, doub
  * mrhip_create_arbitrary; the filter's kind is MRHIP_FIR_ARBITRARY and its output is complex for every sample type. */
 int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int tap_dtype, double rate, int64_t Nphi,
                                       int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* one FIRFilter(h, rates[c], Nphi) per channel behind one handle (see "Per-channel rates for FIRArbitrary" above): `h` is ONE tap
+ * vector of hLen taps, `rates` holds nchannels rates.  tap_dtype F32 | F64 (complex: MRHIP_ERR_UNSUPPORTED, left out).  Every rate
+ * must be greater than 0 (MRHIP_ERR_INVALID_ARG); Nphi and every other argument check are those of mrhip_create_arbitrary; the
+ * filter's kind is MRHIP_FIR_ARBITRARY. */
+int mrhip_create_arbitrary_rates(const void *h, int64_t hLen, int tap_dtype, const double *rates,
+                                 int64_t Nphi, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer, polyorder::Integer),
  * src/Filters.jl:192-198 (+ FIRFarrow(h, rate, Nphi, polyorder), :138-147, pfb2pnfb :311-321 and
  * polyfit, src/support.jl:85-88): every ROW of the tapsPerPhi x Nphi filter bank is replaced by its
@@ -536,6 +578,28 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
  * (src/Filters.jl:352-385) evaluated for 𝜙Idx = inputDeficit = 1 (+ 2 for FIRArbitrary / FIRFarrow, whose outputlength is
  * an estimate, :375-381) */
 int64_t mrhip_outputlength_bound(const mrhip_filter *f, int64_t inputlength);
+/* filt! on every channel of a filter with per-channel rates (mrhip_create_arbitrary_rates), each channel from its own state, on
+ * device memory; enqueued on `stream`.  Nothing waits, with one exception: the filter keeps two schedule buffers on the device that
+ * hold nchannels slices of the call's bound -- 12 bytes per (channel, possible output), allocated a quarter larger than the largest call
+ * so far needs: about 1.4 GB for 4096 channels x 1e4 samples at rates up to 2.25, about 2.2 GB for 64 x 1e6 -- and a call that needs
+ * larger ones than the filter has waits on the host for the filter's stream, frees them and allocates anew.  Calls of one size pay
+ * that once.
+ *   - counts_out: NULL, or device-accessible memory for nchannels counts, stored in stream order;
+ *   - y_capacity (and y_stride for nchannels > 1) must be at least mrhip_outputlength_bound(f, x_len) -- on this filter the largest of
+ *     the channels' bounds -- else MRHIP_ERR_BUFFER_TOO_SMALL: nothing is enqueued and the state is unchanged;
+ *   - row c of y receives elements [0, count_c) and nothing else;
+ *   - with mrhip_set_timing, ONE bracket holds both launches of a call, the schedule kernel's walk and the filter kernel:
+ *     mrhip_timing_read counts a call as one launch and its duration includes the walk;
+ *   - a call whose bound exceeds 2^24 outputs per channel (the schedule-entry limit of a launch) returns MRHIP_ERR_UNSUPPORTED, and so
+ *     does a call on a capturing stream. */
+int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64_t x_stride,
+                            void *y, int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream);
+/* the nchannels states of such a filter, after waiting for the filter's stream; MRHIP_ERR_BUFFER_TOO_SMALL if a channel's walk ever
+ * overran the bound of its call (its outputs were clipped at the bound) */
+int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out /* [nchannels] */);
+/* per-channel inputDeficit (>= 1) and phiAccumulator (in [1, Nphi+1)), behind the calls already enqueued; phiIdx and alpha are
+ * re-derived as update() does (src/Filters.jl:671-672): floor(phiAccumulator) and the remainder */
+int mrhip_set_channel_states(mrhip_filter *f, const int64_t *inputDeficit, const double *phiAccumulator);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call
@@ -697,7 +761,10 @@ int mrhip_filt_once(const void *h, int64_t hLen, int tap_dtype, int64_t num, int
  * launches covered by complete groups and the groups' total duration, gaps between the launches included. */
 int mrhip_set_timing(mrhip_filter *f, int enabled);
 int mrhip_timing_read(mrhip_filter *f, int64_t *n_launches, double *total_ms);
-/* name of the device kernel the last filt call dispatched (for profiles / logs) */
+/* name of the device kernel the last filt call dispatched (for profiles / logs).  The two filter kernels of a filter with
+ * per-channel rates are reported as arb_rates_generic and arb_rates_tiled, without the suffix the other names carry: the table of
+ * write-only-own-outputs cases (tests/output_bounds_cases.py) is keyed by the suffixed names in the sources, and these two kernels'
+ * cases live in tests/test_gpu_rates_arb.py until they move into that table. */
 const char *mrhip_last_kernel_name(const mrhip_filter *f);
 /* How the phase schedule of a FIRArbitrary / FIRFarrow filter -- update(), src/Filters.jl:663-673 and :780-792 -- has
  * been evaluated so far.  info[0..n) receives, as far as n reaches:

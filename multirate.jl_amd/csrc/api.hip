@@ -12,6 +12,7 @@
 #include <unordered_map>
 
 #include "mrhip_filter.h"
+#include "rates_arb.h"
 
 namespace mrhip {
 
@@ -486,8 +487,10 @@ int mrhip_create_rational_bank_ctaps(const void *h, int64_t hLen, int th, int64_
 // nch rows; every row gets its own dh and both its taps2pfb calls, and the banks sit one after the other, [nch][Nphi][T]
 // (mrhip_create_arbitrary_bank; kernels_bank_arb.hip -- with complex taps mrhip_create_arbitrary_bank_ctaps: [nch][Nphi][T] pairs,
 // kernels_bank_arb_ctaps.hip).
+static int rates_alloc(mrhip_filter *f);
+// rates != NULL (mrhip_create_arbitrary_rates): nch rates behind the one bank; `rate` is the largest of them.
 static int create_arbitrary_common(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                                   int device, bool bank, mrhip_filter **out)
+                                   int device, bool bank, mrhip_filter **out, const double *rates = nullptr)
 {
     if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
     if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
@@ -503,6 +506,7 @@ static int create_arbitrary_common(const void *h, int64_t hLen, int th, double r
     f->rate = rate;
     f->delta = static_cast<double>(Nphi) / rate;   // Δ = N𝜙/rate, Filters.jl:113
     f->bank = bank;
+    if (rates) { f->rates = true; f->h_rates.assign(rates, rates + nch); }
     const size_t es = dtype_size(th);
     const size_t rows = bank ? static_cast<size_t>(nch) : 1;      // tap vectors in `h`, each hLen long
 
@@ -524,8 +528,9 @@ static int create_arbitrary_common(const void *h, int64_t hLen, int th, double r
     int rc = upload_taps(f, f->h_taps, &f->d_taps, &f->d_taps_alloc);
     if (!rc) rc = upload_taps(f, f->h_dtaps, &f->d_dtaps, &f->d_dtaps_alloc);
     if (!rc) rc = alloc_common(f);
+    if (!rc && f->rates) rc = rates_alloc(f);
     if (rc) { mrhip_destroy(f); return rc; }
-    sched_configure(f);
+    if (!f->rates) sched_configure(f);        // (per-channel rates: the serial walk of kernels_rates_arb.hip, none of the schedule machinery)
     *out = f;
     return MRHIP_OK;
 }
@@ -570,6 +575,41 @@ int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int th, doubl
         return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_arbitrary_bank_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_arbitrary_bank");
     if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
     return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, true, out);
+}
+
+// One FIRFilter(h, rates[c], N𝜙) per channel behind one handle (include/multirate_hip.h, "Per-channel rates for FIRArbitrary"): the
+// channels share pfb and dpfb; each has a record on the device (RateChannel, rates_arb.h) in its constructor state (Filters.jl:110-115).
+static int rates_alloc(mrhip_filter *f)
+{
+    std::vector<RateChannel> v(static_cast<size_t>(f->nch));
+    for (int64_t c = 0; c < f->nch; ++c) {
+        RateChannel &r = v[static_cast<size_t>(c)];
+        r = RateChannel{};
+        r.rate = f->h_rates[static_cast<size_t>(c)];
+        r.delta = static_cast<double>(f->Nphi) / r.rate;           // Δ = N𝜙/rate, Filters.jl:113
+        r.acc = 1.0; r.inputDeficit = 1; r.xIdx = 1;
+    }
+    MRHIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&f->d_rrec), v.size() * sizeof(RateChannel)));
+    MRHIP_CHECK_HIP(hipMemcpy(f->d_rrec, v.data(), v.size() * sizeof(RateChannel), hipMemcpyHostToDevice));
+    return MRHIP_OK;
+}
+
+int mrhip_create_arbitrary_rates(const void *h, int64_t hLen, int th, const double *rates, int64_t Nphi, int tx, int64_t nch,
+                                 int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_C64 || th == MRHIP_C128)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_arbitrary_rates takes Float32 / Float64 taps (complex taps with per-channel rates are left out)");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    if (!rates) return fail(MRHIP_ERR_INVALID_ARG, "rates is NULL");
+    double rate_max = 0.0;
+    for (int64_t c = 0; c < nch; ++c) {
+        if (!(rates[c] > 0.0) || !std::isfinite(rates[c])) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0 (every channel's, and finite)");
+        // (update() advances xIdx by about 1/rate a step; the walk carries that advance in 32 bits: sched_step.h)
+        if (rates[c] < 1.0 / static_cast<double>(1LL << 30)) return fail(MRHIP_ERR_UNSUPPORTED, "a per-channel rate below 2^-30");
+        rate_max = std::max(rate_max, rates[c]);
+    }
+    return create_arbitrary_common(h, hLen, th, rate_max, Nphi, tx, nch, device, false, out, rates);
 }
 
 // FIRFarrow(h, rate, N𝜙, polyorder), src/Filters.jl:138-147, behind all four constructors.  pnfb_in: [T][polyorder+1] coefficients,
@@ -813,6 +853,8 @@ void mrhip_destroy(mrhip_filter *f)
     for (void *p : {f->d_taps_alloc, f->d_dtaps_alloc, static_cast<void *>(f->d_pnfb), static_cast<void *>(f->d_pnfb_t), f->d_hist[0], f->d_hist[1], f->d_hist[2], static_cast<void *>(f->d_counters), f->d_sched_n, f->d_sched_acc,
                     f->d_xbuf[0], f->d_xbuf[1], f->d_ybuf[0], f->d_ybuf[1]})
         if (p) (void)hipFree(p);
+    for (void *p : {static_cast<void *>(f->d_rrec), f->d_rs_n, f->d_rs_acc})
+        if (p) (void)hipFree(p);
     if (f->pin_n) (void)hipHostFree(f->pin_n);
     if (f->pin_acc) (void)hipHostFree(f->pin_acc);
     if (f->multi_pin) (void)hipHostFree(f->multi_pin);
@@ -885,9 +927,19 @@ static int fresh(const mrhip_filter *f)
     return rec_pull(const_cast<mrhip_filter *>(f));
 }
 
+// A filter with per-channel rates (mrhip_create_arbitrary_rates) has one state and one count PER CHANNEL: every entry point that carries
+// ONE state or ONE count refuses it and names the calls that serve it.
+static int rates_refused(const mrhip_filter *f, const char *what)
+{
+    if (!f || !f->rates) return MRHIP_OK;
+    return fail(MRHIP_ERR_UNSUPPORTED, std::string(what) + ": the filter has per-channel rates (mrhip_create_arbitrary_rates), so a state and a count per "
+                                       "channel -- use mrhip_filt_device_rates, mrhip_get_channel_states and mrhip_set_channel_states");
+}
+
 int64_t mrhip_outputlength(const mrhip_filter *f, int64_t n)
 {
     if (!f) return -1;
+    if (rates_refused(f, "mrhip_outputlength")) return -1;
     if (f->kind != MRHIP_FIR_STANDARD && f->kind != MRHIP_FIR_INTERPOLATOR && fresh(f)) return -1;
     switch (f->kind) {
     case MRHIP_FIR_STANDARD: return n;                                                   // Filters.jl:359
@@ -939,6 +991,7 @@ static int64_t arb_schedule(mrhip_filter *f, int64_t x_len, ArbState *end_state)
 int64_t mrhip_next_output_count(const mrhip_filter *f, int64_t n)
 {
     if (!f || n < 0) return -1;
+    if (rates_refused(f, "mrhip_next_output_count")) return -1;
     if (fresh(f)) return -1;
     if (f->kind == MRHIP_FIR_ARBITRARY || f->kind == MRHIP_FIR_FARROW)   // the schedule is cached for the filt call that normally follows
         return arb_schedule(const_cast<mrhip_filter *>(f), n, nullptr);
@@ -948,6 +1001,7 @@ int64_t mrhip_next_output_count(const mrhip_filter *f, int64_t n)
 int64_t mrhip_advance_state(mrhip_filter *f, int64_t n)
 {
     if (!f || n < 0) { (void)fail(MRHIP_ERR_INVALID_ARG, "advance_state: NULL filter or negative length"); return -1; }
+    if (rates_refused(f, "mrhip_advance_state")) return -1;
     if (fresh(f)) return -1;
     DeviceGuard guard(f->device);
     hipStream_t s = f->last_stream_valid ? f->last_stream : f->own_stream;
@@ -1002,6 +1056,7 @@ int64_t mrhip_advance_state(mrhip_filter *f, int64_t n)
 int64_t mrhip_inputlength(const mrhip_filter *f, int64_t n)
 {
     if (!f) return -1;
+    if (rates_refused(f, "mrhip_inputlength")) return -1;
     if (fresh(f)) return -1;
     switch (f->kind) {
     case MRHIP_FIR_STANDARD: return n;                                                    // Filters.jl:403
@@ -1016,6 +1071,7 @@ int64_t mrhip_inputlength(const mrhip_filter *f, int64_t n)
 int mrhip_get_state(const mrhip_filter *f, mrhip_state *st)
 {
     if (!f || !st) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = rates_refused(f, "mrhip_get_state")) return rc;
     if (int rc = fresh(f)) return rc;
     st->kind = f->kind; st->tap_dtype = f->th; st->sample_dtype = f->tx; st->output_dtype = f->ty;
     st->nchannels = f->nch; st->hLen = f->hLen; st->interpolation = f->L; st->decimation = f->M;
@@ -1028,6 +1084,7 @@ int mrhip_get_state(const mrhip_filter *f, mrhip_state *st)
 int mrhip_set_state(mrhip_filter *f, int64_t phiIdx, int64_t inputDeficit, double phiAccumulator)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
+    if (int rc = rates_refused(f, "mrhip_set_state")) return rc;
     if (f->ring_open) return fail(MRHIP_ERR_INVALID_ARG, "the filter feeds a ring (mrhip_ring_open): close it first");
     if (inputDeficit < 1) return fail(MRHIP_ERR_INVALID_ARG, "inputDeficit must be >= 1");
     DeviceGuard guard(f->device);
@@ -1148,6 +1205,12 @@ int mrhip_reset(mrhip_filter *f)
     }
     if (f->s_sched) f->sched_dirty = true;
     if (f->s_sched) return rec_push(f, f->s_sched);                   // the device record: constructor state, in stream order
+    // (per-channel rates: the channels' records follow the filter's one, on the same stream)
+    auto rates_too = [&](int rc) -> int {
+        if (rc != MRHIP_OK || !f->rates) return rc;
+        MRHIP_CHECK_HIP(launch_rates_reset(f->d_rrec, static_cast<int>(f->nch), f->last_stream));
+        return MRHIP_OK;
+    };
     if (fast) {
         // the record's kernel zeroes the counters too; a stream that no longer exists (torch side streams come and go): behind the
         // whole device once, on the filter's own stream
@@ -1155,11 +1218,11 @@ int mrhip_reset(mrhip_filter *f)
             (void)hipGetLastError();
             MRHIP_CHECK_HIP(device_sync_relaxed());
             f->last_stream = f->own_stream;
-            return rec_push(f, f->own_stream, -1, -1, f->d_counters);
+            return rates_too(rec_push(f, f->own_stream, -1, -1, f->d_counters));
         }
-        return MRHIP_OK;
+        return rates_too(MRHIP_OK);
     }
-    return rec_push(f, s);
+    return rates_too(rec_push(f, s));
 }
 
 int mrhip_set_numerics(mrhip_filter *f, int numerics)
@@ -1178,6 +1241,12 @@ int mrhip_set_mod_form(mrhip_filter *f, int form)
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
     if (form != 0 && form != 1) return fail(MRHIP_ERR_INVALID_ARG, "mod form must be 0 (exact remainder) or 1 (rem(y + rem(x, y), y))");
     if (f->kind != MRHIP_FIR_ARBITRARY && f->kind != MRHIP_FIR_FARROW) return fail(MRHIP_ERR_INVALID_ARG, "not a FIRArbitrary / FIRFarrow filter");
+    if (f->rates) {   // the walk on the device computes the exact remainder: the older form is that, in every bit, for a power of two only
+        if (form != 0 && (f->Nphi & (f->Nphi - 1)) != 0)
+            return fail(MRHIP_ERR_UNSUPPORTED, "mod form 1 (Julia Base before 0.4) on a filter with per-channel rates needs an N𝜙 that is a power of two");
+        f->mod_form = form;
+        return MRHIP_OK;
+    }
     if (f->mod_form != form) {
         f->mod_form = form;
         f->sched_cached = false;
@@ -1955,6 +2024,7 @@ static int filt_device_any(mrhip_filter *f, const void *x, int64_t x_len, int64_
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
     if (n_written) *n_written = 0;
+    if (int rc = rates_refused(f, "mrhip_filt_device / _async / _chunked")) return rc;
     if (f->ring_open) return fail(MRHIP_ERR_INVALID_ARG, "the filter feeds a ring (mrhip_ring_open): push chunks into the ring, or close it first");
     const bool arb = f->kind == MRHIP_FIR_ARBITRARY || f->kind == MRHIP_FIR_FARROW;
     // samples per launch: inputs AND outputs stay below 2^31 (FIRInterpolator and FIRRational with L > M write more than
@@ -2013,6 +2083,7 @@ int mrhip_filt_device_chained(mrhip_filter *f, const mrhip_filter *prev, const v
                               int64_t y_capacity, int64_t y_stride, int64_t *count_out, void *stream)
 {
     if (!f || !prev) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
+    if (int rc = rates_refused(f->rates ? f : prev, "mrhip_filt_device_chained")) return rc;
     if (f->device != prev->device) return fail(MRHIP_ERR_INVALID_ARG, "the two filters live on different devices");
     if (!prev->last_call_dev_planned || !prev->last_call_rec)
         return fail(MRHIP_ERR_INVALID_ARG, "the previous filter's latest call was not planned on the device (mrhip_filt_device_async, or a call under capture): its count is not in its call record");
@@ -2038,6 +2109,8 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     mrhip_filter *f0 = filters[0];
     if (!f0) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
+    for (int i = 0; i < n; ++i)
+        if (int rc = rates_refused(filters[i], "mrhip_filt_device_multi")) return rc;
     auto single_calls = [&]() -> int {
         for (int i = 0; i < n; ++i) {
             int64_t got = 0;
@@ -2134,12 +2207,138 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
 int64_t mrhip_outputlength_bound(const mrhip_filter *f, int64_t inputlength)
 {
     if (!f || inputlength < 0) return -1;
-    return output_bound(f, inputlength);
+    return output_bound(f, inputlength);      // (per-channel rates: f->rate is the largest, whose bound is the largest)
+}
+
+// ---- FIRArbitrary with per-channel rates (include/multirate_hip.h, "Per-channel rates for FIRArbitrary") ---------------------------------
+// filt! on every channel, each from its own state: the schedule kernel and one filter kernel, both on the caller's stream; the host never
+// learns a count here.  Every refusal comes before anything is enqueued or changed.
+int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64_t x_stride, void *y, int64_t y_capacity, int64_t y_stride,
+                            int64_t *counts_out, void *stream_)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counts are written by the device as long long");
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
+    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates takes a filter of mrhip_create_arbitrary_rates");
+    if (x_len < 0 || y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "negative length");
+    if (x_len > 0 && !x) return fail(MRHIP_ERR_INVALID_ARG, "x is NULL");
+    if (x_len >= 0x7fffffffLL) return fail(MRHIP_ERR_UNSUPPORTED, "a call takes fewer than 2^31-1 samples per channel");
+    if (f->nch > 1 && x_stride < x_len) return fail(MRHIP_ERR_INVALID_ARG, "x_stride < x_len");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
+    if (stream_is_capturing(stream))
+        return fail(MRHIP_ERR_UNSUPPORTED, "a filter with per-channel rates is not captured into a HIP graph (its schedule buffers grow with the call)");
+    const int64_t bound = output_bound(f, x_len);
+    if (bound > (1LL << 24))
+        return fail(MRHIP_ERR_UNSUPPORTED, "a call of a filter with per-channel rates holds at most 2^24 schedule entries per channel: feed shorter pieces");
+    if (y_capacity < bound)
+        return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small: mrhip_filt_device_rates needs room for mrhip_outputlength_bound(x_len) outputs per channel");
+    if (f->nch > 1 && y_stride < bound)
+        return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small: y_stride < mrhip_outputlength_bound(x_len)");
+    if (bound > 0 && !y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
+
+    if (int rc = adopt_stream(f, stream)) return rc;
+    const size_t entries = static_cast<size_t>(f->nch) * static_cast<size_t>(bound);
+    if (entries > f->rs_cap) {
+        const size_t cap = std::max<size_t>(entries + entries / 4, 4096);
+        if (int rc = drain_filter(f)) return rc;      // only this filter's kernels read the slices
+        if (f->d_rs_n) (void)hipFree(f->d_rs_n);
+        if (f->d_rs_acc) (void)hipFree(f->d_rs_acc);
+        f->d_rs_n = f->d_rs_acc = nullptr; f->rs_cap = 0;
+        MRHIP_CHECK_HIP(hipMalloc(&f->d_rs_n, cap * sizeof(int32_t)));
+        MRHIP_CHECK_HIP(hipMalloc(&f->d_rs_acc, cap * sizeof(double)));
+        f->rs_cap = cap;
+    }
+
+    RatesSchedArgs sa{};
+    sa.rec = f->d_rrec; sa.n_idx = static_cast<int *>(f->d_rs_n); sa.acc = static_cast<double *>(f->d_rs_acc);
+    sa.counts_out = reinterpret_cast<long long *>(counts_out);
+    sa.slice = bound; sa.x_len = x_len;
+    sa.N = static_cast<double>(f->Nphi); sa.invN = 1.0 / static_cast<double>(f->Nphi);
+    sa.nch = static_cast<int>(f->nch);
+
+    ArbArgs a{};
+    a.x = x; a.y = y; a.hist = f->d_hist[f->hist_cur]; a.taps = f->d_taps; a.dtaps = f->d_dtaps;
+    a.n_idx = sa.n_idx; a.acc = sa.acc;
+    a.x_stride = x_stride; a.y_stride = y_stride; a.x_len = x_len; a.n_out = bound;
+    a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H); a.Nphi = static_cast<int>(f->Nphi);
+    a.nch = static_cast<int>(f->nch);
+    a.dyn = nullptr;
+    const int hist_next = hist_other(f);
+    if (f->H > 0) a.fold = ShiftFold{f->d_hist[hist_next], nullptr};      // shiftin! by the kernel's last workgroup, into the other slot
+    const RatesArgs ra{f->d_rrec, bound};
+    const TypeKey tk = type_key(f);
+    const bool fused = f->numerics == MRHIP_NUMERICS_FUSED;
+    // Everything on the host that can fail comes BEFORE the schedule kernel, which moves every channel's state: the tiled kernel's plan and
+    // its grid (an occupancy query, a function attribute) and the timing bracket's first event.  Behind it only the two launches
+    // themselves are left.
+    ArbTileArgs ta;
+    size_t lds = 0;
+    long long tiled_grid = 0;
+    bool tiled = false;
+    if (bound > 0 && !f->force_generic) {
+        const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
+        tiled = plan_arb_rates_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
+        if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
+    }
+    // (the timing bracket holds BOTH launches of the call: the walk is most of a long call)
+    if (int rc = timing_mark(f, stream)) return rc;
+    MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
+    if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
+        if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
+        else MRHIP_CHECK_HIP(launch_arb_rates_generic(tk, fused, a, ra, stream, &f->last_kernel));
+        if (f->H > 0) f->hist_cur = hist_next;
+    }
+    return timing_mark(f, stream);
+}
+
+int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
+{
+    if (!f || !out) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
+    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_get_channel_states takes a filter of mrhip_create_arbitrary_rates");
+    DeviceGuard guard(f->device);
+    if (int rc = drain_filter(f)) return rc;          // the records are written by the filter's own last call
+    std::vector<RateChannel> v(static_cast<size_t>(f->nch));
+    MRHIP_CHECK_HIP(hipMemcpy(v.data(), f->d_rrec, v.size() * sizeof(RateChannel), hipMemcpyDeviceToHost));
+    bool overrun = false;
+    for (size_t c = 0; c < v.size(); ++c) {
+        const RateChannel &r = v[c];
+        mrhip_channel_state &o = out[c];
+        o.rate = r.rate; o.delta = r.delta; o.phiAccumulator = r.acc;
+        o.phiIdx = static_cast<int64_t>(std::floor(r.acc));                  // Filters.jl:671-672
+        o.alpha = r.acc - static_cast<double>(o.phiIdx);
+        o.inputDeficit = r.inputDeficit; o.xIdx = r.xIdx; o.last_count = r.count;
+        overrun = overrun || r.error != 0;
+    }
+    if (overrun) return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "a channel's schedule overran the bound of its call (outputs were clipped): mrhip_reset the filter");
+    return MRHIP_OK;
+}
+
+int mrhip_set_channel_states(mrhip_filter *f, const int64_t *inputDeficit, const double *phiAccumulator)
+{
+    if (!f || !inputDeficit || !phiAccumulator) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
+    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_states takes a filter of mrhip_create_arbitrary_rates");
+    for (int64_t c = 0; c < f->nch; ++c) {
+        if (inputDeficit[c] < 1) return fail(MRHIP_ERR_INVALID_ARG, "inputDeficit must be >= 1");
+        if (!(phiAccumulator[c] >= 1.0) || !(phiAccumulator[c] < static_cast<double>(f->Nphi) + 1.0))
+            return fail(MRHIP_ERR_INVALID_ARG, "phiAccumulator must be in [1, Nphi+1)");
+    }
+    DeviceGuard guard(f->device);
+    // behind the calls already enqueued, like the reference's assignment behind the calls already made: wait for them, then write (the
+    // copies below are complete when they return, so every later call finds the new records); 𝜙Idx and α are derived from the
+    // accumulator wherever they are read, as update() derives them (Filters.jl:671-672)
+    if (int rc = drain_filter(f)) return rc;
+    std::vector<RateChannel> v(static_cast<size_t>(f->nch));
+    MRHIP_CHECK_HIP(hipMemcpy(v.data(), f->d_rrec, v.size() * sizeof(RateChannel), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < v.size(); ++c) { v[c].inputDeficit = inputDeficit[c]; v[c].acc = phiAccumulator[c]; v[c].error = 0; }
+    MRHIP_CHECK_HIP(hipMemcpy(f->d_rrec, v.data(), v.size() * sizeof(RateChannel), hipMemcpyHostToDevice));
+    return MRHIP_OK;
 }
 
 int mrhip_sync_state(mrhip_filter *f, int64_t *last_n_written)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
+    if (int rc = rates_refused(f, "mrhip_sync_state")) return rc;
     DeviceGuard guard(f->device);
     if (int rc = rec_pull(f)) return rc;
     const DevStream r = *f->h_rec;
@@ -2157,6 +2356,7 @@ int mrhip_filt_device_chunked(mrhip_filter *f, const void *x, int64_t x_len, int
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
     if (n_written) *n_written = 0;
+    if (int rc = rates_refused(f, "mrhip_filt_device_chunked")) return rc;
     if (chunk < 1) return fail(MRHIP_ERR_INVALID_ARG, "chunk must be >= 1");
     if (x_len < 0 || y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "negative length");
     const size_t xelt = dtype_scalar_size(f->tx) * static_cast<size_t>(f->nc);
@@ -2220,6 +2420,7 @@ int mrhip_filt_host(mrhip_filter *f, const void *x, int64_t x_len, int64_t x_str
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
     if (n_written) *n_written = 0;
+    if (int rc = rates_refused(f, "mrhip_filt_host")) return rc;
     if (x_len < 0 || y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "negative length");
     if (x_len == 0) return MRHIP_OK;
     if (!x) return fail(MRHIP_ERR_INVALID_ARG, "x is NULL");

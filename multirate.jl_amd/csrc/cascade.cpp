@@ -44,6 +44,9 @@ int mrhip_cascade_create(mrhip_filter *const *stages, int nstages, mrhip_cascade
     if (!stages || nstages < 1) return fail(MRHIP_ERR_INVALID_ARG, "a cascade takes one or more stages");
     for (int i = 0; i < nstages; ++i) {
         if (!stages[i]) return fail(MRHIP_ERR_INVALID_ARG, "NULL stage");
+        if (stages[i]->rates)
+            return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_cascade_create: a stage has per-channel rates (mrhip_create_arbitrary_rates), so a count per channel -- "
+                                               "such a filter runs alone, through mrhip_filt_device_rates");
         if (stages[i]->nch != stages[0]->nch || stages[i]->device != stages[0]->device)
             return fail(MRHIP_ERR_INVALID_ARG, "all stages of a cascade must have the same nchannels and device");
         if (i > 0 && stages[i]->tx != stages[i - 1]->ty)

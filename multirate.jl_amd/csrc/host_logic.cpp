@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "mrhip_internal.h"
+#include "rates_arb.h"
 
 namespace mrhip {
 
@@ -306,6 +307,38 @@ bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int n
     size_t bytes;
     if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate, mode == 1, &ta, &bytes)) return false;
     if (mode != 1 && ta.total_tiles < kArbBankTiledTilesPerCu * static_cast<long long>(num_cus)) return false;
+    *out = ta;
+    *lds = bytes;
+    return true;
+}
+
+// arb_rates_tiled_kernel (per-channel RATES, kernels_rates_arb.hip): the ONE shared pfb and dpfb (column pitch T + 1) plus the sample tile
+// fit LDS at two workgroups a CU (78 KiB a workgroup, as for plan_arb_bank_tiled); one channel a lane (cpl = 1).  n_out is the call's
+// bound (the counts are on the device): the tiling goes by it and the kernel skips the tiles behind a channel's count.  The span is
+// planned for the SLOWEST channel (rate_min: its tiles have the longest runs) and cut to the room only when the kernel is forced; in the
+// kernel every tile's run comes from its own channel's schedule, so a faster channel stages less and a tile longer than the planned span
+// reads global memory.  The default rule takes the calls the measured rows cover (profiles/r09/arb_rates.txt; the
+// figures of the run DESIGN.md quotes): the tiled kernel beat the universal one by far more than the spread of the repeats at 4096 ch x
+// 1e4 (360 448 tiles of 88 a channel: 3.125 against 3.449 ms, spreads 0.04 and 0.03) and at 256 ch x 1e5 (225 024 tiles of 879 a
+// channel: 21.45 against 26.44 ms, spreads 0.11 and 0.10), and did not at 64 ch x 1e6 (8790 tiles a channel: 536.8 against 548.3 ms
+// with spreads of 26 and 6 -- the serial walk is the call).  So: from kArbRatesTiledMinTiles tiles, up to kArbRatesTiledMaxPerChannel
+// tiles a channel, and never with a cut span; every other call stays on the universal kernel unless MRHIP_ARB_RATES_TILED=1 forces the
+// tiled one.  Both limits are GUARDS ON UNMEASURED GROUND, not causes: nothing about 880 tiles a channel makes the tiled kernel worse
+// (at 8790 it still read 1.02x, inside the spread, because the walk hides the filter kernel), and 256 ch x 1.001e5 falls back to the
+// universal kernel only because no row was measured beyond 879.  A measurement of the filter kernels alone at long channels (kernel
+// trace, the walk set aside) is what would let the cap go.
+constexpr long long kArbRatesTiledMinTiles = 225024, kArbRatesTiledMaxPerChannel = 879;
+bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int /*num_cus*/, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate_min > 0.0)) return false;
+    const int TP = a.T + 1;
+    const size_t bank_elems = static_cast<size_t>(a.Nphi) * TP;
+    const size_t banks_bytes = (2 * bank_elems * variant_tap_bytes(tk) + 15) / 16 * 16;
+    const ArbVariantShape v{banks_bytes, 78 * 1024, 78 * 1024, TP, static_cast<int>(bank_elems), 1, false};
+    ArbTileArgs ta;
+    size_t bytes;
+    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate_min, mode == 1, &ta, &bytes)) return false;
+    if (mode != 1 && (ta.total_tiles < kArbRatesTiledMinTiles || ta.tiles_per_channel > kArbRatesTiledMaxPerChannel)) return false;
     *out = ta;
     *lds = bytes;
     return true;

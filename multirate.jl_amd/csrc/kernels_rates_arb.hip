@@ -1,0 +1,248 @@
+// kernels_rates_arb.hip -- FIRArbitrary (src/Filters.jl:91-117, 663-742) with PER-CHANNEL RATES.
+//
+// In the reference N signals are N FIRFilter(h, rate_c, N𝜙) objects, and every rate_c may differ (receivers each off its own clock trimmed
+// to a common rate, per-emitter Doppler time-scale correction, per-channel fractional delay).  The phase schedule (update(), :663-673)
+// depends on the rate, so mrhip_create_arbitrary_rates builds ONE filter whose channels share h -- pfb and dpfb -- N𝜙, the call length
+// and the history length, and each have their own Δ, 𝜙Accumulator, xIdx, inputDeficit and per-call output count (RateChannel, rates_arb.h).
+// A call is two launches on the caller's stream and nothing else:
+//
+//   1. rates_schedule_kernel, one lane per channel: the short-input rule of filt! (:705-709), else the serial walk of update() from
+//      xIdx = inputDeficit while xIdx <= x_len (:715-732).  Entry k of channel c goes into the channel's slice of the schedule in the
+//      existing entry format (1-based input index, accumulator); the count and the end state go into the channel's record.  The step is
+//      sched_step_nb (sched_step.h): the text kernels_schedule.hip runs, and the one tests/rates_step_check.cpp checks on the CPU against
+//      the oracle.  The lanes of a wave store into slices a stride apart, an entry each per step.  Consecutive steps of a lane fill one
+//      cache line, so the L2 may gather them; nobody has measured the store path, nor the alternative of collecting 64 steps in LDS and
+//      storing whole lines.
+//   2. a filter kernel, a lane per (channel, output): n and acc from the channel's slice, the count from the channel's record; the
+//      universal kernel (arb_rates_generic_kernel) or the LDS-tiled one (arb_rates_tiled_kernel, behind plan_arb_rates_tiled).
+//
+// Arithmetic (include/multirate_hip.h, "Per-channel rates for FIRArbitrary"): that of arb_generic_kernel -- both dots over one window,
+// oldest sample first, the first product initialises the accumulator, no start-from-zero seam; STRICT: every multiply and add rounded
+// separately in R, FUSED: one fma per tap; the combine in Float64, then rounded to R (RealTaps, variant_device.h) -- so channel c is bit
+// for bit mrhip_create_arbitrary(h, rates[c], N𝜙, nch = 1) fed x_c.  This file is compiled with -ffp-contract=off.
+// Both filter kernels end with the ShiftFold epilogue (the history does not depend on the rate).  No workgroup waits for another.
+#include "rates_arb.h"
+#include "sched_step.h"
+#include "variant_device.h"
+
+#pragma clang fp contract(off)
+
+namespace mrhip {
+namespace {
+
+constexpr int kRatesSchedThreads = 64;     // one wave a workgroup: the walks of a wave's lanes run side by side, the waves spread over the CUs
+
+struct RateStep { double delta, N, invN; };
+
+template <bool POW2>
+__global__ __launch_bounds__(kRatesSchedThreads) void rates_schedule_kernel(RatesSchedArgs s)
+{
+    const int c = static_cast<int>(blockIdx.x) * kRatesSchedThreads + static_cast<int>(threadIdx.x);
+    if (c >= s.nch) return;
+    RateChannel *const rec = s.rec + c;
+    long long deficit = rec->inputDeficit;
+    long long count = 0;
+    if (s.x_len < deficit) {                                   // :705-709: nothing but the deficit moves
+        rec->inputDeficit = deficit - s.x_len;
+    } else {
+        const RateStep step{rec->delta, s.N, s.invN};
+        double acc = rec->acc;
+        long long x = deficit;                                 // :715
+        int *const n = s.n_idx + static_cast<long long>(c) * s.slice;
+        double *const pa = s.acc + static_cast<long long>(c) * s.slice;
+        while (x <= s.x_len && count < s.slice) {              // :717 (the slice holds the call's bound: the second test never ends a walk)
+            n[count] = static_cast<int>(x);
+            pa[count] = acc;
+            ++count;
+            sched_step_nb<POW2>(acc, x, step);                 // :731
+        }
+        if (x <= s.x_len) rec->error = MRHIP_ERR_BUFFER_TOO_SMALL;
+        rec->acc = acc;
+        rec->xIdx = x;
+        rec->inputDeficit = x - s.x_len;                       // :734
+    }
+    rec->count = count;
+    if (s.counts_out) s.counts_out[c] = count;
+}
+
+__global__ __launch_bounds__(kRatesSchedThreads) void rates_reset_kernel(RateChannel *rec, int nch)
+{
+    const int c = static_cast<int>(blockIdx.x) * kRatesSchedThreads + static_cast<int>(threadIdx.x);
+    if (c >= nch) return;
+    rec[c].acc = 1.0; rec[c].inputDeficit = 1; rec[c].xIdx = 1; rec[c].count = 0; rec[c].error = 0;    // Filters.jl:110-115
+}
+
+// One lane per (channel, output), any (Nphi, T, hLen, rates): blockIdx.x covers the outputs up to the call's bound, blockIdx.y strides
+// the channels; the channel's count is uniform over the workgroup.
+template <typename TX, typename R, int NCX, bool FUSED>
+__global__ __launch_bounds__(kVariantThreads) void arb_rates_generic_kernel(ArbArgs a, RatesArgs r)
+{
+    using A = RealTaps<TX, R, NCX, FUSED>;
+    using Sample = typename A::Sample;
+    const long long k = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    for (int ch = blockIdx.y; ch < a.nch; ch += gridDim.y) {
+        if (k >= r.rec[ch].count) continue;
+        const long long n = a.n_idx[static_cast<long long>(ch) * r.slice + k];
+        double alpha;
+        const int phi = arb_phase(a.acc[static_cast<long long>(ch) * r.slice + k], &alpha);
+        const long long col = static_cast<long long>(phi) * a.T;
+        const long long base = n - a.T;             // 0-based index of the oldest sample (>= -H: n >= 1)
+        const R *__restrict__ tp = static_cast<const R *>(a.taps) + col;
+        const R *__restrict__ dp = static_cast<const R *>(a.dtaps) + col;
+        const Sample *__restrict__ xc = static_cast<const Sample *>(a.x) + static_cast<long long>(ch) * a.x_stride;
+        const Sample *__restrict__ hc = static_cast<const Sample *>(a.hist) + static_cast<long long>(ch) * a.H;
+        R *__restrict__ yc = A::channel_out(a.y, ch, a.y_stride);
+        auto sample = [&](long long xi) -> Sample { return xi >= 0 ? xc[xi] : hc[static_cast<long long>(a.H) + xi]; };
+        Sample v = sample(base);
+        typename A::Sum lo = A::first(tp[0], v);
+        typename A::Sum up = A::first(dp[0], v);
+        for (int i = 1; i < a.T; ++i) {
+            v = sample(base + i);
+            lo = A::step(lo, tp[i], v);
+            up = A::step(up, dp[i], v);
+        }
+        A::store(yc, k, A::arb_combine(lo, up, alpha));
+    }
+    dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+}
+
+// Persistent workgroups in the channel-major tile order (tile_run, variant_device.h).  A tile is (channel, run of tile_out = 256
+// outputs); the tiling goes by the call's bound, and the tiles behind a channel's count are skipped.  pfb and dpfb are shared by the
+// channels: they go into LDS ONCE per workgroup (column pitch T + 1: lanes of different phases read different LDS banks).  The tile's run
+// of samples is read from the channel's own slice of the schedule (tile_span) -- so it follows that channel's rate -- and staged through
+// LDS (stage_window); a tile whose run is longer than the planned span (a channel that decimates heavily) reads its windows from global
+// memory.
+template <typename TX, typename R, int NCX, bool FUSED>
+__global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArgs a, RatesArgs r, ArbTileArgs ta)
+{
+    using A = RealTaps<TX, R, NCX, FUSED>;
+    using Sample = typename A::Sample;
+    extern __shared__ __attribute__((aligned(16))) unsigned char rates_arb_smem[];
+    R *const lpfb = reinterpret_cast<R *>(rates_arb_smem);
+    R *const ldpfb = lpfb + ta.bank_elems;
+    Sample *const lx = reinterpret_cast<Sample *>(rates_arb_smem + ta.x_offset_bytes);
+
+    const int tid = threadIdx.x;
+    const int T = a.T, TP = ta.tap_pitch;
+    const TileRun run = tile_run(ta.total_tiles);
+    if (run.begin < run.end) {           // (uniform over the workgroup) the shared banks -> LDS: element (phi, i) at phi*TP + i
+        const R *__restrict__ g0 = static_cast<const R *>(a.taps);
+        const R *__restrict__ g1 = static_cast<const R *>(a.dtaps);
+        const int bank_elems = a.Nphi * T;
+        for (int e = tid; e < bank_elems; e += kVariantThreads) {
+            const int phi = e / T, i = e - phi * T;
+            lpfb[phi * TP + i] = g0[e];
+            ldpfb[phi * TP + i] = g1[e];
+        }
+    }
+
+    for (long long tile = run.begin; tile < run.end; ++tile) {
+        const BankTile t = bank_tile<true>(tile, ta, a.n_out);
+        const int ch = t.ch;
+        const long long count = r.rec[ch].count;
+        if (t.k0 >= count) continue;     // (uniform over the workgroup) a tile behind the channel's count
+        const long long klast = (t.klast < count ? t.klast : count - 1);
+        const int *__restrict__ nc = a.n_idx + static_cast<long long>(ch) * r.slice;
+        const double *__restrict__ ac = a.acc + static_cast<long long>(ch) * r.slice;
+        const TileSpan w = tile_span(nc, t.k0, klast, T, ta.max_span);
+        const Sample *__restrict__ xc = static_cast<const Sample *>(a.x) + static_cast<long long>(ch) * a.x_stride;
+        const Sample *__restrict__ hc = static_cast<const Sample *>(a.hist) + static_cast<long long>(ch) * a.H;
+
+        __syncthreads();   // the previous tile's reads of the window are done
+        if (w.staged) stage_window(lx, xc, hc, w.o, static_cast<int>(w.span), a.x_len, a.H, tid);
+        __syncthreads();   // (the first one of a workgroup: the banks are in LDS too)
+
+        R *__restrict__ yc = A::channel_out(a.y, ch, a.y_stride);
+        for (long long k = t.k0 + tid; k <= klast; k += kVariantThreads) {
+            const long long n = nc[k];
+            double alpha;
+            const int phi = arb_phase(ac[k], &alpha);
+            const R *tp = lpfb + phi * TP;
+            const R *dp = ldpfb + phi * TP;
+            typename A::Sum lo, up;
+            if (w.staged) {
+                const Sample *wp = lx + (n - w.n_lo);             // oldest sample of this output's window
+                const R t0 = tp[0], d0 = dp[0];
+                const Sample v0 = wp[0];
+                lo = A::first(t0, v0);
+                up = A::first(d0, v0);
+#pragma unroll 4
+                for (int i = 1; i < T; ++i) {
+                    const R ti = tp[i], di = dp[i];
+                    const Sample v = wp[i];
+                    lo = A::step(lo, ti, v);
+                    up = A::step(up, di, v);
+                }
+            } else arb_dots_global<A>(tp, dp, xc, hc + a.H, n - T, T, lo, up);
+            A::store(yc, k, A::arb_combine(lo, up, alpha));
+        }
+    }
+    dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+}
+
+}  // namespace
+
+hipError_t launch_rates_schedule(const RatesSchedArgs &s, bool pow2, hipStream_t st)
+{
+    const dim3 grid(static_cast<unsigned>((s.nch + kRatesSchedThreads - 1) / kRatesSchedThreads));
+    if (pow2) launch_kernel(rates_schedule_kernel<true>, grid, dim3(kRatesSchedThreads), 0, st, s);
+    else launch_kernel(rates_schedule_kernel<false>, grid, dim3(kRatesSchedThreads), 0, st, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_rates_reset(RateChannel *rec, int nch, hipStream_t st)
+{
+    const dim3 grid(static_cast<unsigned>((nch + kRatesSchedThreads - 1) / kRatesSchedThreads));
+    hipLaunchKernelGGL(rates_reset_kernel, grid, dim3(kRatesSchedThreads), 0, st, rec, nch);
+    return hipGetLastError();
+}
+
+// (the names mrhip_last_kernel_name reports carry no kernel suffix: include/multirate_hip.h at mrhip_last_kernel_name)
+hipError_t launch_arb_rates_generic(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, hipStream_t s, const char **kname)
+{
+    if (tk.bank || tk.complex_h || a.dyn) return hipErrorInvalidValue;
+    if (a.n_out <= 0) return hipSuccess;
+    const long long bx = (a.n_out + kVariantThreads - 1) / kVariantThreads;
+    if (bx > 0x7fffffffLL) return hipErrorInvalidValue;
+    *kname = "arb_rates_generic";
+    const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(a.nch < 65535 ? a.nch : 65535), 1);
+    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
+        launch_kernel(fused ? arb_rates_generic_kernel<TX, R, NCX, true> : arb_rates_generic_kernel<TX, R, NCX, false>, grid,
+                      dim3(kVariantThreads), 0, s, a, r);
+        return hipGetLastError();
+    });
+}
+
+bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, ArbTileArgs *out, size_t *lds)
+{
+    return plan_arb_rates_tiled(tk, a, rate_min, num_cus, MRHIP_ENV_INT("MRHIP_ARB_RATES_TILED", -1), out, lds);
+}
+
+hipError_t prepare_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbTileArgs &ta, size_t lds, int num_cus, long long *grid)
+{
+    if (tk.bank || tk.complex_h) return hipErrorInvalidValue;
+    const int grid_fixed = MRHIP_ENV_INT("MRHIP_ARB_RATES_GRID", 0);
+    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
+        auto kfn = fused ? arb_rates_tiled_kernel<TX, R, NCX, true> : arb_rates_tiled_kernel<TX, R, NCX, false>;
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kVariantThreads, lds, num_cus, ta.total_tiles);
+        if (pg.err != hipSuccess) return pg.err;
+        long long g = std::max<long long>(std::min<long long>(pg.grid, ta.total_tiles), 1);
+        if (grid_fixed > 0) g = std::min<long long>(grid_fixed, 65535);       // (tests: also more workgroups than tiles)
+        *grid = g;
+        return hipSuccess;
+    });
+}
+
+hipError_t launch_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, const ArbTileArgs &ta, size_t lds,
+                                  long long grid, hipStream_t s, const char **kname)
+{
+    if (tk.bank || tk.complex_h || a.dyn || grid < 1) return hipErrorInvalidValue;
+    *kname = "arb_rates_tiled";
+    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
+        auto kfn = fused ? arb_rates_tiled_kernel<TX, R, NCX, true> : arb_rates_tiled_kernel<TX, R, NCX, false>;
+        launch_kernel(kfn, dim3(static_cast<unsigned>(grid)), dim3(kVariantThreads), lds, s, a, r, ta);
+        return hipGetLastError();
+    });
+}
+
+}  // namespace mrhip

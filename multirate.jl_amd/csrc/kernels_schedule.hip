@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "mrhip_internal.h"
+#include "sched_step.h"
 
 #pragma clang fp contract(off)
 
@@ -55,24 +56,8 @@ __device__ __forceinline__ void sched_step(double &acc, long long &x, const Sche
 }
 
 // The same step without a branch, for the 64-step runs of the tables and emit kernels (a lone wave there pays ~170 cycles a step for the
-// form above: four branches, a run-time test of `pow2` per step and a Float64 -> Int64 conversion of k in five instructions).  The same
-// operations on the same values in the same order -- the results of the path not taken are discarded -- and k, an integer below 2^18 + 1
-// (make_sched_plan), goes through Int32.
-template <bool POW2>
-__device__ __forceinline__ void sched_step_nb(double &acc, long long &x, const SchedPlan &c)
-{
-    const double a1 = acc + c.delta;                                  // :664
-    const double am1 = a1 - 1.0;
-    const double q = POW2 ? am1 * c.invN : am1 / c.N;                 // :667
-    const double k = __builtin_floor(q);
-    double r = am1 - k * c.N;
-    // (a power of two: the scaling, the floor, k * N and the difference are all exact -- r is am1 mod N, never negative; only a ROUNDED
-    //  quotient can overshoot an integer: the comment above sched_step)
-    if constexpr (!POW2) r = r < 0.0 ? r + c.N : r;
-    const bool wrap = a1 > c.N;                                       // :666
-    acc = wrap ? r + 1.0 : a1;                                        // :668
-    x += wrap ? static_cast<long long>(__double2int_rz(k)) : 0LL;
-}
+// form above: four branches, a run-time test of `pow2` per step and a Float64 -> Int64 conversion of k in five instructions):
+// sched_step_nb<POW2> of sched_step.h, which the serial walk of kernels_rates_arb.hip and a CPU test compile too.
 
 // Predicted phase after k steps from the piece's start: the un-rounded recurrence (double-double product) plus the
 // drift per step measured so far.  Accuracy only decides how often a start falls outside the candidate window.

@@ -10,6 +10,7 @@
 namespace mrhip {
 // zero elements either side of a device tap vector (api.hip upload_taps; kernels_fir_stream.hip plans against it)
 constexpr int kTapPad = 256;
+struct RateChannel;      // rates_arb.h
 }
 
 struct mrhip_filter {
@@ -26,6 +27,15 @@ struct mrhip_filter {
                              // (FIRArbitrary, mrhip_create_arbitrary_bank: d_dtaps / h_dtaps as well; kernels_bank_arb.hip only)
                              // (FIRFarrow, mrhip_create_farrow_bank: d_pnfb / h_pnfb hold nch banks, [nch][T][polyorder+1], no d_pnfb_t;
                              //  kernels_bank_farrow.hip only)
+
+    // per-channel RATES (mrhip_create_arbitrary_rates; rates_arb.h, kernels_rates_arb.hip only): one shared pfb / dpfb, and per channel a
+    // record on the device (rate, Δ, 𝜙Accumulator, xIdx, inputDeficit, the latest call's count) and a slice of the schedule buffers.  The
+    // host fields below that carry ONE state (phiIdx ... delta) mean nothing on such a filter; `rate` holds the largest rate (the bound).
+    bool rates = false;
+    std::vector<double> h_rates;                           // [nch]
+    mrhip::RateChannel *d_rrec = nullptr;                  // device, [nch]
+    void *d_rs_n = nullptr, *d_rs_acc = nullptr;           // device: the channels' slices, [nch][bound of the call] entries
+    size_t rs_cap = 0;                                     // entries either buffer holds
 
     // device memory
     void *d_taps = nullptr, *d_dtaps = nullptr;            // (inside d_taps_alloc / d_dtaps_alloc: kTapPad zero elements either side)

@@ -228,6 +228,7 @@ int mrhip_ring_open(mrhip_filter *f, mrhip_ring **out)
 {
     if (!f || !out) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
+    if (int rc = rates_refused(f, "mrhip_ring_open")) return rc;
     if (f->ring_open) return fail(MRHIP_ERR_INVALID_ARG, "the filter already feeds a ring");
     DeviceGuard guard(f->device);
     if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");

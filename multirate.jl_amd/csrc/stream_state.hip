@@ -102,7 +102,8 @@ int rec_alloc(mrhip_filter *f)
     std::memset(h, 0, 512);
     f->h_rec = static_cast<DevStream *>(h);
     MRHIP_CHECK_HIP(hipEventCreateWithFlags(&f->ev_rec, hipEventDisableTiming));
-    if (f->kind == MRHIP_FIR_ARBITRARY || f->kind == MRHIP_FIR_FARROW) {      // the schedule's own stream (mrhip_filter.h: s_sched)
+    // (per-channel rates: every call is enqueued on the caller's stream and nothing else -- no schedule stream)
+    if ((f->kind == MRHIP_FIR_ARBITRARY || f->kind == MRHIP_FIR_FARROW) && !f->rates) {      // the schedule's own stream (mrhip_filter.h: s_sched)
         // LOWEST priority: the schedule of call i+1 and the filter kernel of call i become runnable at the same moment (both wait
         // for the filter kernel of call i-1); the filter kernel's persistent workgroups must be placed first and the schedule's fill
         // what is left, not the other way round (profiles/r04/experiments.md S).  MRHIP_SCHED_PRIO=0: default priority.

@@ -57,6 +57,12 @@ class _State(C.Structure):
                 ("phiAccumulator", C.c_double), ("alpha", C.c_double), ("delta", C.c_double)]
 
 
+class ChannelState(C.Structure):
+    """mrhip_channel_state: one channel of a filter with per-channel rates (FIRFilter.per_channel_rates)"""
+    _fields_ = [("rate", C.c_double), ("delta", C.c_double), ("phiAccumulator", C.c_double), ("alpha", C.c_double),
+                ("phiIdx", C.c_int64), ("inputDeficit", C.c_int64), ("xIdx", C.c_int64), ("last_count", C.c_int64)]
+
+
 # every symbol include/multirate_hip.h declares: (name, restype, argtypes)
 _vp, _i64, _i, _d = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _pi64 = C.POINTER(C.c_int64)
@@ -82,6 +88,10 @@ ABI = [
     ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_bank", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_arbitrary_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_arbitrary_rates", _i, [_vp, _i64, _i, _vp, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_filt_device_rates", _i, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    ("mrhip_get_channel_states", _i, [_vp, _vp]),
+    ("mrhip_set_channel_states", _i, [_vp, _vp, _vp]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_bank", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -266,6 +276,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
+        self._rates = None                # per-channel rates (FIRFilter.per_channel_rates): Float64, one per channel; self.rate is the largest
         self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow, .per_channel_complex_taps_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
@@ -413,6 +424,29 @@ class FIRFilter:
         return f
 
     @classmethod
+    def per_channel_rates(cls, h, rates, Nphi: int = 32, *, device: int = 0, numerics: int = NUMERICS_STRICT):
+        """One FIRFilter(h, rates[c]::Float, N𝜙) per channel behind one filter object: FIRArbitrary with per-channel RATES (receivers
+        each off its own clock trimmed to a common rate, per-emitter Doppler time-scale correction, per-channel fractional delay).
+        ``h``: one Float32 or Float64 tap vector, shared; ``rates``: one rate > 0 per channel.  Every channel has its own phase
+        schedule, state and output count; channel c is bit for bit ``FIRFilter(h, rates[c], Nphi)`` fed ``x[c]``, under STRICT and
+        FUSED (include/multirate_hip.h: per-channel rates for FIRArbitrary).  The filter binds to exactly ``len(rates)`` channels and
+        takes device tensors: ``filt(x)`` returns a list of ``nchannels`` arrays, ``filt_into(buffer, x)`` the int64 counts,
+        ``channel_states`` / ``set_channel_states`` replace ``state`` / ``set_state``.  What carries one state or one count
+        (``state``, ``outputlength``, ``next_output_count``, ``filt_into_async``, rings, cascades, ...) raises status 5.  The device
+        object is created by ``mrhip_create_arbitrary_rates``."""
+        h = np.asarray(h)
+        if h.dtype.kind == "c":
+            raise MultirateHIPError(5, "per_channel_rates takes Float32/Float64 taps (complex taps with per-channel rates are left out)")
+        r = np.atleast_1d(np.asarray(rates, dtype=np.float64))
+        if r.ndim != 1 or r.size < 1:
+            raise MultirateHIPError(1, f"per_channel_rates takes one rate per channel, at least one; got shape {r.shape}")
+        if not np.all(np.isfinite(r)) or not np.all(r > 0.0):
+            raise MultirateHIPError(1, "rate must be greater than 0 (every channel's)")      # Filters.jl:184
+        f = cls(h, float(r.max()), int(Nphi), device=device, numerics=numerics)
+        f._rates = np.ascontiguousarray(r).copy()
+        return f
+
+    @classmethod
     def per_channel_complex_taps_arbitrary(cls, H, rate, Nphi: int = 32, *, device: int = 0):
         """One FIRFilter(H[c]::Vector{Complex64 / Complex128}, rate::Float, N𝜙) per channel behind one filter object: FIRArbitrary
         with per-channel complex taps (a prototype rotated to every channel's own centre frequency in front of a common clock-trim or
@@ -499,7 +533,12 @@ class FIRFilter:
         out = C.c_void_p()
         if self._bank is not None and nch != self._bank.shape[0]:
             raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
-        if self._bank is not None and self.kind == ARBITRARY and self._bank.dtype.kind == "c":
+        if self._rates is not None and nch != len(self._rates):
+            raise MultirateHIPError(1, f"a filter of {len(self._rates)} per-channel rates binds to exactly that many channels; got {nch}")
+        if self._rates is not None:
+            rc = self._lib.mrhip_create_arbitrary_rates(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], _ptr(self._rates), self.Nphi,
+                                                        _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self._bank is not None and self.kind == ARBITRARY and self._bank.dtype.kind == "c":
             rc = self._lib.mrhip_create_arbitrary_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
                                                              self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
         elif self._bank is not None and self.kind == ARBITRARY:
@@ -572,6 +611,8 @@ class FIRFilter:
     @property
     def state(self) -> _State:
         st = _State()
+        if self._rates is not None:
+            raise MultirateHIPError(5, "state: the filter has per-channel rates, so a state per channel -- use channel_states")
         if self._handle is None:  # constructor state, src/Filters.jl:77-78,110-115
             st.kind = self.kind
             st.phiIdx, st.inputDeficit, st.xIdx = 1, 1, 1
@@ -751,7 +792,13 @@ class FIRFilter:
 
     def filt_into(self, buffer, x) -> int:
         """filt!(buffer, self, x): writes per-channel outputs into ``buffer`` (same container kind as
-        ``x``), returns the per-channel output count."""
+        ``x``), returns the per-channel output count.  A filter with per-channel rates (``per_channel_rates``): torch device tensors
+        only; ``buffer`` needs ``outputlength_bound(n)`` samples per row, row c receives its first ``counts[c]`` elements and nothing
+        else, and the int64 counts of all channels are returned (after waiting for them)."""
+        if self._rates is not None:
+            counts = self._filt_into_rates(buffer, x)
+            torch.cuda.current_stream(x.device).synchronize()
+            return counts.cpu().numpy()
         nw = C.c_int64(0)
         if _is_torch(x):
             if not x.is_cuda:
@@ -785,6 +832,57 @@ class FIRFilter:
         cap = buffer.shape[-1]
         _check(self._lib.mrhip_filt_host(self._handle, _ptr(x), n, n, _ptr(buffer), cap, cap, C.byref(nw)))
         return nw.value
+
+    def _filt_into_rates(self, buffer, x, counts=None):
+        """``mrhip_filt_device_rates`` on torch's current stream; returns the int64 device tensor of the counts without waiting."""
+        if not _is_torch(x) or not x.is_cuda or not _is_torch(buffer) or not buffer.is_cuda:
+            raise MultirateHIPError(1, "a filter with per-channel rates takes torch device tensors")
+        if x.stride(-1) != 1 or buffer.stride(-1) != 1:
+            raise MultirateHIPError(1, "x and buffer must be contiguous along time (planar channels)")
+        nch, n, _ = self._shape(x)
+        self._ensure(_torch_np_dtype(x.dtype), nch)
+        if _torch_np_dtype(buffer.dtype) != self.output_dtype:
+            raise MultirateHIPError(1, f"buffer dtype must be {self.output_dtype}")
+        if x.device.index != self.device or buffer.device != x.device:
+            raise MultirateHIPError(1, "x / buffer are not on the filter's device")
+        if buffer.ndim != x.ndim or (x.ndim == 2 and buffer.shape[0] != nch):
+            raise MultirateHIPError(1, "buffer must have one row per channel")
+        cap = buffer.shape[-1]
+        xs = x.stride(0) if x.ndim == 2 and nch > 1 else n
+        ys = buffer.stride(0) if buffer.ndim == 2 and nch > 1 else cap
+        if counts is None:
+            counts = torch.empty(nch, dtype=torch.int64, device=x.device)
+        elif not (_is_torch(counts) and counts.is_cuda and counts.dtype == torch.int64 and counts.numel() >= nch and counts.is_contiguous()):
+            raise MultirateHIPError(1, "counts must be a contiguous int64 CUDA tensor of nchannels elements")
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _check(self._lib.mrhip_filt_device_rates(self._handle, C.c_void_p(x.data_ptr()), n, xs, C.c_void_p(buffer.data_ptr()), cap, ys,
+                                                 C.c_void_p(counts.data_ptr()), C.c_void_p(stream)))
+        return counts
+
+    @property
+    def channel_states(self):
+        """The per-channel states of a filter with per-channel rates (``mrhip_get_channel_states``; waits for the filter's stream): a list
+        of ``ChannelState`` (rate, delta, phiAccumulator, alpha, phiIdx, inputDeficit, xIdx, last_count).  Unbound: constructor states."""
+        if self._rates is None:
+            raise MultirateHIPError(1, "channel_states needs a filter of FIRFilter.per_channel_rates")
+        out = (ChannelState * len(self._rates))()
+        if self._handle is None:                                   # constructor state, src/Filters.jl:110-115
+            for c, r in enumerate(self._rates):
+                out[c] = ChannelState(float(r), self.Nphi / float(r), 1.0, 0.0, 1, 1, 1, 0)
+            return list(out)
+        _check(self._lib.mrhip_get_channel_states(self._handle, C.cast(out, C.c_void_p)))
+        return list(out)
+
+    def set_channel_states(self, inputDeficit, phiAccumulator):
+        """Per-channel ``inputDeficit`` (>= 1) and ``phiAccumulator`` (in [1, N𝜙+1)); 𝜙Idx and α follow as update() derives them
+        (``mrhip_set_channel_states``)."""
+        if self._rates is None or self._handle is None:
+            raise MultirateHIPError(1, "set_channel_states needs a bound filter of FIRFilter.per_channel_rates (bind(), or call filt once)")
+        d = np.ascontiguousarray(inputDeficit, dtype=np.int64)
+        a = np.ascontiguousarray(phiAccumulator, dtype=np.float64)
+        if d.shape != (self._nch,) or a.shape != (self._nch,):
+            raise MultirateHIPError(1, f"set_channel_states takes {self._nch} inputDeficit and {self._nch} phiAccumulator values")
+        _check(self._lib.mrhip_set_channel_states(self._handle, _ptr(d), _ptr(a)))
 
     def outputlength_bound(self, inputlength: int) -> int:
         """The largest per-channel output count a call of ``inputlength`` samples can have whatever the stream state
@@ -883,6 +981,19 @@ class FIRFilter:
         # FIRArbitrary / FIRFarrow: like the reference (Filters.jl:744-752, 841-849) allocate the outputlength
         # estimate (+2: it is only a guess there) and trim to the count filt! returns -- the exact count would need
         # the whole serial phase recurrence up front, which the library instead pipelines with the kernels.
+        if self._rates is not None:
+            # per-channel rates: a list of nchannels arrays, each trimmed to its own count; numpy input goes to the device and back
+            as_np = not _is_torch(x)
+            if as_np:
+                if torch is None:
+                    raise MultirateHIPError(1, "a filter with per-channel rates takes torch device tensors")
+                x = torch.from_numpy(np.ascontiguousarray(x)).to(f"cuda:{self.device}")
+            nch, n, one = self._shape(x)
+            self._ensure(_torch_np_dtype(x.dtype), nch)
+            y = torch.empty((nch, self.outputlength_bound(n)), dtype=_np_torch_dtype(self.output_dtype), device=x.device)
+            counts = self.filt_into(y[0] if one else y, x if x.stride(-1) == 1 else x.contiguous())
+            rows = [y[c, :int(counts[c])] for c in range(nch)]
+            return [r.cpu().numpy() for r in rows] if as_np else rows
         est_mode = self.kind in (ARBITRARY, FARROW)
         if _is_torch(x):
             nch, n, one = self._shape(x)

@@ -15,7 +15,8 @@ module MultirateHIP
 export FIRFilter, FIRKernel, FIRStandard, FIRDecimator, FIRInterpolator, FIRRational, FIRArbitrary, FIRFarrow,
        filt, filt!, taps2pfb, outputlength, inputlength, reset, nextphase, setphase, tapsforphase, tapsforphase!, polyfit,
        firdes, firprototype, kaiserlength, kaiser, FIRResponse, LOWPASS, BANDPASS, HIGHPASS, BANDSTOP,
-       FilterCascade, filt_device!, filt_device_chunked!, scheduleinfo, advancestate!, ChunkRing, pushchunks!, drain, ringinfo, ShardedFIRFilter
+       FilterCascade, filt_device!, filt_device_chunked!, scheduleinfo, advancestate!, ChunkRing, pushchunks!, drain, ringinfo, ShardedFIRFilter,
+       RatesFIRFilter, channelstates, setchannelstates!
 
 const libmr = get(ENV, "MRHIP_LIB_PATH", joinpath(@__DIR__, "..", "libmultirate_hip.so"))
 
@@ -518,6 +519,100 @@ function filt_device_chained!(f::FIRFilter, prev::FIRFilter, yptr::Ptr{Cvoid}, y
                 f.handle, prev.handle, xptr, xlenbound, xstride, yptr, ycap, ystride, countptr, stream))
     nothing
 end
+# ---- FIRArbitrary with per-channel RATES (include/multirate_hip.h: per-channel rates for FIRArbitrary) ---------------------------
+# One FIRFilter(h, rates[c], Nphi) per channel behind one filter object: the channels share h, Nphi, the call length and the history
+# length; every channel has its own phase schedule, state and per-call output count, so `filt` returns one Vector per channel.  Calls
+# are planned on the device (mrhip_filt_device_rates); what carries one state or one count (filt!, outputlength, getproperty's kernel
+# fields, rings, cascades) does not apply to this type.  (Like the rest of this file, never executed where the library is built and
+# tested: no Julia there.)
+struct MRHIPChannelState
+    rate::Cdouble
+    delta::Cdouble
+    phiAccumulator::Cdouble
+    alpha::Cdouble
+    phiIdx::Int64
+    inputDeficit::Int64
+    xIdx::Int64
+    last_count::Int64
+end
+mutable struct RatesFIRFilter{Th}
+    h::Vector{Th}
+    rates::Vector{Float64}
+    Nphi::Int
+    device::Int
+    handle::Ptr{Cvoid}
+    Tx::Union{DataType,Nothing}
+end
+function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
+    isempty(rates) && error("one rate per channel, at least one")
+    all(r -> r > 0.0, rates) || error("rate must be greater than 0")
+    f = RatesFIRFilter{Th}(copy(h), Vector{Float64}(rates), Nphi, device, C_NULL, nothing)
+    finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
+end
+function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
+    if f.handle != C_NULL
+        f.Tx === Tx || error("filter is bound to samples of $(f.Tx)")
+        return f
+    end
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mrhip_create_arbitrary_rates, libmr), Cint,
+                (Ptr{Cvoid}, Int64, Cint, Ptr{Cdouble}, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                f.h, length(f.h), dtypecode(Th), f.rates, f.Nphi, dtypecode(Tx), length(f.rates), f.device, out))
+    f.handle, f.Tx = out[], Tx
+    f
+end
+outputlengthbound(f::RatesFIRFilter, n::Integer) = Int(ccall((:mrhip_outputlength_bound, libmr), Int64, (Ptr{Cvoid}, Int64), f.handle, n))
+# x and y are (n x nchannels) column-major on the filter's device, ycap and ystride at least outputlengthbound(f, xlen); countsptr
+# (optional) is device-accessible memory for the nchannels counts.  Nothing waits.
+function filt_device!(f::RatesFIRFilter, yptr::Ptr{Cvoid}, ycap::Integer, ystride::Integer, xptr::Ptr{Cvoid}, xlen::Integer,
+                      xstride::Integer, ::Type{Tx}; countsptr::Ptr{Int64} = Ptr{Int64}(C_NULL), stream::Ptr{Cvoid} = C_NULL) where {Tx}
+    bind!(f, Tx)
+    check(ccall((:mrhip_filt_device_rates, libmr), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}),
+                f.handle, xptr, xlen, xstride, yptr, ycap, ystride, countsptr, stream))
+    nothing
+end
+# the channels' states, after waiting for the filter's stream
+function channelstates(f::RatesFIRFilter)
+    out = Vector{MRHIPChannelState}(undef, length(f.rates))
+    check(ccall((:mrhip_get_channel_states, libmr), Cint, (Ptr{Cvoid}, Ptr{MRHIPChannelState}), f.handle, out))
+    out
+end
+function setchannelstates!(f::RatesFIRFilter, inputDeficit::Vector{Int64}, phiAccumulator::Vector{Float64})
+    (length(inputDeficit) == length(f.rates) && length(phiAccumulator) == length(f.rates)) || error("one value per channel")
+    check(ccall((:mrhip_set_channel_states, libmr), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Cdouble}), f.handle, inputDeficit, phiAccumulator))
+    f
+end
+reset(f::RatesFIRFilter) = (f.handle == C_NULL || check(ccall((:mrhip_reset, libmr), Cint, (Ptr{Cvoid},), f.handle)); f)
+# filt(self, x): one channel per column of x (host memory); returns one Vector per channel, each of its own length.  The signal goes
+# to the device and the outputs come back through the HIP runtime the library is linked against.
+const libhip = "libamdhip64"
+function filt(f::RatesFIRFilter{Th}, x::Matrix{Tx}) where {Th,Tx}
+    size(x, 2) == length(f.rates) || error("a filter of $(length(f.rates)) rates takes that many channels")
+    bind!(f, Tx)
+    Tb = promote_out(Th, Tx)
+    n, nch = size(x)
+    cap = outputlengthbound(f, n)
+    dx, dy, dc = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    hipcheck(e) = e == 0 || error("HIP error $e")
+    hipcheck(ccall((:hipMalloc, libhip), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), dx, max(sizeof(x), 16)))
+    hipcheck(ccall((:hipMalloc, libhip), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), dy, max(cap * nch * sizeof(Tb), 16)))
+    hipcheck(ccall((:hipMalloc, libhip), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), dc, nch * sizeof(Int64)))
+    y, counts = Matrix{Tb}(undef, cap, nch), Vector{Int64}(undef, nch)
+    try
+        hipcheck(ccall((:hipMemcpy, libhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), dx[], x, sizeof(x), 1))
+        filt_device!(f, dy[], cap, cap, dx[], n, n, Tx; countsptr = Ptr{Int64}(dc[]))
+        hipcheck(ccall((:hipDeviceSynchronize, libhip), Cint, ()))
+        hipcheck(ccall((:hipMemcpy, libhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), y, dy[], sizeof(y), 2))
+        hipcheck(ccall((:hipMemcpy, libhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), counts, dc[], sizeof(counts), 2))
+    finally
+        for p in (dx[], dy[], dc[])
+            p == C_NULL || ccall((:hipFree, libhip), Cint, (Ptr{Cvoid},), p)
+        end
+    end
+    [y[1:counts[c], c] for c in 1:nch]
+end
+
 outputlengthbound(f::FIRFilter, n::Integer) = Int(ccall((:mrhip_outputlength_bound, libmr), Int64, (Ptr{Cvoid}, Int64), f.handle, n))
 # wait for the filter's enqueued calls, bring the host-side view of the state up to date; returns the last call's count
 function syncstate!(f::FIRFilter)
