@@ -288,10 +288,42 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     mrhip_ring_open, mrhip_cascade_create, mrhip_get_state, mrhip_set_state, mrhip_sync_state, mrhip_outputlength,
  *     mrhip_inputlength, mrhip_next_output_count, mrhip_advance_state; mrhip_sharded_create has no such constructor;
  *   - every other constructor and filter answers exactly as before;
- *   - left out on purpose: FIRFarrow with per-channel rates; complex or per-channel taps combined with per-channel rates; evaluating
+ *   - the rates may change between calls: mrhip_set_channel_rates; mrhip_reset restores the constructor STATE of every channel and
+ *     keeps the current rates;
+ *   - left out on purpose: complex or per-channel taps combined with per-channel rates; evaluating
  *     a long channel's schedule with the parallel tables / chain / emit machinery instead of the serial walk (the next speed step
  *     for few long channels); graph capture, rings, cascades and sharding of such a filter; a mrhip_filt_device_multi that serves
  *     FIRArbitrary streams in one launch. */
+
+/* Per-channel rates for FIRFarrow (mrhip_create_farrow_rates, mrhip_create_farrow_rates_pnfb; Th in {F32,F64}): one
+ * FIRFilter(h, rates[c], Nphi, polyorder) per channel behind one handle -- FIRFarrow is the kernel the reference offers for a
+ * continuously variable rate, so the users of per-channel rates named above are Farrow users first.  The channels share h -- so the ONE
+ * polynomial bank pnfb, fitted once by the fit of mrhip_create_farrow (or handed over) -- Nphi, polyorder, the call length and the history
+ * length; each channel has its own rate, delta, phiIdx (the Float64 phase: phiAccumulator of mrhip_channel_state), xIdx, inputDeficit
+ * and per-call output count.
+ *   - the constructor state of a channel is FIRFarrow's (src/Filters.jl:141-144: phiIdx = 1.0, inputDeficit = xIdx = 1), which is the
+ *     state the records of the FIRArbitrary filter start from: both filters share the reset of their records, the schedule kernel
+ *     (update(), :780-786, is the recurrence of :663-669 on the same Float64 quantity) and mrhip_filt_device_rates,
+ *     mrhip_get_channel_states, mrhip_set_channel_states, mrhip_set_channel_rates;
+ *   - parity: channel c is bit for bit mrhip_create_farrow(h, rates[c], Nphi, polyorder, nchannels = 1) (with a handed-over bank:
+ *     mrhip_create_farrow_pnfb) fed x_c, under STRICT and under FUSED: the outputs, the count of every call, the end state and the
+ *     history.  That includes the short-input path (:805-809) and the zero-start seam of outputs with xIdx < tapsPerPhi (:819-820) on
+ *     EVERY call: a call of this filter always starts a filt!, it never continues one;
+ *   - arithmetic: that of "Per-channel taps for FIRFarrow" on the one bank -- Horner in Float64 from the highest power, product and sum
+ *     rounded separately and never fused, also under FUSED; the tap rounded once to the tap type; the dot oldest sample first, the first
+ *     product initialises the accumulator;
+ *   - mrhip_channel_state reports per channel what mrhip_get_state reports for a one-channel FIRFarrow filter: phiAccumulator is the
+ *     Float64 phase, phiIdx = floor(phiAccumulator) and alpha the remainder;
+ *   - tap types F32 and F64 (complex taps: MRHIP_ERR_UNSUPPORTED, left out); all four sample types; the rate checks are those of
+ *     mrhip_create_arbitrary_rates, Nphi, polyorder and every other check those of mrhip_create_farrow (_pnfb);
+ *   - mrhip_get_pnfb and mrhip_farrow_tapsforphase answer as on a one-channel FIRFarrow filter of h;
+ *   - the call contract is the one stated for FIRArbitrary: two launches on the caller's stream, every host-side failure before the
+ *     schedule kernel, no capture, at most 2^24 entries a channel, the same schedule buffers and their one reallocation wait, one timing
+ *     bracket around both launches, and every entry point that carries ONE state or ONE count refuses the filter;
+ *   - kernels: farrow_rates_generic (any shape) and farrow_rates_multi (four outputs a lane share each tap's scalar coefficient loads;
+ *     MRHIP_FARROW_RATES_MULTI = 1 selects it, the default rule selects it nowhere until measurements say where);
+ *   - left out on purpose: complex or per-channel taps combined with per-channel rates; graph capture, rings, cascades and sharding of
+ *     such a filter; the parallel schedule for long channels, which stays the named next speed step and is shared by both filters. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -318,7 +350,7 @@ typedef struct {
     double delta;            /* Δ :100 */
 } mrhip_state;
 
-/* One channel of a filter with per-channel rates (mrhip_create_arbitrary_rates): the FIRArbitrary fields that differ from channel to
+/* One channel of a filter with per-channel rates (mrhip_create_arbitrary_rates, mrhip_create_farrow_rates): the FIRArbitrary fields that differ from channel to
  * channel (src/Filters.jl:91-117), and the output count of the channel's latest call. */
 typedef struct { double rate, delta, phiAccumulator, alpha;
                  int64_t phiIdx, inputDeficit, xIdx, last_count; } mrhip_channel_state;
@@ -418,6 +450,15 @@ int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int tap_dtype
  * filter's kind is MRHIP_FIR_ARBITRARY. */
 int mrhip_create_arbitrary_rates(const void *h, int64_t hLen, int tap_dtype, const double *rates,
                                  int64_t Nphi, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+/* one FIRFilter(h, rates[c], Nphi, polyorder) per channel behind one handle (see "Per-channel rates for FIRFarrow" above): `h` is ONE
+ * tap vector of hLen taps, `rates` holds nchannels rates.  tap_dtype F32 | F64 (complex: MRHIP_ERR_UNSUPPORTED, left out).  The rate
+ * checks are those of mrhip_create_arbitrary_rates; Nphi, polyorder and every other argument check are those of mrhip_create_farrow;
+ * the filter's kind is MRHIP_FIR_FARROW.  _pnfb: the polynomial bank supplied by the caller, with the contract of
+ * mrhip_create_farrow_pnfb. */
+int mrhip_create_farrow_rates(const void *h, int64_t hLen, int tap_dtype, const double *rates, int64_t Nphi, int64_t polyorder,
+                              int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
+int mrhip_create_farrow_rates_pnfb(const double *pnfb, int64_t hLen, int tap_dtype, const double *rates, int64_t Nphi,
+                                   int64_t polyorder, int sample_dtype, int64_t nchannels, int device, mrhip_filter **out);
 /* replaces FIRFilter(h::Vector, rate::FloatingPoint, Nphi::Integer, polyorder::Integer),
  * src/Filters.jl:192-198 (+ FIRFarrow(h, rate, Nphi, polyorder), :138-147, pfb2pnfb :311-321 and
  * polyfit, src/support.jl:85-88): every ROW of the tapsPerPhi x Nphi filter bank is replaced by its
@@ -578,7 +619,7 @@ int mrhip_filt_device_multi(mrhip_filter *const *filters, int n, const void *con
  * (src/Filters.jl:352-385) evaluated for 𝜙Idx = inputDeficit = 1 (+ 2 for FIRArbitrary / FIRFarrow, whose outputlength is
  * an estimate, :375-381) */
 int64_t mrhip_outputlength_bound(const mrhip_filter *f, int64_t inputlength);
-/* filt! on every channel of a filter with per-channel rates (mrhip_create_arbitrary_rates), each channel from its own state, on
+/* filt! on every channel of a filter with per-channel rates (mrhip_create_arbitrary_rates, mrhip_create_farrow_rates), each channel from its own state, on
  * device memory; enqueued on `stream`.  Nothing waits, with one exception: the filter keeps two schedule buffers on the device that
  * hold nchannels slices of the call's bound -- 12 bytes per (channel, possible output), allocated a quarter larger than the largest call
  * so far needs: about 1.4 GB for 4096 channels x 1e4 samples at rates up to 2.25, about 2.2 GB for 64 x 1e6 -- and a call that needs
@@ -600,6 +641,15 @@ int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out /* [nchan
 /* per-channel inputDeficit (>= 1) and phiAccumulator (in [1, Nphi+1)), behind the calls already enqueued; phiIdx and alpha are
  * re-derived as update() does (src/Filters.jl:671-672): floor(phiAccumulator) and the remainder */
 int mrhip_set_channel_states(mrhip_filter *f, const int64_t *inputDeficit, const double *phiAccumulator);
+/* new rates for a filter with per-channel rates (either constructor), behind the calls already enqueued (it waits for the filter's
+ * stream as mrhip_set_channel_states does): rate and delta = Nphi / rate of every channel are rewritten; phiAccumulator, inputDeficit,
+ * history and taps stay.  The checks are the constructors' (any rate <= 0 or not finite: MRHIP_ERR_INVALID_ARG, below 2^-30:
+ * MRHIP_ERR_UNSUPPORTED; nothing is changed then).  mrhip_outputlength_bound follows the new largest rate, and a later call that
+ * outgrows the schedule buffers reallocates them by the rule above.  After the call channel c continues bit for bit as the one-channel
+ * filter constructed at the new rates[c] would, given channel c's (inputDeficit, phiAccumulator) through mrhip_set_state and its
+ * history through mrhip_set_history.  mrhip_reset restores the constructor state and KEEPS the current rates.  A filter without
+ * per-channel rates: MRHIP_ERR_INVALID_ARG. */
+int mrhip_set_channel_rates(mrhip_filter *f, const double *rates /* [nchannels] */);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call
@@ -764,7 +814,8 @@ int mrhip_timing_read(mrhip_filter *f, int64_t *n_launches, double *total_ms);
 /* name of the device kernel the last filt call dispatched (for profiles / logs).  The two filter kernels of a filter with
  * per-channel rates are reported as arb_rates_generic and arb_rates_tiled, without the suffix the other names carry: the table of
  * write-only-own-outputs cases (tests/output_bounds_cases.py) is keyed by the suffixed names in the sources, and these two kernels'
- * cases live in tests/test_gpu_rates_arb.py until they move into that table. */
+ * cases live in tests/test_gpu_rates_arb.py until they move into that table.  The same holds for farrow_rates_generic and
+ * farrow_rates_multi (FIRFarrow with per-channel rates; their cases: tests/test_gpu_rates_farrow.py). */
 const char *mrhip_last_kernel_name(const mrhip_filter *f);
 /* How the phase schedule of a FIRArbitrary / FIRFarrow filter -- update(), src/Filters.jl:663-673 and :780-792 -- has
  * been evaluated so far.  info[0..n) receives, as far as n reaches:

@@ -594,6 +594,20 @@ static int rates_alloc(mrhip_filter *f)
     return MRHIP_OK;
 }
 
+// the rate checks of the constructors with per-channel rates and of mrhip_set_channel_rates; *rate_max: the largest rate
+static int check_channel_rates(const double *rates, int64_t nch, double *rate_max)
+{
+    if (!rates) return fail(MRHIP_ERR_INVALID_ARG, "rates is NULL");
+    *rate_max = 0.0;
+    for (int64_t c = 0; c < nch; ++c) {
+        if (!(rates[c] > 0.0) || !std::isfinite(rates[c])) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0 (every channel's, and finite)");
+        // (update() advances xIdx by about 1/rate a step; the walk carries that advance in 32 bits: sched_step.h)
+        if (rates[c] < 1.0 / static_cast<double>(1LL << 30)) return fail(MRHIP_ERR_UNSUPPORTED, "a per-channel rate below 2^-30");
+        *rate_max = std::max(*rate_max, rates[c]);
+    }
+    return MRHIP_OK;
+}
+
 int mrhip_create_arbitrary_rates(const void *h, int64_t hLen, int th, const double *rates, int64_t Nphi, int tx, int64_t nch,
                                  int device, mrhip_filter **out)
 {
@@ -601,14 +615,8 @@ int mrhip_create_arbitrary_rates(const void *h, int64_t hLen, int th, const doub
     if (th == MRHIP_C64 || th == MRHIP_C128)
         return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_arbitrary_rates takes Float32 / Float64 taps (complex taps with per-channel rates are left out)");
     if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    if (!rates) return fail(MRHIP_ERR_INVALID_ARG, "rates is NULL");
     double rate_max = 0.0;
-    for (int64_t c = 0; c < nch; ++c) {
-        if (!(rates[c] > 0.0) || !std::isfinite(rates[c])) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0 (every channel's, and finite)");
-        // (update() advances xIdx by about 1/rate a step; the walk carries that advance in 32 bits: sched_step.h)
-        if (rates[c] < 1.0 / static_cast<double>(1LL << 30)) return fail(MRHIP_ERR_UNSUPPORTED, "a per-channel rate below 2^-30");
-        rate_max = std::max(rate_max, rates[c]);
-    }
+    if (int rc = check_channel_rates(rates, nch, &rate_max)) return rc;
     return create_arbitrary_common(h, hLen, th, rate_max, Nphi, tx, nch, device, false, out, rates);
 }
 
@@ -616,8 +624,9 @@ int mrhip_create_arbitrary_rates(const void *h, int64_t hLen, int th, const doub
 // ascending powers -- scalars for real taps, (re, im) pairs for complex ones (the layout kernels_ctaps_farrow.hip reads).  bank: pnfb_in
 // holds nch such banks one after the other, [nch][T][polyorder+1] (mrhip_create_farrow_bank; kernels_bank_farrow.hip -- with complex taps
 // mrhip_create_farrow_bank_ctaps: pairs, kernels_bank_farrow_ctaps.hip), and the degree-major copy for farrow_wave_kernel is never built.
+// rates != NULL (mrhip_create_farrow_rates, mrhip_create_farrow_rates_pnfb): nch rates behind the one bank; `rate` is the largest of them.
 static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen, int th, double rate, int64_t Nphi,
-                                int64_t polyorder, int tx, int64_t nch, int device, bool bank, mrhip_filter **out)
+                                int64_t polyorder, int tx, int64_t nch, int device, bool bank, mrhip_filter **out, const double *rates = nullptr)
 {
     DeviceGuard guard(device);
     if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
@@ -631,6 +640,7 @@ static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen
     f->delta = static_cast<double>(Nphi) / rate;   // Δ = N𝜙/rate, Filters.jl:143
     f->polyorder = polyorder;
     f->bank = bank;
+    if (rates) { f->rates = true; f->h_rates.assign(rates, rates + nch); }
     f->T = (hLen + Nphi - 1) / Nphi;
     f->H = f->T - 1;
     f->h_pnfb = pnfb_in;
@@ -640,7 +650,7 @@ static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen
     if (hipMalloc(reinterpret_cast<void **>(&f->d_pnfb), f->h_pnfb.size() * sizeof(double)) != hipSuccess ||
         hipMemcpy(f->d_pnfb, f->h_pnfb.data(), f->h_pnfb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(MRHIP_ERR_HIP, "uploading the polynomial filter bank failed");
-    if (!rc && f->T <= 32 && !dtype_is_complex(th) && !bank) {   // the same bank degree-major, padded to 32 taps with zeros (kernels_farrow_wave.hip)
+    if (!rc && f->T <= 32 && !dtype_is_complex(th) && !bank && !rates) {   // the same bank degree-major, padded to 32 taps with zeros (kernels_farrow_wave.hip)
         std::vector<double> t(static_cast<size_t>(polyorder + 1) * 32, 0.0);
         for (int64_t i = 0; i < f->T; ++i)
             for (int64_t j = 0; j <= polyorder; ++j) t[static_cast<size_t>(j) * 32 + i] = f->h_pnfb[static_cast<size_t>(i) * (polyorder + 1) + j];
@@ -649,8 +659,9 @@ static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen
             rc = fail(MRHIP_ERR_HIP, "uploading the polynomial filter bank failed");
     }
     if (!rc) rc = alloc_common(f);
+    if (!rc && f->rates) rc = rates_alloc(f);
     if (rc) { mrhip_destroy(f); return rc; }
-    sched_configure(f);
+    if (!f->rates) sched_configure(f);        // (per-channel rates: the serial walk of kernels_rates_arb.hip, none of the schedule machinery)
     *out = f;
     return MRHIP_OK;
 }
@@ -743,6 +754,43 @@ int mrhip_create_farrow_pnfb(const double *pnfb, int64_t hLen, int th, double ra
     const int64_t T = (hLen + Nphi - 1) / Nphi;
     std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1));
     return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
+}
+
+// One FIRFilter(h, rates[c], N𝜙, polyorder) per channel behind one handle (include/multirate_hip.h, "Per-channel rates for FIRFarrow"):
+// the channels share the ONE polynomial bank, fitted once by farrow_fit; each has a record on the device (RateChannel, rates_arb.h) in
+// its constructor state (Filters.jl:141-144: the state rates_alloc and rates_reset_kernel write).
+int mrhip_create_farrow_rates(const void *h, int64_t hLen, int th, const double *rates, int64_t Nphi, int64_t polyorder, int tx,
+                              int64_t nch, int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_C64 || th == MRHIP_C128)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_rates takes Float32 / Float64 taps (complex taps with per-channel rates are left out)");
+    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
+    double rate_max = 0.0;
+    if (int rc = check_channel_rates(rates, nch, &rate_max)) return rc;
+    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
+    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
+        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
+    const int64_t T = (hLen + Nphi - 1) / Nphi;
+    std::vector<double> pn(static_cast<size_t>(T) * (polyorder + 1));
+    if (!farrow_fit(h, hLen, th, Nphi, polyorder, pn.data())) return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
+    return create_farrow_common(pn, hLen, th, rate_max, Nphi, polyorder, tx, nch, device, false, out, rates);
+}
+
+int mrhip_create_farrow_rates_pnfb(const double *pnfb, int64_t hLen, int th, const double *rates, int64_t Nphi, int64_t polyorder,
+                                   int tx, int64_t nch, int device, mrhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (th == MRHIP_C64 || th == MRHIP_C128)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_rates_pnfb takes Float32 / Float64 taps (complex taps with per-channel rates are left out)");
+    if (int rc = check_create_args(pnfb, hLen, th, tx, nch, device, out)) return rc;
+    double rate_max = 0.0;
+    if (int rc = check_channel_rates(rates, nch, &rate_max)) return rc;
+    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
+    if (polyorder < 0 || polyorder > 32) return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32");
+    const int64_t T = (hLen + Nphi - 1) / Nphi;
+    std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1));
+    return create_farrow_common(pn, hLen, th, rate_max, Nphi, polyorder, tx, nch, device, false, out, rates);
 }
 
 // The same two constructors for COMPLEX taps (include/multirate_hip.h, "Complex taps", FIRFarrow part); the fit: farrow_fit_ctaps.
@@ -927,12 +975,12 @@ static int fresh(const mrhip_filter *f)
     return rec_pull(const_cast<mrhip_filter *>(f));
 }
 
-// A filter with per-channel rates (mrhip_create_arbitrary_rates) has one state and one count PER CHANNEL: every entry point that carries
+// A filter with per-channel rates (mrhip_create_arbitrary_rates, mrhip_create_farrow_rates) has one state and one count PER CHANNEL: every entry point that carries
 // ONE state or ONE count refuses it and names the calls that serve it.
 static int rates_refused(const mrhip_filter *f, const char *what)
 {
     if (!f || !f->rates) return MRHIP_OK;
-    return fail(MRHIP_ERR_UNSUPPORTED, std::string(what) + ": the filter has per-channel rates (mrhip_create_arbitrary_rates), so a state and a count per "
+    return fail(MRHIP_ERR_UNSUPPORTED, std::string(what) + ": the filter has per-channel rates (mrhip_create_arbitrary_rates, mrhip_create_farrow_rates), so a state and a count per "
                                        "channel -- use mrhip_filt_device_rates, mrhip_get_channel_states and mrhip_set_channel_states");
 }
 
@@ -2210,7 +2258,7 @@ int64_t mrhip_outputlength_bound(const mrhip_filter *f, int64_t inputlength)
     return output_bound(f, inputlength);      // (per-channel rates: f->rate is the largest, whose bound is the largest)
 }
 
-// ---- FIRArbitrary with per-channel rates (include/multirate_hip.h, "Per-channel rates for FIRArbitrary") ---------------------------------
+// ---- FIRArbitrary and FIRFarrow with per-channel rates (include/multirate_hip.h, "Per-channel rates for FIRArbitrary" / "... for FIRFarrow") ----
 // filt! on every channel, each from its own state: the schedule kernel and one filter kernel, both on the caller's stream; the host never
 // learns a count here.  Every refusal comes before anything is enqueued or changed.
 int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64_t x_stride, void *y, int64_t y_capacity, int64_t y_stride,
@@ -2218,7 +2266,7 @@ int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64
 {
     static_assert(sizeof(long long) == sizeof(int64_t), "the counts are written by the device as long long");
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL filter");
-    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates takes a filter of mrhip_create_arbitrary_rates");
+    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates");
     if (x_len < 0 || y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "negative length");
     if (x_len > 0 && !x) return fail(MRHIP_ERR_INVALID_ARG, "x is NULL");
     if (x_len >= 0x7fffffffLL) return fail(MRHIP_ERR_UNSUPPORTED, "a call takes fewer than 2^31-1 samples per channel");
@@ -2266,6 +2314,18 @@ int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64
     a.dyn = nullptr;
     const int hist_next = hist_other(f);
     if (f->H > 0) a.fold = ShiftFold{f->d_hist[hist_next], nullptr};      // shiftin! by the kernel's last workgroup, into the other slot
+    const bool farrow = f->kind == MRHIP_FIR_FARROW;
+    FarrowArgs fa{};                // (mrhip_create_farrow_rates: the same call over the one polynomial bank)
+    if (farrow) {
+        fa.x = x; fa.y = y; fa.hist = a.hist; fa.pnfb = f->d_pnfb;
+        fa.n_idx = sa.n_idx; fa.acc = sa.acc;
+        fa.x_stride = x_stride; fa.y_stride = y_stride; fa.x_len = x_len; fa.n_out = bound;
+        fa.T = a.T; fa.H = a.H; fa.polyorder = static_cast<int>(f->polyorder);
+        fa.tap_f32 = !dtype_is_f64(f->th); fa.nch = a.nch;
+        fa.seam_below = a.T;        // every call starts a filt! (Filters.jl:819): a rates call is never a continuation piece
+        fa.dyn = nullptr;
+        fa.fold = a.fold;
+    }
     const RatesArgs ra{f->d_rrec, bound};
     const TypeKey tk = type_key(f);
     const bool fused = f->numerics == MRHIP_NUMERICS_FUSED;
@@ -2276,7 +2336,10 @@ int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64
     size_t lds = 0;
     long long tiled_grid = 0;
     bool tiled = false;
-    if (bound > 0 && !f->force_generic) {
+    if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
+        tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
+        if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
+    } else if (bound > 0 && !f->force_generic) {
         const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
         tiled = plan_arb_rates_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
         if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
@@ -2285,7 +2348,9 @@ int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64
     if (int rc = timing_mark(f, stream)) return rc;
     MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
     if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
-        if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
+        if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
+        else if (farrow) MRHIP_CHECK_HIP(launch_farrow_rates_generic(tk, fused, fa, ra, stream, &f->last_kernel));
+        else if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
         else MRHIP_CHECK_HIP(launch_arb_rates_generic(tk, fused, a, ra, stream, &f->last_kernel));
         if (f->H > 0) f->hist_cur = hist_next;
     }
@@ -2295,7 +2360,7 @@ int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64
 int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
 {
     if (!f || !out) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
-    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_get_channel_states takes a filter of mrhip_create_arbitrary_rates");
+    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_get_channel_states takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates");
     DeviceGuard guard(f->device);
     if (int rc = drain_filter(f)) return rc;          // the records are written by the filter's own last call
     std::vector<RateChannel> v(static_cast<size_t>(f->nch));
@@ -2317,7 +2382,7 @@ int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
 int mrhip_set_channel_states(mrhip_filter *f, const int64_t *inputDeficit, const double *phiAccumulator)
 {
     if (!f || !inputDeficit || !phiAccumulator) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
-    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_states takes a filter of mrhip_create_arbitrary_rates");
+    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_states takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates");
     for (int64_t c = 0; c < f->nch; ++c) {
         if (inputDeficit[c] < 1) return fail(MRHIP_ERR_INVALID_ARG, "inputDeficit must be >= 1");
         if (!(phiAccumulator[c] >= 1.0) || !(phiAccumulator[c] < static_cast<double>(f->Nphi) + 1.0))
@@ -2332,6 +2397,28 @@ int mrhip_set_channel_states(mrhip_filter *f, const int64_t *inputDeficit, const
     MRHIP_CHECK_HIP(hipMemcpy(v.data(), f->d_rrec, v.size() * sizeof(RateChannel), hipMemcpyDeviceToHost));
     for (size_t c = 0; c < v.size(); ++c) { v[c].inputDeficit = inputDeficit[c]; v[c].acc = phiAccumulator[c]; v[c].error = 0; }
     MRHIP_CHECK_HIP(hipMemcpy(f->d_rrec, v.data(), v.size() * sizeof(RateChannel), hipMemcpyHostToDevice));
+    return MRHIP_OK;
+}
+
+// The rates of a filter with per-channel rates, changed between calls: rate and delta = N𝜙 / rate of every record (Filters.jl:113, :143);
+// accumulator, inputDeficit, history and taps stay.  f->rate (mrhip_outputlength_bound) becomes the new largest rate, h_rates (the
+// tiled kernel's plan) holds the new ones; a later call that outgrows the schedule buffers reallocates by mrhip_filt_device_rates' rule.
+int mrhip_set_channel_rates(mrhip_filter *f, const double *rates)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
+    if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_rates takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates");
+    double rate_max = 0.0;
+    if (int rc = check_channel_rates(rates, f->nch, &rate_max)) return rc;
+    DeviceGuard guard(f->device);
+    // behind the calls already enqueued, as mrhip_set_channel_states: wait for them, then write (the copies are complete on return)
+    if (int rc = drain_filter(f)) return rc;
+    std::vector<RateChannel> v(static_cast<size_t>(f->nch));
+    MRHIP_CHECK_HIP(hipMemcpy(v.data(), f->d_rrec, v.size() * sizeof(RateChannel), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < v.size(); ++c) { v[c].rate = rates[c]; v[c].delta = static_cast<double>(f->Nphi) / rates[c]; }
+    MRHIP_CHECK_HIP(hipMemcpy(f->d_rrec, v.data(), v.size() * sizeof(RateChannel), hipMemcpyHostToDevice));
+    f->h_rates.assign(rates, rates + f->nch);
+    f->rate = rate_max;
+    f->delta = static_cast<double>(f->Nphi) / rate_max;
     return MRHIP_OK;
 }
 

@@ -344,6 +344,41 @@ bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, 
     return true;
 }
 
+// farrow_rates_multi_kernel (FIRFarrow with per-channel RATES, kernels_rates_farrow.hip): no LDS -- the one polynomial bank is read as
+// scalar operands, the windows from global memory -- so the plan is the tiling alone: a tile is kFarrowRatesOPL consecutive runs of
+// kVariantThreads outputs of one channel, one channel a lane (cpl = 1), and the tiling goes by n_out, the call's bound (the counts are
+// on the device; the kernel skips the tiles and the slots at or behind a channel's count).  The default rule takes the calls the
+// measured rows cover (profiles/r10/farrow_rates.txt): the multi kernel beat the universal one by more than the
+// spread of the repeats in both runs at 4096 ch x 1e4 (90 112 tiles of 22 a channel: 2.722 against 2.856 ms and 2.703 against 2.843,
+// spreads <= 0.05), and did not at 256 ch x 1e5 (56 320 tiles of 220 a channel: 21.86 against 21.83 ms and 21.85 against 21.81) nor at
+// 64 ch x 1e6 (140 672 tiles of 2198 a channel: 508.5 against 519.0 ms with spreads of 33 and 38) -- there the serial walk is the call.
+// So: from kFarrowRatesMultiMinTiles tiles, up to kFarrowRatesMultiMaxPerChannel tiles a channel; every other call stays on the
+// universal kernel unless MRHIP_FARROW_RATES_MULTI=1 selects the multi kernel.  As for plan_arb_rates_tiled both limits are GUARDS ON
+// UNMEASURED GROUND, not causes.  The kernel trace of the same file says where the gain is: alone, the multi kernel took 0.584 ms
+// against the universal one's 0.745 in the first row (8 taps per phase) and was level with it in the other two (32 taps per phase: 2.94
+// against 2.80 ms in the longest launches), where the walk is 95 % and more of the call anyway.
+constexpr long long kFarrowRatesMultiMinTiles = 90112, kFarrowRatesMultiMaxPerChannel = 22;
+bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int /*num_cus*/, int mode, ArbTileArgs *out)
+{
+    if (mode == 0 || tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || a.nch < 1) return false;
+    ArbTileArgs ta{};
+    ta.cpl = 1;
+    ta.tile_out = static_cast<long long>(kFarrowRatesOPL) * kVariantThreads;
+    ta.tiles_per_channel = (a.n_out + ta.tile_out - 1) / ta.tile_out;
+    ta.total_tiles = ta.tiles_per_channel * a.nch;
+    if (mode != 1 && (ta.total_tiles < kFarrowRatesMultiMinTiles || ta.tiles_per_channel > kFarrowRatesMultiMaxPerChannel)) return false;
+    *out = ta;
+    return true;
+}
+
+// its persistent grid: what the chip holds, no more workgroups than tiles, at least one; a test's replacement (MRHIP_FARROW_RATES_GRID)
+// may also ask for more workgroups than tiles (their runs are empty)
+long long farrow_rates_multi_grid(long long total_tiles, long long chip_grid, int grid_fixed)
+{
+    if (grid_fixed > 0) return std::min<long long>(grid_fixed, 65535);
+    return std::max<long long>(std::min<long long>(chip_grid, total_tiles), 1);
+}
+
 // arb_bank_ctaps_tiled_kernel: both banks of ONE channel as (re, im) pairs of R (column pitch T + 1) plus the sample tile fit LDS at
 // two workgroups a CU (78 KiB a workgroup, as for plan_arb_bank_tiled); one channel a lane (cpl = 1); the span follows from the rate
 // and is cut only when the kernel is forced.  The default rule: the tiled kernel was faster than the universal one by far more than

@@ -1,6 +1,7 @@
 // rates_arb.h -- FIRArbitrary with PER-CHANNEL RATES (mrhip_create_arbitrary_rates; include/multirate_hip.h, "Per-channel rates for
-// FIRArbitrary"): what api.hip, host_logic.cpp (the tiled kernel's plan) and kernels_rates_arb.hip (the three kernels) share.  Kept out
-// of mrhip_internal.h so that only those units depend on it.
+// FIRArbitrary"): what api.hip, host_logic.cpp (the tiled kernel's plan) and kernels_rates_arb.hip (the three kernels) share; and, below,
+// FIRFarrow with per-channel rates (mrhip_create_farrow_rates; kernels_rates_farrow.hip), which uses the same records and schedule
+// kernel.  Kept out of mrhip_internal.h so that only those units depend on it.
 #pragma once
 
 #include "mrhip_internal.h"
@@ -47,5 +48,39 @@ hipError_t launch_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbArgs &
                                   long long grid, hipStream_t s, const char **kname);
 // host_logic.cpp: the switch value passed in (MRHIP_ARB_RATES_TILED: 0 never, 1 wherever the plan fits, -1 the default rule)
 bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, int mode, ArbTileArgs *out, size_t *lds);
+
+// ---- FIRFarrow with per-channel rates (mrhip_create_farrow_rates; include/multirate_hip.h, "Per-channel rates for FIRFarrow") --------
+// The schedule kernel, the records, the reset kernel and RatesArgs above serve it unchanged: update() of FIRFarrow (Filters.jl:780-786)
+// is FIRArbitrary's recurrence on the same Float64 quantity, and the constructor state (:141-144) is the one rates_reset_kernel writes
+// (𝜙Idx = 1.0 is the accumulator, inputDeficit = xIdx = 1).  RatesArgs stands beside FarrowArgs (n_idx / acc: the bases of the slices,
+// n_out: the call's bound, dyn NULL, seam_below = T, pnfb: the ONE bank [T][polyorder+1]).
+//
+// farrow_rates_multi_kernel: a lane owns kFarrowRatesOPL outputs of one channel, output `tid` of as many consecutive runs of
+// kVariantThreads outputs; a tile is those runs (tile_out = kFarrowRatesOPL * kVariantThreads outputs of one channel).
+constexpr int kFarrowRatesOPL = 4;
+// the slots of lane `tid` in the tile that starts at output k0 that lie in front of the channel's count: slot j is output
+// k0 + tid + j * kVariantThreads; 0 ... kFarrowRatesOPL (the live slots are the first ones)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int farrow_rates_live_slots(long long k0, int tid, long long count)
+{
+    const long long left = count - k0 - tid;                     // outputs from the lane's first slot to the count
+    if (left <= 0) return 0;
+    const long long slots = (left + kVariantThreads - 1) / kVariantThreads;
+    return slots < kFarrowRatesOPL ? static_cast<int>(slots) : kFarrowRatesOPL;
+}
+
+// kernels_rates_farrow.hip
+hipError_t launch_farrow_rates_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
+bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, ArbTileArgs *out);      // (reads MRHIP_FARROW_RATES_MULTI)
+// the multi kernel's persistent grid (occupancy query): everything about its launch that can fail ahead of the launch
+hipError_t prepare_farrow_rates_multi(const TypeKey &tk, bool fused, const ArbTileArgs &ta, int num_cus, long long *grid);
+hipError_t launch_farrow_rates_multi(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, const ArbTileArgs &ta,
+                                     long long grid, hipStream_t s, const char **kname);
+// host_logic.cpp: the switch value passed in (MRHIP_FARROW_RATES_MULTI: 0 never, 1 every call, -1 the default rule), and the grid from
+// what the chip holds (chip_grid), the tile count and a test's replacement (grid_fixed > 0: also more workgroups than tiles)
+bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
+long long farrow_rates_multi_grid(long long total_tiles, long long chip_grid, int grid_fixed);
 
 }  // namespace mrhip

@@ -92,6 +92,9 @@ ABI = [
     ("mrhip_filt_device_rates", _i, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     ("mrhip_get_channel_states", _i, [_vp, _vp]),
     ("mrhip_set_channel_states", _i, [_vp, _vp, _vp]),
+    ("mrhip_create_farrow_rates", _i, [_vp, _i64, _i, _vp, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_create_farrow_rates_pnfb", _i, [_vp, _i64, _i, _vp, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    ("mrhip_set_channel_rates", _i, [_vp, _vp]),
     ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_bank", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_create_farrow_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
@@ -276,7 +279,7 @@ class FIRFilter:
         self._nch = None
         self.polyorder = None
         self._pnfb_in = None
-        self._rates = None                # per-channel rates (FIRFilter.per_channel_rates): Float64, one per channel; self.rate is the largest
+        self._rates = None                # per-channel rates (FIRFilter.per_channel_rates, .per_channel_rates_farrow): Float64, one per channel; self.rate is the largest
         self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow, .per_channel_complex_taps_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
@@ -437,13 +440,44 @@ class FIRFilter:
         h = np.asarray(h)
         if h.dtype.kind == "c":
             raise MultirateHIPError(5, "per_channel_rates takes Float32/Float64 taps (complex taps with per-channel rates are left out)")
+        r = cls._checked_rates(rates, "per_channel_rates")
+        f = cls(h, float(r.max()), int(Nphi), device=device, numerics=numerics)
+        f._rates = r
+        return f
+
+    @staticmethod
+    def _checked_rates(rates, who):
+        """one finite rate > 0 per channel, at least one, as a Float64 vector (the checks the library repeats)"""
         r = np.atleast_1d(np.asarray(rates, dtype=np.float64))
         if r.ndim != 1 or r.size < 1:
-            raise MultirateHIPError(1, f"per_channel_rates takes one rate per channel, at least one; got shape {r.shape}")
+            raise MultirateHIPError(1, f"{who} takes one rate per channel, at least one; got shape {r.shape}")
         if not np.all(np.isfinite(r)) or not np.all(r > 0.0):
             raise MultirateHIPError(1, "rate must be greater than 0 (every channel's)")      # Filters.jl:184
-        f = cls(h, float(r.max()), int(Nphi), device=device, numerics=numerics)
-        f._rates = np.ascontiguousarray(r).copy()
+        return np.ascontiguousarray(r).copy()
+
+    @classmethod
+    def per_channel_rates_farrow(cls, h, rates, Nphi: int = 32, polyorder=4, *, pnfb=None, device: int = 0, numerics: int = NUMERICS_STRICT):
+        """One FIRFilter(h, rates[c]::Float, N𝜙, polyorder) per channel behind one filter object: FIRFarrow with per-channel RATES
+        (the same users as ``per_channel_rates``; FIRFarrow is the reference's kernel for a continuously variable rate).  ``h``: one
+        Float32 or Float64 tap vector, shared -- so ONE polynomial bank, fitted once, or ``pnfb``: a caller-fitted bank of shape
+        (tapsPer𝜙, polyorder+1), ascending powers; ``rates``: one rate > 0 per channel.  Every channel has its own phase schedule,
+        state and output count; channel c is bit for bit ``FIRFilter(h, rates[c], Nphi, polyorder)`` fed ``x[c]``, under STRICT and
+        FUSED (include/multirate_hip.h: per-channel rates for FIRFarrow).  ``filt``, ``filt_into``, ``channel_states``,
+        ``set_channel_states``, ``set_channel_rates``, ``outputlength_bound``, ``reset`` and ``history`` behave as on the filter of
+        ``per_channel_rates``; ``pnfb()`` and ``tapsforphase`` as on a one-channel FIRFarrow filter.  The device object is created by
+        ``mrhip_create_farrow_rates`` / ``mrhip_create_farrow_rates_pnfb``."""
+        h = np.asarray(h)
+        if h.dtype.kind == "c":
+            raise MultirateHIPError(5, "per_channel_rates_farrow takes Float32/Float64 taps (complex taps with per-channel rates are left out)")
+        if polyorder is None:
+            raise MultirateHIPError(1, "per_channel_rates_farrow takes a polyorder (without one: FIRFilter.per_channel_rates)")
+        r = cls._checked_rates(rates, "per_channel_rates_farrow")
+        if not 0 <= int(polyorder) <= 32 or (pnfb is None and int(polyorder) + 1 > int(Nphi)):
+            raise MultirateHIPError(1, "polyorder must be in 0..min(32, Nphi-1)")
+        f = cls(h, float(r.max()), int(Nphi), int(polyorder), device=device, numerics=numerics, pnfb=pnfb)
+        if f._pnfb_in is not None and f._pnfb_in.shape != (f.tapsPerPhi, f.polyorder + 1):
+            raise MultirateHIPError(1, f"pnfb must have shape (tapsPerPhi, polyorder+1) = {(f.tapsPerPhi, f.polyorder + 1)}")
+        f._rates = r
         return f
 
     @classmethod
@@ -535,7 +569,13 @@ class FIRFilter:
             raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
         if self._rates is not None and nch != len(self._rates):
             raise MultirateHIPError(1, f"a filter of {len(self._rates)} per-channel rates binds to exactly that many channels; got {nch}")
-        if self._rates is not None:
+        if self._rates is not None and self.kind == FARROW and self._pnfb_in is not None:
+            rc = self._lib.mrhip_create_farrow_rates_pnfb(_ptr(self._pnfb_in), len(self.h), _NP2DT[self.h.dtype], _ptr(self._rates), self.Nphi,
+                                                          self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self._rates is not None and self.kind == FARROW:
+            rc = self._lib.mrhip_create_farrow_rates(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], _ptr(self._rates), self.Nphi,
+                                                     self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
+        elif self._rates is not None:
             rc = self._lib.mrhip_create_arbitrary_rates(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], _ptr(self._rates), self.Nphi,
                                                         _NP2DT[tx], nch, self.device, C.byref(out))
         elif self._bank is not None and self.kind == ARBITRARY and self._bank.dtype.kind == "c":
@@ -864,9 +904,9 @@ class FIRFilter:
         """The per-channel states of a filter with per-channel rates (``mrhip_get_channel_states``; waits for the filter's stream): a list
         of ``ChannelState`` (rate, delta, phiAccumulator, alpha, phiIdx, inputDeficit, xIdx, last_count).  Unbound: constructor states."""
         if self._rates is None:
-            raise MultirateHIPError(1, "channel_states needs a filter of FIRFilter.per_channel_rates")
+            raise MultirateHIPError(1, "channel_states needs a filter of FIRFilter.per_channel_rates or FIRFilter.per_channel_rates_farrow")
         out = (ChannelState * len(self._rates))()
-        if self._handle is None:                                   # constructor state, src/Filters.jl:110-115
+        if self._handle is None:                                   # constructor state, src/Filters.jl:110-115 (FIRFarrow: 141-144)
             for c, r in enumerate(self._rates):
                 out[c] = ChannelState(float(r), self.Nphi / float(r), 1.0, 0.0, 1, 1, 1, 0)
             return list(out)
@@ -883,6 +923,20 @@ class FIRFilter:
         if d.shape != (self._nch,) or a.shape != (self._nch,):
             raise MultirateHIPError(1, f"set_channel_states takes {self._nch} inputDeficit and {self._nch} phiAccumulator values")
         _check(self._lib.mrhip_set_channel_states(self._handle, _ptr(d), _ptr(a)))
+
+    def set_channel_rates(self, rates):
+        """New per-channel rates between calls (``mrhip_set_channel_rates``; waits for the filter's stream): rate and delta of every
+        channel change, phiAccumulator, inputDeficit, history and taps stay, ``outputlength_bound`` follows the new largest rate.
+        Channel c continues bit for bit as ``FIRFilter(h, rates[c], ...)`` given its state and history would.  ``reset()`` keeps the
+        current rates.  Unbound: the filter will be created at the new rates."""
+        if self._rates is None:
+            raise MultirateHIPError(1, "set_channel_rates needs a filter of FIRFilter.per_channel_rates or FIRFilter.per_channel_rates_farrow")
+        r = self._checked_rates(rates, "set_channel_rates")
+        if r.shape != self._rates.shape:
+            raise MultirateHIPError(1, f"set_channel_rates takes {len(self._rates)} rates, one per channel; got {len(r)}")
+        if self._handle is not None:
+            _check(self._lib.mrhip_set_channel_rates(self._handle, _ptr(r)))
+        self._rates, self.rate = r, float(r.max())
 
     def outputlength_bound(self, inputlength: int) -> int:
         """The largest per-channel output count a call of ``inputlength`` samples can have whatever the stream state

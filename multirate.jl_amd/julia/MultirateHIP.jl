@@ -16,7 +16,7 @@ export FIRFilter, FIRKernel, FIRStandard, FIRDecimator, FIRInterpolator, FIRRati
        filt, filt!, taps2pfb, outputlength, inputlength, reset, nextphase, setphase, tapsforphase, tapsforphase!, polyfit,
        firdes, firprototype, kaiserlength, kaiser, FIRResponse, LOWPASS, BANDPASS, HIGHPASS, BANDSTOP,
        FilterCascade, filt_device!, filt_device_chunked!, scheduleinfo, advancestate!, ChunkRing, pushchunks!, drain, ringinfo, ShardedFIRFilter,
-       RatesFIRFilter, channelstates, setchannelstates!
+       RatesFIRFilter, channelstates, setchannelstates!, setrates!
 
 const libmr = get(ENV, "MRHIP_LIB_PATH", joinpath(@__DIR__, "..", "libmultirate_hip.so"))
 
@@ -539,6 +539,7 @@ mutable struct RatesFIRFilter{Th}
     h::Vector{Th}
     rates::Vector{Float64}
     Nphi::Int
+    polyorder::Int                  # -1: FIRArbitrary (mrhip_create_arbitrary_rates); >= 0: FIRFarrow (mrhip_create_farrow_rates)
     device::Int
     handle::Ptr{Cvoid}
     Tx::Union{DataType,Nothing}
@@ -546,7 +547,16 @@ end
 function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
-    f = RatesFIRFilter{Th}(copy(h), Vector{Float64}(rates), Nphi, device, C_NULL, nothing)
+    f = RatesFIRFilter{Th}(copy(h), Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing)
+    finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
+end
+# FIRFilter(h, rates::Vector, N𝜙, polyorder): one FIRFilter(h, rates[c], N𝜙, polyorder) -- FIRFarrow -- per channel behind one object
+# (include/multirate_hip.h, "Per-channel rates for FIRFarrow"); everything below serves it as it serves the FIRArbitrary filter.
+function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{Float32,Float64}}
+    isempty(rates) && error("one rate per channel, at least one")
+    all(r -> r > 0.0, rates) || error("rate must be greater than 0")
+    0 <= polyorder <= min(32, Nphi - 1) || error("polyorder must be in 0..min(32, Nphi-1)")
+    f = RatesFIRFilter{Th}(copy(h), Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
@@ -555,9 +565,15 @@ function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
         return f
     end
     out = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:mrhip_create_arbitrary_rates, libmr), Cint,
-                (Ptr{Cvoid}, Int64, Cint, Ptr{Cdouble}, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
-                f.h, length(f.h), dtypecode(Th), f.rates, f.Nphi, dtypecode(Tx), length(f.rates), f.device, out))
+    if f.polyorder >= 0
+        check(ccall((:mrhip_create_farrow_rates, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Ptr{Cdouble}, Int64, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, length(f.h), dtypecode(Th), f.rates, f.Nphi, f.polyorder, dtypecode(Tx), length(f.rates), f.device, out))
+    else
+        check(ccall((:mrhip_create_arbitrary_rates, libmr), Cint,
+                    (Ptr{Cvoid}, Int64, Cint, Ptr{Cdouble}, Int64, Cint, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                    f.h, length(f.h), dtypecode(Th), f.rates, f.Nphi, dtypecode(Tx), length(f.rates), f.device, out))
+    end
     f.handle, f.Tx = out[], Tx
     f
 end
@@ -581,6 +597,16 @@ end
 function setchannelstates!(f::RatesFIRFilter, inputDeficit::Vector{Int64}, phiAccumulator::Vector{Float64})
     (length(inputDeficit) == length(f.rates) && length(phiAccumulator) == length(f.rates)) || error("one value per channel")
     check(ccall((:mrhip_set_channel_states, libmr), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Cdouble}), f.handle, inputDeficit, phiAccumulator))
+    f
+end
+# new rates between calls (mrhip_set_channel_rates): every channel keeps its phase, deficit and history and continues at its new rate;
+# reset keeps the current rates.  An unbound filter is created at the new rates.
+function setrates!(f::RatesFIRFilter, rates::Vector{<:AbstractFloat})
+    length(rates) == length(f.rates) || error("one rate per channel")
+    all(r -> r > 0.0, rates) || error("rate must be greater than 0")
+    r = Vector{Float64}(rates)
+    f.handle == C_NULL || check(ccall((:mrhip_set_channel_rates, libmr), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), f.handle, r))
+    f.rates = r
     f
 end
 reset(f::RatesFIRFilter) = (f.handle == C_NULL || check(ccall((:mrhip_reset, libmr), Cint, (Ptr{Cvoid},), f.handle)); f)
