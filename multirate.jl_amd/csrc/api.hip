@@ -1,4 +1,4 @@
-// api.hip -- the extern "C" surface of libmultirate_hip.so (include/multirate_hip.h).
+// api.hip -- the extern "C" surface of libmultirate_hip.so (include/multirate_hip.h), except the constructors (create.hip).
 //
 // There is deliberately NO CPU execution path in this library: if no gfx950 device is visible
 // every constructor fails with MRHIP_ERR_NO_DEVICE.
@@ -12,6 +12,7 @@
 #include <unordered_map>
 
 #include "mrhip_filter.h"
+#include "create.h"
 #include "rates_arb.h"
 
 namespace mrhip {
@@ -59,23 +60,6 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
-namespace {
-
-// RAII: make the filter's device current for the duration of an API call, then restore.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 bool device_is_gfx950(int dev)
 {
     hipDeviceProp_t prop;
@@ -83,63 +67,15 @@ bool device_is_gfx950(int dev)
     return std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
 
+namespace {
+
 TypeKey type_key(const mrhip_filter *f)
 {
     return TypeKey{dtype_is_f64(f->tx), f->r_f64, f->nc == 2, dtype_is_complex(f->th), f->bank};
 }
 
-size_t r_size(const mrhip_filter *f) { return f->r_f64 ? 8 : 4; }
 size_t x_elt(const mrhip_filter *f) { return dtype_size(f->tx); }
 size_t y_elt(const mrhip_filter *f) { return dtype_size(f->ty); }
-
-// upload taps (tap dtype on the host) as R-typed device array; f32 -> f64 widening is exact and is
-// what Julia's promotion does on every multiply (Real*Real / Real*Complex methods).  Complex taps are
-// interleaved (re, im) pairs: the same array of scalars, widened the same way.
-// The vector sits between two runs of kTapPad zero elements: fir_stream_rt_kernel reads whole blocks of taps around the
-// ends of a window (it discards what the out-of-window ones produce) without a clamp per tap.
-int upload_taps(mrhip_filter *f, const std::vector<unsigned char> &src, void **dptr, void **alloc)
-{
-    const size_t n = src.size() / dtype_scalar_size(f->th);
-    const size_t pad = static_cast<size_t>(mrhip::kTapPad) * r_size(f);
-    const size_t bytes = std::max<size_t>(n * r_size(f), 16) + 2 * pad;
-    MRHIP_CHECK_HIP(hipMalloc(alloc, bytes));
-    MRHIP_CHECK_HIP(hipMemset(*alloc, 0, bytes));
-    *dptr = static_cast<unsigned char *>(*alloc) + pad;
-    if (f->r_f64 && !dtype_is_f64(f->th)) {
-        std::vector<double> w(n);
-        const float *s = reinterpret_cast<const float *>(src.data());
-        for (size_t i = 0; i < n; ++i) w[i] = static_cast<double>(s[i]);
-        MRHIP_CHECK_HIP(hipMemcpy(*dptr, w.data(), n * 8, hipMemcpyHostToDevice));
-    } else {
-        MRHIP_CHECK_HIP(hipMemcpy(*dptr, src.data(), src.size(), hipMemcpyHostToDevice));
-    }
-    return MRHIP_OK;
-}
-
-int alloc_common(mrhip_filter *f)
-{
-    const size_t hbytes = std::max<size_t>(static_cast<size_t>(f->nch) * f->H * x_elt(f), 16);
-    // Every later launch goes to a non-blocking stream, which the null stream's memsets are not ordered with: zero
-    // on the filter's own stream and wait for it here (construction may block; nothing else in the library does).
-    MRHIP_CHECK_HIP(hipStreamCreateWithFlags(&f->own_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 3; ++i) {
-        MRHIP_CHECK_HIP(hipMalloc(&f->d_hist[i], hbytes));
-        MRHIP_CHECK_HIP(hipMemsetAsync(f->d_hist[i], 0, hbytes, f->own_stream));   // history = zeros(historyLen), Filters.jl:177
-    }
-    MRHIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&f->d_counters), mrhip::kCounterBytes));
-    MRHIP_CHECK_HIP(hipMemsetAsync(f->d_counters, 0, mrhip::kCounterBytes, f->own_stream));
-    MRHIP_CHECK_HIP(hipStreamSynchronize(f->own_stream));
-    {
-        hipDeviceProp_t prop;
-        MRHIP_CHECK_HIP(hipGetDeviceProperties(&prop, f->device));
-        f->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        const char *fg = std::getenv("MRHIP_FORCE_GENERIC");
-        f->force_generic = fg && fg[0] == '1';
-    }
-    MRHIP_CHECK_HIP(hipEventCreateWithFlags(&f->sched_copied, hipEventDisableTiming));
-    MRHIP_CHECK_HIP(hipEventCreateWithFlags(&f->xs_event, hipEventDisableTiming));
-    return rec_alloc(f);              // the stream state on the device (stream_state.hip), constructor state
-}
 
 // Is `stream` being captured into a HIP graph?  (The legacy null stream cannot be; while another stream captures in
 // global mode the query itself fails for it, which means "no".)
@@ -198,26 +134,6 @@ int drain_filter(mrhip_filter *f)
         (void)hipGetLastError();
         MRHIP_CHECK_HIP(device_sync_relaxed());
     }
-    return MRHIP_OK;
-}
-
-int check_create_args(const void *h, int64_t hLen, int th, int tx, int64_t nch, int device, mrhip_filter **out, bool complex_taps_ok = false)
-{
-    if (!out) return fail(MRHIP_ERR_INVALID_ARG, "out is NULL");
-    *out = nullptr;
-    if (!h || hLen < 1) return fail(MRHIP_ERR_INVALID_ARG, "h must hold at least one tap");
-    if (th < MRHIP_F32 || th > MRHIP_C128) return fail(MRHIP_ERR_INVALID_ARG, "bad tap dtype");
-    if (dtype_is_complex(th) && !complex_taps_ok)
-        return fail(MRHIP_ERR_UNSUPPORTED, "complex taps are supported by the rational family only (mrhip_create_rational: FIRStandard, FIRDecimator, "
-                                           "FIRInterpolator, FIRRational); FIRArbitrary and FIRFarrow take Float32 or Float64 taps");
-    if (tx < MRHIP_F32 || tx > MRHIP_C128) return fail(MRHIP_ERR_INVALID_ARG, "bad sample dtype");
-    if (nch < 1) return fail(MRHIP_ERR_INVALID_ARG, "nchannels must be >= 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MRHIP_ERR_NO_DEVICE, "no HIP device visible; libmultirate_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(MRHIP_ERR_INVALID_ARG, "device ordinal out of range");
-    if (!device_is_gfx950(device))
-        return fail(MRHIP_ERR_NO_DEVICE, "device is not gfx950 (MI355X); kernels are built for gfx950 only");
     return MRHIP_OK;
 }
 
@@ -403,449 +319,6 @@ int mrhip_output_dtype(int th, int tx)
     const bool f64 = dtype_is_f64(th) || dtype_is_f64(tx);
     if (dtype_is_complex(tx) || dtype_is_complex(th)) return f64 ? MRHIP_C128 : MRHIP_C64;
     return f64 ? MRHIP_F64 : MRHIP_F32;
-}
-
-// FIRFilter(h, ratio), src/Filters.jl:158-180, behind its three constructors.  bank: `h` holds nch rows, every row goes through taps2pfb on
-// its own and the banks sit one after the other, [nch][Nphi][T] (upload_taps widens them exactly to R; complex taps: [nch][Nphi][T]
-// (re, im) pairs, widened as the interleaved scalars they are).
-static int create_rational_common(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
-                                  int device, bool bank, mrhip_filter **out)
-{
-    if (num < 1 || den < 1) return fail(MRHIP_ERR_INVALID_ARG, "ratio must be positive");
-    const int64_t g = std::gcd(num, den);
-    const int64_t L = num / g, M = den / g;
-    if (L > 0x7fffffff || M > 0x7fffffff || hLen > 0x7fffffff)
-        return fail(MRHIP_ERR_INVALID_ARG, "L, M and hLen must fit in 31 bits");
-
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
-    auto *f = new mrhip_filter();
-    f->th = th; f->tx = tx; f->ty = mrhip_output_dtype(th, tx);
-    f->nc = dtype_is_complex(tx) ? 2 : 1;
-    f->r_f64 = dtype_is_f64(f->ty);
-    f->nch = nch; f->hLen = hLen; f->L = L; f->M = M; f->device = device;
-    f->bank = bank;
-    const size_t es = dtype_size(th);
-    const size_t rows = bank ? static_cast<size_t>(nch) : 1;      // tap vectors in `h`, each hLen long
-
-    if (L == 1) {            // STANDARD (Filters.jl:163-165) / DECIMATOR (:166-168): h = flipud(h)
-        f->kind = M == 1 ? MRHIP_FIR_STANDARD : MRHIP_FIR_DECIMATOR;
-        f->Nphi = 1; f->T = hLen; f->H = hLen - 1;
-    } else {                 // INTERPOLATOR (:169-171) / RATIONAL (:172-174)
-        f->kind = M == 1 ? MRHIP_FIR_INTERPOLATOR : MRHIP_FIR_RATIONAL;
-        f->Nphi = L;
-        f->T = taps2pfb(h, hLen, th, L, nullptr);
-        f->H = f->T - 1;
-    }
-    {
-        const size_t bank_bytes = static_cast<size_t>(f->T) * static_cast<size_t>(f->Nphi) * es;
-        f->h_taps.resize(bank_bytes * rows);
-        for (size_t r = 0; r < rows; ++r)           // (L == 1: one column, reversed == flipud)
-            taps2pfb(static_cast<const unsigned char *>(h) + r * static_cast<size_t>(hLen) * es, hLen, th, f->Nphi, f->h_taps.data() + r * bank_bytes);
-    }
-    int rc = upload_taps(f, f->h_taps, &f->d_taps, &f->d_taps_alloc);
-    if (!rc) rc = alloc_common(f);
-    if (rc) { mrhip_destroy(f); return rc; }
-    *out = f;
-    return MRHIP_OK;
-}
-
-int mrhip_create_rational(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
-                          int device, mrhip_filter **out)
-{
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
-    return create_rational_common(h, hLen, th, num, den, tx, nch, device, false, out);
-}
-
-// One FIRFilter(h_c, ratio) per channel behind one handle (include/multirate_hip.h, "Per-channel taps"): `h` holds nch rows of hLen taps.
-int mrhip_create_rational_bank(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
-                               int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_C64 || th == MRHIP_C128)
-        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_rational_bank takes Float32 / Float64 taps (complex taps in a bank are not supported)");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    return create_rational_common(h, hLen, th, num, den, tx, nch, device, true, out);
-}
-
-// One FIRFilter(h_c::Vector{Complex}, ratio) per channel behind one handle (include/multirate_hip.h, "Per-channel complex taps"): `h`
-// holds nch rows of hLen (re, im) pairs.  taps2pfb moves whole elements of the tap type, upload_taps widens the interleaved scalars of
-// all rows exactly to R: the device holds [nch][Nphi][T] pairs of R, what kernels_bank_ctaps.hip reads.
-int mrhip_create_rational_bank_ctaps(const void *h, int64_t hLen, int th, int64_t num, int64_t den, int tx, int64_t nch,
-                                     int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_F32 || th == MRHIP_F64)
-        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_rational_bank_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_rational_bank");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
-    return create_rational_common(h, hLen, th, num, den, tx, nch, device, true, out);
-}
-
-// FIRArbitrary(h, rate, N𝜙), src/Filters.jl:105-117, behind both constructors: real taps (mrhip_create_arbitrary) and complex
-// ones (mrhip_create_arbitrary_ctaps).  The banks are held in the tap type on the host; upload_taps widens them exactly to R
-// (complex taps: as interleaved (re, im) scalars, the [Nphi][T] layout of pairs that kernels_ctaps_arb.hip reads).  bank: `h` holds
-// nch rows; every row gets its own dh and both its taps2pfb calls, and the banks sit one after the other, [nch][Nphi][T]
-// (mrhip_create_arbitrary_bank; kernels_bank_arb.hip -- with complex taps mrhip_create_arbitrary_bank_ctaps: [nch][Nphi][T] pairs,
-// kernels_bank_arb_ctaps.hip).
-static int rates_alloc(mrhip_filter *f);
-// rates != NULL (mrhip_create_arbitrary_rates): nch rates behind the one bank; `rate` is the largest of them.
-static int create_arbitrary_common(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                                   int device, bool bank, mrhip_filter **out, const double *rates = nullptr)
-{
-    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
-    auto *f = new mrhip_filter();
-    f->kind = MRHIP_FIR_ARBITRARY;
-    f->th = th; f->tx = tx; f->ty = mrhip_output_dtype(th, tx);
-    f->nc = dtype_is_complex(tx) ? 2 : 1;
-    f->r_f64 = dtype_is_f64(f->ty);
-    f->nch = nch; f->hLen = hLen; f->L = Nphi; f->M = 1; f->Nphi = Nphi; f->device = device;
-    f->rate = rate;
-    f->delta = static_cast<double>(Nphi) / rate;   // Δ = N𝜙/rate, Filters.jl:113
-    f->bank = bank;
-    if (rates) { f->rates = true; f->h_rates.assign(rates, rates + nch); }
-    const size_t es = dtype_size(th);
-    const size_t rows = bank ? static_cast<size_t>(nch) : 1;      // tap vectors in `h`, each hLen long
-
-    f->T = taps2pfb(h, hLen, th, Nphi, nullptr);
-    f->H = f->T - 1;
-    const size_t bank_bytes = static_cast<size_t>(f->T) * Nphi * es;
-    f->h_taps.resize(bank_bytes * rows);
-    f->h_dtaps.resize(bank_bytes * rows);
-    std::vector<unsigned char> dh(static_cast<size_t>(hLen) * es);
-    for (size_t r = 0; r < rows; ++r) {
-        const unsigned char *hr = static_cast<const unsigned char *>(h) + r * static_cast<size_t>(hLen) * es;
-        // dh = [diff(h), 0] in the tap type (Filters.jl:106)
-        std::fill(dh.begin(), dh.end(), static_cast<unsigned char>(0));
-        arbitrary_dh(hr, hLen, th, dh.data());
-        taps2pfb(hr, hLen, th, Nphi, f->h_taps.data() + r * bank_bytes);
-        taps2pfb(dh.data(), hLen, th, Nphi, f->h_dtaps.data() + r * bank_bytes);
-    }
-
-    int rc = upload_taps(f, f->h_taps, &f->d_taps, &f->d_taps_alloc);
-    if (!rc) rc = upload_taps(f, f->h_dtaps, &f->d_dtaps, &f->d_dtaps_alloc);
-    if (!rc) rc = alloc_common(f);
-    if (!rc && f->rates) rc = rates_alloc(f);
-    if (rc) { mrhip_destroy(f); return rc; }
-    if (!f->rates) sched_configure(f);        // (per-channel rates: the serial walk of kernels_rates_arb.hip, none of the schedule machinery)
-    *out = f;
-    return MRHIP_OK;
-}
-
-int mrhip_create_arbitrary(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                           int device, mrhip_filter **out)
-{
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, false, out);
-}
-
-int mrhip_create_arbitrary_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                                 int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_F32 || th == MRHIP_F64)
-        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_arbitrary_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_arbitrary");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
-    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, false, out);
-}
-
-// One FIRFilter(h_c, rate, N𝜙) per channel behind one handle (include/multirate_hip.h, "Per-channel taps for FIRArbitrary"): `h`
-// holds nch rows of hLen taps.
-int mrhip_create_arbitrary_bank(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                                int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_C64 || th == MRHIP_C128)
-        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_arbitrary_bank takes Float32 / Float64 taps (complex taps in a FIRArbitrary bank are left out)");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, true, out);
-}
-
-// The same with COMPLEX taps (include/multirate_hip.h, "Per-channel complex taps for FIRArbitrary"): `h` holds nch rows of hLen
-// interleaved (re, im) pairs; every row gets its own dh per component and both its taps2pfb calls, upload_taps widens the scalars
-// exactly to R: the device holds pfb and dpfb as [nch][Nphi][T] pairs of R, what kernels_bank_arb_ctaps.hip reads.
-int mrhip_create_arbitrary_bank_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int tx, int64_t nch,
-                                      int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_F32 || th == MRHIP_F64)
-        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_arbitrary_bank_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_arbitrary_bank");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
-    return create_arbitrary_common(h, hLen, th, rate, Nphi, tx, nch, device, true, out);
-}
-
-// One FIRFilter(h, rates[c], N𝜙) per channel behind one handle (include/multirate_hip.h, "Per-channel rates for FIRArbitrary"): the
-// channels share pfb and dpfb; each has a record on the device (RateChannel, rates_arb.h) in its constructor state (Filters.jl:110-115).
-static int rates_alloc(mrhip_filter *f)
-{
-    std::vector<RateChannel> v(static_cast<size_t>(f->nch));
-    for (int64_t c = 0; c < f->nch; ++c) {
-        RateChannel &r = v[static_cast<size_t>(c)];
-        r = RateChannel{};
-        r.rate = f->h_rates[static_cast<size_t>(c)];
-        r.delta = static_cast<double>(f->Nphi) / r.rate;           // Δ = N𝜙/rate, Filters.jl:113
-        r.acc = 1.0; r.inputDeficit = 1; r.xIdx = 1;
-    }
-    MRHIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&f->d_rrec), v.size() * sizeof(RateChannel)));
-    MRHIP_CHECK_HIP(hipMemcpy(f->d_rrec, v.data(), v.size() * sizeof(RateChannel), hipMemcpyHostToDevice));
-    return MRHIP_OK;
-}
-
-// the rate checks of the constructors with per-channel rates and of mrhip_set_channel_rates; *rate_max: the largest rate
-static int check_channel_rates(const double *rates, int64_t nch, double *rate_max)
-{
-    if (!rates) return fail(MRHIP_ERR_INVALID_ARG, "rates is NULL");
-    *rate_max = 0.0;
-    for (int64_t c = 0; c < nch; ++c) {
-        if (!(rates[c] > 0.0) || !std::isfinite(rates[c])) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0 (every channel's, and finite)");
-        // (update() advances xIdx by about 1/rate a step; the walk carries that advance in 32 bits: sched_step.h)
-        if (rates[c] < 1.0 / static_cast<double>(1LL << 30)) return fail(MRHIP_ERR_UNSUPPORTED, "a per-channel rate below 2^-30");
-        *rate_max = std::max(*rate_max, rates[c]);
-    }
-    return MRHIP_OK;
-}
-
-int mrhip_create_arbitrary_rates(const void *h, int64_t hLen, int th, const double *rates, int64_t Nphi, int tx, int64_t nch,
-                                 int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_C64 || th == MRHIP_C128)
-        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_arbitrary_rates takes Float32 / Float64 taps (complex taps with per-channel rates are left out)");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    double rate_max = 0.0;
-    if (int rc = check_channel_rates(rates, nch, &rate_max)) return rc;
-    return create_arbitrary_common(h, hLen, th, rate_max, Nphi, tx, nch, device, false, out, rates);
-}
-
-// FIRFarrow(h, rate, N𝜙, polyorder), src/Filters.jl:138-147, behind all four constructors.  pnfb_in: [T][polyorder+1] coefficients,
-// ascending powers -- scalars for real taps, (re, im) pairs for complex ones (the layout kernels_ctaps_farrow.hip reads).  bank: pnfb_in
-// holds nch such banks one after the other, [nch][T][polyorder+1] (mrhip_create_farrow_bank; kernels_bank_farrow.hip -- with complex taps
-// mrhip_create_farrow_bank_ctaps: pairs, kernels_bank_farrow_ctaps.hip), and the degree-major copy for farrow_wave_kernel is never built.
-// rates != NULL (mrhip_create_farrow_rates, mrhip_create_farrow_rates_pnfb): nch rates behind the one bank; `rate` is the largest of them.
-static int create_farrow_common(const std::vector<double> &pnfb_in, int64_t hLen, int th, double rate, int64_t Nphi,
-                                int64_t polyorder, int tx, int64_t nch, int device, bool bank, mrhip_filter **out, const double *rates = nullptr)
-{
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
-    auto *f = new mrhip_filter();
-    f->kind = MRHIP_FIR_FARROW;
-    f->th = th; f->tx = tx; f->ty = mrhip_output_dtype(th, tx);
-    f->nc = dtype_is_complex(tx) ? 2 : 1;
-    f->r_f64 = dtype_is_f64(f->ty);
-    f->nch = nch; f->hLen = hLen; f->L = Nphi; f->M = 1; f->Nphi = Nphi; f->device = device;
-    f->rate = rate;
-    f->delta = static_cast<double>(Nphi) / rate;   // Δ = N𝜙/rate, Filters.jl:143
-    f->polyorder = polyorder;
-    f->bank = bank;
-    if (rates) { f->rates = true; f->h_rates.assign(rates, rates + nch); }
-    f->T = (hLen + Nphi - 1) / Nphi;
-    f->H = f->T - 1;
-    f->h_pnfb = pnfb_in;
-    // Poly{T} storage: coefficients live in the tap type (Filters.jl:313 Array(Poly{T}, ...)), complex ones per component
-    if (!dtype_is_f64(th)) for (double &c : f->h_pnfb) c = static_cast<double>(static_cast<float>(c));
-    int rc = MRHIP_OK;
-    if (hipMalloc(reinterpret_cast<void **>(&f->d_pnfb), f->h_pnfb.size() * sizeof(double)) != hipSuccess ||
-        hipMemcpy(f->d_pnfb, f->h_pnfb.data(), f->h_pnfb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(MRHIP_ERR_HIP, "uploading the polynomial filter bank failed");
-    if (!rc && f->T <= 32 && !dtype_is_complex(th) && !bank && !rates) {   // the same bank degree-major, padded to 32 taps with zeros (kernels_farrow_wave.hip)
-        std::vector<double> t(static_cast<size_t>(polyorder + 1) * 32, 0.0);
-        for (int64_t i = 0; i < f->T; ++i)
-            for (int64_t j = 0; j <= polyorder; ++j) t[static_cast<size_t>(j) * 32 + i] = f->h_pnfb[static_cast<size_t>(i) * (polyorder + 1) + j];
-        if (hipMalloc(reinterpret_cast<void **>(&f->d_pnfb_t), t.size() * sizeof(double)) != hipSuccess ||
-            hipMemcpy(f->d_pnfb_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(MRHIP_ERR_HIP, "uploading the polynomial filter bank failed");
-    }
-    if (!rc) rc = alloc_common(f);
-    if (!rc && f->rates) rc = rates_alloc(f);
-    if (rc) { mrhip_destroy(f); return rc; }
-    if (!f->rates) sched_configure(f);        // (per-channel rates: the serial walk of kernels_rates_arb.hip, none of the schedule machinery)
-    *out = f;
-    return MRHIP_OK;
-}
-
-// pfb = taps2pfb(h, Nphi); one polynomial per ROW (Filters.jl:139-140, :315-318): the fit of one tap vector `h` into pn, [T][polyorder+1].
-// false: the fit is rank deficient.
-static bool farrow_fit(const void *h, int64_t hLen, int th, int64_t Nphi, int64_t polyorder, double *pn)
-{
-    const size_t es = dtype_scalar_size(th);
-    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
-    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
-    taps2pfb(h, hLen, th, Nphi, pfb.data());
-    std::vector<double> row(static_cast<size_t>(Nphi));
-    for (int64_t i = 0; i < T; ++i) {
-        for (int64_t c = 0; c < Nphi; ++c)          // element (row i, column c) of the column-major bank
-            row[static_cast<size_t>(c)] = th == MRHIP_F32 ? static_cast<double>(reinterpret_cast<const float *>(pfb.data())[c * T + i])
-                                                          : reinterpret_cast<const double *>(pfb.data())[c * T + i];
-        if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), &pn[static_cast<size_t>(i) * (polyorder + 1)])) return false;
-    }
-    return true;
-}
-
-// The same for one COMPLEX tap vector `h` (hLen (re, im) pairs) into pn, [T][polyorder+1] pairs.  The Vandermonde matrix of the fit is
-// real, so the least-squares fit of a complex row is the fit of its real parts and the fit of its imaginary parts.
-static bool farrow_fit_ctaps(const void *h, int64_t hLen, int th, int64_t Nphi, int64_t polyorder, double *pn)
-{
-    const size_t es = dtype_size(th);
-    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
-    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
-    taps2pfb(h, hLen, th, Nphi, pfb.data());                // column-major T x Nphi of (re, im) pairs
-    const size_t np = static_cast<size_t>(polyorder + 1);
-    std::vector<double> row(static_cast<size_t>(Nphi)), fit(np);
-    for (int64_t i = 0; i < T; ++i)
-        for (int comp = 0; comp < 2; ++comp) {
-            for (int64_t c = 0; c < Nphi; ++c) {
-                const size_t e = static_cast<size_t>(c * T + i) * 2 + comp;
-                row[static_cast<size_t>(c)] = dtype_is_f64(th) ? reinterpret_cast<const double *>(pfb.data())[e]
-                                                               : static_cast<double>(reinterpret_cast<const float *>(pfb.data())[e]);
-            }
-            if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), fit.data())) return false;
-            for (size_t j = 0; j < np; ++j) pn[(static_cast<size_t>(i) * np + j) * 2 + comp] = fit[j];
-        }
-    return true;
-}
-
-int mrhip_create_farrow(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
-                        int64_t nch, int device, mrhip_filter **out)
-{
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
-        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    std::vector<double> pn(static_cast<size_t>(T) * (polyorder + 1));
-    if (!farrow_fit(h, hLen, th, Nphi, polyorder, pn.data())) return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
-}
-
-// One FIRFilter(h_c, rate, N𝜙, polyorder) per channel behind one handle (include/multirate_hip.h, "Per-channel taps for FIRFarrow"): `h`
-// holds nch rows of hLen taps; every row goes through taps2pfb and the per-row fit on its own.
-int mrhip_create_farrow_bank(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
-                             int64_t nch, int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_C64 || th == MRHIP_C128)
-        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_bank takes Float32 / Float64 taps (complex taps in a FIRFarrow bank are left out of "
-                                           "this entry point: mrhip_create_farrow_bank_ctaps)");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
-        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    const size_t bank_elems = static_cast<size_t>(T) * (polyorder + 1), es = dtype_scalar_size(th);
-    std::vector<double> pn(bank_elems * static_cast<size_t>(nch));
-    for (int64_t r = 0; r < nch; ++r)
-        if (!farrow_fit(static_cast<const unsigned char *>(h) + static_cast<size_t>(r) * hLen * es, hLen, th, Nphi, polyorder, &pn[r * bank_elems]))
-            return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, true, out);
-}
-
-int mrhip_create_farrow_pnfb(const double *pnfb, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder,
-                             int tx, int64_t nch, int device, mrhip_filter **out)
-{
-    if (int rc = check_create_args(pnfb, hLen, th, tx, nch, device, out)) return rc;
-    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32) return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1));
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
-}
-
-// One FIRFilter(h, rates[c], N𝜙, polyorder) per channel behind one handle (include/multirate_hip.h, "Per-channel rates for FIRFarrow"):
-// the channels share the ONE polynomial bank, fitted once by farrow_fit; each has a record on the device (RateChannel, rates_arb.h) in
-// its constructor state (Filters.jl:141-144: the state rates_alloc and rates_reset_kernel write).
-int mrhip_create_farrow_rates(const void *h, int64_t hLen, int th, const double *rates, int64_t Nphi, int64_t polyorder, int tx,
-                              int64_t nch, int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_C64 || th == MRHIP_C128)
-        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_rates takes Float32 / Float64 taps (complex taps with per-channel rates are left out)");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out)) return rc;
-    double rate_max = 0.0;
-    if (int rc = check_channel_rates(rates, nch, &rate_max)) return rc;
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
-        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    std::vector<double> pn(static_cast<size_t>(T) * (polyorder + 1));
-    if (!farrow_fit(h, hLen, th, Nphi, polyorder, pn.data())) return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
-    return create_farrow_common(pn, hLen, th, rate_max, Nphi, polyorder, tx, nch, device, false, out, rates);
-}
-
-int mrhip_create_farrow_rates_pnfb(const double *pnfb, int64_t hLen, int th, const double *rates, int64_t Nphi, int64_t polyorder,
-                                   int tx, int64_t nch, int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_C64 || th == MRHIP_C128)
-        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_create_farrow_rates_pnfb takes Float32 / Float64 taps (complex taps with per-channel rates are left out)");
-    if (int rc = check_create_args(pnfb, hLen, th, tx, nch, device, out)) return rc;
-    double rate_max = 0.0;
-    if (int rc = check_channel_rates(rates, nch, &rate_max)) return rc;
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32) return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1));
-    return create_farrow_common(pn, hLen, th, rate_max, Nphi, polyorder, tx, nch, device, false, out, rates);
-}
-
-// The same two constructors for COMPLEX taps (include/multirate_hip.h, "Complex taps", FIRFarrow part); the fit: farrow_fit_ctaps.
-int mrhip_create_farrow_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
-                              int64_t nch, int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_F32 || th == MRHIP_F64)
-        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_farrow_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_farrow");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
-    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
-        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    std::vector<double> pn(static_cast<size_t>(T) * (polyorder + 1) * 2);
-    if (!farrow_fit_ctaps(h, hLen, th, Nphi, polyorder, pn.data())) return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
-}
-
-// One FIRFilter(h_c::Vector{Complex}, rate, N𝜙, polyorder) per channel behind one handle (include/multirate_hip.h, "Per-channel complex
-// taps for FIRFarrow"): `h` holds nch rows of hLen (re, im) pairs; every row goes through taps2pfb and the per-component fit on its own.
-int mrhip_create_farrow_bank_ctaps(const void *h, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder, int tx,
-                                   int64_t nch, int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_F32 || th == MRHIP_F64)
-        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_farrow_bank_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_farrow_bank");
-    if (int rc = check_create_args(h, hLen, th, tx, nch, device, out, true)) return rc;
-    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32 || polyorder + 1 > Nphi)
-        return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    const size_t bank_scalars = static_cast<size_t>(T) * (polyorder + 1) * 2, es = dtype_size(th);
-    std::vector<double> pn(bank_scalars * static_cast<size_t>(nch));
-    for (int64_t r = 0; r < nch; ++r)
-        if (!farrow_fit_ctaps(static_cast<const unsigned char *>(h) + static_cast<size_t>(r) * hLen * es, hLen, th, Nphi, polyorder, &pn[r * bank_scalars]))
-            return fail(MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient");
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, true, out);
-}
-
-int mrhip_create_farrow_pnfb_ctaps(const double *pnfb, int64_t hLen, int th, double rate, int64_t Nphi, int64_t polyorder,
-                                   int tx, int64_t nch, int device, mrhip_filter **out)
-{
-    if (out) *out = nullptr;
-    if (th == MRHIP_F32 || th == MRHIP_F64)
-        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_create_farrow_pnfb_ctaps takes Complex64 / Complex128 taps; real taps: mrhip_create_farrow_pnfb");
-    if (int rc = check_create_args(pnfb, hLen, th, tx, nch, device, out, true)) return rc;
-    if (!(rate > 0.0)) return fail(MRHIP_ERR_INVALID_ARG, "rate must be greater than 0");
-    if (Nphi < 1 || Nphi > 0x7fffffff || hLen > 0x7fffffff) return fail(MRHIP_ERR_INVALID_ARG, "bad Nphi");
-    if (polyorder < 0 || polyorder > 32) return fail(MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32");
-    const int64_t T = (hLen + Nphi - 1) / Nphi;
-    std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(T) * (polyorder + 1) * 2);
-    return create_farrow_common(pn, hLen, th, rate, Nphi, polyorder, tx, nch, device, false, out);
 }
 
 int mrhip_polyfit(const double *y, int64_t n, int64_t polyorder, double *coef)
@@ -2408,7 +1881,7 @@ int mrhip_set_channel_rates(mrhip_filter *f, const double *rates)
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
     if (!f->rates) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_rates takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates");
     double rate_max = 0.0;
-    if (int rc = check_channel_rates(rates, f->nch, &rate_max)) return rc;
+    if (Refusal r = check_channel_rates(rates, f->nch, &rate_max)) return fail(r.status, r.message);
     DeviceGuard guard(f->device);
     // behind the calls already enqueued, as mrhip_set_channel_states: wait for them, then write (the copies are complete on return)
     if (int rc = drain_filter(f)) return rc;

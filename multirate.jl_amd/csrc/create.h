@@ -1,0 +1,86 @@
+// create.h -- what the sixteen mrhip_create_* constructors (create.hip) are made of that makes no HIP call: the description of an entry
+// point, its argument and parameter checks and the host-side bank building.  All of it is in host_logic.cpp, as pure functions, so the
+// stand-alone check programs under tests/ run it on the CPU (tests/create_check.cpp).
+#pragma once
+
+#include <string_view>
+
+#include "mrhip_internal.h"
+
+namespace mrhip {
+
+enum CreateFamily { kCreateRational, kCreateArbitrary, kCreateFarrow };
+enum CreateTaps { kTapsReal, kTapsComplex, kTapsEither };
+
+// One entry point, as data.  `hint` != NULL: the entry point has a tap-class refusal of its own, given BEFORE every other check (and
+// *out is cleared first, where out is not NULL): real-only ones answer MRHIP_ERR_UNSUPPORTED with "<name> takes Float32 / Float64 taps
+// (<hint>)", complex-only ones MRHIP_ERR_INVALID_ARG with "<name> takes Complex64 / Complex128 taps; real taps: <hint>" -- there the hint
+// is the sibling's name.  hint == NULL: complex taps, where not accepted, get the generic text of create_check_args after the h / hLen
+// and dtype checks.
+struct CreateEntry {
+    CreateFamily family;
+    CreateTaps taps;             // tap class accepted
+    bool bank, rates, pnfb;      // `h` holds nch rows / nch rates behind the one bank / `h` is a caller-fitted polynomial bank (no fit)
+    const char *name, *hint;
+};
+inline constexpr const char *kRatesHint = "complex taps with per-channel rates are left out";
+inline constexpr CreateEntry kCreateEntries[] = {
+    //                                         bank   rates  pnfb
+    {kCreateRational,  kTapsEither,  false, false, false, "mrhip_create_rational", nullptr},
+    {kCreateRational,  kTapsReal,    true,  false, false, "mrhip_create_rational_bank", "complex taps in a bank are not supported"},
+    {kCreateRational,  kTapsComplex, true,  false, false, "mrhip_create_rational_bank_ctaps", "mrhip_create_rational_bank"},
+    {kCreateArbitrary, kTapsReal,    false, false, false, "mrhip_create_arbitrary", nullptr},
+    {kCreateArbitrary, kTapsComplex, false, false, false, "mrhip_create_arbitrary_ctaps", "mrhip_create_arbitrary"},
+    {kCreateArbitrary, kTapsReal,    true,  false, false, "mrhip_create_arbitrary_bank", "complex taps in a FIRArbitrary bank are left out"},
+    {kCreateArbitrary, kTapsComplex, true,  false, false, "mrhip_create_arbitrary_bank_ctaps", "mrhip_create_arbitrary_bank"},
+    {kCreateArbitrary, kTapsReal,    false, true,  false, "mrhip_create_arbitrary_rates", kRatesHint},
+    {kCreateFarrow,    kTapsReal,    false, false, false, "mrhip_create_farrow", nullptr},
+    {kCreateFarrow,    kTapsReal,    true,  false, false, "mrhip_create_farrow_bank",
+     "complex taps in a FIRFarrow bank are left out of this entry point: mrhip_create_farrow_bank_ctaps"},
+    {kCreateFarrow,    kTapsReal,    false, false, true,  "mrhip_create_farrow_pnfb", nullptr},
+    {kCreateFarrow,    kTapsReal,    false, true,  false, "mrhip_create_farrow_rates", kRatesHint},
+    {kCreateFarrow,    kTapsReal,    false, true,  true,  "mrhip_create_farrow_rates_pnfb", kRatesHint},
+    {kCreateFarrow,    kTapsComplex, false, false, false, "mrhip_create_farrow_ctaps", "mrhip_create_farrow"},
+    {kCreateFarrow,    kTapsComplex, true,  false, false, "mrhip_create_farrow_bank_ctaps", "mrhip_create_farrow_bank"},
+    {kCreateFarrow,    kTapsComplex, false, false, true,  "mrhip_create_farrow_pnfb_ctaps", "mrhip_create_farrow_pnfb"},
+};
+// the row of an entry point; in a constant expression (as create.hip uses it) a name the table does not hold does not compile
+constexpr const CreateEntry &create_entry(std::string_view name)
+{
+    for (const CreateEntry &e : kCreateEntries)
+        if (name == e.name) return e;
+    throw "no such entry point";
+}
+
+// What differs between the families' signatures.  In: num / den, or rate or rates, Nphi, polyorder.  create_check_params leaves the
+// reduced ratio in L / M and, with per-channel rates, the largest rate in `rate`.
+struct CreateParams {
+    int64_t num = 1, den = 1;
+    double rate = 0.0;
+    const double *rates = nullptr;
+    int64_t Nphi = 1, polyorder = 0;
+    int64_t L = 1, M = 1;
+};
+
+// What a check answers: MRHIP_OK, or the status and the text of mrhip_last_error -- as a value, so that nothing here touches the
+// library's error state (the caller hands it to fail()).
+struct Refusal {
+    int status = MRHIP_OK;
+    std::string message;
+    explicit operator bool() const { return status != MRHIP_OK; }
+};
+
+// (a) the checks in front of the device query: out, h / hLen, the dtypes, the tap class, nch
+Refusal create_check_args(const CreateEntry &e, const void *h, int64_t hLen, int th, int tx, int64_t nch, mrhip_filter **out);
+// (b) the checks behind the device checks: ratio and the 31-bit limits; rate or rates, then Nphi, then (FIRFarrow) polyorder
+Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, CreateParams *p);
+// the rate checks of the constructors with per-channel rates and of mrhip_set_channel_rates; *rate_max: the largest rate
+Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max);
+// (c) the banks, `rows` tap vectors of hLen taps each, one bank per row, one after the other.  taps2pfb of every row into pfb and
+// (dpfb != NULL: FIRArbitrary) of its dh = [diff(h), 0] into dpfb; returns tapsPerPhi
+int64_t create_pfb_banks(const void *h, int64_t hLen, int th, int64_t Nphi, size_t rows, std::vector<unsigned char> *pfb, std::vector<unsigned char> *dpfb);
+// FIRFarrow: pfb = taps2pfb(row, Nphi) and one polynomial per row of it (Filters.jl:139-140, :315-318), per component for complex taps,
+// into pn, [rows][T][polyorder+1] scalars or (re, im) pairs.  false: a fit is rank deficient.
+bool create_farrow_banks(const void *h, int64_t hLen, int th, int64_t Nphi, int64_t polyorder, size_t rows, std::vector<double> *pn);
+
+}  // namespace mrhip

@@ -2,7 +2,8 @@
 //
 // Everything here depends only on lengths and on the (phase, deficit) state, never on sample
 // values, so the host can size buffers, pick grids and advance the stream state without ever
-// reading back from the device.
+// reading back from the device.  At the end: the host side of the constructors
+// (create.h) -- their checks and the filter banks, which depend on the arguments and the taps alone.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "mrhip_internal.h"
+#include "create.h"
 #include "rates_arb.h"
 
 namespace mrhip {
@@ -661,6 +663,112 @@ bool polyfit_rows(const double *y, int64_t n, int polyorder, double *coef)
         const double d = A[static_cast<size_t>(c) * m + c];
         if (d == 0.0) return false;
         coef[c] = sacc / d;
+    }
+    return true;
+}
+
+// ---- the constructors' host side (create.h; the device work is create.hip's) --------------------------------------------------------
+
+Refusal create_check_args(const CreateEntry &e, const void *h, int64_t hLen, int th, int tx, int64_t nch, mrhip_filter **out)
+{
+    if (e.hint) {            // an entry point with a tap-class refusal of its own gives it first, whatever else is wrong
+        if (out) *out = nullptr;
+        if (e.taps == kTapsReal && (th == MRHIP_C64 || th == MRHIP_C128))
+            return {MRHIP_ERR_UNSUPPORTED, std::string(e.name) + " takes Float32 / Float64 taps (" + e.hint + ")"};
+        if (e.taps == kTapsComplex && (th == MRHIP_F32 || th == MRHIP_F64))
+            return {MRHIP_ERR_INVALID_ARG, std::string(e.name) + " takes Complex64 / Complex128 taps; real taps: " + e.hint};
+    }
+    if (!out) return {MRHIP_ERR_INVALID_ARG, "out is NULL"};
+    *out = nullptr;
+    if (!h || hLen < 1) return {MRHIP_ERR_INVALID_ARG, "h must hold at least one tap"};
+    if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, "bad tap dtype"};
+    if (dtype_is_complex(th) && e.taps == kTapsReal)     // (a text older than the *_ctaps constructors: DESIGN.md, known)
+        return {MRHIP_ERR_UNSUPPORTED, "complex taps are supported by the rational family only (mrhip_create_rational: FIRStandard, FIRDecimator, "
+                                       "FIRInterpolator, FIRRational); FIRArbitrary and FIRFarrow take Float32 or Float64 taps"};
+    if (tx < MRHIP_F32 || tx > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, "bad sample dtype"};
+    if (nch < 1) return {MRHIP_ERR_INVALID_ARG, "nchannels must be >= 1"};
+    return {};
+}
+
+Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max)
+{
+    if (!rates) return {MRHIP_ERR_INVALID_ARG, "rates is NULL"};
+    *rate_max = 0.0;
+    for (int64_t c = 0; c < nch; ++c) {
+        if (!(rates[c] > 0.0) || !std::isfinite(rates[c])) return {MRHIP_ERR_INVALID_ARG, "rate must be greater than 0 (every channel's, and finite)"};
+        // (update() advances xIdx by about 1/rate a step; the walk carries that advance in 32 bits: sched_step.h)
+        if (rates[c] < 1.0 / static_cast<double>(1LL << 30)) return {MRHIP_ERR_UNSUPPORTED, "a per-channel rate below 2^-30"};
+        *rate_max = std::max(*rate_max, rates[c]);
+    }
+    return {};
+}
+
+Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, CreateParams *p)
+{
+    if (e.family == kCreateRational) {
+        if (p->num < 1 || p->den < 1) return {MRHIP_ERR_INVALID_ARG, "ratio must be positive"};
+        int64_t g = p->num, r = p->den;                  // gcd
+        while (r) { const int64_t t = g % r; g = r; r = t; }
+        p->L = p->num / g; p->M = p->den / g;
+        if (p->L > 0x7fffffff || p->M > 0x7fffffff || hLen > 0x7fffffff)
+            return {MRHIP_ERR_INVALID_ARG, "L, M and hLen must fit in 31 bits"};
+        return {};
+    }
+    if (e.rates) {
+        if (Refusal r = check_channel_rates(p->rates, nch, &p->rate)) return r;
+    } else if (!(p->rate > 0.0)) {
+        return {MRHIP_ERR_INVALID_ARG, "rate must be greater than 0"};
+    }
+    if (p->Nphi < 1 || p->Nphi > 0x7fffffff || hLen > 0x7fffffff) return {MRHIP_ERR_INVALID_ARG, "bad Nphi"};
+    if (e.family != kCreateFarrow) return {};
+    if (e.pnfb) {            // a caller-fitted bank: nothing is fitted, so Nphi does not bound the order
+        if (p->polyorder < 0 || p->polyorder > 32) return {MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..32"};
+    } else if (p->polyorder < 0 || p->polyorder > 32 || p->polyorder + 1 > p->Nphi) {
+        return {MRHIP_ERR_INVALID_ARG, "polyorder must be in 0..min(32, Nphi-1)"};
+    }
+    return {};
+}
+
+int64_t create_pfb_banks(const void *h, int64_t hLen, int th, int64_t Nphi, size_t rows, std::vector<unsigned char> *pfb, std::vector<unsigned char> *dpfb)
+{
+    const size_t es = dtype_size(th);
+    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
+    const size_t bank_bytes = static_cast<size_t>(T) * static_cast<size_t>(Nphi) * es;
+    pfb->resize(bank_bytes * rows);
+    if (dpfb) dpfb->resize(bank_bytes * rows);
+    std::vector<unsigned char> dh(dpfb ? static_cast<size_t>(hLen) * es : 0);
+    for (size_t r = 0; r < rows; ++r) {                  // (Nphi == 1: one column, reversed == flipud)
+        const unsigned char *hr = static_cast<const unsigned char *>(h) + r * static_cast<size_t>(hLen) * es;
+        taps2pfb(hr, hLen, th, Nphi, pfb->data() + r * bank_bytes);
+        if (!dpfb) continue;
+        arbitrary_dh(hr, hLen, th, dh.data());          // dh = [diff(h), 0] in the tap type (Filters.jl:106)
+        taps2pfb(dh.data(), hLen, th, Nphi, dpfb->data() + r * bank_bytes);
+    }
+    return T;
+}
+
+// The Vandermonde matrix of the fit is real, so the least-squares fit of a complex row is the fit of its real parts and the fit of its
+// imaginary parts: one loop over the nc components of a tap.
+bool create_farrow_banks(const void *h, int64_t hLen, int th, int64_t Nphi, int64_t polyorder, size_t rows, std::vector<double> *pn)
+{
+    const size_t es = dtype_size(th), nc = dtype_is_complex(th) ? 2 : 1, np = static_cast<size_t>(polyorder + 1);
+    const int64_t T = taps2pfb(h, hLen, th, Nphi, nullptr);
+    pn->resize(rows * static_cast<size_t>(T) * np * nc);
+    std::vector<unsigned char> pfb(static_cast<size_t>(T) * Nphi * es);
+    std::vector<double> row(static_cast<size_t>(Nphi)), fit(np);
+    for (size_t r = 0; r < rows; ++r) {
+        taps2pfb(static_cast<const unsigned char *>(h) + r * static_cast<size_t>(hLen) * es, hLen, th, Nphi, pfb.data());   // column-major T x Nphi
+        double *bank = pn->data() + r * static_cast<size_t>(T) * np * nc;
+        for (int64_t i = 0; i < T; ++i)
+            for (size_t comp = 0; comp < nc; ++comp) {
+                for (int64_t c = 0; c < Nphi; ++c) {     // element (row i, column c) of the bank
+                    const size_t s = static_cast<size_t>(c * T + i) * nc + comp;
+                    row[static_cast<size_t>(c)] = dtype_is_f64(th) ? reinterpret_cast<const double *>(pfb.data())[s]
+                                                                   : static_cast<double>(reinterpret_cast<const float *>(pfb.data())[s]);
+                }
+                if (!polyfit_rows(row.data(), Nphi, static_cast<int>(polyorder), fit.data())) return false;
+                for (size_t j = 0; j < np; ++j) bank[(static_cast<size_t>(i) * np + j) * nc + comp] = fit[j];
+            }
     }
     return true;
 }

@@ -1,5 +1,5 @@
-// mrhip_filter.h -- the filter object behind the opaque mrhip_filter handle (api.hip, arb_schedule.hip, stream_state.hip,
-// cascade.cpp).  Kept out of mrhip_internal.h so that a change here does not rebuild the kernel translation units.
+// mrhip_filter.h -- the filter object behind the opaque mrhip_filter handle (api.hip, create.hip, arb_schedule.hip, stream_state.hip,
+// cascade.cpp). Kept out of mrhip_internal.h so that a change here does not rebuild the kernel translation units.
 #pragma once
 
 #include "mrhip_internal.h"
@@ -234,6 +234,24 @@ inline hipError_t device_sync_relaxed()
     if (swapped) (void)hipThreadExchangeStreamCaptureMode(&mode);
     return e;
 }
+
+namespace mrhip {
+// RAII: make the filter's device current for the duration of an API call, then restore.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+bool device_is_gfx950(int dev);      // api.hip
+}  // namespace mrhip
 
 // The history slot the next call WRITES (the slots 0 and 1 ping-pong; slot 2 holds zeros and is what reset() makes current instead of
 // zeroing a slot: read-only until a captured call adopts it as its in-place slot -- after which reset() zeroes the current slot itself)

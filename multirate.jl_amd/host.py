@@ -66,6 +66,21 @@ class ChannelState(C.Structure):
 # every symbol include/multirate_hip.h declares: (name, restype, argtypes)
 _vp, _i64, _i, _d = C.c_void_p, C.c_int64, C.c_int, C.c_double
 _pi64 = C.POINTER(C.c_int64)
+
+# the sixteen constructors: (taps or pnfb, hLen, tap dtype) + the family's middle part + (sample dtype, nchannels, device, out); a
+# ``_rates`` constructor takes a pointer to the rates where the others take the rate
+_CREATE = {"rational": ([_i64, _i64], ("", "_bank", "_bank_ctaps")),
+           "arbitrary": ([_d, _i64], ("", "_ctaps", "_bank", "_bank_ctaps", "_rates")),
+           "farrow": ([_d, _i64, _i64], ("", "_bank", "_pnfb", "_rates", "_rates_pnfb", "_ctaps", "_bank_ctaps", "_pnfb_ctaps"))}
+
+
+def _create_rows():
+    for family, (middle, variants) in _CREATE.items():
+        for v in variants:
+            mid = [_vp] + middle[1:] if "_rates" in v else middle
+            yield "mrhip_create_" + family + v, _i, [_vp, _i64, _i] + mid + [_i, _i64, _i, C.POINTER(_vp)]
+
+
 ABI = [
     ("mrhip_abi_version", _i, []),
     ("mrhip_last_error", C.c_char_p, []),
@@ -81,26 +96,11 @@ ABI = [
     ("mrhip_firprototype", _i64, [_i64, _vp, _i, _i, _vp]),
     ("mrhip_firdes", _i64, [_i64, _vp, _i, _i, _d, _d, _vp, _vp]),
     ("mrhip_firdes_kaiser", _i64, [_vp, _i, _d, _d, _i, _d, _vp]),
-    ("mrhip_create_rational", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_rational_bank", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_rational_bank_ctaps", _i, [_vp, _i64, _i, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_arbitrary", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_arbitrary_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_arbitrary_bank", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_arbitrary_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_arbitrary_rates", _i, [_vp, _i64, _i, _vp, _i64, _i, _i64, _i, C.POINTER(_vp)]),
+    *_create_rows(),
     ("mrhip_filt_device_rates", _i, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     ("mrhip_get_channel_states", _i, [_vp, _vp]),
     ("mrhip_set_channel_states", _i, [_vp, _vp, _vp]),
-    ("mrhip_create_farrow_rates", _i, [_vp, _i64, _i, _vp, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_farrow_rates_pnfb", _i, [_vp, _i64, _i, _vp, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_set_channel_rates", _i, [_vp, _vp]),
-    ("mrhip_create_farrow", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_farrow_bank", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_farrow_bank_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_farrow_pnfb", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_farrow_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
-    ("mrhip_create_farrow_pnfb_ctaps", _i, [_vp, _i64, _i, _d, _i64, _i64, _i, _i64, _i, C.POINTER(_vp)]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -213,6 +213,52 @@ def _as_taps(h, allow_complex: bool = False) -> np.ndarray:
                                "through FIRFilter.complex_taps)")
 
 
+# ---- the argument checks the FIRFilter classmethods share: `who` is the method, `other` what its message points to -----------------
+def _takes_ratio(ratio, who: str, other: str):
+    if isinstance(ratio, (float, np.floating)):
+        raise MultirateHIPError(5, f"{who} builds the rational family only ({other})")
+
+
+def _takes_rate(rate, who: str, other: str):
+    if not isinstance(rate, (float, np.floating)):
+        raise MultirateHIPError(1, f"{who} takes a floating-point rate (a Rational ratio: FIRFilter.{other})")
+
+
+def _takes_polyorder(polyorder, who: str, other: str):
+    if polyorder is None:
+        raise MultirateHIPError(1, f"{who} takes a polyorder (without one: FIRFilter.{other})")
+
+
+def _real_taps(h, who: str, other: str) -> np.ndarray:
+    h = np.asarray(h)
+    if h.dtype.kind == "c":
+        raise MultirateHIPError(5, f"{who} takes Float32/Float64 taps ({other})")
+    return h
+
+
+def _complex_taps(h, who: str = "", other=None) -> np.ndarray:
+    """complex taps as they are; real ones are promoted, or refused where the method has a sibling for them (`other`)"""
+    h = np.ascontiguousarray(h)
+    if h.dtype != np.complex64 and h.dtype != np.complex128:
+        if other is not None:
+            raise MultirateHIPError(1, f"{who} takes Complex64/Complex128 taps, got {h.dtype} (real taps: FIRFilter.{other})")
+        h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
+    return h
+
+
+def _tap_matrix(H, who: str) -> np.ndarray:
+    H = np.asarray(H)
+    if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
+        raise MultirateHIPError(1, f"{who} takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
+    return H
+
+
+def _pnfb_shape(f):
+    if f._pnfb_in is not None and f._pnfb_in.shape != (f.tapsPerPhi, f.polyorder + 1):
+        raise MultirateHIPError(1, f"pnfb must have shape (tapsPerPhi, polyorder+1) = {(f.tapsPerPhi, f.polyorder + 1)}")
+    return f
+
+
 def _is_torch(x) -> bool:
     return torch is not None and isinstance(x, torch.Tensor)
 
@@ -323,12 +369,8 @@ class FIRFilter:
         front of a resampler is just a FIRFilter there.  Rational family only (FIRStandard, FIRDecimator, FIRInterpolator,
         FIRRational); the output is always complex (Complex128 if either side is 64-bit).  Real ``h`` is promoted to
         complex.  STRICT numerics only (include/multirate_hip.h: complex taps)."""
-        if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "complex_taps builds the rational family only (a float rate: FIRFilter.complex_taps_arbitrary; FIRFarrow takes Float32/Float64 taps)")
-        h = np.ascontiguousarray(h)
-        if h.dtype != np.complex64 and h.dtype != np.complex128:
-            h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
-        return cls(h, ratio, device=device, _complex_taps=True)
+        _takes_ratio(ratio, "complex_taps", "a float rate: FIRFilter.complex_taps_arbitrary; FIRFarrow takes Float32/Float64 taps")
+        return cls(_complex_taps(h), ratio, device=device, _complex_taps=True)
 
     @classmethod
     def complex_taps_arbitrary(cls, h, rate, Nphi: int = 32, *, device: int = 0):
@@ -337,12 +379,8 @@ class FIRFilter:
         and tapsforphase are complex).  The output is always complex (Complex128 if either side is 64-bit); real ``h`` is
         promoted to complex.  STRICT numerics only (include/multirate_hip.h: complex taps).  The device object is created by
         ``mrhip_create_arbitrary_ctaps``."""
-        if not isinstance(rate, (float, np.floating)):
-            raise MultirateHIPError(1, "complex_taps_arbitrary takes a floating-point rate (a Rational ratio: FIRFilter.complex_taps)")
-        h = np.ascontiguousarray(h)
-        if h.dtype != np.complex64 and h.dtype != np.complex128:
-            h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
-        return cls(h, float(rate), int(Nphi), device=device, _complex_taps=True)
+        _takes_rate(rate, "complex_taps_arbitrary", "complex_taps")
+        return cls(_complex_taps(h), float(rate), int(Nphi), device=device, _complex_taps=True)
 
     @classmethod
     def complex_taps_farrow(cls, h, rate, Nphi, polyorder, *, pnfb=None, device: int = 0):
@@ -352,17 +390,9 @@ class FIRFilter:
         (tapsPer𝜙, polyorder+1), ascending powers.  The output is always complex (Complex128 if either side is 64-bit); real
         ``h`` is promoted to complex.  STRICT numerics only (include/multirate_hip.h: complex taps).  The device object is created
         by ``mrhip_create_farrow_ctaps`` / ``mrhip_create_farrow_pnfb_ctaps``."""
-        if not isinstance(rate, (float, np.floating)):
-            raise MultirateHIPError(1, "complex_taps_farrow takes a floating-point rate (a Rational ratio: FIRFilter.complex_taps)")
-        if polyorder is None:
-            raise MultirateHIPError(1, "complex_taps_farrow takes a polyorder (without one: FIRFilter.complex_taps_arbitrary)")
-        h = np.ascontiguousarray(h)
-        if h.dtype != np.complex64 and h.dtype != np.complex128:
-            h = h.astype(np.complex64 if h.dtype == np.float32 else np.complex128)
-        f = cls(h, float(rate), int(Nphi), int(polyorder), device=device, pnfb=pnfb, _complex_taps=True)
-        if f._pnfb_in is not None and f._pnfb_in.shape != (f.tapsPerPhi, f.polyorder + 1):
-            raise MultirateHIPError(1, f"pnfb must have shape (tapsPerPhi, polyorder+1) = {(f.tapsPerPhi, f.polyorder + 1)}")
-        return f
+        _takes_rate(rate, "complex_taps_farrow", "complex_taps")
+        _takes_polyorder(polyorder, "complex_taps_farrow", "complex_taps_arbitrary")
+        return _pnfb_shape(cls(_complex_taps(h), float(rate), int(Nphi), int(polyorder), device=device, pnfb=pnfb, _complex_taps=True))
 
     @classmethod
     def per_channel(cls, H, ratio=1, *, device: int = 0, numerics: int = NUMERICS_STRICT):
@@ -372,17 +402,9 @@ class FIRFilter:
         c is bit for bit ``FIRFilter(H[c], ratio)`` fed ``x[c]`` (include/multirate_hip.h: per-channel taps).  Rational family
         only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape (nchannels, tapsPer𝜙, N𝜙).  The device
         object is created by ``mrhip_create_rational_bank``."""
-        if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "per_channel builds the rational family only (a float rate: FIRFilter.per_channel_arbitrary, FIRFilter.per_channel_farrow)")
-        H = np.asarray(H)
-        if H.dtype.kind == "c":
-            raise MultirateHIPError(5, "per_channel takes Float32/Float64 taps (complex taps in a bank are not supported)")
-        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
-            raise MultirateHIPError(1, f"per_channel takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
-        H = np.ascontiguousarray(_as_taps(H))
-        f = cls(H[0], ratio, device=device, numerics=numerics)
-        f._bank = H.copy()
-        return f
+        _takes_ratio(ratio, "per_channel", "a float rate: FIRFilter.per_channel_arbitrary, FIRFilter.per_channel_farrow")
+        H = _tap_matrix(_real_taps(H, "per_channel", "complex taps in a bank are not supported"), "per_channel")
+        return cls._of_bank(_as_taps(H), ratio, device=device, numerics=numerics)
 
     @classmethod
     def per_channel_complex_taps(cls, H, ratio=1, *, device: int = 0):
@@ -393,17 +415,8 @@ class FIRFilter:
         (include/multirate_hip.h: per-channel complex taps).  Rational family only; the output is always complex (Complex128 if
         either side is 64-bit); STRICT numerics only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps()`` has shape
         (nchannels, tapsPer𝜙, N𝜙), complex.  The device object is created by ``mrhip_create_rational_bank_ctaps``."""
-        if isinstance(ratio, (float, np.floating)):
-            raise MultirateHIPError(5, "per_channel_complex_taps builds the rational family only (a float rate: FIRFilter.per_channel_complex_taps_arbitrary, FIRFilter.per_channel_complex_taps_farrow)")
-        H = np.asarray(H)
-        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
-            raise MultirateHIPError(1, f"per_channel_complex_taps takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
-        if H.dtype != np.complex64 and H.dtype != np.complex128:
-            H = H.astype(np.complex64 if H.dtype == np.float32 else np.complex128)
-        H = np.ascontiguousarray(H)
-        f = cls(H[0], ratio, device=device, _complex_taps=True)
-        f._bank = H.copy()
-        return f
+        _takes_ratio(ratio, "per_channel_complex_taps", "a float rate: FIRFilter.per_channel_complex_taps_arbitrary, FIRFilter.per_channel_complex_taps_farrow")
+        return cls._of_bank(_complex_taps(_tap_matrix(H, "per_channel_complex_taps")), ratio, device=device, _complex_taps=True)
 
     @classmethod
     def per_channel_arbitrary(cls, H, rate, Nphi: int = 32, *, device: int = 0, numerics: int = NUMERICS_STRICT):
@@ -414,17 +427,9 @@ class FIRFilter:
         for bit ``FIRFilter(H[c], rate, Nphi)`` fed ``x[c]``, under STRICT and FUSED (include/multirate_hip.h: per-channel taps for
         FIRArbitrary).  The filter binds to exactly ``H.shape[0]`` channels; ``taps(which)`` has shape (nchannels, tapsPer𝜙, N𝜙) and
         ``tapsforphase`` (nchannels, tapsPer𝜙).  The device object is created by ``mrhip_create_arbitrary_bank``."""
-        if not isinstance(rate, (float, np.floating)):
-            raise MultirateHIPError(1, "per_channel_arbitrary takes a floating-point rate (a Rational ratio: FIRFilter.per_channel)")
-        H = np.asarray(H)
-        if H.dtype.kind == "c":
-            raise MultirateHIPError(5, "per_channel_arbitrary takes Float32/Float64 taps (complex taps: FIRFilter.per_channel_complex_taps_arbitrary)")
-        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
-            raise MultirateHIPError(1, f"per_channel_arbitrary takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
-        H = np.ascontiguousarray(_as_taps(H))
-        f = cls(H[0], float(rate), int(Nphi), device=device, numerics=numerics)
-        f._bank = H.copy()
-        return f
+        _takes_rate(rate, "per_channel_arbitrary", "per_channel")
+        H = _tap_matrix(_real_taps(H, "per_channel_arbitrary", "complex taps: FIRFilter.per_channel_complex_taps_arbitrary"), "per_channel_arbitrary")
+        return cls._of_bank(_as_taps(H), float(rate), int(Nphi), device=device, numerics=numerics)
 
     @classmethod
     def per_channel_rates(cls, h, rates, Nphi: int = 32, *, device: int = 0, numerics: int = NUMERICS_STRICT):
@@ -437,9 +442,7 @@ class FIRFilter:
         ``channel_states`` / ``set_channel_states`` replace ``state`` / ``set_state``.  What carries one state or one count
         (``state``, ``outputlength``, ``next_output_count``, ``filt_into_async``, rings, cascades, ...) raises status 5.  The device
         object is created by ``mrhip_create_arbitrary_rates``."""
-        h = np.asarray(h)
-        if h.dtype.kind == "c":
-            raise MultirateHIPError(5, "per_channel_rates takes Float32/Float64 taps (complex taps with per-channel rates are left out)")
+        h = _real_taps(h, "per_channel_rates", "complex taps with per-channel rates are left out")
         r = cls._checked_rates(rates, "per_channel_rates")
         f = cls(h, float(r.max()), int(Nphi), device=device, numerics=numerics)
         f._rates = r
@@ -466,17 +469,12 @@ class FIRFilter:
         ``set_channel_states``, ``set_channel_rates``, ``outputlength_bound``, ``reset`` and ``history`` behave as on the filter of
         ``per_channel_rates``; ``pnfb()`` and ``tapsforphase`` as on a one-channel FIRFarrow filter.  The device object is created by
         ``mrhip_create_farrow_rates`` / ``mrhip_create_farrow_rates_pnfb``."""
-        h = np.asarray(h)
-        if h.dtype.kind == "c":
-            raise MultirateHIPError(5, "per_channel_rates_farrow takes Float32/Float64 taps (complex taps with per-channel rates are left out)")
-        if polyorder is None:
-            raise MultirateHIPError(1, "per_channel_rates_farrow takes a polyorder (without one: FIRFilter.per_channel_rates)")
+        h = _real_taps(h, "per_channel_rates_farrow", "complex taps with per-channel rates are left out")
+        _takes_polyorder(polyorder, "per_channel_rates_farrow", "per_channel_rates")
         r = cls._checked_rates(rates, "per_channel_rates_farrow")
         if not 0 <= int(polyorder) <= 32 or (pnfb is None and int(polyorder) + 1 > int(Nphi)):
             raise MultirateHIPError(1, "polyorder must be in 0..min(32, Nphi-1)")
-        f = cls(h, float(r.max()), int(Nphi), int(polyorder), device=device, numerics=numerics, pnfb=pnfb)
-        if f._pnfb_in is not None and f._pnfb_in.shape != (f.tapsPerPhi, f.polyorder + 1):
-            raise MultirateHIPError(1, f"pnfb must have shape (tapsPerPhi, polyorder+1) = {(f.tapsPerPhi, f.polyorder + 1)}")
+        f = _pnfb_shape(cls(h, float(r.max()), int(Nphi), int(polyorder), device=device, numerics=numerics, pnfb=pnfb))
         f._rates = r
         return f
 
@@ -492,17 +490,10 @@ class FIRFilter:
         numerics only.  The filter binds to exactly ``H.shape[0]`` channels; ``taps(which)`` has shape (nchannels, tapsPer𝜙, N𝜙)
         and ``tapsforphase`` (nchannels, tapsPer𝜙), both complex.  The device object is created by
         ``mrhip_create_arbitrary_bank_ctaps``."""
-        if not isinstance(rate, (float, np.floating)):
-            raise MultirateHIPError(1, "per_channel_complex_taps_arbitrary takes a floating-point rate (a Rational ratio: FIRFilter.per_channel_complex_taps)")
-        H = np.asarray(H)
-        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
-            raise MultirateHIPError(1, f"per_channel_complex_taps_arbitrary takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
-        if H.dtype != np.complex64 and H.dtype != np.complex128:
-            raise MultirateHIPError(1, f"per_channel_complex_taps_arbitrary takes Complex64/Complex128 taps, got {H.dtype} (real taps: FIRFilter.per_channel_arbitrary)")
-        H = np.ascontiguousarray(H)
-        f = cls(H[0], float(rate), int(Nphi), device=device, _complex_taps=True)
-        f._bank = H.copy()
-        return f
+        who = "per_channel_complex_taps_arbitrary"
+        _takes_rate(rate, who, "per_channel_complex_taps")
+        H = _complex_taps(_tap_matrix(H, who), who, "per_channel_arbitrary")
+        return cls._of_bank(H, float(rate), int(Nphi), device=device, _complex_taps=True)
 
     @classmethod
     def per_channel_farrow(cls, H, rate, Nphi: int = 32, polyorder=4, *, device: int = 0, numerics: int = NUMERICS_STRICT):
@@ -514,19 +505,10 @@ class FIRFilter:
         for FIRFarrow).  The filter binds to exactly ``H.shape[0]`` channels; ``pnfb()`` has shape (nchannels, tapsPer𝜙, polyorder+1)
         and ``tapsforphase`` (nchannels, tapsPer𝜙).  A caller-fitted ``pnfb`` is not accepted here.  The device object is created by
         ``mrhip_create_farrow_bank``."""
-        if not isinstance(rate, (float, np.floating)):
-            raise MultirateHIPError(1, "per_channel_farrow takes a floating-point rate (a Rational ratio: FIRFilter.per_channel)")
-        if polyorder is None:
-            raise MultirateHIPError(1, "per_channel_farrow takes a polyorder (without one: FIRFilter.per_channel_arbitrary)")
-        H = np.asarray(H)
-        if H.dtype.kind == "c":
-            raise MultirateHIPError(5, "per_channel_farrow takes Float32/Float64 taps (complex taps: FIRFilter.per_channel_complex_taps_farrow)")
-        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
-            raise MultirateHIPError(1, f"per_channel_farrow takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
-        H = np.ascontiguousarray(_as_taps(H))
-        f = cls(H[0], float(rate), int(Nphi), int(polyorder), device=device, numerics=numerics)
-        f._bank = H.copy()
-        return f
+        _takes_rate(rate, "per_channel_farrow", "per_channel")
+        _takes_polyorder(polyorder, "per_channel_farrow", "per_channel_arbitrary")
+        H = _tap_matrix(_real_taps(H, "per_channel_farrow", "complex taps: FIRFilter.per_channel_complex_taps_farrow"), "per_channel_farrow")
+        return cls._of_bank(_as_taps(H), float(rate), int(Nphi), int(polyorder), device=device, numerics=numerics)
 
     @classmethod
     def per_channel_complex_taps_farrow(cls, H, rate, Nphi: int = 32, polyorder=4, *, device: int = 0):
@@ -540,17 +522,17 @@ class FIRFilter:
         to exactly ``H.shape[0]`` channels; ``pnfb()`` has shape (nchannels, tapsPer𝜙, polyorder+1) and ``tapsforphase``
         (nchannels, tapsPer𝜙), both complex.  A caller-fitted ``pnfb`` is not accepted here.  The device object is created by
         ``mrhip_create_farrow_bank_ctaps``."""
-        if not isinstance(rate, (float, np.floating)):
-            raise MultirateHIPError(1, "per_channel_complex_taps_farrow takes a floating-point rate (a Rational ratio: FIRFilter.per_channel_complex_taps)")
-        if polyorder is None:
-            raise MultirateHIPError(1, "per_channel_complex_taps_farrow takes a polyorder (without one: FIRFilter.per_channel_complex_taps_arbitrary)")
-        H = np.asarray(H)
-        if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] < 1:
-            raise MultirateHIPError(1, f"per_channel_complex_taps_farrow takes a (nchannels, hLen) matrix of taps; got shape {H.shape}")
-        if H.dtype != np.complex64 and H.dtype != np.complex128:
-            raise MultirateHIPError(1, f"per_channel_complex_taps_farrow takes Complex64/Complex128 taps, got {H.dtype} (real taps: FIRFilter.per_channel_farrow)")
+        who = "per_channel_complex_taps_farrow"
+        _takes_rate(rate, who, "per_channel_complex_taps")
+        _takes_polyorder(polyorder, who, "per_channel_complex_taps_arbitrary")
+        H = _complex_taps(_tap_matrix(H, who), who, "per_channel_farrow")
+        return cls._of_bank(H, float(rate), int(Nphi), int(polyorder), device=device, _complex_taps=True)
+
+    @classmethod
+    def _of_bank(cls, H, *args, **kwargs):
+        """the filter of row 0 of the (nchannels, hLen) matrix, with the matrix behind it"""
         H = np.ascontiguousarray(H)
-        f = cls(H[0], float(rate), int(Nphi), int(polyorder), device=device, _complex_taps=True)
+        f = cls(H[0], *args, **kwargs)
         f._bank = H.copy()
         return f
 
@@ -569,58 +551,21 @@ class FIRFilter:
             raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
         if self._rates is not None and nch != len(self._rates):
             raise MultirateHIPError(1, f"a filter of {len(self._rates)} per-channel rates binds to exactly that many channels; got {nch}")
-        if self._rates is not None and self.kind == FARROW and self._pnfb_in is not None:
-            rc = self._lib.mrhip_create_farrow_rates_pnfb(_ptr(self._pnfb_in), len(self.h), _NP2DT[self.h.dtype], _ptr(self._rates), self.Nphi,
-                                                          self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self._rates is not None and self.kind == FARROW:
-            rc = self._lib.mrhip_create_farrow_rates(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], _ptr(self._rates), self.Nphi,
-                                                     self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self._rates is not None:
-            rc = self._lib.mrhip_create_arbitrary_rates(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], _ptr(self._rates), self.Nphi,
-                                                        _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self._bank is not None and self.kind == ARBITRARY and self._bank.dtype.kind == "c":
-            rc = self._lib.mrhip_create_arbitrary_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
-                                                             self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self._bank is not None and self.kind == ARBITRARY:
-            rc = self._lib.mrhip_create_arbitrary_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
-                                                       self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self._bank is not None and self.kind == FARROW and self._bank.dtype.kind == "c":
-            rc = self._lib.mrhip_create_farrow_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
-                                                          self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self._bank is not None and self.kind == FARROW:
-            rc = self._lib.mrhip_create_farrow_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype], self.rate,
-                                                    self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self._bank is not None and self._bank.dtype.kind == "c":
-            rc = self._lib.mrhip_create_rational_bank_ctaps(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype],
-                                                            self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
-                                                            self.device, C.byref(out))
-        elif self._bank is not None:
-            rc = self._lib.mrhip_create_rational_bank(_ptr(self._bank), self._bank.shape[1], _NP2DT[self._bank.dtype],
-                                                      self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
-                                                      self.device, C.byref(out))
-        elif self.kind == FARROW and self.h.dtype.kind == "c":
-            if self._pnfb_in is not None:
-                rc = self._lib.mrhip_create_farrow_pnfb_ctaps(_ptr(self._pnfb_in), len(self.h), _NP2DT[self.h.dtype], self.rate,
-                                                              self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-            else:
-                rc = self._lib.mrhip_create_farrow_ctaps(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate, self.Nphi,
-                                                         self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self.kind == FARROW and self._pnfb_in is not None:
-            rc = self._lib.mrhip_create_farrow_pnfb(_ptr(self._pnfb_in), len(self.h), _NP2DT[self.h.dtype], self.rate,
-                                                    self.Nphi, self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self.kind == FARROW:
-            rc = self._lib.mrhip_create_farrow(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate, self.Nphi,
-                                               self.polyorder, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self.kind == ARBITRARY and self.h.dtype.kind == "c":
-            rc = self._lib.mrhip_create_arbitrary_ctaps(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate,
-                                                        self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
-        elif self.kind == ARBITRARY:
-            rc = self._lib.mrhip_create_arbitrary(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype], self.rate,
-                                                  self.Nphi, _NP2DT[tx], nch, self.device, C.byref(out))
+        # the entry point follows from what the object holds: family, then _bank or _rates, _pnfb for a bank handed in, _ctaps for
+        # complex taps (mrhip_create_rational itself takes both tap classes)
+        family = {ARBITRARY: "arbitrary", FARROW: "farrow"}.get(self.kind, "rational")
+        taps = self.h if self._bank is None else self._bank
+        name = "mrhip_create_" + family + ("_bank" if self._bank is not None else "_rates" if self._rates is not None else "")
+        first = taps
+        if self.kind == FARROW and self._pnfb_in is not None and self._bank is None:
+            name, first = name + "_pnfb", self._pnfb_in
+        if taps.dtype.kind == "c" and name != "mrhip_create_rational":
+            name += "_ctaps"
+        if family == "rational":
+            middle = (self.ratio.numerator, self.ratio.denominator)
         else:
-            rc = self._lib.mrhip_create_rational(_ptr(self.h), len(self.h), _NP2DT[self.h.dtype],
-                                                 self.ratio.numerator, self.ratio.denominator, _NP2DT[tx], nch,
-                                                 self.device, C.byref(out))
+            middle = (self.rate if self._rates is None else _ptr(self._rates), self.Nphi) + ((self.polyorder,) if self.kind == FARROW else ())
+        rc = getattr(self._lib, name)(_ptr(first), taps.shape[-1], _NP2DT[taps.dtype], *middle, _NP2DT[tx], nch, self.device, C.byref(out))
         _check(rc)
         self._handle, self._tx, self._nch = out, tx, nch
         if self.numerics != NUMERICS_STRICT:
