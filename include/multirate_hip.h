@@ -290,6 +290,8 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *   - every other constructor and filter answers exactly as before;
  *   - the rates may change between calls: mrhip_set_channel_rates; mrhip_reset restores the constructor STATE of every channel and
  *     keeps the current rates;
+ *   - the call length is shared through mrhip_filt_device_rates; mrhip_filt_device_rates_ragged feeds every channel its own number of
+ *     samples (both filters with per-channel rates; the contract stands at its declaration);
  *   - left out on purpose: complex or per-channel taps combined with per-channel rates; evaluating
  *     a long channel's schedule with the parallel tables / chain / emit machinery instead of the serial walk (the next speed step
  *     for few long channels); graph capture, rings, cascades and sharding of such a filter; a mrhip_filt_device_multi that serves
@@ -635,6 +637,33 @@ int64_t mrhip_outputlength_bound(const mrhip_filter *f, int64_t inputlength);
  *     does a call on a capturing stream. */
 int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64_t x_stride,
                             void *y, int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream);
+/* Per-channel input lengths for the filters with per-channel rates: mrhip_filt_device_rates with channel c fed x_c[0 : x_lens[c]) --
+ * receivers off their own clocks deliver different numbers of samples per interval, and the caller feeds what arrived.  x_lens is a
+ * HOST array of nchannels lengths; x holds the rows x_stride apart as before.
+ *   - parity: channel c is bit for bit mrhip_create_arbitrary(h, rates[c], Nphi, nchannels = 1) -- mrhip_create_farrow(...) for the
+ *     FIRFarrow filter -- fed x_c[0 : x_lens[c]): the outputs, the count of every call, the end state (inputDeficit, phiAccumulator,
+ *     xIdx) and the history, under STRICT and under FUSED.  That includes the short-input path of filt! (src/Filters.jl:705-709,
+ *     :805-809) per channel, and FIRFarrow's zero-start seam on every call;
+ *   - a channel with x_lens[c] == 0 keeps its state and its history and files a count of 0, whatever its neighbours do;
+ *   - when all lengths are equal the result is that of mrhip_filt_device_rates at that length;
+ *   - the bound of a call is mrhip_outputlength_bound(f, the largest of x_lens): y_capacity (and y_stride for nchannels > 1) must
+ *     reach it, else MRHIP_ERR_BUFFER_TOO_SMALL.  Row c of y receives elements [0, count_c) and nothing else; samples of row c of x
+ *     at and behind x_lens[c] are not used;
+ *   - refused before anything is enqueued or any state moves, each with a message that names this function: a NULL f or x_lens, a
+ *     filter without per-channel rates, a negative length or y_capacity, x NULL with a length above 0, x_stride below the largest
+ *     length for nchannels > 1 (all MRHIP_ERR_INVALID_ARG); a length of 2^31-1 or more, a capturing stream, a bound above 2^24
+ *     (MRHIP_ERR_UNSUPPORTED); capacity or stride below the bound (MRHIP_ERR_BUFFER_TOO_SMALL);
+ *   - x_lens may be reused or freed when the call returns: the library copies it into one of FOUR pinned staging slots it owns, used in
+ *     turn, and from there, in stream order on `stream`, into the filter's one device array of lengths that the kernels read.  The
+ *     call waits on the host where mrhip_filt_device_rates does (growth of the schedule buffers) and in one more place: for a staging
+ *     slot whose upload, four ragged calls back, has not run yet;
+ *   - the launches, the kernels (mrhip_last_kernel_name: the same four names), the timing bracket, mrhip_get_channel_states,
+ *     mrhip_set_channel_states, mrhip_set_channel_rates and mrhip_reset are those of mrhip_filt_device_rates, and the two calls mix
+ *     freely on one filter.  A ragged call sizes its grid by the longest channel and skips the tiles behind a channel's count;
+ *   - left out on purpose: lengths that live on the device; compacting the tiles of channels that end early; graph capture,
+ *     cascades, rings and sharding. */
+int mrhip_filt_device_rates_ragged(mrhip_filter *f, const void *x, const int64_t *x_lens /* HOST, [nchannels] */, int64_t x_stride,
+                                   void *y, int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream);
 /* the nchannels states of such a filter, after waiting for the filter's stream; MRHIP_ERR_BUFFER_TOO_SMALL if a channel's walk ever
  * overran the bound of its call (its outputs were clipped at the bound) */
 int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out /* [nchannels] */);

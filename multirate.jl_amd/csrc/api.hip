@@ -374,8 +374,11 @@ void mrhip_destroy(mrhip_filter *f)
     for (void *p : {f->d_taps_alloc, f->d_dtaps_alloc, static_cast<void *>(f->d_pnfb), static_cast<void *>(f->d_pnfb_t), f->d_hist[0], f->d_hist[1], f->d_hist[2], static_cast<void *>(f->d_counters), f->d_sched_n, f->d_sched_acc,
                     f->d_xbuf[0], f->d_xbuf[1], f->d_ybuf[0], f->d_ybuf[1]})
         if (p) (void)hipFree(p);
-    for (void *p : {static_cast<void *>(f->d_rrec), f->d_rs_n, f->d_rs_acc})
+    for (void *p : {static_cast<void *>(f->d_rrec), f->d_rs_n, f->d_rs_acc, static_cast<void *>(f->d_xlens)})
         if (p) (void)hipFree(p);
+    if (f->rag_pin) (void)hipHostFree(f->rag_pin);
+    for (hipEvent_t e : f->rag_ev)
+        if (e) (void)hipEventDestroy(e);
     if (f->pin_n) (void)hipHostFree(f->pin_n);
     if (f->pin_acc) (void)hipHostFree(f->pin_acc);
     if (f->multi_pin) (void)hipHostFree(f->multi_pin);
@@ -1732,6 +1735,118 @@ int64_t mrhip_outputlength_bound(const mrhip_filter *f, int64_t inputlength)
 }
 
 // ---- FIRArbitrary and FIRFarrow with per-channel rates (include/multirate_hip.h, "Per-channel rates for FIRArbitrary" / "... for FIRFarrow") ----
+// The channels' lengths of a ragged call: kRatesRaggedSlots pinned host slots of nch lengths each, used in turn, and the filter's ONE
+// device array the kernels read.  A slot is guarded by an event recorded behind its upload: the only host wait of a ragged call beyond
+// mrhip_filt_device_rates' own is for a slot whose upload, kRatesRaggedSlots calls back, has not run yet.
+static int ragged_staging(mrhip_filter *f)
+{
+    if (f->d_xlens) return MRHIP_OK;
+    const size_t row = static_cast<size_t>(f->nch) * sizeof(long long);
+    if (!f->rag_pin) MRHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&f->rag_pin), row * kRatesRaggedSlots, hipHostMallocDefault));
+    for (hipEvent_t &e : f->rag_ev)
+        if (!e) MRHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    MRHIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&f->d_xlens), row));
+    return MRHIP_OK;
+}
+
+// ... the caller's lengths into the next slot and from there into the device array, in stream order: the caller's array is free on return
+static int ragged_upload(mrhip_filter *f, const int64_t *h_lens, hipStream_t stream)
+{
+    const int slot = f->rag_next;
+    if (f->rag_busy[slot]) { MRHIP_CHECK_HIP(hipEventSynchronize(f->rag_ev[slot])); f->rag_busy[slot] = false; }
+    long long *const pin = f->rag_pin + static_cast<size_t>(slot) * static_cast<size_t>(f->nch);
+    for (int64_t c = 0; c < f->nch; ++c) pin[c] = h_lens[c];
+    MRHIP_CHECK_HIP(hipMemcpyAsync(f->d_xlens, pin, static_cast<size_t>(f->nch) * sizeof(long long), hipMemcpyHostToDevice, stream));
+    MRHIP_CHECK_HIP(hipEventRecord(f->rag_ev[slot], stream));
+    f->rag_busy[slot] = true;
+    f->rag_next = (slot + 1) % kRatesRaggedSlots;
+    return MRHIP_OK;
+}
+
+// What both entry points enqueue once their checks are through.  x_len: the call's one length, or the largest of h_lens (HOST, [nch]: a
+// ragged call); bound: mrhip_outputlength_bound of it.
+static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64_t *h_lens, int64_t x_stride, void *y, int64_t y_stride,
+                      int64_t bound, int64_t *counts_out, hipStream_t stream)
+{
+    if (int rc = adopt_stream(f, stream)) return rc;
+    if (h_lens) {
+        if (int rc = ragged_staging(f)) return rc;
+    }
+    const long long *const d_lens = h_lens ? f->d_xlens : nullptr;
+    const size_t entries = static_cast<size_t>(f->nch) * static_cast<size_t>(bound);
+    if (entries > f->rs_cap) {
+        const size_t cap = std::max<size_t>(entries + entries / 4, 4096);
+        if (int rc = drain_filter(f)) return rc;      // only this filter's kernels read the slices
+        if (f->d_rs_n) (void)hipFree(f->d_rs_n);
+        if (f->d_rs_acc) (void)hipFree(f->d_rs_acc);
+        f->d_rs_n = f->d_rs_acc = nullptr; f->rs_cap = 0;
+        MRHIP_CHECK_HIP(hipMalloc(&f->d_rs_n, cap * sizeof(int32_t)));
+        MRHIP_CHECK_HIP(hipMalloc(&f->d_rs_acc, cap * sizeof(double)));
+        f->rs_cap = cap;
+    }
+
+    RatesSchedArgs sa{};
+    sa.rec = f->d_rrec; sa.n_idx = static_cast<int *>(f->d_rs_n); sa.acc = static_cast<double *>(f->d_rs_acc);
+    sa.counts_out = reinterpret_cast<long long *>(counts_out);
+    sa.slice = bound; sa.x_len = x_len; sa.x_lens = d_lens;
+    sa.N = static_cast<double>(f->Nphi); sa.invN = 1.0 / static_cast<double>(f->Nphi);
+    sa.nch = static_cast<int>(f->nch);
+
+    ArbArgs a{};
+    a.x = x; a.y = y; a.hist = f->d_hist[f->hist_cur]; a.taps = f->d_taps; a.dtaps = f->d_dtaps;
+    a.n_idx = sa.n_idx; a.acc = sa.acc;
+    a.x_stride = x_stride; a.y_stride = y_stride; a.x_len = x_len; a.n_out = bound;
+    a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H); a.Nphi = static_cast<int>(f->Nphi);
+    a.nch = static_cast<int>(f->nch);
+    a.dyn = nullptr;
+    const int hist_next = hist_other(f);
+    if (f->H > 0) a.fold = ShiftFold{f->d_hist[hist_next], nullptr};      // shiftin! by the kernel's last workgroup, into the other slot
+    const bool farrow = f->kind == MRHIP_FIR_FARROW;
+    FarrowArgs fa{};                // (mrhip_create_farrow_rates: the same call over the one polynomial bank)
+    if (farrow) {
+        fa.x = x; fa.y = y; fa.hist = a.hist; fa.pnfb = f->d_pnfb;
+        fa.n_idx = sa.n_idx; fa.acc = sa.acc;
+        fa.x_stride = x_stride; fa.y_stride = y_stride; fa.x_len = x_len; fa.n_out = bound;
+        fa.T = a.T; fa.H = a.H; fa.polyorder = static_cast<int>(f->polyorder);
+        fa.tap_f32 = !dtype_is_f64(f->th); fa.nch = a.nch;
+        fa.seam_below = a.T;        // every call starts a filt! (Filters.jl:819): a rates call is never a continuation piece
+        fa.dyn = nullptr;
+        fa.fold = a.fold;
+    }
+    const RatesArgs ra{f->d_rrec, bound, d_lens};
+    const TypeKey tk = type_key(f);
+    const bool fused = f->numerics == MRHIP_NUMERICS_FUSED;
+    // Everything on the host that can fail comes BEFORE the schedule kernel, which moves every channel's state: the tiled kernel's plan and
+    // its grid (an occupancy query, a function attribute) and the timing bracket's first event.  Behind it only the two launches
+    // themselves are left.
+    ArbTileArgs ta;
+    size_t lds = 0;
+    long long tiled_grid = 0;
+    bool tiled = false;
+    if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
+        tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
+        if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
+    } else if (bound > 0 && !f->force_generic) {
+        const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
+        tiled = plan_arb_rates_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
+        if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
+    }
+    if (h_lens) {
+        if (int rc = ragged_upload(f, h_lens, stream)) return rc;
+    }
+    // (the timing bracket holds BOTH launches of the call: the walk is most of a long call, DESIGN.md 9 item 17)
+    if (int rc = timing_mark(f, stream)) return rc;
+    MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
+    if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
+        if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
+        else if (farrow) MRHIP_CHECK_HIP(launch_farrow_rates_generic(tk, fused, fa, ra, stream, &f->last_kernel));
+        else if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
+        else MRHIP_CHECK_HIP(launch_arb_rates_generic(tk, fused, a, ra, stream, &f->last_kernel));
+        if (f->H > 0) f->hist_cur = hist_next;
+    }
+    return timing_mark(f, stream);
+}
+
 // filt! on every channel, each from its own state: the schedule kernel and one filter kernel, both on the caller's stream; the host never
 // learns a count here.  Every refusal comes before anything is enqueued or changed.
 int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64_t x_stride, void *y, int64_t y_capacity, int64_t y_stride,
@@ -1758,76 +1873,38 @@ int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64
         return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small: y_stride < mrhip_outputlength_bound(x_len)");
     if (bound > 0 && !y) return fail(MRHIP_ERR_INVALID_ARG, "y is NULL");
 
-    if (int rc = adopt_stream(f, stream)) return rc;
-    const size_t entries = static_cast<size_t>(f->nch) * static_cast<size_t>(bound);
-    if (entries > f->rs_cap) {
-        const size_t cap = std::max<size_t>(entries + entries / 4, 4096);
-        if (int rc = drain_filter(f)) return rc;      // only this filter's kernels read the slices
-        if (f->d_rs_n) (void)hipFree(f->d_rs_n);
-        if (f->d_rs_acc) (void)hipFree(f->d_rs_acc);
-        f->d_rs_n = f->d_rs_acc = nullptr; f->rs_cap = 0;
-        MRHIP_CHECK_HIP(hipMalloc(&f->d_rs_n, cap * sizeof(int32_t)));
-        MRHIP_CHECK_HIP(hipMalloc(&f->d_rs_acc, cap * sizeof(double)));
-        f->rs_cap = cap;
-    }
+    return rates_call(f, x, x_len, nullptr, x_stride, y, y_stride, bound, counts_out, stream);
+}
 
-    RatesSchedArgs sa{};
-    sa.rec = f->d_rrec; sa.n_idx = static_cast<int *>(f->d_rs_n); sa.acc = static_cast<double *>(f->d_rs_acc);
-    sa.counts_out = reinterpret_cast<long long *>(counts_out);
-    sa.slice = bound; sa.x_len = x_len;
-    sa.N = static_cast<double>(f->Nphi); sa.invN = 1.0 / static_cast<double>(f->Nphi);
-    sa.nch = static_cast<int>(f->nch);
-
-    ArbArgs a{};
-    a.x = x; a.y = y; a.hist = f->d_hist[f->hist_cur]; a.taps = f->d_taps; a.dtaps = f->d_dtaps;
-    a.n_idx = sa.n_idx; a.acc = sa.acc;
-    a.x_stride = x_stride; a.y_stride = y_stride; a.x_len = x_len; a.n_out = bound;
-    a.T = static_cast<int>(f->T); a.H = static_cast<int>(f->H); a.Nphi = static_cast<int>(f->Nphi);
-    a.nch = static_cast<int>(f->nch);
-    a.dyn = nullptr;
-    const int hist_next = hist_other(f);
-    if (f->H > 0) a.fold = ShiftFold{f->d_hist[hist_next], nullptr};      // shiftin! by the kernel's last workgroup, into the other slot
-    const bool farrow = f->kind == MRHIP_FIR_FARROW;
-    FarrowArgs fa{};                // (mrhip_create_farrow_rates: the same call over the one polynomial bank)
-    if (farrow) {
-        fa.x = x; fa.y = y; fa.hist = a.hist; fa.pnfb = f->d_pnfb;
-        fa.n_idx = sa.n_idx; fa.acc = sa.acc;
-        fa.x_stride = x_stride; fa.y_stride = y_stride; fa.x_len = x_len; fa.n_out = bound;
-        fa.T = a.T; fa.H = a.H; fa.polyorder = static_cast<int>(f->polyorder);
-        fa.tap_f32 = !dtype_is_f64(f->th); fa.nch = a.nch;
-        fa.seam_below = a.T;        // every call starts a filt! (Filters.jl:819): a rates call is never a continuation piece
-        fa.dyn = nullptr;
-        fa.fold = a.fold;
-    }
-    const RatesArgs ra{f->d_rrec, bound};
-    const TypeKey tk = type_key(f);
-    const bool fused = f->numerics == MRHIP_NUMERICS_FUSED;
-    // Everything on the host that can fail comes BEFORE the schedule kernel, which moves every channel's state: the tiled kernel's plan and
-    // its grid (an occupancy query, a function attribute) and the timing bracket's first event.  Behind it only the two launches
-    // themselves are left.
-    ArbTileArgs ta;
-    size_t lds = 0;
-    long long tiled_grid = 0;
-    bool tiled = false;
-    if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
-        tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
-        if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
-    } else if (bound > 0 && !f->force_generic) {
-        const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
-        tiled = plan_arb_rates_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
-        if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
-    }
-    // (the timing bracket holds BOTH launches of the call: the walk is most of a long call, DESIGN.md 9 item 17)
-    if (int rc = timing_mark(f, stream)) return rc;
-    MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
-    if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
-        if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
-        else if (farrow) MRHIP_CHECK_HIP(launch_farrow_rates_generic(tk, fused, fa, ra, stream, &f->last_kernel));
-        else if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
-        else MRHIP_CHECK_HIP(launch_arb_rates_generic(tk, fused, a, ra, stream, &f->last_kernel));
-        if (f->H > 0) f->hist_cur = hist_next;
-    }
-    return timing_mark(f, stream);
+// filt! on every channel from its own state over its OWN number of samples (include/multirate_hip.h at the declaration): the checks of
+// mrhip_filt_device_rates with the largest length in the place of x_len, every refusal in this function's name; then the same call.
+int mrhip_filt_device_rates_ragged(mrhip_filter *f, const void *x, const int64_t *x_lens, int64_t x_stride, void *y, int64_t y_capacity,
+                                   int64_t y_stride, int64_t *counts_out, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: NULL filter");
+    if (!f->rates)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates");
+    if (y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: negative y_capacity");
+    int64_t len_max = 0;
+    if (Refusal r = check_ragged_lengths(x_lens, f->nch, x == nullptr, x_stride, &len_max)) return fail(r.status, r.message);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "mrhip_filt_device_rates_ragged: hipSetDevice failed");
+    if (stream_is_capturing(stream))
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_filt_device_rates_ragged: a filter with per-channel rates is not captured into a HIP graph (its "
+                                           "schedule buffers grow with the call)");
+    const int64_t bound = output_bound(f, len_max);
+    if (bound > (1LL << 24))
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_filt_device_rates_ragged: a call of a filter with per-channel rates holds at most 2^24 schedule "
+                                           "entries per channel: feed shorter pieces");
+    if (y_capacity < bound)
+        return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small: mrhip_filt_device_rates_ragged needs room for mrhip_outputlength_bound(the "
+                                                "largest of x_lens) outputs per channel");
+    if (f->nch > 1 && y_stride < bound)
+        return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small: mrhip_filt_device_rates_ragged needs y_stride >= mrhip_outputlength_bound(the "
+                                                "largest of x_lens)");
+    if (bound > 0 && !y) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: y is NULL");
+    return rates_call(f, x, len_max, x_lens, x_stride, y, y_stride, bound, counts_out, stream);
 }
 
 int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)

@@ -76,6 +76,9 @@ Refusal create_check_args(const CreateEntry &e, const void *h, int64_t hLen, int
 Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, CreateParams *p);
 // the rate checks of the constructors with per-channel rates and of mrhip_set_channel_rates; *rate_max: the largest rate
 Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max);
+// the length checks of mrhip_filt_device_rates_ragged, in its order: x_lens itself, every length (negative, then 2^31-1 and above), x
+// against the largest length, x_stride against it for nch > 1; *len_max: the largest length (what the call's bound is taken from)
+Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null, int64_t x_stride, int64_t *len_max);
 // (c) the banks, `rows` tap vectors of hLen taps each, one bank per row, one after the other.  taps2pfb of every row into pfb and
 // (dpfb != NULL: FIRArbitrary) of its dh = [diff(h), 0] into dpfb; returns tapsPerPhi
 int64_t create_pfb_banks(const void *h, int64_t hLen, int th, int64_t Nphi, size_t rows, std::vector<unsigned char> *pfb, std::vector<unsigned char> *dpfb);

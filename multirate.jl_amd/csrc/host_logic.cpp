@@ -703,6 +703,21 @@ Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max)
     return {};
 }
 
+Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null, int64_t x_stride, int64_t *len_max)
+{
+    if (!x_lens) return {MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: x_lens is NULL"};
+    *len_max = 0;
+    for (int64_t c = 0; c < nch; ++c) {
+        if (x_lens[c] < 0) return {MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: negative length (every channel's must be >= 0)"};
+        if (x_lens[c] >= 0x7fffffffLL)
+            return {MRHIP_ERR_UNSUPPORTED, "mrhip_filt_device_rates_ragged: a call takes fewer than 2^31-1 samples per channel"};
+        *len_max = std::max(*len_max, x_lens[c]);
+    }
+    if (*len_max > 0 && x_is_null) return {MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: x is NULL"};
+    if (nch > 1 && x_stride < *len_max) return {MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: x_stride < the largest of x_lens"};
+    return {};
+}
+
 Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, CreateParams *p)
 {
     if (e.family == kCreateRational) {

@@ -13,6 +13,8 @@
 //      the oracle.  The lanes of a wave store into slices a stride apart, an entry each per step.  Consecutive steps of a lane fill one
 //      cache line, so the L2 may gather them; nobody has measured the store path, nor the alternative of collecting 64 steps in LDS and
 //      storing whole lines.
+//      A call with per-channel input lengths (mrhip_filt_device_rates_ragged) runs rates_ragged_schedule_kernel: the same walk, every
+//      lane against its channel's own length.
 //   2. a filter kernel, a lane per (channel, output): n and acc from the channel's slice, the count from the channel's record; the
 //      universal kernel (arb_rates_generic_kernel) or the LDS-tiled one (arb_rates_tiled_kernel, behind plan_arb_rates_tiled).
 //
@@ -34,36 +36,45 @@ constexpr int kRatesSchedThreads = 64;     // one wave a workgroup: the walks of
 
 struct RateStep { double delta, N, invN; };
 
-template <bool POW2>
-__global__ __launch_bounds__(kRatesSchedThreads) void rates_schedule_kernel(RatesSchedArgs s)
+// The walk of lane c.  RAGGED: against the channel's own length (mrhip_filt_device_rates_ragged); else against the call's one length, a
+// scalar -- the statement mrhip_filt_device_rates has always run, in instantiations of its own: with the lookup decided at run time the
+// old call's walk measured 3 % slower.
+template <bool POW2, bool RAGGED>
+__device__ __forceinline__ void rates_walk(const RatesSchedArgs &s)
 {
     const int c = static_cast<int>(blockIdx.x) * kRatesSchedThreads + static_cast<int>(threadIdx.x);
     if (c >= s.nch) return;
     RateChannel *const rec = s.rec + c;
+    const long long len = RAGGED ? rates_channel_len(s.x_lens, s.x_len, c) : s.x_len;
     long long deficit = rec->inputDeficit;
     long long count = 0;
-    if (s.x_len < deficit) {                                   // :705-709: nothing but the deficit moves
-        rec->inputDeficit = deficit - s.x_len;
+    if (len < deficit) {                                       // :705-709: nothing but the deficit moves (len == 0: nothing at all)
+        rec->inputDeficit = deficit - len;
     } else {
         const RateStep step{rec->delta, s.N, s.invN};
         double acc = rec->acc;
         long long x = deficit;                                 // :715
         int *const n = s.n_idx + static_cast<long long>(c) * s.slice;
         double *const pa = s.acc + static_cast<long long>(c) * s.slice;
-        while (x <= s.x_len && count < s.slice) {              // :717 (the slice holds the call's bound: the second test never ends a walk)
+        while (x <= len && count < s.slice) {                  // :717 (the slice holds the call's bound: the second test never ends a walk)
             n[count] = static_cast<int>(x);
             pa[count] = acc;
             ++count;
             sched_step_nb<POW2>(acc, x, step);                 // :731
         }
-        if (x <= s.x_len) rec->error = MRHIP_ERR_BUFFER_TOO_SMALL;
+        if (x <= len) rec->error = MRHIP_ERR_BUFFER_TOO_SMALL;
         rec->acc = acc;
         rec->xIdx = x;
-        rec->inputDeficit = x - s.x_len;                       // :734
+        rec->inputDeficit = x - len;                           // :734
     }
     rec->count = count;
     if (s.counts_out) s.counts_out[c] = count;
 }
+
+template <bool POW2>
+__global__ __launch_bounds__(kRatesSchedThreads) void rates_schedule_kernel(RatesSchedArgs s) { rates_walk<POW2, false>(s); }
+template <bool POW2>
+__global__ __launch_bounds__(kRatesSchedThreads) void rates_ragged_schedule_kernel(RatesSchedArgs s) { rates_walk<POW2, true>(s); }
 
 __global__ __launch_bounds__(kRatesSchedThreads) void rates_reset_kernel(RateChannel *rec, int nch)
 {
@@ -103,7 +114,8 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_generic_kernel(ArbA
         }
         A::store(yc, k, A::arb_combine(lo, up, alpha));
     }
-    dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+    if (r.x_lens) dev::shiftin_ragged_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, r.x_lens, a.H, a.nch, RatesHistSource{});
+    else dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }
 
 // Persistent workgroups in the channel-major tile order (tile_run, variant_device.h).  A tile is (channel, run of tile_out = 256
@@ -141,6 +153,7 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArg
         const int ch = t.ch;
         const long long count = r.rec[ch].count;
         if (t.k0 >= count) continue;     // (uniform over the workgroup) a tile behind the channel's count
+        const long long len = rates_channel_len(r.x_lens, a.x_len, ch);      // (uniform too: the window is staged up to the channel's own end)
         const long long klast = (t.klast < count ? t.klast : count - 1);
         const int *__restrict__ nc = a.n_idx + static_cast<long long>(ch) * r.slice;
         const double *__restrict__ ac = a.acc + static_cast<long long>(ch) * r.slice;
@@ -149,7 +162,7 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArg
         const Sample *__restrict__ hc = static_cast<const Sample *>(a.hist) + static_cast<long long>(ch) * a.H;
 
         __syncthreads();   // the previous tile's reads of the window are done
-        if (w.staged) stage_window(lx, xc, hc, w.o, static_cast<int>(w.span), a.x_len, a.H, tid);
+        if (w.staged) stage_window(lx, xc, hc, w.o, static_cast<int>(w.span), len, a.H, tid);
         __syncthreads();   // (the first one of a workgroup: the banks are in LDS too)
 
         R *__restrict__ yc = A::channel_out(a.y, ch, a.y_stride);
@@ -177,7 +190,8 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArg
             A::store(yc, k, A::arb_combine(lo, up, alpha));
         }
     }
-    dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+    if (r.x_lens) dev::shiftin_ragged_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, r.x_lens, a.H, a.nch, RatesHistSource{});
+    else dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }
 
 }  // namespace
@@ -185,7 +199,8 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArg
 hipError_t launch_rates_schedule(const RatesSchedArgs &s, bool pow2, hipStream_t st)
 {
     const dim3 grid(static_cast<unsigned>((s.nch + kRatesSchedThreads - 1) / kRatesSchedThreads));
-    if (pow2) launch_kernel(rates_schedule_kernel<true>, grid, dim3(kRatesSchedThreads), 0, st, s);
+    if (s.x_lens) launch_kernel(pow2 ? rates_ragged_schedule_kernel<true> : rates_ragged_schedule_kernel<false>, grid, dim3(kRatesSchedThreads), 0, st, s);
+    else if (pow2) launch_kernel(rates_schedule_kernel<true>, grid, dim3(kRatesSchedThreads), 0, st, s);
     else launch_kernel(rates_schedule_kernel<false>, grid, dim3(kRatesSchedThreads), 0, st, s);
     return hipGetLastError();
 }

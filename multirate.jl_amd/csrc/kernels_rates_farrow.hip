@@ -80,7 +80,8 @@ __global__ __launch_bounds__(kVariantThreads) void farrow_rates_generic_kernel(F
     };
     if (P == kFarrowBankUnrolledP) channels.template operator()<kFarrowBankUnrolledP>();
     else channels.template operator()<-1>();
-    dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+    if (r.x_lens) dev::shiftin_ragged_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, r.x_lens, a.H, a.nch, RatesHistSource{});
+    else dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }
 
 // OPL Horner chains of ONE polynomial side by side, each at its own phase: the P+1 coefficients are loaded once as scalars and feed all
@@ -197,7 +198,8 @@ __global__ __launch_bounds__(kVariantThreads) void farrow_rates_multi_kernel(Far
             farrow_rates_dots<A, kFarrowBankUnrolledP, OPL>(pc, P, T, tap_f32, phase, base, seam, xc, he, yc, k_first, live);
         else farrow_rates_dots<A, -1, OPL>(pc, P, T, tap_f32, phase, base, seam, xc, he, yc, k_first, live);
     }
-    dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
+    if (r.x_lens) dev::shiftin_ragged_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, r.x_lens, a.H, a.nch, RatesHistSource{});
+    else dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }
 
 template <typename TX, typename R, int NCX>

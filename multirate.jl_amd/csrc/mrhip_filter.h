@@ -11,6 +11,7 @@ namespace mrhip {
 // zero elements either side of a device tap vector (api.hip upload_taps; kernels_fir_stream.hip plans against it)
 constexpr int kTapPad = 256;
 struct RateChannel;      // rates_arb.h
+constexpr int kRatesRaggedSlots = 4;      // staging slots for the lengths of ragged calls (include/multirate_hip.h states the number)
 }
 
 struct mrhip_filter {
@@ -36,6 +37,13 @@ struct mrhip_filter {
     mrhip::RateChannel *d_rrec = nullptr;                  // device, [nch]
     void *d_rs_n = nullptr, *d_rs_acc = nullptr;           // device: the channels' slices, [nch][bound of the call] entries
     size_t rs_cap = 0;                                     // entries either buffer holds
+    // ... and a ragged call's lengths (mrhip_filt_device_rates_ragged; api.hip: ragged_staging): pinned host slots used in turn, each
+    // guarded by the event recorded behind its upload, and the ONE device array [nch] the kernels read
+    long long *rag_pin = nullptr;                          // pinned host, [kRatesRaggedSlots][nch]
+    long long *d_xlens = nullptr;                          // device, [nch]
+    hipEvent_t rag_ev[mrhip::kRatesRaggedSlots] = {};
+    bool rag_busy[mrhip::kRatesRaggedSlots] = {};
+    int rag_next = 0;
 
     // device memory
     void *d_taps = nullptr, *d_dtaps = nullptr;            // (inside d_taps_alloc / d_dtaps_alloc: kTapPad zero elements either side)

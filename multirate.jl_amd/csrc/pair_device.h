@@ -129,6 +129,28 @@ __device__ __forceinline__ void shiftin_by_last_workgroup(const ShiftFold &sf, c
     }
 }
 
+// The ragged form (mrhip_filt_device_rates_ragged): channel ch was fed x_lens[ch] samples, so every channel folds by its own length --
+// source(i, len, H) says where element i of a channel's new history comes from (rates_hist_source, rates_arb.h: {from_hist, index}).
+// A channel of length 0 is copied across too: the call makes the OTHER slot current.  Only that form of the fold exists here (sf.done
+// == NULL: such a filter is never captured), so nothing is counted and nothing waited for: the grid's last workgroup copies.
+template <typename TX, int NC, typename Source>
+__device__ __forceinline__ void shiftin_ragged_by_last_workgroup(const ShiftFold &sf, const void *x, const void *hist, long long x_stride,
+                                                                 const long long *__restrict__ x_lens, int H, int nch, Source source)
+{
+    if (!sf.hist_new) return;                                  // (kernel argument: uniform)
+    if (blockIdx.x + 1u != gridDim.x || blockIdx.y != 0u || blockIdx.z != 0u) return;
+    const long long total = static_cast<long long>(nch) * H;
+    for (long long t = threadIdx.x; t < total; t += blockDim.x) {
+        const long long ch = t / H, i = t - ch * H;
+        const auto from = source(i, x_lens[ch], H);
+        const TX *src = from.from_hist ? static_cast<const TX *>(hist) + (ch * H + from.index) * NC
+                                       : static_cast<const TX *>(x) + (ch * x_stride + from.index) * NC;
+        TX *dst = static_cast<TX *>(sf.hist_new) + t * NC;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) dst[c] = src[c];
+    }
+}
+
 // A 16-byte LDS read, complete when the statement is (read and wait are one asm statement: no register with a read in flight, and the
 // compiler's own wait insertion -- which puts a vmcnt(0) in front of every LDS read it sees behind an LDS-DMA operation -- stays out of it)
 __device__ __forceinline__ v4u_t lds_read16_now(unsigned byte_addr)

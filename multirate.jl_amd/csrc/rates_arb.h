@@ -30,11 +30,36 @@ struct RatesSchedArgs {            // the schedule kernel: one lane per channel
     long long x_len;
     double N, invN;                // N𝜙, 1 / N𝜙
     int nch;
+    const long long *x_lens;       // NULL (mrhip_filt_device_rates: every channel is fed x_len samples), or [nch]: the channels' own lengths
 };
 
 struct RatesArgs {                 // beside ArbArgs (whose n_idx / acc are the bases of the slices, n_out the call's bound, dyn NULL)
     const RateChannel *rec;
     long long slice;
+    const long long *x_lens;       // as in RatesSchedArgs (the filter's one device array, written in stream order ahead of the call)
+};
+
+#if defined(__HIPCC__)
+#define MRHIP_RATES_HD __host__ __device__
+#else
+#define MRHIP_RATES_HD
+#endif
+
+// the samples channel c is fed by this call: its own length (mrhip_filt_device_rates_ragged), else the call's one length
+MRHIP_RATES_HD inline long long rates_channel_len(const long long *x_lens, long long x_len, int c) { return x_lens ? x_lens[c] : x_len; }
+
+// shiftin! (support.jl:61-80) of ONE channel that was fed `len` samples: the new history is the last H samples of [hist ; x[0:len)], so
+// element i (0 <= i < H) comes from the old history at index i + len when that is < H, else from x at index i + len - H.  len == 0
+// gives the old history back; len >= H takes everything from x.  The kernels' ragged epilogue and tests/rates_ragged_check.cpp run
+// this text.
+struct HistSource { bool from_hist; long long index; };
+MRHIP_RATES_HD inline HistSource rates_hist_source(long long i, long long len, int H)
+{
+    const long long e = i + len;                                 // index into [hist ; x]
+    return e < H ? HistSource{true, e} : HistSource{false, e - H};
+}
+struct RatesHistSource {           // the rule as the argument of dev::shiftin_ragged_by_last_workgroup (pair_device.h)
+    MRHIP_RATES_HD HistSource operator()(long long i, long long len, int H) const { return rates_hist_source(i, len, H); }
 };
 
 // kernels_rates_arb.hip
@@ -60,10 +85,7 @@ bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, 
 constexpr int kFarrowRatesOPL = 4;
 // the slots of lane `tid` in the tile that starts at output k0 that lie in front of the channel's count: slot j is output
 // k0 + tid + j * kVariantThreads; 0 ... kFarrowRatesOPL (the live slots are the first ones)
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline int farrow_rates_live_slots(long long k0, int tid, long long count)
+MRHIP_RATES_HD inline int farrow_rates_live_slots(long long k0, int tid, long long count)
 {
     const long long left = count - k0 - tid;                     // outputs from the lane's first slot to the count
     if (left <= 0) return 0;

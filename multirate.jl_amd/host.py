@@ -98,6 +98,7 @@ ABI = [
     ("mrhip_firdes_kaiser", _i64, [_vp, _i, _d, _d, _i, _d, _vp]),
     *_create_rows(),
     ("mrhip_filt_device_rates", _i, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    ("mrhip_filt_device_rates_ragged", _i, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     ("mrhip_get_channel_states", _i, [_vp, _vp]),
     ("mrhip_set_channel_states", _i, [_vp, _vp, _vp]),
     ("mrhip_set_channel_rates", _i, [_vp, _vp]),
@@ -775,13 +776,17 @@ class FIRFilter:
             return x.shape[0], x.shape[1], False
         raise MultirateHIPError(1, "x must be (n,) or (nchannels, n)")
 
-    def filt_into(self, buffer, x) -> int:
+    def filt_into(self, buffer, x, lengths=None) -> int:
         """filt!(buffer, self, x): writes per-channel outputs into ``buffer`` (same container kind as
         ``x``), returns the per-channel output count.  A filter with per-channel rates (``per_channel_rates``): torch device tensors
         only; ``buffer`` needs ``outputlength_bound(n)`` samples per row, row c receives its first ``counts[c]`` elements and nothing
-        else, and the int64 counts of all channels are returned (after waiting for them)."""
+        else, and the int64 counts of all channels are returned (after waiting for them).  ``lengths`` (such a filter only): one
+        input length per channel -- channel c is fed ``x[c, :lengths[c]]``, ``x`` is the ``(nchannels, max_len)`` tensor and
+        ``buffer`` needs ``outputlength_bound(max(lengths))`` per row (``mrhip_filt_device_rates_ragged``)."""
+        if lengths is not None and self._rates is None:
+            raise MultirateHIPError(1, "lengths needs a filter of FIRFilter.per_channel_rates or FIRFilter.per_channel_rates_farrow")
         if self._rates is not None:
-            counts = self._filt_into_rates(buffer, x)
+            counts = self._filt_into_rates(buffer, x, lengths=lengths)
             torch.cuda.current_stream(x.device).synchronize()
             return counts.cpu().numpy()
         nw = C.c_int64(0)
@@ -818,11 +823,12 @@ class FIRFilter:
         _check(self._lib.mrhip_filt_host(self._handle, _ptr(x), n, n, _ptr(buffer), cap, cap, C.byref(nw)))
         return nw.value
 
-    def _filt_into_rates(self, buffer, x, counts=None):
-        """``mrhip_filt_device_rates`` on torch's current stream; returns the int64 device tensor of the counts without waiting."""
+    def _filt_into_rates(self, buffer, x, counts=None, lengths=None):
+        """``mrhip_filt_device_rates`` (with ``lengths``: ``mrhip_filt_device_rates_ragged``) on torch's current stream; returns the
+        int64 device tensor of the counts without waiting.  ``lengths`` may be reused as soon as the call returns."""
         if not _is_torch(x) or not x.is_cuda or not _is_torch(buffer) or not buffer.is_cuda:
             raise MultirateHIPError(1, "a filter with per-channel rates takes torch device tensors")
-        if x.stride(-1) != 1 or buffer.stride(-1) != 1:
+        if (x.shape[-1] > 0 and x.stride(-1) != 1) or (buffer.shape[-1] > 0 and buffer.stride(-1) != 1):      # (an empty row has no stride to speak of)
             raise MultirateHIPError(1, "x and buffer must be contiguous along time (planar channels)")
         nch, n, _ = self._shape(x)
         self._ensure(_torch_np_dtype(x.dtype), nch)
@@ -840,6 +846,15 @@ class FIRFilter:
         elif not (_is_torch(counts) and counts.is_cuda and counts.dtype == torch.int64 and counts.numel() >= nch and counts.is_contiguous()):
             raise MultirateHIPError(1, "counts must be a contiguous int64 CUDA tensor of nchannels elements")
         stream = torch.cuda.current_stream(x.device).cuda_stream
+        if lengths is not None:
+            lens = np.ascontiguousarray(lengths, dtype=np.int64)
+            if lens.shape != (nch,):
+                raise MultirateHIPError(1, f"lengths takes {nch} input lengths, one per channel; got shape {lens.shape}")
+            if lens.size and int(lens.max()) > n:
+                raise MultirateHIPError(1, f"a length of {int(lens.max())} exceeds the {n} samples a row of x holds")
+            _check(self._lib.mrhip_filt_device_rates_ragged(self._handle, C.c_void_p(x.data_ptr()), _ptr(lens), xs, C.c_void_p(buffer.data_ptr()),
+                                                            cap, ys, C.c_void_p(counts.data_ptr()), C.c_void_p(stream)))
+            return counts
         _check(self._lib.mrhip_filt_device_rates(self._handle, C.c_void_p(x.data_ptr()), n, xs, C.c_void_p(buffer.data_ptr()), cap, ys,
                                                  C.c_void_p(counts.data_ptr()), C.c_void_p(stream)))
         return counts
@@ -974,9 +989,12 @@ class FIRFilter:
             raise MultirateHIPError(1, "open_ring needs a bound filter (bind(), or pass dtype and nchannels)")
         return ChunkRing(self)
 
-    def filt(self, x):
+    def filt(self, x, lengths=None):
         """filt(self, x): allocate the output, run filt!, trim to the samples written
-        (src/Filters.jl:475,519,577,633,744)."""
+        (src/Filters.jl:475,519,577,633,744).  ``lengths`` (a filter with per-channel rates only): channel c is fed
+        ``x[c, :lengths[c]]``; the list of per-channel arrays is returned as without it."""
+        if lengths is not None and self._rates is None:
+            raise MultirateHIPError(1, "lengths needs a filter of FIRFilter.per_channel_rates or FIRFilter.per_channel_rates_farrow")
         # FIRArbitrary / FIRFarrow: like the reference (Filters.jl:744-752, 841-849) allocate the outputlength
         # estimate (+2: it is only a guess there) and trim to the count filt! returns -- the exact count would need
         # the whole serial phase recurrence up front, which the library instead pipelines with the kernels.
@@ -989,8 +1007,9 @@ class FIRFilter:
                 x = torch.from_numpy(np.ascontiguousarray(x)).to(f"cuda:{self.device}")
             nch, n, one = self._shape(x)
             self._ensure(_torch_np_dtype(x.dtype), nch)
-            y = torch.empty((nch, self.outputlength_bound(n)), dtype=_np_torch_dtype(self.output_dtype), device=x.device)
-            counts = self.filt_into(y[0] if one else y, x if x.stride(-1) == 1 else x.contiguous())
+            n_max = n if lengths is None else max(int(np.max(lengths, initial=0)), 0)
+            y = torch.empty((nch, max(self.outputlength_bound(n_max), 0)), dtype=_np_torch_dtype(self.output_dtype), device=x.device)
+            counts = self.filt_into(y[0] if one else y, x if x.stride(-1) == 1 else x.contiguous(), lengths)
             rows = [y[c, :int(counts[c])] for c in range(nch)]
             return [r.cpu().numpy() for r in rows] if as_np else rows
         est_mode = self.kind in (ARBITRARY, FARROW)

@@ -588,6 +588,16 @@ function filt_device!(f::RatesFIRFilter, yptr::Ptr{Cvoid}, ycap::Integer, ystrid
                 f.handle, xptr, xlen, xstride, yptr, ycap, ystride, countsptr, stream))
     nothing
 end
+# ... with one input length per channel (a HOST vector, free for reuse on return): channel c is fed its first xlens[c] samples
+function filt_device!(f::RatesFIRFilter, yptr::Ptr{Cvoid}, ycap::Integer, ystride::Integer, xptr::Ptr{Cvoid}, xlens::Vector{Int64},
+                      xstride::Integer, ::Type{Tx}; countsptr::Ptr{Int64} = Ptr{Int64}(C_NULL), stream::Ptr{Cvoid} = C_NULL) where {Tx}
+    bind!(f, Tx)
+    length(xlens) == length(f.rates) || error("one length per channel")
+    check(ccall((:mrhip_filt_device_rates_ragged, libmr), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}),
+                f.handle, xptr, xlens, xstride, yptr, ycap, ystride, countsptr, stream))
+    nothing
+end
 # the channels' states, after waiting for the filter's stream
 function channelstates(f::RatesFIRFilter)
     out = Vector{MRHIPChannelState}(undef, length(f.rates))
@@ -613,21 +623,27 @@ reset(f::RatesFIRFilter) = (f.handle == C_NULL || check(ccall((:mrhip_reset, lib
 # filt(self, x): one channel per column of x (host memory); returns one Vector per channel, each of its own length.  The signal goes
 # to the device and the outputs come back through the HIP runtime the library is linked against.
 const libhip = "libamdhip64"
-function filt(f::RatesFIRFilter{Th}, x::Matrix{Tx}) where {Th,Tx}
+# (lengths: nothing, or one input length per channel -- channel c is fed x[1:lengths[c], c], mrhip_filt_device_rates_ragged)
+function rates_filt_host!(y::Matrix{Tb}, f::RatesFIRFilter{Th}, x::Matrix{Tx}, lengths::Union{Nothing,Vector{Int64}}) where {Tb,Th,Tx}
     size(x, 2) == length(f.rates) || error("a filter of $(length(f.rates)) rates takes that many channels")
     bind!(f, Tx)
-    Tb = promote_out(Th, Tx)
+    Tb === promote_out(Th, Tx) || error("the outputs are $(promote_out(Th, Tx))")
     n, nch = size(x)
-    cap = outputlengthbound(f, n)
+    cap = size(y, 1)
+    size(y, 2) == nch || error("one column of y per channel")
     dx, dy, dc = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
     hipcheck(e) = e == 0 || error("HIP error $e")
     hipcheck(ccall((:hipMalloc, libhip), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), dx, max(sizeof(x), 16)))
     hipcheck(ccall((:hipMalloc, libhip), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), dy, max(cap * nch * sizeof(Tb), 16)))
     hipcheck(ccall((:hipMalloc, libhip), Cint, (Ptr{Ptr{Cvoid}}, Csize_t), dc, nch * sizeof(Int64)))
-    y, counts = Matrix{Tb}(undef, cap, nch), Vector{Int64}(undef, nch)
+    counts = Vector{Int64}(undef, nch)
     try
         hipcheck(ccall((:hipMemcpy, libhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), dx[], x, sizeof(x), 1))
-        filt_device!(f, dy[], cap, cap, dx[], n, n, Tx; countsptr = Ptr{Int64}(dc[]))
+        if lengths === nothing
+            filt_device!(f, dy[], cap, cap, dx[], n, n, Tx; countsptr = Ptr{Int64}(dc[]))
+        else
+            filt_device!(f, dy[], cap, cap, dx[], lengths, n, Tx; countsptr = Ptr{Int64}(dc[]))
+        end
         hipcheck(ccall((:hipDeviceSynchronize, libhip), Cint, ()))
         hipcheck(ccall((:hipMemcpy, libhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), y, dy[], sizeof(y), 2))
         hipcheck(ccall((:hipMemcpy, libhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), counts, dc[], sizeof(counts), 2))
@@ -636,7 +652,26 @@ function filt(f::RatesFIRFilter{Th}, x::Matrix{Tx}) where {Th,Tx}
             p == C_NULL || ccall((:hipFree, libhip), Cint, (Ptr{Cvoid},), p)
         end
     end
-    [y[1:counts[c], c] for c in 1:nch]
+    counts
+end
+function filt(f::RatesFIRFilter{Th}, x::Matrix{Tx}) where {Th,Tx}
+    bind!(f, Tx)
+    y = Matrix{promote_out(Th, Tx)}(undef, outputlengthbound(f, size(x, 1)), size(x, 2))
+    counts = rates_filt_host!(y, f, x, nothing)
+    [y[1:counts[c], c] for c in 1:size(x, 2)]
+end
+# Per-channel input lengths (mrhip_filt_device_rates_ragged): channel c is fed X[1:lengths[c], c] -- receivers off their own clocks
+# deliver different numbers of samples per interval.  Y needs outputlengthbound(f, maximum(lengths)) rows; column c receives its first
+# counts[c] elements and nothing else; the counts are returned.
+function filt!(Y::Matrix, f::RatesFIRFilter, X::Matrix, lengths::Vector{<:Integer})
+    (length(lengths) == length(f.rates) && all(l -> 0 <= l <= size(X, 1), lengths)) || error("one length in 0:size(X, 1) per channel")
+    rates_filt_host!(Y, f, X, Vector{Int64}(lengths))
+end
+function filt(f::RatesFIRFilter{Th}, X::Matrix{Tx}, lengths::Vector{<:Integer}) where {Th,Tx}
+    bind!(f, Tx)
+    Y = Matrix{promote_out(Th, Tx)}(undef, outputlengthbound(f, maximum(lengths; init = 0)), size(X, 2))
+    counts = filt!(Y, f, X, lengths)
+    [Y[1:counts[c], c] for c in 1:size(X, 2)]
 end
 
 outputlengthbound(f::FIRFilter, n::Integer) = Int(ccall((:mrhip_outputlength_bound, libmr), Int64, (Ptr{Cvoid}, Int64), f.handle, n))
