@@ -292,7 +292,9 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     keeps the current rates;
  *   - the call length is shared through mrhip_filt_device_rates; mrhip_filt_device_rates_ragged feeds every channel its own number of
  *     samples (both filters with per-channel rates; the contract stands at its declaration);
- *   - left out on purpose: complex or per-channel taps combined with per-channel rates; evaluating
+ *   - per-channel taps on top of the per-channel rates: mrhip_set_channel_taps ("Per-channel taps with per-channel rates for
+ *     FIRArbitrary", below);
+ *   - left out on purpose: complex taps combined with per-channel rates; evaluating
  *     a long channel's schedule with the parallel tables / chain / emit machinery instead of the serial walk (the next speed step
  *     for few long channels); graph capture, rings, cascades and sharding of such a filter; a mrhip_filt_device_multi that serves
  *     FIRArbitrary streams in one launch. */
@@ -324,8 +326,9 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     bracket around both launches, and every entry point that carries ONE state or ONE count refuses the filter;
  *   - kernels: farrow_rates_generic (any shape) and farrow_rates_multi (four outputs a lane share each tap's scalar coefficient loads;
  *     MRHIP_FARROW_RATES_MULTI = 1 selects it, the default rule selects it nowhere until measurements say where);
- *   - left out on purpose: complex or per-channel taps combined with per-channel rates; graph capture, rings, cascades and sharding of
- *     such a filter; the parallel schedule for long channels, which stays the named next speed step and is shared by both filters. */
+ *   - left out on purpose: complex or per-channel taps combined with per-channel rates (FIRArbitrary has the per-channel taps:
+ *     mrhip_set_channel_taps; here they need the fit of every row and a Horner kernel over a bank per channel); graph capture, rings,
+ *     cascades and sharding of such a filter; the parallel schedule for long channels, which stays the named next speed step and is shared by both filters. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
 
@@ -679,6 +682,43 @@ int mrhip_set_channel_states(mrhip_filter *f, const int64_t *inputDeficit, const
  * history through mrhip_set_history.  mrhip_reset restores the constructor state and KEEPS the current rates.  A filter without
  * per-channel rates: MRHIP_ERR_INVALID_ARG. */
 int mrhip_set_channel_rates(mrhip_filter *f, const double *rates /* [nchannels] */);
+/* Per-channel taps with per-channel rates for FIRArbitrary (mrhip_set_channel_taps on a filter of mrhip_create_arbitrary_rates): one
+ * FIRFilter(h_c, rates[c], Nphi) per channel behind one handle, taps AND rate differing per channel -- receivers each off its own clock
+ * and each with its own front-end equaliser or calibration filter, per-emitter Doppler time-scale correction with the emitter's own
+ * matched pulse; and taps that adapt at run time (a block-LMS equaliser) as the rates do through mrhip_set_channel_rates.  The feature
+ * is a CALL on an existing filter, the twin of mrhip_set_channel_rates, not a constructor.
+ *   - h holds nchannels rows of hLen taps, row-major, row c = h_c: the layout of mrhip_create_arbitrary_bank;
+ *   - filter kinds: f must come from mrhip_create_arbitrary_rates.  A filter of mrhip_create_farrow_rates* answers MRHIP_ERR_UNSUPPORTED
+ *     (left out: it needs the fit of every row and a Horner kernel over a bank per channel; the message says so); any other filter
+ *     answers MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps takes a filter of mrhip_create_arbitrary_rates";
+ *   - argument checks: h == NULL is MRHIP_ERR_INVALID_ARG; hLen other than the filter's hLen is MRHIP_ERR_INVALID_ARG (tapsPerPhi, the
+ *     history length and the history do not change); a complex tap_dtype is MRHIP_ERR_UNSUPPORTED (complex taps with per-channel rates
+ *     are left out); a real tap_dtype other than the filter's is MRHIP_ERR_INVALID_ARG;
+ *   - effect: every row goes through dh_c = [diff(h_c), 0] in the tap type and the two taps2pfb calls, exactly as
+ *     mrhip_create_arbitrary_bank builds and widens its banks; the call waits for the filter's stream (as mrhip_set_channel_rates
+ *     does), then installs nchannels pfb and nchannels dpfb banks on the device: nchannels * 2 * Nphi * tapsPerPhi * sizeof(R) bytes,
+ *     allocated by the first call and reused by every later one.  Everything that can fail -- the checks, the host banks, the first
+ *     call's allocation -- happens BEFORE anything of the filter changes: a refused or failed call leaves the filter bit for bit as
+ *     it was;
+ *   - parity: from the next call on channel c is bit for bit mrhip_create_arbitrary(h_c, rates[c], Nphi, nchannels = 1) fed x_c, that
+ *     filter given channel c's (inputDeficit, phiAccumulator) through mrhip_set_state and its history through mrhip_set_history:
+ *     the outputs, the count of every call, the end state and the history, under STRICT and under FUSED, through
+ *     mrhip_filt_device_rates and mrhip_filt_device_rates_ragged, including the short-input path of filt! (src/Filters.jl:705-709)
+ *     and a channel of ragged length 0;
+ *   - state: phiAccumulator, inputDeficit, rates and history stay untouched.  Called again the function replaces the taps: they may
+ *     change between calls.  mrhip_reset keeps the current taps, as it keeps the current rates.  mrhip_set_channel_rates,
+ *     mrhip_set_channel_states, mrhip_set_numerics, mrhip_set_history*, mrhip_outputlength_bound and mrhip_set_mod_form work as before;
+ *   - tap queries: after a successful call mrhip_get_taps and mrhip_arbitrary_tapsforphase answer in the layout of "Per-channel taps
+ *     for FIRArbitrary" -- nchannels banks or rows one after the other; before it they answer as on any filter of
+ *     mrhip_create_arbitrary_rates;
+ *   - kernels: arb_rates_bank_generic (any shape) and arb_rates_bank_tiled (ONE channel's two banks in LDS, reloaded when a
+ *     workgroup's run crosses into another channel; MRHIP_ARB_RATES_BANK_TILED = 1 selects it wherever its plan fits);
+ *     MRHIP_FORCE_GENERIC = 1 keeps the universal one;
+ *   - a filter on which the function was never called runs the launches, kernels and messages it always ran; every entry point that
+ *     refuses a filter with per-channel rates keeps refusing; the ABI version stays 1;
+ *   - left out on purpose: FIRFarrow; complex taps; going back to shared taps; a stream-ordered update without the host wait (it
+ *     needs double-buffered banks); graph capture, rings, cascades and sharding; the parallel schedule for long channels. */
+int mrhip_set_channel_taps(mrhip_filter *f, const void *h /* [nchannels][hLen] */, int64_t hLen, int tap_dtype);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call
@@ -844,7 +884,8 @@ int mrhip_timing_read(mrhip_filter *f, int64_t *n_launches, double *total_ms);
  * per-channel rates are reported as arb_rates_generic and arb_rates_tiled, without the suffix the other names carry: the table of
  * write-only-own-outputs cases (tests/output_bounds_cases.py) is keyed by the suffixed names in the sources, and these two kernels'
  * cases live in tests/test_gpu_rates_arb.py until they move into that table.  The same holds for farrow_rates_generic and
- * farrow_rates_multi (FIRFarrow with per-channel rates; their cases: tests/test_gpu_rates_farrow.py). */
+ * farrow_rates_multi (FIRFarrow with per-channel rates; their cases: tests/test_gpu_rates_farrow.py), and for arb_rates_bank_generic
+ * and arb_rates_bank_tiled (per-channel taps with per-channel rates; their cases: tests/test_gpu_rates_bank_arb.py). */
 const char *mrhip_last_kernel_name(const mrhip_filter *f);
 /* How the phase schedule of a FIRArbitrary / FIRFarrow filter -- update(), src/Filters.jl:663-673 and :780-792 -- has
  * been evaluated so far.  info[0..n) receives, as far as n reaches:

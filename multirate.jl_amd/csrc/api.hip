@@ -1826,6 +1826,10 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
         tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
         if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
+    } else if (bound > 0 && !f->force_generic && tk.bank) {      // (mrhip_set_channel_taps: kernels_rates_bank_arb.hip; no plan_* below sees such a call)
+        const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
+        tiled = plan_arb_rates_bank_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
+        if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_bank_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
     } else if (bound > 0 && !f->force_generic) {
         const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
         tiled = plan_arb_rates_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
@@ -1840,6 +1844,8 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
         if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
         else if (farrow) MRHIP_CHECK_HIP(launch_farrow_rates_generic(tk, fused, fa, ra, stream, &f->last_kernel));
+        else if (tk.bank && tiled) MRHIP_CHECK_HIP(launch_arb_rates_bank_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
+        else if (tk.bank) MRHIP_CHECK_HIP(launch_arb_rates_bank_generic(tk, fused, a, ra, stream, &f->last_kernel));
         else if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
         else MRHIP_CHECK_HIP(launch_arb_rates_generic(tk, fused, a, ra, stream, &f->last_kernel));
         if (f->H > 0) f->hist_cur = hist_next;
@@ -1969,6 +1975,56 @@ int mrhip_set_channel_rates(mrhip_filter *f, const double *rates)
     f->h_rates.assign(rates, rates + f->nch);
     f->rate = rate_max;
     f->delta = static_cast<double>(f->Nphi) / rate_max;
+    return MRHIP_OK;
+}
+
+// Per-channel taps on a filter of mrhip_create_arbitrary_rates (include/multirate_hip.h, "Per-channel taps with per-channel rates for
+// FIRArbitrary"): nch pfb and nch dpfb banks in the place of the shared pair -- create_pfb_banks with rows = nch, widened to R as
+// upload_taps widens mrhip_create_arbitrary_bank's.  Checks, host banks and the first call's two allocations come before anything of the
+// filter changes; then the call waits for the filter's stream (the kernels enqueued so far read the banks) and installs the new ones.
+// Records, rates, history and the schedule buffers stay; TypeKey::bank is set from here on (rates_call: kernels_rates_bank_arb.hip).
+int mrhip_set_channel_taps(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
+    if (Refusal r = check_channel_taps(f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th)) return fail(r.status, r.message);
+    std::vector<unsigned char> pfb, dpfb;
+    (void)create_pfb_banks(h, hLen, tap_dtype, f->Nphi, static_cast<size_t>(f->nch), &pfb, &dpfb);
+    const size_t n = pfb.size() / dtype_scalar_size(f->th), rsize = f->r_f64 ? 8 : 4;
+    std::vector<double> wide[2];                                    // Float32 taps under Float64 arithmetic: widened exactly
+    const void *src[2] = {pfb.data(), dpfb.data()};
+    if (f->r_f64 && !dtype_is_f64(f->th))
+        for (int b = 0; b < 2; ++b) {
+            const float *s = static_cast<const float *>(src[b]);
+            wide[b].assign(s, s + n);
+            src[b] = wide[b].data();
+        }
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
+    void *d_new[2] = {f->d_taps, f->d_dtaps};                       // (a later call: the banks of the first one, reused)
+    if (!f->bank) {
+        d_new[0] = d_new[1] = nullptr;
+        if (hipMalloc(&d_new[0], n * rsize) != hipSuccess || hipMalloc(&d_new[1], n * rsize) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d_new[0]) (void)hipFree(d_new[0]);
+            return fail(MRHIP_ERR_HIP, "mrhip_set_channel_taps: no device memory for the channels' filter banks");
+        }
+    }
+    int rc = drain_filter(f);
+    for (int b = 0; b < 2 && !rc; ++b)                                  // (complete on return)
+        if (hipMemcpy(d_new[b], src[b], n * rsize, hipMemcpyHostToDevice) != hipSuccess) rc = fail(MRHIP_ERR_HIP, "mrhip_set_channel_taps: uploading the filter banks failed");
+    if (rc) {
+        if (!f->bank) { (void)hipFree(d_new[0]); (void)hipFree(d_new[1]); }
+        return rc;
+    }
+    if (!f->bank) {
+        (void)hipFree(f->d_taps_alloc);
+        (void)hipFree(f->d_dtaps_alloc);
+        f->d_taps = f->d_taps_alloc = d_new[0];
+        f->d_dtaps = f->d_dtaps_alloc = d_new[1];
+        f->bank = true;
+    }
+    f->h_taps.swap(pfb);
+    f->h_dtaps.swap(dpfb);
     return MRHIP_OK;
 }
 

@@ -76,6 +76,8 @@ Refusal create_check_args(const CreateEntry &e, const void *h, int64_t hLen, int
 Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, CreateParams *p);
 // the rate checks of the constructors with per-channel rates and of mrhip_set_channel_rates; *rate_max: the largest rate
 Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max);
+// the checks of mrhip_set_channel_taps that need no device: the filter's kind, h, hLen and the tap type against the filter's own
+Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th);
 // the length checks of mrhip_filt_device_rates_ragged, in its order: x_lens itself, every length (negative, then 2^31-1 and above), x
 // against the largest length, x_stride against it for nch > 1; *len_max: the largest length (what the call's bound is taken from)
 Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null, int64_t x_stride, int64_t *len_max);

@@ -346,6 +346,36 @@ bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, 
     return true;
 }
 
+// arb_rates_bank_tiled_kernel (per-channel RATES and per-channel TAPS, kernels_rates_bank_arb.hip): the LDS geometry of
+// plan_arb_bank_tiled -- ONE channel's pfb and dpfb (column pitch T + 1) plus the sample tile at two workgroups a CU (78 KiB a
+// workgroup); one channel a lane (cpl = 1) -- and the tiling and span of plan_arb_rates_tiled: n_out is the call's bound (the counts
+// are on the device), the kernel skips the tiles at or behind a channel's count, the span is planned for the SLOWEST channel (rate_min)
+// and cut to the room only when the kernel is forced.  The default rule takes the calls the measured rows cover (DESIGN.md 9 item 21,
+// profiles/r12/arb_rates_bank.txt, both runs): the tiled kernel beat the universal one by far more than the spread of the repeats at
+// 4096 ch x 1e4 (360 448 tiles of 88 a channel: 2.804 against 3.105 ms and 2.797 against 3.122, spreads <= 0.053) and at 256 ch x 1e5
+// (225 024 tiles of 879 a channel: 18.101 against 23.016 ms and 18.119 against 23.027, spreads <= 0.035), and did not at 64 ch x 1e6
+// (8790 tiles a channel: 464.8 against 459.2 ms and 431.4 against 479.8 with spreads of 29 to 55 -- the serial walk is the call).  So:
+// from kArbRatesBankTiledMinTiles tiles, up to kArbRatesBankTiledMaxPerChannel tiles a channel, and never with a cut span; every other
+// call stays on the universal kernel unless MRHIP_ARB_RATES_BANK_TILED=1 forces the tiled one.  As for plan_arb_rates_tiled both limits
+// are GUARDS ON UNMEASURED GROUND, not causes: nothing about 880 tiles a channel makes the tiled kernel worse (at 8790 the rows cannot
+// tell the kernels apart because the walk hides them), and a call of fewer tiles falls back only because no smaller row was measured.
+constexpr long long kArbRatesBankTiledMinTiles = 225024, kArbRatesBankTiledMaxPerChannel = 879;
+bool plan_arb_rates_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int /*num_cus*/, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate_min > 0.0)) return false;
+    const int TP = a.T + 1;
+    const size_t bank_elems = static_cast<size_t>(a.Nphi) * TP;
+    const size_t banks_bytes = (2 * bank_elems * variant_tap_bytes(tk) + 15) / 16 * 16;
+    const ArbVariantShape v{banks_bytes, 78 * 1024, 78 * 1024, TP, static_cast<int>(bank_elems), 1, false};
+    ArbTileArgs ta;
+    size_t bytes;
+    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate_min, mode == 1, &ta, &bytes)) return false;
+    if (mode != 1 && (ta.total_tiles < kArbRatesBankTiledMinTiles || ta.tiles_per_channel > kArbRatesBankTiledMaxPerChannel)) return false;
+    *out = ta;
+    *lds = bytes;
+    return true;
+}
+
 // farrow_rates_multi_kernel (FIRFarrow with per-channel RATES, kernels_rates_farrow.hip): no LDS -- the one polynomial bank is read as
 // scalar operands, the windows from global memory -- so the plan is the tiling alone: a tile is kFarrowRatesOPL consecutive runs of
 // kVariantThreads outputs of one channel, one channel a lane (cpl = 1), and the tiling goes by n_out, the call's bound (the counts are
@@ -700,6 +730,25 @@ Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max)
         if (rates[c] < 1.0 / static_cast<double>(1LL << 30)) return {MRHIP_ERR_UNSUPPORTED, "a per-channel rate below 2^-30"};
         *rate_max = std::max(*rate_max, rates[c]);
     }
+    return {};
+}
+
+// mrhip_set_channel_taps (the public header, "Per-channel taps with per-channel rates for FIRArbitrary"): what the call refuses
+// before it touches the device, in its order -- the filter (is_rates: of a *_rates constructor; is_farrow), then h, hLen and the tap type
+// against the filter's own (f_hLen, f_th)
+Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th)
+{
+    if (is_rates && is_farrow)
+        return {MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps: FIRFarrow with per-channel taps and per-channel rates is left out (it needs the fit of every "
+                                       "row and a Horner kernel over a bank per channel); mrhip_create_arbitrary_rates filters take the call"};
+    if (!is_rates) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps takes a filter of mrhip_create_arbitrary_rates"};
+    if (!h) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: h is NULL"};
+    if (hLen != f_hLen)
+        return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: hLen must be the filter's (" + std::to_string(f_hLen) + " taps a channel; got " +
+                                       std::to_string(hLen) + "): tapsPerPhi, the history length and the history do not change"};
+    if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: bad tap dtype"};
+    if (dtype_is_complex(th)) return {MRHIP_ERR_UNSUPPORTED, std::string("mrhip_set_channel_taps: ") + kRatesHint + " (the taps are Float32 / Float64)"};
+    if (th != f_th) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: the taps must have the filter's tap dtype"};
     return {};
 }
 

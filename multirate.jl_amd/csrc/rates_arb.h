@@ -74,7 +74,21 @@ hipError_t launch_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbArgs &
 // host_logic.cpp: the switch value passed in (MRHIP_ARB_RATES_TILED: 0 never, 1 wherever the plan fits, -1 the default rule)
 bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, int mode, ArbTileArgs *out, size_t *lds);
 
-// ---- FIRFarrow with per-channel rates (mrhip_create_farrow_rates; include/multirate_hip.h, "Per-channel rates for FIRFarrow") --------
+// ---- FIRArbitrary with per-channel rates AND per-channel taps (mrhip_set_channel_taps on a filter of mrhip_create_arbitrary_rates;
+// include/multirate_hip.h, "Per-channel taps with per-channel rates for FIRArbitrary") ---------------------------------------------------
+// Records, slices, schedule kernel and RatesArgs above serve it unchanged; ArbArgs::taps / dtaps hold nch banks, [nch][Nphi][T] in R,
+// and TypeKey::bank is set.
+// kernels_rates_bank_arb.hip
+hipError_t launch_arb_rates_bank_generic(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
+bool plan_arb_rates_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, ArbTileArgs *out, size_t *lds);   // (reads MRHIP_ARB_RATES_BANK_TILED)
+// the tiled kernel's persistent grid (occupancy query, LDS attribute; MRHIP_ARB_RATES_BANK_GRID): what can fail ahead of the launch
+hipError_t prepare_arb_rates_bank_tiled(const TypeKey &tk, bool fused, const ArbTileArgs &ta, size_t lds, int num_cus, long long *grid);
+hipError_t launch_arb_rates_bank_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, const ArbTileArgs &ta, size_t lds,
+                                       long long grid, hipStream_t s, const char **kname);
+// host_logic.cpp: the switch value passed in (MRHIP_ARB_RATES_BANK_TILED: 0 never, 1 wherever the plan fits, -1 the default rule)
+bool plan_arb_rates_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, int mode, ArbTileArgs *out, size_t *lds);
+
+// ---- FIRFarrow with per-channel rates (mrhip_create_farrow_rates;include/multirate_hip.h, "Per-channel rates for FIRFarrow") --------
 // The schedule kernel, the records, the reset kernel and RatesArgs above serve it unchanged: update() of FIRFarrow (Filters.jl:780-786)
 // is FIRArbitrary's recurrence on the same Float64 quantity, and the constructor state (:141-144) is the one rates_reset_kernel writes
 // (𝜙Idx = 1.0 is the accumulator, inputDeficit = xIdx = 1).  RatesArgs stands beside FarrowArgs (n_idx / acc: the bases of the slices,

@@ -102,6 +102,7 @@ ABI = [
     ("mrhip_get_channel_states", _i, [_vp, _vp]),
     ("mrhip_set_channel_states", _i, [_vp, _vp, _vp]),
     ("mrhip_set_channel_rates", _i, [_vp, _vp]),
+    ("mrhip_set_channel_taps", _i, [_vp, _vp, _i64, _i]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -327,6 +328,7 @@ class FIRFilter:
         self.polyorder = None
         self._pnfb_in = None
         self._rates = None                # per-channel rates (FIRFilter.per_channel_rates, .per_channel_rates_farrow): Float64, one per channel; self.rate is the largest
+        self._chan_taps = None            # per-channel taps ON TOP of per-channel rates (FIRFilter.set_channel_taps, .per_channel_taps_and_rates): the (nchannels, hLen) matrix, installed by mrhip_set_channel_taps
         self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow, .per_channel_complex_taps_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
@@ -447,6 +449,21 @@ class FIRFilter:
         r = cls._checked_rates(rates, "per_channel_rates")
         f = cls(h, float(r.max()), int(Nphi), device=device, numerics=numerics)
         f._rates = r
+        return f
+
+    @classmethod
+    def per_channel_taps_and_rates(cls, H, rates, Nphi: int = 32, *, device: int = 0, numerics: int = NUMERICS_STRICT):
+        """One FIRFilter(H[c], rates[c]::Float, N𝜙) per channel behind one filter object: FIRArbitrary with per-channel taps AND
+        per-channel rates (receivers each off its own clock, each with its own front-end equaliser or calibration filter; per-emitter
+        Doppler correction with the emitter's own matched pulse).  ``H``: shape (nchannels, hLen), Float32 or Float64; ``rates``: one
+        rate > 0 per channel.  It is the filter of ``per_channel_rates(H[0], rates, Nphi)`` followed by ``set_channel_taps(H)``:
+        channel c is bit for bit ``FIRFilter(H[c], rates[c], Nphi)`` fed ``x[c]``, under STRICT and FUSED (include/multirate_hip.h:
+        per-channel taps with per-channel rates for FIRArbitrary).  ``taps(which)`` has shape (nchannels, tapsPer𝜙, N𝜙) and
+        ``tapsforphase`` (nchannels, tapsPer𝜙); everything else behaves as on the filter of ``per_channel_rates``."""
+        who = "per_channel_taps_and_rates"
+        H = _as_taps(_tap_matrix(_real_taps(H, who, "complex taps with per-channel rates are left out"), who))
+        f = cls.per_channel_rates(H[0], rates, Nphi, device=device, numerics=numerics)
+        f.set_channel_taps(H)
         return f
 
     @staticmethod
@@ -571,6 +588,8 @@ class FIRFilter:
         self._handle, self._tx, self._nch = out, tx, nch
         if self.numerics != NUMERICS_STRICT:
             _check(self._lib.mrhip_set_numerics(self._handle, self.numerics))
+        if self._chan_taps is not None:                              # (set_channel_taps on the unbound filter)
+            _check(self._lib.mrhip_set_channel_taps(self._handle, _ptr(self._chan_taps), self._chan_taps.shape[1], _NP2DT[self._chan_taps.dtype]))
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -639,7 +658,7 @@ class FIRFilter:
         shape (nchannels, tapsPer𝜙, N𝜙)."""
         if self._handle is None:
             raise MultirateHIPError(1, "taps() needs a bound filter")
-        if self._bank is not None:
+        if self._bank is not None or self._chan_taps is not None:
             out = np.zeros((self._nch, self.Nphi, self.tapsPerPhi), dtype=self.h.dtype)
             _check(self._lib.mrhip_get_taps(self._handle, which, _ptr(out)))
             return out.transpose(0, 2, 1).copy()
@@ -662,7 +681,8 @@ class FIRFilter:
         tapsforphase(kernel::FIRFarrow, phase), src/Filters.jl:764-775."""
         if self._handle is None or self.kind not in (ARBITRARY, FARROW):
             raise MultirateHIPError(1, "tapsforphase() needs a bound FIRArbitrary or FIRFarrow filter")
-        rows = (self._nch, self.tapsPerPhi) if self._bank is not None else self.tapsPerPhi   # (a per-channel filter: one row per channel)
+        banks = self._bank is not None or (self._chan_taps is not None and self.kind == ARBITRARY)
+        rows = (self._nch, self.tapsPerPhi) if banks else self.tapsPerPhi   # (a per-channel filter: one row per channel)
         out = np.zeros(rows, dtype=self.h.dtype)
         fn = self._lib.mrhip_farrow_tapsforphase if self.kind == FARROW else self._lib.mrhip_arbitrary_tapsforphase
         _check(fn(self._handle, float(phase), _ptr(out)))
@@ -897,6 +917,27 @@ class FIRFilter:
         if self._handle is not None:
             _check(self._lib.mrhip_set_channel_rates(self._handle, _ptr(r)))
         self._rates, self.rate = r, float(r.max())
+
+    def set_channel_taps(self, H):
+        """Per-channel taps on a filter of ``per_channel_rates`` (``mrhip_set_channel_taps``; waits for the filter's stream): ``H`` has
+        shape (nchannels, hLen) in the filter's tap dtype, row c replaces ``h`` for channel c.  phiAccumulator, inputDeficit, rates and
+        history stay; channel c continues bit for bit as ``FIRFilter(H[c], rates[c], Nphi)`` given its state and history would.  The
+        taps may change between calls (an adaptive equaliser); ``reset()`` keeps the current taps.  From then on ``taps(which)`` has
+        shape (nchannels, tapsPer𝜙, N𝜙) and ``tapsforphase`` (nchannels, tapsPer𝜙).  Unbound: the taps are installed at ``bind``.
+        FIRArbitrary only (``per_channel_rates_farrow``: status 5); complex taps: status 5."""
+        if self._rates is None:
+            raise MultirateHIPError(1, "set_channel_taps needs a filter of FIRFilter.per_channel_rates")
+        if self.kind != ARBITRARY:
+            raise MultirateHIPError(5, "set_channel_taps: FIRFarrow with per-channel taps and per-channel rates is left out (FIRFilter.per_channel_rates takes the call)")
+        H = _tap_matrix(_real_taps(H, "set_channel_taps", "complex taps with per-channel rates are left out"), "set_channel_taps")
+        if H.shape != (len(self._rates), len(self.h)):
+            raise MultirateHIPError(1, f"set_channel_taps takes a {(len(self._rates), len(self.h))} matrix, one row of the filter's hLen taps per channel; got {H.shape}")
+        if H.dtype != self.h.dtype:
+            raise MultirateHIPError(1, f"set_channel_taps takes taps of the filter's tap dtype {self.h.dtype}; got {H.dtype}")
+        H = np.ascontiguousarray(H).copy()
+        if self._handle is not None:
+            _check(self._lib.mrhip_set_channel_taps(self._handle, _ptr(H), H.shape[1], _NP2DT[H.dtype]))
+        self._chan_taps = H
 
     def outputlength_bound(self, inputlength: int) -> int:
         """The largest per-channel output count a call of ``inputlength`` samples can have whatever the stream state

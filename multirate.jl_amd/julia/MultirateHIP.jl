@@ -537,6 +537,7 @@ struct MRHIPChannelState
 end
 mutable struct RatesFIRFilter{Th}
     h::Vector{Th}
+    H::Union{Nothing,Matrix{Th}}    # per-channel taps (set_channel_taps!): one column of hLen taps per channel, installed at bind!
     rates::Vector{Float64}
     Nphi::Int
     polyorder::Int                  # -1: FIRArbitrary (mrhip_create_arbitrary_rates); >= 0: FIRFarrow (mrhip_create_farrow_rates)
@@ -547,7 +548,7 @@ end
 function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
-    f = RatesFIRFilter{Th}(copy(h), Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing)
+    f = RatesFIRFilter{Th}(copy(h), nothing, Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 # FIRFilter(h, rates::Vector, N𝜙, polyorder): one FIRFilter(h, rates[c], N𝜙, polyorder) -- FIRFarrow -- per channel behind one object
@@ -556,7 +557,7 @@ function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer,
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
     0 <= polyorder <= min(32, Nphi - 1) || error("polyorder must be in 0..min(32, Nphi-1)")
-    f = RatesFIRFilter{Th}(copy(h), Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing)
+    f = RatesFIRFilter{Th}(copy(h), nothing, Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
@@ -575,7 +576,25 @@ function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
                     f.h, length(f.h), dtypecode(Th), f.rates, f.Nphi, dtypecode(Tx), length(f.rates), f.device, out))
     end
     f.handle, f.Tx = out[], Tx
+    f.H === nothing || set_channel_taps!(f, f.H)
     f
+end
+# per-channel taps on top of the per-channel rates (mrhip_set_channel_taps; include/multirate_hip.h, "Per-channel taps with per-channel
+# rates for FIRArbitrary"): column c of H is channel c's h_c, size(H) == (length(f.h), nchannels).  Every channel keeps its phase, deficit,
+# rate and history; the taps may change between calls (the call waits for the filter's stream); reset keeps the current taps.  An unbound
+# filter installs them at bind!.  FIRArbitrary only.
+function set_channel_taps!(f::RatesFIRFilter{Th}, H::Matrix{Th}) where {Th}
+    f.polyorder < 0 || error("per-channel taps with per-channel rates: FIRArbitrary only")
+    size(H) == (length(f.h), length(f.rates)) || error("H takes one column of $(length(f.h)) taps per channel")
+    f.handle == C_NULL || check(ccall((:mrhip_set_channel_taps, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint), f.handle, H, size(H, 1), dtypecode(Th)))
+    f.H = copy(H)
+    f
+end
+# FIRFilter(H::Matrix, rates::Vector, N𝜙): one FIRFilter(H[:, c], rates[c], N𝜙) per channel behind one object -- the filter of
+# FIRFilter(H[:, 1], rates, N𝜙) with set_channel_taps!(f, H)
+function FIRFilter(H::Matrix{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
+    size(H, 2) == length(rates) || error("one column of taps and one rate per channel")
+    set_channel_taps!(FIRFilter(H[:, 1], rates, Nphi; device = device), H)
 end
 outputlengthbound(f::RatesFIRFilter, n::Integer) = Int(ccall((:mrhip_outputlength_bound, libmr), Int64, (Ptr{Cvoid}, Int64), f.handle, n))
 # x and y are (n x nchannels) column-major on the filter's device, ycap and ystride at least outputlengthbound(f, xlen); countsptr
