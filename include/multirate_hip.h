@@ -326,8 +326,9 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     bracket around both launches, and every entry point that carries ONE state or ONE count refuses the filter;
  *   - kernels: farrow_rates_generic (any shape) and farrow_rates_multi (four outputs a lane share each tap's scalar coefficient loads;
  *     MRHIP_FARROW_RATES_MULTI = 1 selects it, the default rule selects it nowhere until measurements say where);
- *   - left out on purpose: complex or per-channel taps combined with per-channel rates (FIRArbitrary has the per-channel taps:
- *     mrhip_set_channel_taps; here they need the fit of every row and a Horner kernel over a bank per channel); graph capture, rings,
+ *   - per-channel taps on top of the per-channel rates: mrhip_set_channel_taps_farrow and mrhip_set_channel_pnfb ("Per-channel taps
+ *     with per-channel rates for FIRFarrow", below);
+ *   - left out on purpose: complex taps combined with per-channel rates; graph capture, rings,
  *     cascades and sharding of such a filter; the parallel schedule for long channels, which stays the named next speed step and is shared by both filters. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
@@ -689,7 +690,8 @@ int mrhip_set_channel_rates(mrhip_filter *f, const double *rates /* [nchannels] 
  * is a CALL on an existing filter, the twin of mrhip_set_channel_rates, not a constructor.
  *   - h holds nchannels rows of hLen taps, row-major, row c = h_c: the layout of mrhip_create_arbitrary_bank;
  *   - filter kinds: f must come from mrhip_create_arbitrary_rates.  A filter of mrhip_create_farrow_rates* answers MRHIP_ERR_UNSUPPORTED
- *     (left out: it needs the fit of every row and a Horner kernel over a bank per channel; the message says so); any other filter
+ *     (not this call's: it needs the fit of every row; the message names mrhip_set_channel_taps_farrow and mrhip_set_channel_pnfb, which
+ *     take such a filter -- "Per-channel taps with per-channel rates for FIRFarrow", below); any other filter
  *     answers MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps takes a filter of mrhip_create_arbitrary_rates";
  *   - argument checks: h == NULL is MRHIP_ERR_INVALID_ARG; hLen other than the filter's hLen is MRHIP_ERR_INVALID_ARG (tapsPerPhi, the
  *     history length and the history do not change); a complex tap_dtype is MRHIP_ERR_UNSUPPORTED (complex taps with per-channel rates
@@ -716,9 +718,55 @@ int mrhip_set_channel_rates(mrhip_filter *f, const double *rates /* [nchannels] 
  *     MRHIP_FORCE_GENERIC = 1 keeps the universal one;
  *   - a filter on which the function was never called runs the launches, kernels and messages it always ran; every entry point that
  *     refuses a filter with per-channel rates keeps refusing; the ABI version stays 1;
- *   - left out on purpose: FIRFarrow; complex taps; going back to shared taps; a stream-ordered update without the host wait (it
+ *   - left out on purpose: FIRFarrow (it has its own two calls, below); complex taps; going back to shared taps; a stream-ordered update without the host wait (it
  *     needs double-buffered banks); graph capture, rings, cascades and sharding; the parallel schedule for long channels. */
 int mrhip_set_channel_taps(mrhip_filter *f, const void *h /* [nchannels][hLen] */, int64_t hLen, int tap_dtype);
+/* Per-channel taps with per-channel rates for FIRFarrow (mrhip_set_channel_taps_farrow and mrhip_set_channel_pnfb on a filter of
+ * mrhip_create_farrow_rates or mrhip_create_farrow_rates_pnfb): one FIRFilter(h_c, rates[c], Nphi, polyorder) per channel behind one
+ * handle, taps AND rate differing per channel.  FIRFarrow is the kernel the reference offers for a continuously variable rate: Doppler
+ * and clock trackers that call mrhip_set_channel_rates every chunk and carry a per-emitter matched pulse or a per-receiver equaliser.
+ * Both are CALLS on an existing filter, the twins of mrhip_set_channel_taps / mrhip_set_channel_rates, not constructors.
+ *   - mrhip_set_channel_taps_farrow: h holds nchannels rows of hLen taps, row-major, row c = h_c (the layout of
+ *     mrhip_create_farrow_bank).  Every row goes through taps2pfb and one polynomial fit per row of it, then the rounding to the tap
+ *     type, exactly as mrhip_create_farrow_bank builds its banks: bank c is bit for bit the bank of mrhip_create_farrow(h_c, ...).  A
+ *     rank-deficient fit is MRHIP_ERR_INVALID_ARG;
+ *   - mrhip_set_channel_pnfb: pnfb holds nchannels caller-fitted banks one after the other, [nchannels][tapsPerPhi][polyorder+1] Float64
+ *     in ascending powers, rounded to the tap type as mrhip_create_farrow_pnfb rounds: the path of a block-adaptive user who updates
+ *     coefficients directly, and of a test that hands an oracle and the device the same numbers;
+ *   - refusals, each before anything changes, in this order, each message naming the function: f == NULL is MRHIP_ERR_INVALID_ARG; a
+ *     filter of mrhip_create_arbitrary_rates is MRHIP_ERR_INVALID_ARG with a message that points to mrhip_set_channel_taps; any other
+ *     filter is MRHIP_ERR_INVALID_ARG; then h / pnfb == NULL (MRHIP_ERR_INVALID_ARG); then hLen, or tapsPerPhi and polyorder, other
+ *     than the filter's (MRHIP_ERR_INVALID_ARG: the history length and the history do not change); then (mrhip_set_channel_taps_farrow)
+ *     the tap dtype: out of range MRHIP_ERR_INVALID_ARG, complex MRHIP_ERR_UNSUPPORTED (complex taps with per-channel rates are left
+ *     out), a real type other than the filter's MRHIP_ERR_INVALID_ARG;
+ *   - effect: the checks, the host banks (the fit included) and the first call's allocation come first; then the call waits for the
+ *     filter's stream (as mrhip_set_channel_rates does) and uploads nchannels * tapsPerPhi * (polyorder+1) Float64, allocated by the
+ *     first call of either function and reused by every later one; the one shared bank is freed.  A refused or failed call leaves the
+ *     filter bit for bit as it was;
+ *   - parity: from the next call on channel c is bit for bit mrhip_create_farrow_pnfb(bank_c, rates[c], Nphi, polyorder, nchannels = 1)
+ *     fed x_c, that filter given channel c's (inputDeficit, phiAccumulator) through mrhip_set_state and its history through
+ *     mrhip_set_history: the outputs, the count of every call, the end state and the history, under STRICT and under FUSED, through
+ *     mrhip_filt_device_rates and mrhip_filt_device_rates_ragged, including the short-input path, a channel of ragged length 0 and
+ *     FIRFarrow's zero-start seam on every call;
+ *   - arithmetic: that of "Per-channel rates for FIRFarrow" on bank c -- Horner in Float64, never fused, also under FUSED; the tap
+ *     rounded once to the tap type and widened exactly; the dot oldest sample first; STRICT a separate multiply and add per tap, FUSED
+ *     one explicit fma per tap;
+ *   - state: phiAccumulator, inputDeficit, rates and history stay untouched.  Either function may be called again, so the taps may
+ *     change between calls.  mrhip_reset keeps the current taps, as it keeps the current rates.  mrhip_set_channel_rates,
+ *     mrhip_set_channel_states, mrhip_get_channel_states, mrhip_set_numerics, mrhip_set_history*, mrhip_outputlength_bound and both
+ *     mrhip_filt_device_rates* calls work as before;
+ *   - tap queries: after a successful call mrhip_get_pnfb and mrhip_farrow_tapsforphase answer in the layout of "Per-channel taps for
+ *     FIRFarrow" -- nchannels banks or rows one after the other; before it they answer as on any filter of mrhip_create_farrow_rates*;
+ *   - kernels: farrow_rates_bank_generic (any shape) and farrow_rates_bank_multi (four outputs a lane share each tap's scalar
+ *     coefficient loads, a tile is one channel and so one bank; MRHIP_FARROW_RATES_BANK_MULTI = 1 selects it wherever its plan fits, 0
+ *     never, the default rule follows the measured rows); MRHIP_FORCE_GENERIC = 1 keeps the universal one;
+ *   - mrhip_set_channel_taps keeps answering MRHIP_ERR_UNSUPPORTED for a FIRFarrow filter; a filter on which neither function was
+ *     called runs the launches and kernels it always ran; the ABI version stays 1; there are still sixteen constructors;
+ *   - left out on purpose: complex taps with per-channel rates; going back to shared taps; a stream-ordered update without the host
+ *     wait (it needs double-buffered banks); the fit on the device; graph capture, rings, cascades and sharding; the parallel schedule
+ *     for long channels. */
+int mrhip_set_channel_taps_farrow(mrhip_filter *f, const void *h /* [nchannels][hLen] */, int64_t hLen, int tap_dtype);
+int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb /* [nchannels][tapsPerPhi][polyorder+1] */, int64_t tapsPerPhi, int64_t polyorder);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call
@@ -885,7 +933,8 @@ int mrhip_timing_read(mrhip_filter *f, int64_t *n_launches, double *total_ms);
  * write-only-own-outputs cases (tests/output_bounds_cases.py) is keyed by the suffixed names in the sources, and these two kernels'
  * cases live in tests/test_gpu_rates_arb.py until they move into that table.  The same holds for farrow_rates_generic and
  * farrow_rates_multi (FIRFarrow with per-channel rates; their cases: tests/test_gpu_rates_farrow.py), and for arb_rates_bank_generic
- * and arb_rates_bank_tiled (per-channel taps with per-channel rates; their cases: tests/test_gpu_rates_bank_arb.py). */
+ * and arb_rates_bank_tiled (per-channel taps with per-channel rates; their cases: tests/test_gpu_rates_bank_arb.py), and for
+ * farrow_rates_bank_generic and farrow_rates_bank_multi (the same for FIRFarrow; their cases: tests/test_gpu_rates_bank_farrow.py). */
 const char *mrhip_last_kernel_name(const mrhip_filter *f);
 /* How the phase schedule of a FIRArbitrary / FIRFarrow filter -- update(), src/Filters.jl:663-673 and :780-792 -- has
  * been evaluated so far.  info[0..n) receives, as far as n reaches:

@@ -1802,7 +1802,7 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     const int hist_next = hist_other(f);
     if (f->H > 0) a.fold = ShiftFold{f->d_hist[hist_next], nullptr};      // shiftin! by the kernel's last workgroup, into the other slot
     const bool farrow = f->kind == MRHIP_FIR_FARROW;
-    FarrowArgs fa{};                // (mrhip_create_farrow_rates: the same call over the one polynomial bank)
+    FarrowArgs fa{};                // (mrhip_create_farrow_rates: the same call over the one polynomial bank, or over a bank per channel: f->bank)
     if (farrow) {
         fa.x = x; fa.y = y; fa.hist = a.hist; fa.pnfb = f->d_pnfb;
         fa.n_idx = sa.n_idx; fa.acc = sa.acc;
@@ -1823,7 +1823,10 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     size_t lds = 0;
     long long tiled_grid = 0;
     bool tiled = false;
-    if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
+    if (bound > 0 && !f->force_generic && farrow && tk.bank) {      // (mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb: kernels_rates_bank_farrow.hip; tiled: its multi kernel)
+        tiled = plan_farrow_rates_bank_multi(tk, fa, f->num_cus, &ta);
+        if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_bank_multi(tk, fused, ta, f->num_cus, &tiled_grid));
+    } else if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
         tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
         if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
     } else if (bound > 0 && !f->force_generic && tk.bank) {      // (mrhip_set_channel_taps: kernels_rates_bank_arb.hip; no plan_* below sees such a call)
@@ -1842,7 +1845,9 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     if (int rc = timing_mark(f, stream)) return rc;
     MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
     if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
-        if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
+        if (farrow && tk.bank && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_bank_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
+        else if (farrow && tk.bank) MRHIP_CHECK_HIP(launch_farrow_rates_bank_generic(tk, fused, fa, ra, stream, &f->last_kernel));
+        else if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
         else if (farrow) MRHIP_CHECK_HIP(launch_farrow_rates_generic(tk, fused, fa, ra, stream, &f->last_kernel));
         else if (tk.bank && tiled) MRHIP_CHECK_HIP(launch_arb_rates_bank_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
         else if (tk.bank) MRHIP_CHECK_HIP(launch_arb_rates_bank_generic(tk, fused, a, ra, stream, &f->last_kernel));
@@ -2026,6 +2031,64 @@ int mrhip_set_channel_taps(mrhip_filter *f, const void *h, int64_t hLen, int tap
     f->h_taps.swap(pfb);
     f->h_dtaps.swap(dpfb);
     return MRHIP_OK;
+}
+
+// Per-channel taps on a filter of mrhip_create_farrow_rates* (include/multirate_hip.h, "Per-channel taps with per-channel rates for
+// FIRFarrow"): nch polynomial banks, [nch][T][polyorder+1], in the place of the shared one.  `pn` holds them as the caller or the fit gave
+// them; they are rounded to the tap type here, as create_filter rounds (Poly{T} storage).  The first call's allocation comes before
+// anything of the filter changes; then the call waits for the filter's stream (the kernels enqueued so far read the bank) and installs
+// the new ones.  Records, rates, history and the schedule buffers stay; TypeKey::bank is set from here on (rates_call:
+// kernels_rates_bank_farrow.hip).
+static int install_channel_pnfb(mrhip_filter *f, const std::string &who, std::vector<double> &pn)
+{
+    if (!dtype_is_f64(f->th)) for (double &c : pn) c = static_cast<double>(static_cast<float>(c));
+    const size_t bytes = pn.size() * sizeof(double);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
+    double *d_new = f->d_pnfb;                                          // (a later call: the banks of the first one, reused)
+    if (!f->bank) {
+        d_new = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&d_new), bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MRHIP_ERR_HIP, who + ": no device memory for the channels' polynomial banks");
+        }
+    }
+    int rc = drain_filter(f);
+    if (!rc && hipMemcpy(d_new, pn.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)     // (complete on return)
+        rc = fail(MRHIP_ERR_HIP, who + ": uploading the polynomial banks failed");
+    if (rc) {
+        if (!f->bank) (void)hipFree(d_new);
+        return rc;
+    }
+    if (!f->bank) {
+        (void)hipFree(f->d_pnfb);
+        if (f->d_pnfb_t) (void)hipFree(f->d_pnfb_t);
+        f->d_pnfb = d_new;
+        f->d_pnfb_t = nullptr;
+        f->bank = true;
+    }
+    f->h_pnfb.swap(pn);
+    return MRHIP_OK;
+}
+
+int mrhip_set_channel_taps_farrow(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps_farrow: NULL filter");
+    if (Refusal r = check_channel_taps_farrow(false, f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, f->polyorder, tap_dtype, f->hLen, f->polyorder, f->th))
+        return fail(r.status, r.message);
+    std::vector<double> pn;                                             // one fit per row, as mrhip_create_farrow_bank builds its banks
+    if (!create_farrow_banks(h, hLen, tap_dtype, f->Nphi, f->polyorder, static_cast<size_t>(f->nch), &pn))
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps_farrow: polynomial fit is rank deficient");
+    return install_channel_pnfb(f, "mrhip_set_channel_taps_farrow", pn);
+}
+
+int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb, int64_t tapsPerPhi, int64_t polyorder)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_pnfb: NULL filter");
+    if (Refusal r = check_channel_taps_farrow(true, f->rates, f->kind == MRHIP_FIR_FARROW, pnfb, tapsPerPhi, polyorder, f->th, f->T, f->polyorder, f->th))
+        return fail(r.status, r.message);
+    std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1));
+    return install_channel_pnfb(f, "mrhip_set_channel_pnfb", pn);
 }
 
 int mrhip_sync_state(mrhip_filter *f, int64_t *last_n_written)

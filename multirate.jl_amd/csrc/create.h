@@ -78,6 +78,10 @@ Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, Cre
 Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max);
 // the checks of mrhip_set_channel_taps that need no device: the filter's kind, h, hLen and the tap type against the filter's own
 Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th);
+// the same for mrhip_set_channel_taps_farrow (pnfb_call false: src = h, len = hLen against the filter's hLen, th against its tap type)
+// and mrhip_set_channel_pnfb (pnfb_call true: src = pnfb, len = tapsPerPhi and polyorder against the filter's; th is not looked at)
+Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder, int th,
+                                  int64_t f_len, int64_t f_polyorder, int f_th);
 // the length checks of mrhip_filt_device_rates_ragged, in its order: x_lens itself, every length (negative, then 2^31-1 and above), x
 // against the largest length, x_stride against it for nch > 1; *len_max: the largest length (what the call's bound is taken from)
 Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null, int64_t x_stride, int64_t *len_max);

@@ -411,6 +411,33 @@ long long farrow_rates_multi_grid(long long total_tiles, long long chip_grid, in
     return std::max<long long>(std::min<long long>(chip_grid, total_tiles), 1);
 }
 
+// farrow_rates_bank_multi_kernel (FIRFarrow with per-channel RATES and per-channel TAPS, kernels_rates_bank_farrow.hip): the tiling of
+// plan_farrow_rates_multi -- a tile is kFarrowRatesOPL consecutive runs of kVariantThreads outputs of ONE channel, so one polynomial bank,
+// one channel a lane (cpl = 1), the tiling goes by n_out, the call's bound -- on a filter that HAS a bank per channel (tk.bank).  No LDS,
+// so nothing else to plan; the grid is farrow_rates_multi_grid's.  The default rule (mode -1) takes the calls the measured rows cover
+// (profiles/r13/farrow_rates_bank.txt, both runs): the multi kernel beat the universal one by far more than the
+// spread of the repeats at 4096 ch x 1e4 (90 112 tiles of 22 a channel: 2.349 against 2.561 ms and 2.364 against 2.563, spreads <= 0.019)
+// and did not at 256 ch x 1e5 (56 320 tiles of 220 a channel: 18.460 against 18.473 ms and 18.422 against 18.525, spreads 0.06 to 0.17)
+// nor at 64 ch x 1e6 (140 672 tiles of 2198 a channel: 464.5 against 464.6 ms and 462.6 against 477.4 with spreads of 5 to 45 -- the serial
+// walk is the call).  So: from kFarrowRatesBankMultiMinTiles tiles, up to kFarrowRatesBankMultiMaxPerChannel tiles a channel; every other
+// call stays on the universal kernel unless MRHIP_FARROW_RATES_BANK_MULTI=1 selects the multi kernel.  As for plan_farrow_rates_multi,
+// whose limits came out the same, both are GUARDS ON UNMEASURED GROUND, not causes.  (A limit < 0 would mean: never.)
+constexpr long long kFarrowRatesBankMultiMinTiles = 90112, kFarrowRatesBankMultiMaxPerChannel = 22;
+bool plan_farrow_rates_bank_multi(const TypeKey &tk, const FarrowArgs &a, int /*num_cus*/, int mode, ArbTileArgs *out)
+{
+    if (mode == 0 || !tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || a.nch < 1) return false;
+    ArbTileArgs ta{};
+    ta.cpl = 1;
+    ta.tile_out = static_cast<long long>(kFarrowRatesOPL) * kVariantThreads;
+    ta.tiles_per_channel = (a.n_out + ta.tile_out - 1) / ta.tile_out;
+    ta.total_tiles = ta.tiles_per_channel * a.nch;
+    if (mode != 1 && (kFarrowRatesBankMultiMinTiles < 0 || ta.total_tiles < kFarrowRatesBankMultiMinTiles ||
+                      ta.tiles_per_channel > kFarrowRatesBankMultiMaxPerChannel))
+        return false;
+    *out = ta;
+    return true;
+}
+
 // arb_bank_ctaps_tiled_kernel: both banks of ONE channel as (re, im) pairs of R (column pitch T + 1) plus the sample tile fit LDS at
 // two workgroups a CU (78 KiB a workgroup, as for plan_arb_bank_tiled); one channel a lane (cpl = 1); the span follows from the rate
 // and is cut only when the kernel is forced.  The default rule: the tiled kernel was faster than the universal one by far more than
@@ -739,8 +766,8 @@ Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max)
 Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th)
 {
     if (is_rates && is_farrow)
-        return {MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps: FIRFarrow with per-channel taps and per-channel rates is left out (it needs the fit of every "
-                                       "row and a Horner kernel over a bank per channel); mrhip_create_arbitrary_rates filters take the call"};
+        return {MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps: FIRFarrow with per-channel taps and per-channel rates is not this call's (it needs the fit of "
+                                       "every row): mrhip_set_channel_taps_farrow or mrhip_set_channel_pnfb; mrhip_create_arbitrary_rates filters take this call"};
     if (!is_rates) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps takes a filter of mrhip_create_arbitrary_rates"};
     if (!h) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: h is NULL"};
     if (hLen != f_hLen)
@@ -749,6 +776,33 @@ Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t
     if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: bad tap dtype"};
     if (dtype_is_complex(th)) return {MRHIP_ERR_UNSUPPORTED, std::string("mrhip_set_channel_taps: ") + kRatesHint + " (the taps are Float32 / Float64)"};
     if (th != f_th) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: the taps must have the filter's tap dtype"};
+    return {};
+}
+
+// mrhip_set_channel_taps_farrow and mrhip_set_channel_pnfb (the public header, "Per-channel taps with per-channel rates for FIRFarrow"):
+// what the two calls refuse before they touch the device, in their order and each naming the function -- the filter (a FIRArbitrary one
+// with per-channel rates is pointed to its own call), then h / pnfb, then hLen or (tapsPerPhi, polyorder) against the filter's own, then
+// (taps only) the tap type: out of range, complex, the other real one
+Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder, int th,
+                                  int64_t f_len, int64_t f_polyorder, int f_th)
+{
+    const std::string who = pnfb_call ? "mrhip_set_channel_pnfb" : "mrhip_set_channel_taps_farrow";
+    if (is_rates && !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + ": a filter of mrhip_create_arbitrary_rates takes mrhip_set_channel_taps"};
+    if (!is_rates || !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + " takes a filter of mrhip_create_farrow_rates or mrhip_create_farrow_rates_pnfb"};
+    if (!src) return {MRHIP_ERR_INVALID_ARG, who + (pnfb_call ? ": pnfb is NULL" : ": h is NULL")};
+    if (pnfb_call) {
+        if (len != f_len || polyorder != f_polyorder)
+            return {MRHIP_ERR_INVALID_ARG, who + ": tapsPerPhi and polyorder must be the filter's (" + std::to_string(f_len) + " polynomials of order " +
+                                           std::to_string(f_polyorder) + " a channel; got " + std::to_string(len) + " of order " + std::to_string(polyorder) +
+                                           "): the history length and the history do not change"};
+        return {};
+    }
+    if (len != f_len)
+        return {MRHIP_ERR_INVALID_ARG, who + ": hLen must be the filter's (" + std::to_string(f_len) + " taps a channel; got " + std::to_string(len) +
+                                       "): tapsPerPhi, the history length and the history do not change"};
+    if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, who + ": bad tap dtype"};
+    if (dtype_is_complex(th)) return {MRHIP_ERR_UNSUPPORTED, who + ": " + kRatesHint + " (the taps are Float32 / Float64)"};
+    if (th != f_th) return {MRHIP_ERR_INVALID_ARG, who + ": the taps must have the filter's tap dtype"};
     return {};
 }
 

@@ -24,22 +24,18 @@
 // What sets this filter apart from the Farrow bank (kernels_bank_farrow.hip): there the coefficients are uniform per CHANNEL; here pnfb is
 // shared by all channels, so the coefficient address pnfb + i*(P+1) + j is uniform over the whole grid, whatever channel or output a lane
 // holds.  Every coefficient is a scalar operand read through the constant address space (farrow_coef_t, variant_device.h), and ONE set
-// of scalar loads can serve several outputs of a lane: the multi kernel.
+// of scalar loads can serve several outputs of a lane: the multi kernel.  The rounding of a tap, the Horner chains and the dots of a
+// lane (farrow_rates_round, farrow_rates_horner, farrow_rates_dots) are stated in rates_farrow_device.h, which this unit shares with
+// kernels_rates_bank_farrow.hip (a bank per channel).
 // Both kernels end with the ShiftFold epilogue (the history does not depend on the rate).  No workgroup waits for another.
 #include "rates_arb.h"
 #include "variant_device.h"
+#include "rates_farrow_device.h"
 
 #pragma clang fp contract(off)
 
 namespace mrhip {
 namespace {
-
-// the evaluated tap, stored into currentTaps::Vector{Th} (one rounding to the tap type), widened exactly to R
-template <typename R>
-__device__ __forceinline__ R farrow_rates_round(const double v, const bool tap_f32)
-{
-    return tap_f32 ? static_cast<R>(static_cast<float>(v)) : static_cast<R>(v);
-}
 
 // One lane per (channel, output), any (T, polyorder, rates): farrow_bank_generic_kernel's statement with the ONE bank and per-channel
 // slices of the schedule.  blockIdx.x covers the outputs up to the call's bound, blockIdx.y strides the channels; the channel's count
@@ -82,73 +78,6 @@ __global__ __launch_bounds__(kVariantThreads) void farrow_rates_generic_kernel(F
     else channels.template operator()<-1>();
     if (r.x_lens) dev::shiftin_ragged_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, r.x_lens, a.H, a.nch, RatesHistSource{});
     else dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
-}
-
-// OPL Horner chains of ONE polynomial side by side, each at its own phase: the P+1 coefficients are loaded once as scalars and feed all
-// the chains, which are independent, so they interleave and cover each other's Float64 latency.  Per chain the statement of
-// farrow_bank_horner (variant_device.h): t = 𝜙*v; v = coef + t, the product and the sum each rounded once, never fused.  PP >= 0: the
-// polyorder at compile time, the loads issued together and waited for once; PP < 0: any polyorder, one load per Horner step.
-template <int PP, int OPL>
-__device__ __forceinline__ void farrow_rates_horner(farrow_coef_t c, const int P, const double (&phase)[OPL], double (&v)[OPL])
-{
-    if constexpr (PP >= 0) {
-        double cj[PP + 1];
-#pragma unroll
-        for (int e = 0; e <= PP; ++e) cj[e] = c[e];
-#pragma unroll
-        for (int q = 0; q < OPL; ++q) v[q] = cj[PP];
-#pragma unroll
-        for (int j = PP - 1; j >= 0; --j) {
-#pragma unroll
-            for (int q = 0; q < OPL; ++q) {
-                const double t = phase[q] * v[q];
-                v[q] = cj[j] + t;
-            }
-        }
-    } else {
-        const double top = c[P];
-#pragma unroll
-        for (int q = 0; q < OPL; ++q) v[q] = top;
-        for (int j = P - 1; j >= 0; --j) {
-            const double cj = c[j];
-#pragma unroll
-            for (int q = 0; q < OPL; ++q) {
-                const double t = phase[q] * v[q];
-                v[q] = cj + t;
-            }
-        }
-    }
-}
-
-// The OPL dots of one lane: per tap ONE evaluation of the coefficients' scalar loads, OPL Horner chains, OPL multiply-adds; sample xi of
-// a window comes from x (xi >= 0) or from the end of the history (he[xi], xi < 0).  The first `live` slots are stored.
-template <typename A, int PP, int OPL>
-__device__ __forceinline__ void farrow_rates_dots(farrow_coef_t pc, const int P, const int T, const bool tap_f32, const double (&phase)[OPL],
-                                                  const long long (&base)[OPL], const bool (&seam)[OPL],
-                                                  const typename A::Sample *__restrict__ xc, const typename A::Sample *__restrict__ he,
-                                                  typename A::Out *__restrict__ yc, const long long k_first, const int live)
-{
-    using R = typename A::Tap;
-    typename A::Sum acc[OPL];
-    double v[OPL];
-    farrow_rates_horner<PP, OPL>(pc, P, phase, v);
-#pragma unroll
-    for (int j = 0; j < OPL; ++j) {
-        const long long xi = base[j];
-        acc[j] = A::first(farrow_rates_round<R>(v[j], tap_f32), xi >= 0 ? xc[xi] : he[xi]);
-        if (seam[j]) acc[j] = A::zero_start(acc[j]);
-    }
-    for (int i = 1; i < T; ++i) {
-        farrow_rates_horner<PP, OPL>(pc + i * (P + 1), P, phase, v);
-#pragma unroll
-        for (int j = 0; j < OPL; ++j) {
-            const long long xi = base[j] + i;
-            acc[j] = A::step(acc[j], farrow_rates_round<R>(v[j], tap_f32), xi >= 0 ? xc[xi] : he[xi]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < OPL; ++j)
-        if (j < live) A::store(yc, k_first + j * kVariantThreads, acc[j]);
 }
 
 // Persistent workgroups in the channel-major tile order (tile_run, variant_device.h).  A tile is (channel, OPL consecutive runs of 256

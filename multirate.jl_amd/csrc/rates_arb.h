@@ -119,4 +119,19 @@ hipError_t launch_farrow_rates_multi(const TypeKey &tk, bool fused, const Farrow
 bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
 long long farrow_rates_multi_grid(long long total_tiles, long long chip_grid, int grid_fixed);
 
+// ---- FIRFarrow with per-channel rates AND per-channel taps (mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb on a filter of
+// mrhip_create_farrow_rates*; include/multirate_hip.h, "Per-channel taps with per-channel rates for FIRFarrow") -------------------------
+// Records, slices, schedule kernel, RatesArgs and the tile of kFarrowRatesOPL runs above serve it unchanged; FarrowArgs::pnfb holds nch
+// banks, [nch][T][polyorder+1], and TypeKey::bank is set.  The Horner chains and the dots both units run: rates_farrow_device.h.
+// kernels_rates_bank_farrow.hip
+hipError_t launch_farrow_rates_bank_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
+bool plan_farrow_rates_bank_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, ArbTileArgs *out);   // (reads MRHIP_FARROW_RATES_BANK_MULTI)
+// the multi kernel's persistent grid (occupancy query; MRHIP_FARROW_RATES_BANK_GRID): what can fail ahead of the launch
+hipError_t prepare_farrow_rates_bank_multi(const TypeKey &tk, bool fused, const ArbTileArgs &ta, int num_cus, long long *grid);
+hipError_t launch_farrow_rates_bank_multi(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, const ArbTileArgs &ta,
+                                          long long grid, hipStream_t s, const char **kname);
+// host_logic.cpp: the switch value passed in (MRHIP_FARROW_RATES_BANK_MULTI: 0 never, 1 wherever the plan fits, -1 the default rule);
+// the grid is farrow_rates_multi_grid's
+bool plan_farrow_rates_bank_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
+
 }  // namespace mrhip

@@ -103,6 +103,8 @@ ABI = [
     ("mrhip_set_channel_states", _i, [_vp, _vp, _vp]),
     ("mrhip_set_channel_rates", _i, [_vp, _vp]),
     ("mrhip_set_channel_taps", _i, [_vp, _vp, _i64, _i]),
+    ("mrhip_set_channel_taps_farrow", _i, [_vp, _vp, _i64, _i]),
+    ("mrhip_set_channel_pnfb", _i, [_vp, _vp, _i64, _i64]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -329,6 +331,7 @@ class FIRFilter:
         self._pnfb_in = None
         self._rates = None                # per-channel rates (FIRFilter.per_channel_rates, .per_channel_rates_farrow): Float64, one per channel; self.rate is the largest
         self._chan_taps = None            # per-channel taps ON TOP of per-channel rates (FIRFilter.set_channel_taps, .per_channel_taps_and_rates): the (nchannels, hLen) matrix, installed by mrhip_set_channel_taps
+        self._chan_farrow = None          # the same for FIRFarrow (FIRFilter.set_channel_taps_farrow, .set_channel_pnfb, .per_channel_taps_and_rates_farrow): ("taps", the (nchannels, hLen) matrix) or ("pnfb", the (nchannels, tapsPer𝜙, polyorder+1) banks), whichever call came last
         self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow, .per_channel_complex_taps_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
             if not ratio > 0.0:
@@ -497,6 +500,30 @@ class FIRFilter:
         return f
 
     @classmethod
+    def per_channel_taps_and_rates_farrow(cls, H, rates, Nphi: int = 32, polyorder=4, *, pnfb=None, device: int = 0, numerics: int = NUMERICS_STRICT):
+        """One FIRFilter(H[c], rates[c]::Float, N𝜙, polyorder) per channel behind one filter object: FIRFarrow with per-channel taps AND
+        per-channel rates (Doppler and clock trackers that call ``set_channel_rates`` every chunk and carry a per-emitter matched pulse
+        or a per-receiver equaliser).  ``H``: shape (nchannels, hLen), Float32 or Float64; ``rates``: one rate > 0 per channel.  It is
+        the filter of ``per_channel_rates_farrow(H[0], rates, Nphi, polyorder)`` followed by ``set_channel_taps_farrow(H)`` -- every row
+        fitted on its own -- or, with ``pnfb`` of shape (nchannels, tapsPer𝜙, polyorder+1), by ``set_channel_pnfb(pnfb)``: caller-fitted
+        banks in ascending powers, ``H`` then only gives hLen and the tap dtype.  Channel c is bit for bit
+        ``FIRFilter(H[c], rates[c], Nphi, polyorder)`` (on bank c) fed ``x[c]``, under STRICT and FUSED (include/multirate_hip.h:
+        per-channel taps with per-channel rates for FIRFarrow).  ``pnfb()`` has shape (nchannels, tapsPer𝜙, polyorder+1) and
+        ``tapsforphase`` (nchannels, tapsPer𝜙); everything else behaves as on the filter of ``per_channel_rates_farrow``."""
+        who = "per_channel_taps_and_rates_farrow"
+        H = _as_taps(_tap_matrix(_real_taps(H, who, "complex taps with per-channel rates are left out"), who))
+        if pnfb is None:
+            f = cls.per_channel_rates_farrow(H[0], rates, Nphi, polyorder, device=device, numerics=numerics)
+            f.set_channel_taps_farrow(H)
+        else:
+            PN = np.asarray(pnfb)
+            if PN.ndim != 3 or PN.shape[0] < 1:
+                raise MultirateHIPError(1, f"{who} takes pnfb of shape (nchannels, tapsPerPhi, polyorder+1); got {PN.shape}")
+            f = cls.per_channel_rates_farrow(H[0], rates, Nphi, polyorder, pnfb=PN[0], device=device, numerics=numerics)
+            f.set_channel_pnfb(PN)
+        return f
+
+    @classmethod
     def per_channel_complex_taps_arbitrary(cls, H, rate, Nphi: int = 32, *, device: int = 0):
         """One FIRFilter(H[c]::Vector{Complex64 / Complex128}, rate::Float, N𝜙) per channel behind one filter object: FIRArbitrary
         with per-channel complex taps (a prototype rotated to every channel's own centre frequency in front of a common clock-trim or
@@ -590,6 +617,14 @@ class FIRFilter:
             _check(self._lib.mrhip_set_numerics(self._handle, self.numerics))
         if self._chan_taps is not None:                              # (set_channel_taps on the unbound filter)
             _check(self._lib.mrhip_set_channel_taps(self._handle, _ptr(self._chan_taps), self._chan_taps.shape[1], _NP2DT[self._chan_taps.dtype]))
+        if self._chan_farrow is not None:                            # (set_channel_taps_farrow / set_channel_pnfb on the unbound filter)
+            self._install_chan_farrow(*self._chan_farrow)
+
+    def _install_chan_farrow(self, what, M):
+        if what == "taps":
+            _check(self._lib.mrhip_set_channel_taps_farrow(self._handle, _ptr(M), M.shape[1], _NP2DT[M.dtype]))
+        else:
+            _check(self._lib.mrhip_set_channel_pnfb(self._handle, _ptr(M), M.shape[1], M.shape[2] - 1))
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -672,7 +707,7 @@ class FIRFilter:
         if self._handle is None or self.kind != FARROW:
             raise MultirateHIPError(1, "pnfb() needs a bound FIRFarrow filter")
         shape = (self.tapsPerPhi, self.polyorder + 1)
-        out = np.zeros((self._nch,) + shape if self._bank is not None else shape, dtype=np.complex128 if self.h.dtype.kind == "c" else np.float64)
+        out = np.zeros((self._nch,) + shape if self._bank is not None or self._chan_farrow is not None else shape, dtype=np.complex128 if self.h.dtype.kind == "c" else np.float64)
         _check(self._lib.mrhip_get_pnfb(self._handle, _ptr(out)))
         return out
 
@@ -681,7 +716,7 @@ class FIRFilter:
         tapsforphase(kernel::FIRFarrow, phase), src/Filters.jl:764-775."""
         if self._handle is None or self.kind not in (ARBITRARY, FARROW):
             raise MultirateHIPError(1, "tapsforphase() needs a bound FIRArbitrary or FIRFarrow filter")
-        banks = self._bank is not None or (self._chan_taps is not None and self.kind == ARBITRARY)
+        banks = self._bank is not None or (self._chan_taps is not None and self.kind == ARBITRARY) or (self._chan_farrow is not None and self.kind == FARROW)
         rows = (self._nch, self.tapsPerPhi) if banks else self.tapsPerPhi   # (a per-channel filter: one row per channel)
         out = np.zeros(rows, dtype=self.h.dtype)
         fn = self._lib.mrhip_farrow_tapsforphase if self.kind == FARROW else self._lib.mrhip_arbitrary_tapsforphase
@@ -928,7 +963,7 @@ class FIRFilter:
         if self._rates is None:
             raise MultirateHIPError(1, "set_channel_taps needs a filter of FIRFilter.per_channel_rates")
         if self.kind != ARBITRARY:
-            raise MultirateHIPError(5, "set_channel_taps: FIRFarrow with per-channel taps and per-channel rates is left out (FIRFilter.per_channel_rates takes the call)")
+            raise MultirateHIPError(5, "set_channel_taps: FIRFarrow with per-channel taps and per-channel rates is not this call's (set_channel_taps_farrow or set_channel_pnfb; FIRFilter.per_channel_rates takes this call)")
         H = _tap_matrix(_real_taps(H, "set_channel_taps", "complex taps with per-channel rates are left out"), "set_channel_taps")
         if H.shape != (len(self._rates), len(self.h)):
             raise MultirateHIPError(1, f"set_channel_taps takes a {(len(self._rates), len(self.h))} matrix, one row of the filter's hLen taps per channel; got {H.shape}")
@@ -938,6 +973,48 @@ class FIRFilter:
         if self._handle is not None:
             _check(self._lib.mrhip_set_channel_taps(self._handle, _ptr(H), H.shape[1], _NP2DT[H.dtype]))
         self._chan_taps = H
+
+    def _takes_farrow_rates(self, who):
+        if self._rates is not None and self.kind == ARBITRARY:
+            raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates takes set_channel_taps")
+        if self._rates is None or self.kind != FARROW:
+            raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates_farrow")
+
+    def set_channel_taps_farrow(self, H):
+        """Per-channel taps on a filter of ``per_channel_rates_farrow`` (``mrhip_set_channel_taps_farrow``; waits for the filter's
+        stream): ``H`` has shape (nchannels, hLen) in the filter's tap dtype, row c replaces ``h`` for channel c and is fitted on its own,
+        as ``per_channel_farrow`` fits its rows.  phiAccumulator, inputDeficit, rates and history stay; channel c continues bit for bit
+        as ``FIRFilter(H[c], rates[c], Nphi, polyorder)`` given its state and history would.  The taps may change between calls;
+        ``reset()`` keeps the current taps.  From then on ``pnfb()`` has shape (nchannels, tapsPer𝜙, polyorder+1) and ``tapsforphase``
+        (nchannels, tapsPer𝜙).  Unbound: the taps are installed at ``bind``.  Complex taps: status 5."""
+        who = "set_channel_taps_farrow"
+        self._takes_farrow_rates(who)
+        H = _tap_matrix(_real_taps(H, who, "complex taps with per-channel rates are left out"), who)
+        if H.shape != (len(self._rates), len(self.h)):
+            raise MultirateHIPError(1, f"{who} takes a {(len(self._rates), len(self.h))} matrix, one row of the filter's hLen taps per channel; got {H.shape}")
+        if H.dtype != self.h.dtype:
+            raise MultirateHIPError(1, f"{who} takes taps of the filter's tap dtype {self.h.dtype}; got {H.dtype}")
+        H = np.ascontiguousarray(H).copy()
+        if self._handle is not None:
+            self._install_chan_farrow("taps", H)
+        self._chan_farrow = ("taps", H)
+
+    def set_channel_pnfb(self, PN):
+        """Caller-fitted per-channel polynomial banks on a filter of ``per_channel_rates_farrow`` (``mrhip_set_channel_pnfb``; waits for
+        the filter's stream): ``PN`` has shape (nchannels, tapsPer𝜙, polyorder+1), ascending powers, and is rounded to the filter's tap
+        dtype as a handed-over ``pnfb`` is.  The path of a block-adaptive user who updates coefficients directly.  State, rates and
+        history stay, the banks may change between calls, ``reset()`` keeps them; ``pnfb()`` and ``tapsforphase`` answer per channel
+        from then on.  Unbound: the banks are installed at ``bind``.  Complex banks: status 5."""
+        who = "set_channel_pnfb"
+        self._takes_farrow_rates(who)
+        PN = _real_taps(PN, who, "complex taps with per-channel rates are left out")
+        want = (len(self._rates), self.tapsPerPhi, self.polyorder + 1)
+        if PN.shape != want:
+            raise MultirateHIPError(1, f"{who} takes banks of shape (nchannels, tapsPerPhi, polyorder+1) = {want}; got {PN.shape}")
+        PN = np.ascontiguousarray(PN, dtype=np.float64).copy()
+        if self._handle is not None:
+            self._install_chan_farrow("pnfb", PN)
+        self._chan_farrow = ("pnfb", PN)
 
     def outputlength_bound(self, inputlength: int) -> int:
         """The largest per-channel output count a call of ``inputlength`` samples can have whatever the stream state

@@ -537,7 +537,8 @@ struct MRHIPChannelState
 end
 mutable struct RatesFIRFilter{Th}
     h::Vector{Th}
-    H::Union{Nothing,Matrix{Th}}    # per-channel taps (set_channel_taps!): one column of hLen taps per channel, installed at bind!
+    H::Union{Nothing,Matrix{Th}}    # per-channel taps (set_channel_taps!, set_channel_taps_farrow!): one column of hLen taps per channel, installed at bind!
+    PN::Union{Nothing,Array{Float64,3}}  # per-channel caller-fitted banks (set_channel_pnfb!, FIRFarrow): (polyorder+1) x tapsPer𝜙 x nchannels, installed at bind!
     rates::Vector{Float64}
     Nphi::Int
     polyorder::Int                  # -1: FIRArbitrary (mrhip_create_arbitrary_rates); >= 0: FIRFarrow (mrhip_create_farrow_rates)
@@ -548,7 +549,7 @@ end
 function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
-    f = RatesFIRFilter{Th}(copy(h), nothing, Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing)
+    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 # FIRFilter(h, rates::Vector, N𝜙, polyorder): one FIRFilter(h, rates[c], N𝜙, polyorder) -- FIRFarrow -- per channel behind one object
@@ -557,7 +558,7 @@ function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer,
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
     0 <= polyorder <= min(32, Nphi - 1) || error("polyorder must be in 0..min(32, Nphi-1)")
-    f = RatesFIRFilter{Th}(copy(h), nothing, Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing)
+    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
@@ -576,7 +577,8 @@ function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
                     f.h, length(f.h), dtypecode(Th), f.rates, f.Nphi, dtypecode(Tx), length(f.rates), f.device, out))
     end
     f.handle, f.Tx = out[], Tx
-    f.H === nothing || set_channel_taps!(f, f.H)
+    f.H === nothing || (f.polyorder >= 0 ? set_channel_taps_farrow!(f, f.H) : set_channel_taps!(f, f.H))
+    f.PN === nothing || set_channel_pnfb!(f, f.PN)
     f
 end
 # per-channel taps on top of the per-channel rates (mrhip_set_channel_taps; include/multirate_hip.h, "Per-channel taps with per-channel
@@ -595,6 +597,32 @@ end
 function FIRFilter(H::Matrix{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     size(H, 2) == length(rates) || error("one column of taps and one rate per channel")
     set_channel_taps!(FIRFilter(H[:, 1], rates, Nphi; device = device), H)
+end
+# the same for FIRFarrow (mrhip_set_channel_taps_farrow, mrhip_set_channel_pnfb; include/multirate_hip.h, "Per-channel taps with per-channel
+# rates for FIRFarrow"): column c of H is channel c's h_c and is fitted on its own; or PN[:, i, c] holds the polyorder+1 coefficients, in
+# ascending powers, of polynomial i of channel c's caller-fitted bank (the memory layout [nchannels][tapsPer𝜙][polyorder+1] of the C call).
+# Every channel keeps its phase, deficit, rate and history; taps and banks may change between calls; reset keeps them; the later of the two
+# calls holds.  An unbound filter installs them at bind!.
+function set_channel_taps_farrow!(f::RatesFIRFilter{Th}, H::Matrix{Th}) where {Th}
+    f.polyorder >= 0 || error("set_channel_taps_farrow!: FIRFarrow only (FIRArbitrary: set_channel_taps!)")
+    size(H) == (length(f.h), length(f.rates)) || error("H takes one column of $(length(f.h)) taps per channel")
+    f.handle == C_NULL || check(ccall((:mrhip_set_channel_taps_farrow, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint), f.handle, H, size(H, 1), dtypecode(Th)))
+    f.H, f.PN = copy(H), nothing
+    f
+end
+function set_channel_pnfb!(f::RatesFIRFilter{Th}, PN::Array{Float64,3}) where {Th}
+    f.polyorder >= 0 || error("set_channel_pnfb!: FIRFarrow only")
+    T = cld(length(f.h), f.Nphi)
+    size(PN) == (f.polyorder + 1, T, length(f.rates)) || error("PN takes $(f.polyorder + 1) coefficients x $T polynomials per channel")
+    f.handle == C_NULL || check(ccall((:mrhip_set_channel_pnfb, libmr), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Int64, Int64), f.handle, PN, T, f.polyorder))
+    f.H, f.PN = nothing, copy(PN)
+    f
+end
+# FIRFilter(H::Matrix, rates::Vector, N𝜙, polyorder): one FIRFilter(H[:, c], rates[c], N𝜙, polyorder) per channel behind one object -- the
+# filter of FIRFilter(H[:, 1], rates, N𝜙, polyorder) with set_channel_taps_farrow!(f, H)
+function FIRFilter(H::Matrix{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{Float32,Float64}}
+    size(H, 2) == length(rates) || error("one column of taps and one rate per channel")
+    set_channel_taps_farrow!(FIRFilter(H[:, 1], rates, Nphi, polyorder; device = device), H)
 end
 outputlengthbound(f::RatesFIRFilter, n::Integer) = Int(ccall((:mrhip_outputlength_bound, libmr), Int64, (Ptr{Cvoid}, Int64), f.handle, n))
 # x and y are (n x nchannels) column-major on the filter's device, ycap and ystride at least outputlengthbound(f, xlen); countsptr
