@@ -67,7 +67,7 @@ void fir_stream_rt_kernel(PolyArgs a, PairArgs pa)
         pair_loader_wave<NW>(a, pa, smem, lane);
         return;
     }
-    volatile unsigned *const tile_flag = reinterpret_cast<volatile unsigned *>(smem + pa.flags_off);
+    const unsigned desc_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>(smem)) + static_cast<unsigned>(pa.flags_off);   // the tile descriptors (pair_device.h: desc_get2)
     typedef const __attribute__((address_space(4))) R *const_taps_t;   // scalar tap loads (see fir_stream_kernel.inc)
     const const_taps_t tc = (const_taps_t)(static_cast<const R *>(__builtin_assume_aligned(a.taps, 64)));
     const int T = a.T;
@@ -91,8 +91,8 @@ void fir_stream_rt_kernel(PolyArgs a, PairArgs pa)
     for (int s = 0;; s = (s + 1 == pa.ns ? 0 : s + 1)) {
         __builtin_amdgcn_s_barrier();             // one barrier per tile, no memory wait (opair_kernel.inc)
         asm volatile("" ::: "memory");
-        const unsigned tg = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(tile_flag[2 * s])));
-        const unsigned tj = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(tile_flag[2 * s + 1])));
+        unsigned tg, tj;
+        desc_get2(desc_base + 8u * static_cast<unsigned>(s), tg, tj);
         if (tj == 0u) break;                      // end marker
         const TileAt ta = pair_tile_at(pa, tg, tj);
         const int J = ta.jt;

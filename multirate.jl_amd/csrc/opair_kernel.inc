@@ -52,7 +52,8 @@ __device__ __forceinline__ R slot_mac(R tap, R w, R acc, bool used)
 // Float32), (Float64, Float64) and the reference README's mixed case (Float32 samples, Float64 taps: every sample is
 // widened exactly, as Julia's promotion does on every multiply).  Float64 arithmetic doubles the tap registers (~135
 // VGPRs: three waves per SIMD; capping it at 128 spills a tap pair into the step loop, whose reload would make the
-// compute waves wait on vmcnt, i.e. on their own output stores).
+// compute waves wait on vmcnt, i.e. on their own output stores -- the one thing their tile loop never does: descriptors come by LDS
+// instructions, pair_device.h: desc_get2).
 // PLAIN: an instantiation for calls the host planned for ONE filter (no call record, no stream descriptors): its kernel arguments
 // are never overwritten at entry, so they can be re-read from the kernarg segment instead of living in -- and being spilled
 // from -- SGPRs (profiles/r04/experiments.md A: the overrides cost the headline 0.6-0.8 % and its 1e6-sample launches 1.5 %).
@@ -101,7 +102,7 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
         return;
     }
     if constexpr (RING) { if (blockIdx.x == 0) return; }   // workgroup 0 is the ring's feeder (its last wave): no barrier is ever used there
-    volatile unsigned *const tile_flag = reinterpret_cast<volatile unsigned *>(smem + pa.flags_off);
+    const unsigned desc_base = lds_base + static_cast<unsigned>(pa.flags_off);   // the tile descriptors (pair_device.h: desc_put / desc_get)
 
     // ---- the lane's two outputs: window starts, offsets into the even-aligned run, shifted tap columns, masks ----
     // 32-bit: plan_rational_opair guarantees c*L <= 1024 and M < 2L, so every product below is < 2^22
@@ -185,6 +186,16 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
     unsigned long long mA0 = lanes_of(useA0), mAT = lanes_of(useAT);
     unsigned long long mB0 = lanes_of(useB0), mB1 = lanes_of(useB1), mBT = lanes_of(useBT), mBT1 = lanes_of(useBT1);
 
+    // The lane's constants of the tile loop, kept in registers: where its run starts within a stage, where its output pair lies within a
+    // step, and which lanes own a pair at all (an SGPR pair).  They move only with u0 (a ring's new chunk).  (They used to be re-derived
+    // per tile from a fresh lane id -- a 32-bit division, ~29 VALU instructions per tile -- to spare the registers; since the step loop
+    // keeps ONE window address and the store's base advances on the scalar side, they fit.)
+    unsigned loff = (static_cast<unsigned>(run0) - static_cast<unsigned>(pa.q0)) * ES;
+    const unsigned my_out = 2u * static_cast<unsigned>(tid);              // first of the lane's two outputs within a step
+    unsigned voff = my_out * OS;
+    pin(voff);
+    const unsigned long long mIn = lanes_of(act);                         // my_out + 1 < P
+
     const int n_out = static_cast<int>(a.n_out);
 #ifdef MRHIP_OPAIR_PROBE
     unsigned long long pr_wait = 0, pr_tiles = 0;
@@ -199,7 +210,8 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
     unsigned p_slot = 0, p_shard = 0, p_cnt = 0, p_nshards = 0, p_seq_lo = 0, p_seq_hi = 0;
     for (int s = 0;; s = (s + 1 == pa.ns ? 0 : s + 1)) {
         // One barrier per tile and no memory wait: the loader arrives only after this tile's data has landed and its
-        // descriptor is in LDS; all compute waves arriving proves the oldest stage is no longer read.
+        // descriptor is in LDS; all compute waves arriving proves the oldest stage is no longer read.  The descriptor is fetched
+        // by an LDS read (lgkmcnt): the output stores of the tile before stay in flight across the hand-over.
 #ifdef MRHIP_OPAIR_PROBE
         const unsigned long long pr_a = clock64();
 #endif
@@ -216,9 +228,11 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
         R *__restrict__ yc;
         unsigned ring_flags = 0, ring_slot = 0, ring_shard = 0, ring_cnt = 0, ring_nshards = 0, ring_seq_lo = 0, ring_seq_hi = 0;
         if constexpr (RING) {
-            auto word = [&](int w) -> unsigned { return static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(tile_flag[kRingTileWords * s + w]))); };
-            const unsigned tj = word(0);
-            ring_flags = word(1);
+            const unsigned td = desc_base + kRingTileWords * 4u * static_cast<unsigned>(s);
+            unsigned w0[4], w1[4], w2[4];
+            desc_get4<0>(td, w0);
+            const unsigned tj = w0[0];
+            ring_flags = w0[1];
             // the grab that ended with the tile before this one: its write-through stores have had this tile's landing time to drain;
             // the wave of the workgroup that gets here last reports it (the last grab of a chunk raises the host's flag)
             if (pend) {
@@ -238,16 +252,19 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
             if (tj == 0u) break;                  // the ring is closed and consumed
             if (ring_flags & 2u) continue;        // a FLUSH tile: nothing to compute (the loader had nothing to stage and grabs were unreported)
             J = static_cast<int>(tj);
-            yc = reinterpret_cast<R *>((static_cast<unsigned long long>(word(3)) << 32) | word(2));
-            remaining = static_cast<int>(word(4));
-            const int u0_t = static_cast<int>(word(5));
-            ring_slot = word(6); ring_shard = word(7); ring_seq_lo = word(8); ring_seq_hi = word(9); ring_cnt = word(10); ring_nshards = word(11);
+            desc_get4<16>(td, w1);
+            desc_get4<32>(td, w2);
+            yc = reinterpret_cast<R *>((static_cast<unsigned long long>(w0[3]) << 32) | w0[2]);
+            remaining = static_cast<int>(w1[0]);
+            const int u0_t = static_cast<int>(w1[1]);
+            ring_slot = w1[2]; ring_shard = w1[3]; ring_seq_lo = w2[0]; ring_seq_hi = w2[1]; ring_cnt = w2[2]; ring_nshards = w2[3];
             if (u0_t != u0) {                     // a chunk that starts elsewhere in the phase cycle: this lane's columns and offsets move
                 u0 = u0_t;
                 uA = u0 + (act ? 2 * tid : 0) * Mi; uB = uA + Mi;
                 qA = uA / Li; phA = uA - qA * Li;
                 qB = uB / Li; phB = uB - qB * Li;
                 run0 = qA & ~1; offA = qA - run0; dB = qB - run0 - SMIN;
+                loff = (static_cast<unsigned>(run0) - static_cast<unsigned>(pa.q0)) * ES;
                 gather_taps();
                 useA0 = offA == 0; useAT = offA == 1;
                 useB0 = dB == 0; useB1 = dB <= 1; useBT = dB >= 1; useBT1 = dB == 2;
@@ -255,8 +272,8 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
                 mB0 = lanes_of(useB0); mB1 = lanes_of(useB1); mBT = lanes_of(useBT); mBT1 = lanes_of(useBT1);
             }
         } else {
-            const unsigned tg = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(tile_flag[2 * s])));
-            const unsigned tj = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(tile_flag[2 * s + 1])));
+            unsigned tg, tj;
+            desc_get2(desc_base + 8u * static_cast<unsigned>(s), tg, tj);
             if (tj == 0u) break;                      // end marker
             const TileAt ta = pair_tile_at(pa, tg, tj);
             J = ta.jt;
@@ -264,15 +281,20 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
             remaining = n_out - ta.st * pa.Sout;                          // outputs of this channel from this tile on
         }
         const bool full = remaining >= (J - 1) * pa.Sout + pa.P;          // wave-uniform (steps are Sout outputs apart: P unless the workgroup owns a block of the period)
-        // lane-constant addresses are re-derived per tile from a fresh lane id (opaque to the compiler): kept live across
-        // the tile loop they would cost registers the step loop never uses
-        unsigned lane_t;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_t));
-        const unsigned tid_t = static_cast<unsigned>(wave) * 64u + lane_t;
-        const unsigned my_out = 2u * tid_t;                               // first of the lane's two outputs within a step
-        const unsigned uA_t = static_cast<unsigned>(u0) + (2u * tid_t < static_cast<unsigned>(pa.P) ? 2u * tid_t : 0u) * static_cast<unsigned>(Mi);
-        const unsigned R_t = (uA_t / static_cast<unsigned>(Li)) & ~1u;
-        const unsigned wbase = lds_base + static_cast<unsigned>(s) * pa.stage_bytes + (R_t - static_cast<unsigned>(pa.q0)) * ES;
+        const unsigned wbase = lds_base + static_cast<unsigned>(s) * pa.stage_bytes + loff;
+        // Which lanes store: a step whose outputs are all inside the channel stores the pairs of mIn.  A tile at a channel's end has at most ONE
+        // step that is partly inside (steps are Sout >= P outputs apart): its lanes with both outputs inside, and the one with only its first,
+        // are found here, once; the steps behind it store nothing.  In the loop the choice is scalar and the masks go into EXEC as they are.
+        unsigned long long mPart2 = 0, mPart1 = 0;
+        if constexpr (!RING) {
+            if (!full) {
+                int rp = remaining;
+                while (rp >= pa.P) rp -= pa.Sout;
+                const unsigned lim_p = rp > 0 ? static_cast<unsigned>(rp) : 0u;
+                mPart2 = lanes_of(my_out + 1 < lim_p);
+                mPart1 = lanes_of(my_out < lim_p) & ~mPart2;
+            }
+        }
 
         auto run_steps = [&](auto full_tag) {
             constexpr bool FULL = decltype(full_tag)::value;
@@ -280,18 +302,19 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
             constexpr int NPRV = (NPR + KP - 1) / KP * KP;
             constexpr bool PAIRED_WAITS = KP >= 5;
             pair_t pring[KP];
-            char *const ybytes = reinterpret_cast<char *>(yc);
+            char *ybytes = reinterpret_cast<char *>(yc);      // the step's first output: advances on the scalar side (the store's saddr)
+            const unsigned wstep = pa.lds_step * ES;
+            unsigned wcur = wbase;                            // the ONE window address: this step's run, then -- behind its last read -- the next step's
+            unsigned kj = 0;                                  // outputs of the tile in front of this step
             auto read_pair = [&](auto off_tag, unsigned addr) -> pair_t {
                 constexpr int OFFP = decltype(off_tag)::value;
                 if constexpr (NW == 1) return lds_read_b64<OFFP * 8>(addr);
                 else return lds_read_b128<OFFP * 16>(addr);
             };
-            static_for<0, KP>([&](auto I) { pring[decltype(I)::value] = read_pair(I, wbase); });
+            static_for<0, KP>([&](auto I) { pring[decltype(I)::value] = read_pair(I, wcur); });
 #pragma unroll 1
             for (int j = 0; j < J; ++j) {
-                const int jn = j + 1 < J ? j + 1 : j;         // the last step re-reads its own window (never used)
-                const unsigned wcur = wbase + static_cast<unsigned>(j) * pa.lds_step * ES;
-                const unsigned wnext = wbase + static_cast<unsigned>(jn) * pa.lds_step * ES;
+                const unsigned wadv = j + 1 < J ? wstep : 0u;  // the last step re-reads its own window (never used)
                 R accA[NC] = {}, accB[NC] = {};
                 R headA[NC], headB[NC], sumB[NC];                 // masked heads: slot 0's product, B's sum of slots 0 and 1
                 static_for<0, NPRV>([&](auto I) {
@@ -365,20 +388,22 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
                         }
                     }
                     if constexpr (r + KP < NPR) pring[slot] = read_pair(std::integral_constant<int, r + KP>{}, wcur);
-                    else if constexpr (r + KP >= NPRV) pring[slot] = read_pair(std::integral_constant<int, r + KP - NPRV>{}, wnext);
+                    else if constexpr (r + KP >= NPRV) {
+                        if constexpr (r + KP == NPRV) wcur += wadv;   // (this step's last read is issued: r + KP < NPR was false from NPR - KP on)
+                        pring[slot] = read_pair(std::integral_constant<int, r + KP - NPRV>{}, wcur);
+                    }
                 });
                 // the lane's two adjacent outputs: one dense 2*ES-byte store per lane, straight from the accumulators
                 {
-                    const unsigned kj = static_cast<unsigned>(j) * static_cast<unsigned>(pa.Sout);
-                    char *const dst = ybytes + (kj + my_out) * OS;
+                    char *const dst = ybytes + voff;      // (the ring's stores; the others take ybytes as saddr and voff as voffset: no address register to advance)
                     R v[2 * NC];
 #pragma unroll
                     for (int cc = 0; cc < NC; ++cc) { v[cc] = accA[cc]; v[NC + cc] = accB[cc]; }
                     // (ring mode, small chunks: write-through, so that a chunk's completion flag never overtakes its outputs -- every lane its own
                     //  pair; the round's first form paired neighbours into 16-byte stores by the even lanes: MRHIP_RING_OPTS bit 3)
                     // (ring mode: plain stores too, unless the ring runs the write-through protocol -- mrhip_internal.h: RingDev::flush_req)
-                    auto put2 = [&]() { if constexpr (RING) { if (ring_nshards >> 31) { store_wt<2 * OS>(dst, v); return; } } __builtin_memcpy(dst, v, 2 * OS); };
-                    auto put1 = [&]() { if constexpr (RING) { if (ring_nshards >> 31) { store_wt<OS>(dst, v); return; } } __builtin_memcpy(dst, v, OS); };
+                    auto put2 = [&]() { if constexpr (RING) { if (ring_nshards >> 31) store_wt<2 * OS>(dst, v); else __builtin_memcpy(dst, v, 2 * OS); } else store_sv<2 * OS>(ybytes, voff, v); };
+                    auto put1 = [&]() { if constexpr (RING) { if (ring_nshards >> 31) store_wt<OS>(dst, v); else __builtin_memcpy(dst, v, OS); } else store_sv<OS>(ybytes, voff, v); };
                     bool covered = false;                 // ring, Float32 real: this lane's pair went out with its even neighbour's
                     if constexpr (RING && 2 * OS == 8) {
                         if (!(ring_nshards >> 31)) {
@@ -394,7 +419,7 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
                             q[2] = static_cast<unsigned>(__builtin_amdgcn_mov_dpp(static_cast<int>(q[0]), 0xF5, 0xF, 0xF, false));   // quad_perm [1,1,3,3]: lane 2i reads lane 2i + 1
                             q[3] = static_cast<unsigned>(__builtin_amdgcn_mov_dpp(static_cast<int>(q[1]), 0xF5, 0xF, 0xF, false));
                             const unsigned lim_x = FULL ? static_cast<unsigned>(pa.P) : (static_cast<unsigned>(remaining) > kj ? umin(static_cast<unsigned>(remaining) - kj, static_cast<unsigned>(pa.P)) : 0u);
-                            const bool even = (lane_t & 1u) == 0u;
+                            const bool even = (static_cast<unsigned>(lane) & 1u) == 0u;
                             // an even lane whose neighbour's pair is inside too stores all four; the neighbour then has nothing to do
                             if (even && my_out + 3 < lim_x) {
                                 if (ring_opts & 2048u) {      // (experiment: system scope, the round's first form)
@@ -407,15 +432,26 @@ void rational_opair_kernel(PolyArgs a, PairArgs pa)
                         }
                     }
                     if (!covered) {
-                    if constexpr (FULL) {
-                        if (my_out + 1 < static_cast<unsigned>(pa.P)) put2();
-                    } else {
-                        const unsigned rem_j = static_cast<unsigned>(remaining) > kj ? static_cast<unsigned>(remaining) - kj : 0u;
-                        const unsigned lim = rem_j < static_cast<unsigned>(pa.P) ? rem_j : static_cast<unsigned>(pa.P);
-                        if (my_out + 1 < lim) put2();
-                        else if (my_out < lim) put1();
+                        bool in2, in1 = false;            // both outputs inside; only the first
+                        if constexpr (RING) {
+                            if constexpr (FULL) in2 = my_out + 1 < static_cast<unsigned>(pa.P);
+                            else {
+                                const unsigned rem_j = static_cast<unsigned>(remaining) > kj ? static_cast<unsigned>(remaining) - kj : 0u;
+                                const unsigned lim = rem_j < static_cast<unsigned>(pa.P) ? rem_j : static_cast<unsigned>(pa.P);
+                                in2 = my_out + 1 < lim; in1 = my_out < lim;
+                            }
+                        } else if constexpr (FULL) in2 = __builtin_amdgcn_inverse_ballot_w64(mIn);
+                        else {
+                            const int rem_j = remaining - static_cast<int>(kj);
+                            const bool whole = rem_j >= pa.P, part = rem_j > 0;
+                            in2 = __builtin_amdgcn_inverse_ballot_w64(whole ? mIn : part ? mPart2 : 0ull);
+                            in1 = __builtin_amdgcn_inverse_ballot_w64(whole || !part ? 0ull : mPart1);
+                        }
+                        if (in2) put2();
+                        else if (in1) put1();
                     }
-                    }
+                    ybytes += static_cast<size_t>(pa.Sout) * OS;
+                    kj += static_cast<unsigned>(pa.Sout);
                 }
             }
             lgkm_wait<0>(pring[0]);                           // retires the last step's unused reads

@@ -76,6 +76,46 @@ __device__ __forceinline__ void lds_write_b64(unsigned byte_addr, v2f_t v)   // 
     asm volatile("ds_write_b64 %0, %1" ::"v"(byte_addr), "v"(v));
 }
 
+// ---- tile descriptors: loader wave -> compute waves, through LDS instructions only ----
+// (A `volatile unsigned *` into the dynamic LDS stays a generic pointer -- address-space inference leaves volatile accesses alone -- and
+//  its reads are flat_load_dword + s_waitcnt vmcnt(0): on gfx9 a wave's stores count in vmcnt too, so a compute wave that read a
+//  descriptor that way waited for its own output stores of the tile before.)  desc_put*: the publishing lanes' ds_write, drained by the
+// loader's s_waitcnt lgkmcnt(0) in front of its barrier; desc_get*: every lane reads the same address behind the barrier, read and wait
+// in one statement, the words wave-uniform in SGPRs.  lgkmcnt only.
+__device__ __forceinline__ void desc_put(unsigned byte_addr, unsigned w)
+{
+    asm volatile("ds_write_b32 %0, %1" ::"v"(byte_addr), "v"(w) : "memory");
+}
+__device__ __forceinline__ void desc_put2(unsigned byte_addr, unsigned w0, unsigned w1)   // 8-byte aligned
+{
+    v2u_t v;
+    v.x = w0; v.y = w1;
+    asm volatile("ds_write_b64 %0, %1" ::"v"(byte_addr), "v"(v) : "memory");
+}
+__device__ __forceinline__ unsigned desc_get(unsigned byte_addr)
+{
+    unsigned v;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(byte_addr) : "memory");
+    return static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(v)));
+}
+__device__ __forceinline__ void desc_get2(unsigned byte_addr, unsigned &w0, unsigned &w1)   // 8-byte aligned
+{
+    v2u_t v;
+    asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(byte_addr) : "memory");
+    w0 = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(v.x)));
+    w1 = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(v.y)));
+}
+template <int OFF>
+__device__ __forceinline__ void desc_get4(unsigned byte_addr, unsigned (&w)[4])           // byte_addr + OFF 16-byte aligned
+{
+    v4u_t v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(byte_addr), "n"(OFF) : "memory");
+    w[0] = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(v.x)));
+    w[1] = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(v.y)));
+    w[2] = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(v.z)));
+    w[3] = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(v.w)));
+}
+
 __device__ __forceinline__ void dma16(const void *gsrc, void *lds_wave_base)
 {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
@@ -220,6 +260,29 @@ __device__ __forceinline__ void store_wt(void *dst, const void *regs)
         static_assert(N == 32, "store_wt");
         v4u_t v0, v1; __builtin_memcpy(&v0, regs, 16); __builtin_memcpy(&v1, static_cast<const char *>(regs) + 16, 16);
         asm volatile("global_store_dwordx4 %0, %1, off sc1\n\tglobal_store_dwordx4 %0, %2, off offset:16 sc1" ::"v"(dst), "v"(v0), "v"(v1) : "memory");
+    }
+}
+
+// plain stores of N bytes of a lane's registers (N = 4, 8, 16, 32) to sbase + voff: a wave-uniform base in an SGPR pair (the instruction's
+// saddr) and the lane's 32-bit byte offset -- a base that moves from step to step moves on the scalar side.  (A store of more than 8
+// bytes reads its data for two more cycles: the s_nop keeps the next VALU write of those registers off it -- the compiler does not look
+// into the statement.)
+template <int N>
+__device__ __forceinline__ void store_sv(const void *sbase, unsigned voff, const void *regs)
+{
+    if constexpr (N == 4) {
+        unsigned v; __builtin_memcpy(&v, regs, 4);
+        asm volatile("global_store_dword %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
+    } else if constexpr (N == 8) {
+        v2u_t v; __builtin_memcpy(&v, regs, 8);
+        asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
+    } else if constexpr (N == 16) {
+        v4u_t v; __builtin_memcpy(&v, regs, 16);
+        asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
+    } else {
+        static_assert(N == 32, "store_sv");
+        v4u_t v0, v1; __builtin_memcpy(&v0, regs, 16); __builtin_memcpy(&v1, static_cast<const char *>(regs) + 16, 16);
+        asm volatile("global_store_dwordx4 %0, %1, %3\n\tglobal_store_dwordx4 %0, %2, %3 offset:16\n\ts_nop 1" ::"v"(voff), "v"(v0), "v"(v1), "s"(sbase) : "memory");
     }
 }
 

@@ -65,11 +65,11 @@ __device__ __forceinline__ void pair_take_dyn(PolyArgs &a, PairArgs &pa)
 template <int NC, bool FAST_SEAM = true>
 __device__ __forceinline__ void pair_loader_wave(const PolyArgs &a, const PairArgs &pa, unsigned char *smem, int lane)
 {
-    volatile unsigned *const tile_flag = reinterpret_cast<volatile unsigned *>(smem + pa.flags_off);   // [ns][2]: first step, steps (0 = end)
+    const unsigned tile_desc = static_cast<unsigned>(reinterpret_cast<uintptr_t>(smem)) + static_cast<unsigned>(pa.flags_off);   // [ns][2]: first step, steps (0 = end); pair_device.h: desc_put2
     auto tile_at = [&](unsigned g, unsigned jt) -> TileAt { return pair_tile_at(pa, g, jt); };
     // ================= loader wave: HBM -> LDS, one tile ahead of the compute waves =================
     // It is the only wave that waits on vmcnt, so the compute waves' output stores stay in flight
-    // across tiles (their barrier carries no memory wait).
+    // across tiles (their barrier carries no memory wait, and they fetch the descriptors by LDS reads).
     // Stages one tile; returns the number of LDS-DMA operations it left in flight (0 for the
     // checked register path, which drains everything before returning).
     const unsigned pad_magic = pa.pad_every > 0 ? 0xffffffffu / static_cast<unsigned>(pa.pad_every + 1) + 1u : 0u;   // ceil(2^32 / (cd + 1)) (cd + 1 is no power of two's divisor issue: cd + 1 >= 3 odd)
@@ -109,13 +109,25 @@ __device__ __forceinline__ void pair_loader_wave(const PolyArgs &a, const PairAr
                 }
                 return nslots;
             }
+            if (cd <= 0) {
+                // linear tile: lane l of slot k moves chunk 64 k + l -- a lane-constant byte offset on a base that advances on the scalar
+                // side; only the tile's LAST slot has lanes past the end, which re-read chunk 0
+                const unsigned loff = 16u * static_cast<unsigned>(lane);
+                for (int slot = 0; slot < nslots - 1; ++slot) {
+                    dma16(src + loff, st + static_cast<size_t>(slot) * 1024);
+                    src += 1024;
+                }
+                const int ci = (nslots - 1) * 64 + lane;
+                dma16(ci < nchunks ? src + loff : reinterpret_cast<const unsigned char *>(xc + o * NC), st + static_cast<size_t>(nslots - 1) * 1024);
+                return nslots;
+            }
             for (int slot = 0; slot < nslots; ++slot) {
                 const int ci = slot * 64 + lane;
-                int d = ci;
                 // (the pad period is a run-time value: a multiply-high by ceil(2^32 / (cd + 1)), exact for ci < 2^16, instead of
                 //  an integer division per lane and slot -- ~40 VALU instructions each, on the SIMD the loader shares with a
                 //  compute wave: a third of C3b's VALU instructions were this, profiles/r04/item7/)
-                if (cd > 0) { const int g = static_cast<int>(__umulhi(static_cast<unsigned>(ci), pad_magic)), r = ci - g * (cd + 1); d = r == cd ? 0 : g * cd + r; }
+                const int g = static_cast<int>(__umulhi(static_cast<unsigned>(ci), pad_magic)), r = ci - g * (cd + 1);
+                const int d = r == cd ? 0 : g * cd + r;
                 const int cis = d < nchunks ? d : 0;                     // pad chunks and padding lanes re-read chunk 0
                 dma16(src + static_cast<size_t>(cis) * 16, st + static_cast<size_t>(slot) * 1024);
             }
@@ -199,12 +211,12 @@ __device__ __forceinline__ void pair_loader_wave(const PolyArgs &a, const PairAr
     auto produce = [&](int stage) -> bool {
         if (ra >= rb && more) grab_take();
         if (ra >= rb) {
-            if (lane == 0) { tile_flag[2 * stage] = 0u; tile_flag[2 * stage + 1] = 0u; }
+            if (lane == 0) desc_put2(tile_desc + 8u * static_cast<unsigned>(stage), 0u, 0u);
             hist <<= 6;
             return false;
         }
         const TileAt ta = tile_at(ra, rb - ra);
-        if (lane == 0) { tile_flag[2 * stage] = ra; tile_flag[2 * stage + 1] = static_cast<unsigned>(ta.jt); }
+        if (lane == 0) desc_put2(tile_desc + 8u * static_cast<unsigned>(stage), ra, static_cast<unsigned>(ta.jt));
         hist = (hist << 6) | static_cast<unsigned>((pa.ablate & 1) ? 0 : stage_tile(ta, stage));
         ra += static_cast<unsigned>(ta.jt);
         return true;
@@ -509,7 +521,7 @@ __device__ __forceinline__ void pair_ring_loader_wave(const PolyArgs &a, const P
     RingHost *const rh = a.ring_host;
     if (lane == 0) (void)__hip_atomic_fetch_add(&rd->arrived, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (ring_launch counts the workgroups that started)
     if (blockIdx.x == 0) { if (lane == 0) st_sc1(&rd->grid, static_cast<unsigned long long>(gridDim.x)); ring_feeder(rd, rh, lane); return; }
-    volatile unsigned *const td = reinterpret_cast<volatile unsigned *>(smem + pa.flags_off);   // [ns][kRingTileWords]
+    const unsigned td = static_cast<unsigned>(reinterpret_cast<uintptr_t>(smem)) + static_cast<unsigned>(pa.flags_off);   // [ns][kRingTileWords]; pair_device.h: desc_put
     // (what every lane loads alike goes to scalar registers at once: the compiler takes a vector load's result for divergent, and with it every
     //  branch on it and every value assigned under such a branch -- the chunk context, the scan position -- which then live in VGPRs)
     auto uni = [](unsigned long long v) -> unsigned long long {
@@ -719,7 +731,7 @@ __device__ __forceinline__ void pair_ring_loader_wave(const PolyArgs &a, const P
         return n < 60 ? n : 60;
     };
     auto end_marker = [&](int stage) {
-        if (lane == 0) { td[kRingTileWords * stage] = 0u; td[kRingTileWords * stage + 1] = 0u; }
+        if (lane == 0) desc_put2(td + kRingTileWords * 4u * static_cast<unsigned>(stage), 0u, 0u);
         ops <<= 6;
     };
     // The compute waves report a grab at the START of the tile after it (their write-through stores have had that tile's landing time
@@ -741,7 +753,7 @@ __device__ __forceinline__ void pair_ring_loader_wave(const PolyArgs &a, const P
                     else __builtin_amdgcn_s_sleep(32);
                 }
                 if (ng == kWouldBlock) {
-                    if (lane == 0) { td[kRingTileWords * stage] = 1u; td[kRingTileWords * stage + 1] = 2u; }   // FLUSH / idle
+                    if (lane == 0) desc_put2(td + kRingTileWords * 4u * static_cast<unsigned>(stage), 1u, 2u);   // FLUSH / idle
                     ++st_flush; ++st_flush_run;
                     ops <<= 6;
                     unreported = false;
@@ -773,7 +785,7 @@ __device__ __forceinline__ void pair_ring_loader_wave(const PolyArgs &a, const P
             unsigned mine = w[0];
 #pragma unroll
             for (int k = 1; k < 12; ++k) mine = lane == k ? w[k] : mine;
-            if (lane < 12) td[kRingTileWords * stage + lane] = mine;
+            if (lane < 12) desc_put(td + 4u * (kRingTileWords * static_cast<unsigned>(stage) + static_cast<unsigned>(lane)), mine);
         }
         ops = (ops << 6) | static_cast<unsigned>(n_ops);
         ra += static_cast<unsigned>(ta.jt);
@@ -794,7 +806,7 @@ __device__ __forceinline__ void pair_ring_loader_wave(const PolyArgs &a, const P
         }
         return true;
     };
-    if (lane < pa.ns) td[kRingTileWords * pa.ns + lane] = 0u;   // per stage: compute waves through with a grab's last tile (opair_kernel.inc)
+    if (lane < pa.ns) desc_put(td + 4u * (kRingTileWords * static_cast<unsigned>(pa.ns) + static_cast<unsigned>(lane)), 0u);   // per stage: compute waves through with a grab's last tile (opair_kernel.inc)
     const bool stats = (opts & 256u) != 0u;
     const bool flush_mode = true;                             // (every loader does the write-back duty; chunks choose their protocol: RingDesc::flags)
     unsigned long long fl_since = 0, fl_last = 0, fl_changed = 0;   // when this wave first saw a request its XCD has not taken on; the newest request it has seen, since when
