@@ -767,6 +767,63 @@ int mrhip_set_channel_taps(mrhip_filter *f, const void *h /* [nchannels][hLen] *
  *     for long channels. */
 int mrhip_set_channel_taps_farrow(mrhip_filter *f, const void *h /* [nchannels][hLen] */, int64_t hLen, int tap_dtype);
 int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb /* [nchannels][tapsPerPhi][polyorder+1] */, int64_t tapsPerPhi, int64_t polyorder);
+/* Device-resident updates for the filters with per-channel rates (mrhip_create_arbitrary_rates, mrhip_create_farrow_rates*, with or
+ * without per-channel taps).  A Doppler or clock tracker, or a block-LMS equaliser, computes the next rates and taps on the GPU from the
+ * last chunk's outputs; mrhip_set_channel_rates, mrhip_set_channel_taps and mrhip_set_channel_pnfb take HOST arrays and wait for the
+ * filter's stream, once per chunk.  The three calls below take DEVICE pointers and enqueue on `stream`: a loop of filter call, tracker,
+ * update, filter call runs without the host learning anything or waiting for anything (what mrhip_filt_device_async is to the one-rate
+ * filters).  They answer the "stream-ordered update without the host wait" the sections above list as left out; no double-buffered banks
+ * are needed, since the update kernel runs in stream order between the filter kernels.
+ *   - ordering: each call adopts `stream` as mrhip_filt_device_rates does (a filter whose last call ran on another stream: `stream` waits
+ *     for it through an event) and takes effect behind the calls already enqueued and ahead of every later one.  The device arrays are
+ *     read in stream order: they must hold their values by then and may be overwritten by work enqueued on `stream` afterwards.  A
+ *     capturing stream is MRHIP_ERR_UNSUPPORTED.  Every refusal comes before anything is enqueued or changed, its message naming the
+ *     function;
+ *   - mrhip_set_channel_rates_device: the host cannot see the values, so the caller declares the range they lie in, [rate_lo, rate_hi].
+ *     MRHIP_ERR_INVALID_ARG: f or rates NULL, a filter without per-channel rates, rate_lo or rate_hi not finite or not > 0, rate_hi <
+ *     rate_lo; MRHIP_ERR_UNSUPPORTED: rate_lo < 2^-30, a capturing stream.  From then on mrhip_outputlength_bound and the buffer checks
+ *     of later calls follow rate_hi, the tiled kernels' plans rate_lo; a later mrhip_set_channel_rates replaces both.  On the device
+ *     (rates_set_kernel, one lane per channel) channel c reads r = rates[c]; r finite and rate_lo <= r <= rate_hi: rate = r and delta =
+ *     Nphi / r, one Float64 division, the operation mrhip_set_channel_rates performs; any other value: the channel KEEPS its rate and
+ *     delta, and its record receives the status MRHIP_ERR_INVALID_ARG unless it holds an earlier one.  phiAccumulator, inputDeficit,
+ *     xIdx, the count, the history and the taps are not touched.  A refused value never reaches the walk, an accepted one is inside the
+ *     range the bound and the plans were sized for, and the overrun clip of the schedule kernel stays as the last line (it is what
+ *     catches a refused channel whose OLD rate lies above the new rate_hi: declare a range that holds the rates in force as well);
+ *   - reporting: mrhip_get_channel_states returns MRHIP_ERR_INVALID_ARG while a record holds that status ("a device-resident rate was
+ *     refused ... the channel kept its rate"; the states are filled in all the same); an overrun keeps answering
+ *     MRHIP_ERR_BUFFER_TOO_SMALL with its message and goes first.  mrhip_set_channel_states and mrhip_reset clear the refusal as they
+ *     clear an overrun;
+ *   - parity (rates): from the next call on channel c continues bit for bit as after mrhip_set_channel_rates with the same values --
+ *     outputs, counts, states and history, under STRICT and FUSED, FIRArbitrary and FIRFarrow, shared and per-channel taps, through
+ *     both mrhip_filt_device_rates* calls;
+ *   - mrhip_set_channel_taps_device (FIRArbitrary): h holds nchannels rows of hLen taps in the filter's tap dtype, the layout of
+ *     mrhip_set_channel_taps, whose checks apply unchanged; a FIRFarrow filter is MRHIP_ERR_UNSUPPORTED with a message that points to
+ *     mrhip_set_channel_pnfb_device.  One kernel (rates_bank_build_kernel) writes what mrhip_set_channel_taps uploads, bit for bit: bank
+ *     c holds at c*Nphi*T + phi*T + i the tap h_c[j], j = (T-1-i)*Nphi + phi, 0 for j >= hLen; the dpfb bank h_c[j+1] - h_c[j], one
+ *     subtraction rounded in the tap type, 0 for j >= hLen-1; both widened exactly to the arithmetic type.  From the next call on the
+ *     filter is bit for bit the filter after mrhip_set_channel_taps with the same matrix, and runs the same two kernels
+ *     (arb_rates_bank_generic, arb_rates_bank_tiled);
+ *   - mrhip_set_channel_pnfb_device (FIRFarrow): pnfb holds [nchannels][tapsPerPhi][polyorder+1] Float64, the layout and the checks of
+ *     mrhip_set_channel_pnfb; a filter of mrhip_create_arbitrary_rates is MRHIP_ERR_INVALID_ARG with a message that points to
+ *     mrhip_set_channel_taps_device.  One kernel copies the coefficients, rounding each to Float32 and widening it back on a filter with
+ *     Float32 taps, as mrhip_set_channel_pnfb rounds.  Parity is with mrhip_set_channel_pnfb given the same array;
+ *   - allocation: the FIRST tap or bank call on a filter whose taps are still shared allocates the nchannels banks and waits once, on
+ *     the host, for the filter's stream; the shared pair (the shared bank) is freed right after that one wait -- it is not kept until
+ *     mrhip_destroy.  Every later call enqueues one kernel and returns without waiting.  A failed allocation leaves the filter bit for
+ *     bit as it was;
+ *   - host copies: after a device install the host no longer holds the taps.  mrhip_get_taps and mrhip_arbitrary_tapsforphase
+ *     (mrhip_get_pnfb and mrhip_farrow_tapsforphase) then wait for the filter's stream and read the banks back -- narrowing the
+ *     arithmetic type to the tap type is exact -- and answer in the per-channel layouts.  A later host install makes the host copy
+ *     current again.  mrhip_get_channel_states reports the rates the records hold;
+ *   - a filter on which none of the three was called runs the launches and kernels it always ran; the ABI version stays 1; there are
+ *     still sixteen constructors;
+ *   - left out on purpose: input lengths that live on the device; the FIRFarrow fit on the device (a mrhip_set_channel_taps_farrow
+ *     twin); updates from a stream other than the one the filter's calls run on without ordering by the caller (the device arrays are
+ *     read on `stream`); graph capture; complex taps; the parallel schedule for long channels. */
+int mrhip_set_channel_rates_device(mrhip_filter *f, const double *rates /* DEVICE, [nchannels] */, double rate_lo, double rate_hi, void *stream);
+int mrhip_set_channel_taps_device(mrhip_filter *f, const void *h /* DEVICE, [nchannels][hLen] */, int64_t hLen, int tap_dtype, void *stream);
+int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb /* DEVICE, [nchannels][tapsPerPhi][polyorder+1] */, int64_t tapsPerPhi,
+                                  int64_t polyorder, void *stream);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call

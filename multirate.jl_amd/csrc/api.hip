@@ -287,6 +287,42 @@ hipError_t launch_poly(const mrhip_filter *f, const TypeKey &tk, bool fused, con
 }  // namespace
 
 bool any_capture_active() { return any_capture_active_impl(); }
+
+// The host copies of the banks behind a device-resident update (mrhip_set_channel_taps_device, mrhip_set_channel_pnfb_device): the
+// installs are on the filter's stream, so wait for it, then read the banks back.  FIRArbitrary: d_taps / d_dtaps hold R, the host
+// copies the tap type -- every element is a widened tap or a widened difference of two taps, so narrowing is exact.
+int refresh_host_taps(mrhip_filter *f)
+{
+    if (!f->taps_stale) return MRHIP_OK;
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
+    if (int rc = drain_filter(f)) return rc;
+    if (f->kind == MRHIP_FIR_FARROW) {
+        std::vector<double> pn(static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1));
+        MRHIP_CHECK_HIP(hipMemcpy(pn.data(), f->d_pnfb, pn.size() * sizeof(double), hipMemcpyDeviceToHost));
+        f->h_pnfb.swap(pn);
+    } else {
+        const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->Nphi) * static_cast<size_t>(f->T), es = dtype_scalar_size(f->th);
+        const bool narrow = f->r_f64 && !dtype_is_f64(f->th);
+        std::vector<unsigned char> host[2];
+        std::vector<double> wide(narrow ? n : 0);
+        const void *dev[2] = {f->d_taps, f->d_dtaps};
+        for (int b = 0; b < 2; ++b) {
+            host[b].resize(n * es);
+            if (narrow) {
+                MRHIP_CHECK_HIP(hipMemcpy(wide.data(), dev[b], n * sizeof(double), hipMemcpyDeviceToHost));
+                float *dst = reinterpret_cast<float *>(host[b].data());
+                for (size_t i = 0; i < n; ++i) dst[i] = static_cast<float>(wide[i]);
+            } else {
+                MRHIP_CHECK_HIP(hipMemcpy(host[b].data(), dev[b], n * es, hipMemcpyDeviceToHost));
+            }
+        }
+        f->h_taps.swap(host[0]);
+        f->h_dtaps.swap(host[1]);
+    }
+    f->taps_stale = false;
+    return MRHIP_OK;
+}
 }  // namespace mrhip
 
 using namespace mrhip;
@@ -332,6 +368,7 @@ int mrhip_get_pnfb(const mrhip_filter *f, double *host_out)
 {
     if (!f || !host_out) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
     if (f->kind != MRHIP_FIR_FARROW) return fail(MRHIP_ERR_INVALID_ARG, "not a FIRFarrow filter");
+    if (int rc = refresh_host_taps(const_cast<mrhip_filter *>(f))) return rc;      // (after mrhip_set_channel_pnfb_device: the banks are read back)
     std::memcpy(host_out, f->h_pnfb.data(), f->h_pnfb.size() * sizeof(double));
     return MRHIP_OK;
 }
@@ -342,6 +379,7 @@ int mrhip_farrow_tapsforphase(const mrhip_filter *f, double phase, void *host_ou
     if (f->kind != MRHIP_FIR_FARROW) return fail(MRHIP_ERR_INVALID_ARG, "not a FIRFarrow filter");
     if (!(phase >= 0.0 && phase <= static_cast<double>(f->Nphi) + 1.0))
         return fail(MRHIP_ERR_INVALID_ARG, "phase must be >= 0 and <= Nphi+1");      // Filters.jl:765
+    if (int rc = refresh_host_taps(const_cast<mrhip_filter *>(f))) return rc;      // (after mrhip_set_channel_pnfb_device: the banks are read back)
     const int64_t P = f->polyorder;
     // complex taps: the same statement per component (Real*Complex and Complex+Complex are by components) -- a polynomial is
     // P+1 (re, im) pairs, the result T interleaved pairs
@@ -783,6 +821,7 @@ int mrhip_set_mod_form(mrhip_filter *f, int form)
 int mrhip_get_taps(mrhip_filter *f, int which, void *host_out)
 {
     if (!f || !host_out) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = refresh_host_taps(f)) return rc;        // (after mrhip_set_channel_taps_device: the banks are read back)
     const auto &src = which ? f->h_dtaps : f->h_taps;
     if (src.empty()) return fail(MRHIP_ERR_INVALID_ARG, "filter has no such tap bank");
     std::memcpy(host_out, src.data(), src.size());
@@ -1763,6 +1802,13 @@ static int ragged_upload(mrhip_filter *f, const int64_t *h_lens, hipStream_t str
     return MRHIP_OK;
 }
 
+// the smallest rate the tiled kernels' plans size their spans for: the smallest of the rates the host installed, or the lower end of the
+// range the caller declared for rates that came from device memory (mrhip_set_channel_rates_device)
+static double rates_min(const mrhip_filter *f)
+{
+    return f->dev_rate_lo > 0.0 ? f->dev_rate_lo : *std::min_element(f->h_rates.begin(), f->h_rates.end());
+}
+
 // What both entry points enqueue once their checks are through.  x_len: the call's one length, or the largest of h_lens (HOST, [nch]: a
 // ragged call); bound: mrhip_outputlength_bound of it.
 static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64_t *h_lens, int64_t x_stride, void *y, int64_t y_stride,
@@ -1830,11 +1876,11 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
         tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
         if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
     } else if (bound > 0 && !f->force_generic && tk.bank) {      // (mrhip_set_channel_taps: kernels_rates_bank_arb.hip; no plan_* below sees such a call)
-        const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
+        const double rate_min = rates_min(f);
         tiled = plan_arb_rates_bank_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
         if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_bank_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
     } else if (bound > 0 && !f->force_generic) {
-        const double rate_min = *std::min_element(f->h_rates.begin(), f->h_rates.end());
+        const double rate_min = rates_min(f);
         tiled = plan_arb_rates_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
         if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
     }
@@ -1926,7 +1972,7 @@ int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
     if (int rc = drain_filter(f)) return rc;          // the records are written by the filter's own last call
     std::vector<RateChannel> v(static_cast<size_t>(f->nch));
     MRHIP_CHECK_HIP(hipMemcpy(v.data(), f->d_rrec, v.size() * sizeof(RateChannel), hipMemcpyDeviceToHost));
-    bool overrun = false;
+    bool overrun = false, rate_refused = false;
     for (size_t c = 0; c < v.size(); ++c) {
         const RateChannel &r = v[c];
         mrhip_channel_state &o = out[c];
@@ -1934,9 +1980,13 @@ int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
         o.phiIdx = static_cast<int64_t>(std::floor(r.acc));                  // Filters.jl:671-672
         o.alpha = r.acc - static_cast<double>(o.phiIdx);
         o.inputDeficit = r.inputDeficit; o.xIdx = r.xIdx; o.last_count = r.count;
-        overrun = overrun || r.error != 0;
+        overrun = overrun || (r.error != 0 && r.error != MRHIP_ERR_INVALID_ARG);
+        rate_refused = rate_refused || r.error == MRHIP_ERR_INVALID_ARG;
     }
     if (overrun) return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "a channel's schedule overran the bound of its call (outputs were clipped): mrhip_reset the filter");
+    if (rate_refused)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_rates_device: a device-resident rate was refused (not finite, or outside the declared "
+                                           "[rate_lo, rate_hi]); the channel kept its rate: mrhip_set_channel_states or mrhip_reset clears this");
     return MRHIP_OK;
 }
 
@@ -1978,6 +2028,7 @@ int mrhip_set_channel_rates(mrhip_filter *f, const double *rates)
     for (size_t c = 0; c < v.size(); ++c) { v[c].rate = rates[c]; v[c].delta = static_cast<double>(f->Nphi) / rates[c]; }
     MRHIP_CHECK_HIP(hipMemcpy(f->d_rrec, v.data(), v.size() * sizeof(RateChannel), hipMemcpyHostToDevice));
     f->h_rates.assign(rates, rates + f->nch);
+    f->dev_rate_lo = 0.0;                                             // (the host knows every rate again)
     f->rate = rate_max;
     f->delta = static_cast<double>(f->Nphi) / rate_max;
     return MRHIP_OK;
@@ -2030,6 +2081,7 @@ int mrhip_set_channel_taps(mrhip_filter *f, const void *h, int64_t hLen, int tap
     }
     f->h_taps.swap(pfb);
     f->h_dtaps.swap(dpfb);
+    f->taps_stale = false;                                            // (the host copies are current again)
     return MRHIP_OK;
 }
 
@@ -2068,6 +2120,7 @@ static int install_channel_pnfb(mrhip_filter *f, const std::string &who, std::ve
         f->bank = true;
     }
     f->h_pnfb.swap(pn);
+    f->taps_stale = false;                                            // (the host copy is current again)
     return MRHIP_OK;
 }
 
@@ -2089,6 +2142,117 @@ int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb, int64_t tapsPerP
         return fail(r.status, r.message);
     std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1));
     return install_channel_pnfb(f, "mrhip_set_channel_pnfb", pn);
+}
+
+// ---- Device-resident updates (include/multirate_hip.h, "Device-resident updates for the filters with per-channel rates") ----------------
+// The three calls below take their values from DEVICE memory and enqueue on the caller's stream, adopted as mrhip_filt_device_rates
+// adopts it: behind the filter's calls already enqueued, ahead of every later one.  Every refusal comes before anything is enqueued or
+// changed; a capturing stream is refused.
+static int device_update_stream(mrhip_filter *f, const char *who, hipStream_t stream)
+{
+    if (stream_is_capturing(stream))
+        return fail(MRHIP_ERR_UNSUPPORTED, std::string(who) + ": a filter with per-channel rates is not captured into a HIP graph");
+    return MRHIP_OK;
+}
+
+// rec.rate / rec.delta of every channel from rates[c] (rates_set_kernel); the host keeps the declared range in the place of the values:
+// f->rate = rate_hi (mrhip_outputlength_bound, the buffer checks), dev_rate_lo = rate_lo (the tiled kernels' plans).
+int mrhip_set_channel_rates_device(mrhip_filter *f, const double *rates, double rate_lo, double rate_hi, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_rates_device: NULL filter");
+    if (Refusal r = check_channel_rates_device(f->rates, rates == nullptr, rate_lo, rate_hi)) return fail(r.status, r.message);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "mrhip_set_channel_rates_device: hipSetDevice failed");
+    if (int rc = device_update_stream(f, "mrhip_set_channel_rates_device", stream)) return rc;
+    if (int rc = adopt_stream(f, stream)) return rc;
+    MRHIP_CHECK_HIP(launch_rates_set(f->d_rrec, rates, rate_lo, rate_hi, static_cast<double>(f->Nphi), static_cast<int>(f->nch), stream));
+    f->rate = rate_hi;
+    f->delta = static_cast<double>(f->Nphi) / rate_hi;
+    f->dev_rate_lo = rate_lo;
+    return MRHIP_OK;
+}
+
+// The nch pfb and dpfb banks from h (rates_bank_build_kernel).  A filter whose taps are still shared: the two allocations first (a failure
+// leaves the filter as it was), then ONE wait for the filter's stream -- the kernels enqueued so far read the shared pair, which is freed
+// here --; every later call enqueues its kernel and returns.
+int mrhip_set_channel_taps_device(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps_device: NULL filter");
+    if (Refusal r = check_channel_taps_device(f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th)) return fail(r.status, r.message);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "mrhip_set_channel_taps_device: hipSetDevice failed");
+    if (int rc = device_update_stream(f, "mrhip_set_channel_taps_device", stream)) return rc;
+    const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->Nphi) * static_cast<size_t>(f->T), rsize = f->r_f64 ? 8 : 4;
+    void *d_new[2] = {f->d_taps, f->d_dtaps};                       // (a later call: the banks of the first one, reused)
+    if (!f->bank) {
+        d_new[0] = d_new[1] = nullptr;
+        if (hipMalloc(&d_new[0], n * rsize) != hipSuccess || hipMalloc(&d_new[1], n * rsize) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d_new[0]) (void)hipFree(d_new[0]);
+            return fail(MRHIP_ERR_HIP, "mrhip_set_channel_taps_device: no device memory for the channels' filter banks");
+        }
+    }
+    auto bail = [&](int rc) { if (!f->bank) { (void)hipFree(d_new[0]); (void)hipFree(d_new[1]); } return rc; };
+    if (!f->bank)
+        if (int rc = drain_filter(f)) return bail(rc);
+    if (int rc = adopt_stream(f, stream)) return bail(rc);
+    BankBuildArgs b{};
+    b.h = h; b.pfb = d_new[0]; b.dpfb = d_new[1];
+    b.hLen = f->hLen; b.T = f->T; b.Nphi = f->Nphi; b.nch = static_cast<int>(f->nch);
+    if (launch_rates_bank_build(dtype_is_f64(f->th), f->r_f64, b, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail(MRHIP_ERR_HIP, "mrhip_set_channel_taps_device: the bank build kernel could not be launched"));
+    }
+    if (!f->bank) {
+        (void)hipFree(f->d_taps_alloc);
+        (void)hipFree(f->d_dtaps_alloc);
+        f->d_taps = f->d_taps_alloc = d_new[0];
+        f->d_dtaps = f->d_dtaps_alloc = d_new[1];
+        f->bank = true;
+    }
+    f->taps_stale = true;
+    return MRHIP_OK;
+}
+
+// The nch polynomial banks from pnfb (rates_pnfb_install_kernel), rounded to the tap type as install_channel_pnfb rounds.  The first
+// call's allocation and its one wait, the shared bank and d_pnfb_t: as mrhip_set_channel_taps_device and install_channel_pnfb.
+int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb, int64_t tapsPerPhi, int64_t polyorder, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_pnfb_device: NULL filter");
+    if (Refusal r = check_channel_pnfb_device(f->rates, f->kind == MRHIP_FIR_FARROW, pnfb, tapsPerPhi, polyorder, f->T, f->polyorder, f->th))
+        return fail(r.status, r.message);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "mrhip_set_channel_pnfb_device: hipSetDevice failed");
+    if (int rc = device_update_stream(f, "mrhip_set_channel_pnfb_device", stream)) return rc;
+    const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1);
+    double *d_new = f->d_pnfb;                                          // (a later call: the banks of the first one, reused)
+    if (!f->bank) {
+        d_new = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&d_new), n * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MRHIP_ERR_HIP, "mrhip_set_channel_pnfb_device: no device memory for the channels' polynomial banks");
+        }
+    }
+    auto bail = [&](int rc) { if (!f->bank) (void)hipFree(d_new); return rc; };
+    if (!f->bank)
+        if (int rc = drain_filter(f)) return bail(rc);
+    if (int rc = adopt_stream(f, stream)) return bail(rc);
+    if (launch_rates_pnfb_install(!dtype_is_f64(f->th), pnfb, d_new, static_cast<long long>(n), stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail(MRHIP_ERR_HIP, "mrhip_set_channel_pnfb_device: the install kernel could not be launched"));
+    }
+    if (!f->bank) {
+        (void)hipFree(f->d_pnfb);
+        if (f->d_pnfb_t) (void)hipFree(f->d_pnfb_t);
+        f->d_pnfb = d_new;
+        f->d_pnfb_t = nullptr;
+        f->bank = true;
+    }
+    f->taps_stale = true;
+    return MRHIP_OK;
 }
 
 int mrhip_sync_state(mrhip_filter *f, int64_t *last_n_written)

@@ -219,6 +219,7 @@ int mrhip_arbitrary_tapsforphase(const mrhip_filter *f, double phase, void *host
     const double alpha = std::modf(phase, &ip);                                                 // :681
     const int64_t col = static_cast<int64_t>(ip);                                               // :682
     if (col < 1 || col > f->Nphi) return fail(MRHIP_ERR_INVALID_ARG, "phase selects column 0 or Nphi+1 of the filter bank (BoundsError in the reference)");
+    if (int rc = mrhip::refresh_host_taps(const_cast<mrhip_filter *>(f))) return rc;      // (after mrhip_set_channel_taps_device: the banks are read back)
     // complex taps: the same statement per component (Julia: Complex{T} + Float64 * Complex{T} promotes both components to
     // Float64) -- the column is 2T interleaved scalars
     const size_t nc = dtype_is_complex(f->th) ? 2 : 1;

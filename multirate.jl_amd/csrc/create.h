@@ -85,6 +85,15 @@ Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow,
 // the length checks of mrhip_filt_device_rates_ragged, in its order: x_lens itself, every length (negative, then 2^31-1 and above), x
 // against the largest length, x_stride against it for nch > 1; *len_max: the largest length (what the call's bound is taken from)
 Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null, int64_t x_stride, int64_t *len_max);
+// The device-resident updates (the public header, "Device-resident updates for the filters with per-channel rates"): what the three calls
+// refuse before they look at the stream, each in its own name.
+// mrhip_set_channel_rates_device: f is a filter with per-channel rates, rates is there, and the declared range [rate_lo, rate_hi]
+Refusal check_channel_rates_device(bool is_rates, bool rates_is_null, double rate_lo, double rate_hi);
+// mrhip_set_channel_taps_device: a FIRFarrow filter is pointed to mrhip_set_channel_pnfb_device, then check_channel_taps unchanged
+Refusal check_channel_taps_device(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th);
+// mrhip_set_channel_pnfb_device: a FIRArbitrary filter is pointed to mrhip_set_channel_taps_device, then check_channel_taps_farrow(true, ...)
+Refusal check_channel_pnfb_device(bool is_rates, bool is_farrow, const void *pnfb, int64_t tapsPerPhi, int64_t polyorder, int64_t f_T,
+                                  int64_t f_polyorder, int f_th);
 // (c) the banks, `rows` tap vectors of hLen taps each, one bank per row, one after the other.  taps2pfb of every row into pfb and
 // (dpfb != NULL: FIRArbitrary) of its dh = [diff(h), 0] into dpfb; returns tapsPerPhi
 int64_t create_pfb_banks(const void *h, int64_t hLen, int th, int64_t Nphi, size_t rows, std::vector<unsigned char> *pfb, std::vector<unsigned char> *dpfb);

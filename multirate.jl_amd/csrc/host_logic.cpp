@@ -806,6 +806,36 @@ Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow,
     return {};
 }
 
+// mrhip_set_channel_rates_device: the host cannot see the rates, so the caller declares the range they lie in; the range is held to what
+// check_channel_rates holds every rate to (finite, > 0, not below 2^-30), since the bound and the plans are sized for its two ends
+Refusal check_channel_rates_device(bool is_rates, bool rates_is_null, double rate_lo, double rate_hi)
+{
+    const std::string who = "mrhip_set_channel_rates_device";
+    if (!is_rates) return {MRHIP_ERR_INVALID_ARG, who + " takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates"};
+    if (rates_is_null) return {MRHIP_ERR_INVALID_ARG, who + ": rates is NULL"};
+    if (!std::isfinite(rate_lo) || !std::isfinite(rate_hi) || !(rate_lo > 0.0) || !(rate_hi > 0.0))
+        return {MRHIP_ERR_INVALID_ARG, who + ": rate_lo and rate_hi must be finite and greater than 0"};
+    if (rate_hi < rate_lo) return {MRHIP_ERR_INVALID_ARG, who + ": rate_hi < rate_lo"};
+    if (rate_lo < 1.0 / static_cast<double>(1LL << 30)) return {MRHIP_ERR_UNSUPPORTED, who + ": a per-channel rate below 2^-30 (rate_lo)"};
+    return {};
+}
+
+Refusal check_channel_taps_device(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th)
+{
+    if (is_rates && is_farrow)
+        return {MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps_device: the fit of a FIRFarrow filter's rows on the device is left out: "
+                                       "mrhip_set_channel_pnfb_device takes fitted banks; mrhip_create_arbitrary_rates filters take this call"};
+    return check_channel_taps(is_rates, is_farrow, h, hLen, th, f_hLen, f_th);
+}
+
+Refusal check_channel_pnfb_device(bool is_rates, bool is_farrow, const void *pnfb, int64_t tapsPerPhi, int64_t polyorder, int64_t f_T,
+                                  int64_t f_polyorder, int f_th)
+{
+    if (is_rates && !is_farrow)
+        return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_pnfb_device: a filter of mrhip_create_arbitrary_rates takes mrhip_set_channel_taps_device"};
+    return check_channel_taps_farrow(true, is_rates, is_farrow, pnfb, tapsPerPhi, polyorder, f_th, f_T, f_polyorder, f_th);
+}
+
 Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null, int64_t x_stride, int64_t *len_max)
 {
     if (!x_lens) return {MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_ragged: x_lens is NULL"};

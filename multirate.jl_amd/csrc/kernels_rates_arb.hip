@@ -83,6 +83,20 @@ __global__ __launch_bounds__(kRatesSchedThreads) void rates_reset_kernel(RateCha
     rec[c].acc = 1.0; rec[c].inputDeficit = 1; rec[c].xIdx = 1; rec[c].count = 0; rec[c].error = 0;    // Filters.jl:110-115
 }
 
+// mrhip_set_channel_rates_device: the rate of channel c from DEVICE memory, in stream order.  A value that is finite and inside the range
+// the caller declared (lo <= r <= hi, both finite and > 0: a NaN fails both comparisons) is installed as mrhip_set_channel_rates installs
+// it -- delta = N𝜙 / r, one Float64 division --; any other leaves the record's rate and delta alone and marks the record, unless an
+// earlier status is still there.  Accumulator, inputDeficit, xIdx and count are not touched.
+__global__ __launch_bounds__(kRatesSchedThreads) void rates_set_kernel(RateChannel *rec, const double *__restrict__ rates, double lo, double hi,
+                                                                       double N, int nch)
+{
+    const int c = static_cast<int>(blockIdx.x) * kRatesSchedThreads + static_cast<int>(threadIdx.x);
+    if (c >= nch) return;
+    const double r = rates[c];
+    if (r >= lo && r <= hi) { rec[c].rate = r; rec[c].delta = N / r; }      // Filters.jl:113
+    else if (rec[c].error == 0) rec[c].error = MRHIP_ERR_INVALID_ARG;
+}
+
 // One lane per (channel, output), any (Nphi, T, hLen, rates): blockIdx.x covers the outputs up to the call's bound, blockIdx.y strides
 // the channels; the channel's count is uniform over the workgroup.
 template <typename TX, typename R, int NCX, bool FUSED>
@@ -209,6 +223,13 @@ hipError_t launch_rates_reset(RateChannel *rec, int nch, hipStream_t st)
 {
     const dim3 grid(static_cast<unsigned>((nch + kRatesSchedThreads - 1) / kRatesSchedThreads));
     hipLaunchKernelGGL(rates_reset_kernel, grid, dim3(kRatesSchedThreads), 0, st, rec, nch);
+    return hipGetLastError();
+}
+
+hipError_t launch_rates_set(RateChannel *rec, const double *rates, double lo, double hi, double N, int nch, hipStream_t st)
+{
+    const dim3 grid(static_cast<unsigned>((nch + kRatesSchedThreads - 1) / kRatesSchedThreads));
+    hipLaunchKernelGGL(rates_set_kernel, grid, dim3(kRatesSchedThreads), 0, st, rec, rates, lo, hi, N, nch);
     return hipGetLastError();
 }
 

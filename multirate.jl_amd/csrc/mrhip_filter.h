@@ -36,6 +36,9 @@ struct mrhip_filter {
     // (after mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb on a FIRFarrow one: `bank` is set too, d_pnfb / h_pnfb hold nch banks; kernels_rates_bank_farrow.hip only)
     bool rates = false;
     std::vector<double> h_rates;                           // [nch]
+    // device-resident updates (mrhip_set_channel_rates_device / _taps_device / _pnfb_device): the host no longer knows the values.
+    double dev_rate_lo = 0.0;                              // > 0: the rates came from device memory; they lie in [dev_rate_lo, rate] and h_rates is stale (the plans read dev_rate_lo)
+    bool taps_stale = false;                               // h_taps / h_dtaps (FIRFarrow: h_pnfb) are older than the device banks: refresh_host_taps reads them back
     mrhip::RateChannel *d_rrec = nullptr;                  // device, [nch]
     void *d_rs_n = nullptr, *d_rs_acc = nullptr;           // device: the channels' slices, [nch][bound of the call] entries
     size_t rs_cap = 0;                                     // entries either buffer holds
@@ -229,6 +232,9 @@ int rec_push(mrhip_filter *f, hipStream_t s, long long call_n_out = -1, long lon
 int rec_pull(mrhip_filter *f);
 // api.hip: is a stream the library has been called on still being captured into a graph?
 bool any_capture_active();
+// api.hip: after a device-resident tap update (mrhip_filter::taps_stale) wait for the filter's stream and read the banks back into
+// h_taps / h_dtaps (narrowing R to the tap type is exact) or h_pnfb; nothing otherwise
+int refresh_host_taps(mrhip_filter *f);
 hipError_t launch_poly_plan(mrhip_filter *f, int64_t x_len, long long P, long long y_capacity, long long *count_out, hipStream_t s, const DevCall *x_from = nullptr);
 }  // namespace mrhip
 // hipDeviceSynchronize as the library uses it: the wait for work on streams it never saw (replays of a graph that holds a filter's

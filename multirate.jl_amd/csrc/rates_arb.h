@@ -134,4 +134,38 @@ hipError_t launch_farrow_rates_bank_multi(const TypeKey &tk, bool fused, const F
 // the grid is farrow_rates_multi_grid's
 bool plan_farrow_rates_bank_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
 
+// ---- Device-resident updates (mrhip_set_channel_rates_device, mrhip_set_channel_taps_device, mrhip_set_channel_pnfb_device;
+// include/multirate_hip.h, "Device-resident updates for the filters with per-channel rates") ---------------------------------------------
+// The banks of one channel as create_pfb_banks (host_logic.cpp) builds them from the channel's row h (hLen taps, T = ceil(hLen / N𝜙)):
+// element e = 𝜙*T + i of the bank (phase 𝜙, row i) holds h[j] with j = (T-1-i)*N𝜙 + 𝜙, zero for j >= hLen (taps2pfb); the dpfb bank holds
+// dh[j] = h[j+1] - h[j], ONE subtraction rounded in the tap type, zero for j >= hLen-1 (arbitrary_dh: [diff(h), 0]).  The build kernel
+// (kernels_rates_bank_build.hip) and tests/rates_device_updates_check.cpp run this text.
+MRHIP_RATES_HD inline long long rates_bank_tap_index(long long e, long long T, long long Nphi)
+{
+    const long long phi = e / T, i = e - phi * T;
+    return (T - 1 - i) * Nphi + phi;
+}
+template <typename TAP>
+MRHIP_RATES_HD inline TAP rates_bank_pfb_value(const TAP *h, long long hLen, long long j) { return j < hLen ? h[j] : TAP(0); }
+template <typename TAP>
+MRHIP_RATES_HD inline TAP rates_bank_dpfb_value(const TAP *h, long long hLen, long long j) { return j + 1 < hLen ? TAP(h[j + 1] - h[j]) : TAP(0); }
+
+struct BankBuildArgs {             // the bank build kernel: one workgroup per (channel, slab of kBankBuildSlab bank elements)
+    const void *h;                 // DEVICE, [nch][hLen] in the tap type
+    void *pfb, *dpfb;              // DEVICE, [nch][Nphi*T] in R
+    long long hLen, T, Nphi;
+    int nch;
+    int row_in_lds;                // the channel's row is staged in LDS (hLen taps fit kBankBuildLdsBytes); else the kernel reads global memory
+};
+constexpr int kBankBuildThreads = 256;
+constexpr int kBankBuildSlab = 4 * kBankBuildThreads;      // bank elements of one workgroup
+constexpr long long kBankBuildLdsBytes = 32 * 1024;        // the room a channel's row may take in LDS
+
+// kernels_rates_arb.hip: rates[c] into record c where it is finite and inside [lo, hi], else the refusal into the record's status
+hipError_t launch_rates_set(RateChannel *rec, const double *rates, double lo, double hi, double N, int nch, hipStream_t st);
+// kernels_rates_bank_build.hip (tap_f64 / r_f64: the tap type of h and R of the banks; Float64 taps imply Float64 R)
+hipError_t launch_rates_bank_build(bool tap_f64, bool r_f64, const BankBuildArgs &b, hipStream_t st);
+// ... and n Float64 coefficients into the filter's polynomial banks, rounded to Float32 and widened back for Float32 taps
+hipError_t launch_rates_pnfb_install(bool tap_f32, const double *src, double *dst, long long n, hipStream_t st);
+
 }  // namespace mrhip

@@ -40,6 +40,18 @@ _NP2DT = {np.dtype(np.float32): F32, np.dtype(np.float64): F64,
 _DT2NP = {v: k for k, v in _NP2DT.items()}
 
 
+class _DeviceResident:
+    """What a Python-side mirror (``FIRFilter._rates``, ``._chan_taps``, ``._chan_farrow``) holds after a device-resident update
+    (``set_channel_rates_device`` and its siblings): the values were computed on the GPU and installed in stream order, so the host
+    knows their shape and nothing else.  Queries ask the library; binding such a filter again is refused."""
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+
+    def __len__(self):
+        return self.shape[0]
+
+
 class MultirateHIPError(RuntimeError):
     """Raised where the reference raises Julia ``error(...)`` (and for HIP/runtime failures)."""
 
@@ -105,6 +117,9 @@ ABI = [
     ("mrhip_set_channel_taps", _i, [_vp, _vp, _i64, _i]),
     ("mrhip_set_channel_taps_farrow", _i, [_vp, _vp, _i64, _i]),
     ("mrhip_set_channel_pnfb", _i, [_vp, _vp, _i64, _i64]),
+    ("mrhip_set_channel_rates_device", _i, [_vp, _vp, _d, _d, _vp]),
+    ("mrhip_set_channel_taps_device", _i, [_vp, _vp, _i64, _i, _vp]),
+    ("mrhip_set_channel_pnfb_device", _i, [_vp, _vp, _i64, _i64, _vp]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -591,6 +606,10 @@ class FIRFilter:
             return
         if tx not in _NP2DT:
             raise MultirateHIPError(1, f"unsupported sample dtype {tx}")
+        for mirror, call in ((self._rates, "set_channel_rates_device"), (self._chan_taps, "set_channel_taps_device"), (self._chan_farrow, "set_channel_pnfb_device")):
+            if isinstance(mirror, _DeviceResident):
+                raise MultirateHIPError(1, f"the filter was closed after {call}: its values lived on the device and are gone; install new ones "
+                                           f"through the host call before binding again")
         out = C.c_void_p()
         if self._bank is not None and nch != self._bank.shape[0]:
             raise MultirateHIPError(1, f"a per-channel filter of {self._bank.shape[0]} tap vectors binds to exactly that many channels; got {nch}")
@@ -921,6 +940,8 @@ class FIRFilter:
         if self._rates is None:
             raise MultirateHIPError(1, "channel_states needs a filter of FIRFilter.per_channel_rates or FIRFilter.per_channel_rates_farrow")
         out = (ChannelState * len(self._rates))()
+        if self._handle is None and isinstance(self._rates, _DeviceResident):
+            raise MultirateHIPError(1, "channel_states: the filter was closed after set_channel_rates_device; its rates lived on the device")
         if self._handle is None:                                   # constructor state, src/Filters.jl:110-115 (FIRFarrow: 141-144)
             for c, r in enumerate(self._rates):
                 out[c] = ChannelState(float(r), self.Nphi / float(r), 1.0, 0.0, 1, 1, 1, 0)
@@ -1015,6 +1036,67 @@ class FIRFilter:
         if self._handle is not None:
             self._install_chan_farrow("pnfb", PN)
         self._chan_farrow = ("pnfb", PN)
+
+    # -- device-resident updates (include/multirate_hip.h, "Device-resident updates for the filters with per-channel rates")
+    def _device_update_args(self, who, t, dtype, shape):
+        """the checks the three device calls share: a bound filter, a contiguous torch CUDA tensor on the filter's device of the dtype
+        and shape the C call reads; returns torch's current stream on that device"""
+        if not _is_torch(t) or not t.is_cuda:
+            raise MultirateHIPError(1, f"{who} takes a torch CUDA tensor (host values: the call without _device)")
+        if self._handle is None:
+            raise MultirateHIPError(1, f"{who} needs a bound filter (bind(), or call filt once): the values are installed in stream order")
+        if t.device.index != self.device:
+            raise MultirateHIPError(1, f"{who}: the tensor is not on the filter's device")
+        if t.dtype != _np_torch_dtype(np.dtype(dtype)):
+            raise MultirateHIPError(1, f"{who} takes a tensor of {np.dtype(dtype)}; got {t.dtype}")
+        if tuple(t.shape) != tuple(shape):
+            raise MultirateHIPError(1, f"{who} takes a tensor of shape {tuple(shape)}; got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise MultirateHIPError(1, f"{who} takes a contiguous tensor")
+        return torch.cuda.current_stream(t.device).cuda_stream
+
+    def set_channel_rates_device(self, rates, lo, hi):
+        """New per-channel rates from DEVICE memory (``mrhip_set_channel_rates_device``), enqueued on torch's current stream without any
+        wait: ``rates`` is a contiguous float64 CUDA tensor of nchannels values, ``[lo, hi]`` the range the caller declares for them
+        (finite, > 0, lo >= 2^-30).  A value that is finite and inside the range is installed as ``set_channel_rates`` installs it; any
+        other leaves its channel at the old rate and makes ``channel_states`` raise code 1 until ``set_channel_states`` or ``reset``.
+        ``rate`` and ``outputlength_bound`` follow ``hi``.  The Python mirror no longer knows the rates: ``channel_states`` asks the
+        library, and the filter cannot be bound again after ``close()``."""
+        who = "set_channel_rates_device"
+        if self._rates is None:
+            raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates or FIRFilter.per_channel_rates_farrow")
+        stream = self._device_update_args(who, rates, np.float64, (self._nch,))
+        _check(self._lib.mrhip_set_channel_rates_device(self._handle, C.c_void_p(rates.data_ptr()), float(lo), float(hi), C.c_void_p(stream)))
+        self._rates, self.rate = _DeviceResident((self._nch,)), float(hi)
+
+    def set_channel_taps_device(self, H):
+        """Per-channel taps from DEVICE memory on a filter of ``per_channel_rates`` (``mrhip_set_channel_taps_device``), enqueued on
+        torch's current stream: ``H`` is a contiguous (nchannels, hLen) CUDA tensor in the filter's tap dtype.  The banks are built on
+        the device, bit for bit those of ``set_channel_taps``.  The first call on a filter whose taps are still shared allocates the
+        banks and waits once; every later call only enqueues a kernel.  ``taps()`` and ``tapsforphase`` read the banks back."""
+        who = "set_channel_taps_device"
+        if self._rates is None:
+            raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates")
+        if self.kind != ARBITRARY:
+            raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates_farrow takes set_channel_pnfb_device (the fit on the device is left out)")
+        stream = self._device_update_args(who, H, self.h.dtype, (len(self._rates), len(self.h)))
+        _check(self._lib.mrhip_set_channel_taps_device(self._handle, C.c_void_p(H.data_ptr()), len(self.h), _NP2DT[self.h.dtype], C.c_void_p(stream)))
+        self._chan_taps = _DeviceResident((self._nch, len(self.h)))
+
+    def set_channel_pnfb_device(self, PN):
+        """Per-channel polynomial banks from DEVICE memory on a filter of ``per_channel_rates_farrow``
+        (``mrhip_set_channel_pnfb_device``), enqueued on torch's current stream: ``PN`` is a contiguous float64 CUDA tensor of shape
+        (nchannels, tapsPer𝜙, polyorder+1), rounded to the filter's tap dtype on the device as ``set_channel_pnfb`` rounds on the host.
+        Allocation and waiting as ``set_channel_taps_device``; ``pnfb()`` and ``tapsforphase`` read the banks back."""
+        who = "set_channel_pnfb_device"
+        if self._rates is not None and self.kind == ARBITRARY:
+            raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates takes set_channel_taps_device")
+        if self._rates is None or self.kind != FARROW:
+            raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates_farrow")
+        shape = (len(self._rates), self.tapsPerPhi, self.polyorder + 1)
+        stream = self._device_update_args(who, PN, np.float64, shape)
+        _check(self._lib.mrhip_set_channel_pnfb_device(self._handle, C.c_void_p(PN.data_ptr()), self.tapsPerPhi, self.polyorder, C.c_void_p(stream)))
+        self._chan_farrow = _DeviceResident(shape)
 
     def outputlength_bound(self, inputlength: int) -> int:
         """The largest per-channel output count a call of ``inputlength`` samples can have whatever the stream state

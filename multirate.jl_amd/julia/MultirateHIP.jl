@@ -618,6 +618,25 @@ function set_channel_pnfb!(f::RatesFIRFilter{Th}, PN::Array{Float64,3}) where {T
     f.H, f.PN = nothing, copy(PN)
     f
 end
+# Device-resident updates (include/multirate_hip.h, "Device-resident updates for the filters with per-channel rates"): the values live in
+# DEVICE memory (a tracker computed them there) and the calls enqueue on `stream` without waiting for the filter.  A bound filter only;
+# the pointers are device pointers in the C layouts (rates: nchannels Float64 inside [lo, hi]; h: nchannels rows of length(f.h) taps; pnfb:
+# [nchannels][tapsPer𝜙][polyorder+1] Float64).  The Julia-side copies (f.rates, f.H, f.PN) no longer describe the filter afterwards.
+function set_channel_rates_device!(f::RatesFIRFilter, rates::Ptr{Float64}, lo::Real, hi::Real, stream::Ptr{Cvoid} = C_NULL)
+    f.handle == C_NULL && error("set_channel_rates_device! needs a bound filter")
+    check(ccall((:mrhip_set_channel_rates_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cvoid}), f.handle, rates, Float64(lo), Float64(hi), stream))
+    f
+end
+function set_channel_taps_device!(f::RatesFIRFilter{Th}, h::Ptr{Th}, stream::Ptr{Cvoid} = C_NULL) where {Th}
+    f.handle == C_NULL && error("set_channel_taps_device! needs a bound filter")
+    check(ccall((:mrhip_set_channel_taps_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}), f.handle, h, length(f.h), dtypecode(Th), stream))
+    f
+end
+function set_channel_pnfb_device!(f::RatesFIRFilter, pnfb::Ptr{Float64}, stream::Ptr{Cvoid} = C_NULL)
+    f.handle == C_NULL && error("set_channel_pnfb_device! needs a bound filter")
+    check(ccall((:mrhip_set_channel_pnfb_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}), f.handle, pnfb, cld(length(f.h), f.Nphi), f.polyorder, stream))
+    f
+end
 # FIRFilter(H::Matrix, rates::Vector, N𝜙, polyorder): one FIRFilter(H[:, c], rates[c], N𝜙, polyorder) per channel behind one object -- the
 # filter of FIRFilter(H[:, 1], rates, N𝜙, polyorder) with set_channel_taps_farrow!(f, H)
 function FIRFilter(H::Matrix{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer, polyorder::Integer; device::Integer = 0) where {Th<:Union{Float32,Float64}}
