@@ -1869,19 +1869,11 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     size_t lds = 0;
     long long tiled_grid = 0;
     bool tiled = false;
-    if (bound > 0 && !f->force_generic && farrow && tk.bank) {      // (mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb: kernels_rates_bank_farrow.hip; tiled: its multi kernel)
-        tiled = plan_farrow_rates_bank_multi(tk, fa, f->num_cus, &ta);
-        if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_bank_multi(tk, fused, ta, f->num_cus, &tiled_grid));
-    } else if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
+    if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
         tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
         if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
-    } else if (bound > 0 && !f->force_generic && tk.bank) {      // (mrhip_set_channel_taps: kernels_rates_bank_arb.hip; no plan_* below sees such a call)
-        const double rate_min = rates_min(f);
-        tiled = plan_arb_rates_bank_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
-        if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_bank_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
-    } else if (bound > 0 && !f->force_generic) {
-        const double rate_min = rates_min(f);
-        tiled = plan_arb_rates_tiled(tk, a, rate_min, f->num_cus, &ta, &lds);
+    } else if (bound > 0 && !f->force_generic) {      // (no other plan_* sees such a call)
+        tiled = plan_arb_rates_tiled(tk, a, rates_min(f), f->num_cus, &ta, &lds);
         if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
     }
     if (h_lens) {
@@ -1891,12 +1883,9 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     if (int rc = timing_mark(f, stream)) return rc;
     MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
     if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
-        if (farrow && tk.bank && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_bank_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
-        else if (farrow && tk.bank) MRHIP_CHECK_HIP(launch_farrow_rates_bank_generic(tk, fused, fa, ra, stream, &f->last_kernel));
-        else if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
+        // (tk.bank -- shared taps or a bank per channel -- picks the kernel's instantiation and its reported name inside the launch)
+        if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
         else if (farrow) MRHIP_CHECK_HIP(launch_farrow_rates_generic(tk, fused, fa, ra, stream, &f->last_kernel));
-        else if (tk.bank && tiled) MRHIP_CHECK_HIP(launch_arb_rates_bank_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
-        else if (tk.bank) MRHIP_CHECK_HIP(launch_arb_rates_bank_generic(tk, fused, a, ra, stream, &f->last_kernel));
         else if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
         else MRHIP_CHECK_HIP(launch_arb_rates_generic(tk, fused, a, ra, stream, &f->last_kernel));
         if (f->H > 0) f->hist_cur = hist_next;
@@ -2038,7 +2027,7 @@ int mrhip_set_channel_rates(mrhip_filter *f, const double *rates)
 // FIRArbitrary"): nch pfb and nch dpfb banks in the place of the shared pair -- create_pfb_banks with rows = nch, widened to R as
 // upload_taps widens mrhip_create_arbitrary_bank's.  Checks, host banks and the first call's two allocations come before anything of the
 // filter changes; then the call waits for the filter's stream (the kernels enqueued so far read the banks) and installs the new ones.
-// Records, rates, history and the schedule buffers stay; TypeKey::bank is set from here on (rates_call: kernels_rates_bank_arb.hip).
+// Records, rates, history and the schedule buffers stay; TypeKey::bank is set from here on (rates_call: the BANK kernels of kernels_rates_arb.hip).
 int mrhip_set_channel_taps(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
@@ -2089,8 +2078,8 @@ int mrhip_set_channel_taps(mrhip_filter *f, const void *h, int64_t hLen, int tap
 // FIRFarrow"): nch polynomial banks, [nch][T][polyorder+1], in the place of the shared one.  `pn` holds them as the caller or the fit gave
 // them; they are rounded to the tap type here, as create_filter rounds (Poly{T} storage).  The first call's allocation comes before
 // anything of the filter changes; then the call waits for the filter's stream (the kernels enqueued so far read the bank) and installs
-// the new ones.  Records, rates, history and the schedule buffers stay; TypeKey::bank is set from here on (rates_call:
-// kernels_rates_bank_farrow.hip).
+// the new ones.  Records, rates, history and the schedule buffers stay; TypeKey::bank is set from here on (rates_call: the
+// BANK kernels of kernels_rates_farrow.hip).
 static int install_channel_pnfb(mrhip_filter *f, const std::string &who, std::vector<double> &pn)
 {
     if (!dtype_is_f64(f->th)) for (double &c : pn) c = static_cast<double>(static_cast<float>(c));

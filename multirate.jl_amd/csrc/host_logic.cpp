@@ -314,25 +314,38 @@ bool plan_arb_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate, int n
     return true;
 }
 
-// arb_rates_tiled_kernel (per-channel RATES, kernels_rates_arb.hip): the ONE shared pfb and dpfb (column pitch T + 1) plus the sample tile
+// arb_rates_tiled_kernel (per-channel RATES, kernels_rates_arb.hip; either bank key): ONE pfb and dpfb (column pitch T + 1) -- the pair
+// all channels share, or with per-channel TAPS (tk.bank) one channel's, the LDS geometry of plan_arb_bank_tiled -- plus the sample tile
 // fit LDS at two workgroups a CU (78 KiB a workgroup, as for plan_arb_bank_tiled); one channel a lane (cpl = 1).  n_out is the call's
-// bound (the counts are on the device): the tiling goes by it and the kernel skips the tiles behind a channel's count.  The span is
+// bound (the counts are on the device): the tiling goes by it and the kernel skips the tiles at or behind a channel's count.  The span is
 // planned for the SLOWEST channel (rate_min: its tiles have the longest runs) and cut to the room only when the kernel is forced; in the
 // kernel every tile's run comes from its own channel's schedule, so a faster channel stages less and a tile longer than the planned span
-// reads global memory.  The default rule takes the calls the measured rows cover (profiles/r09/arb_rates.txt; the
-// figures of the run DESIGN.md quotes): the tiled kernel beat the universal one by far more than the spread of the repeats at 4096 ch x
-// 1e4 (360 448 tiles of 88 a channel: 3.125 against 3.449 ms, spreads 0.04 and 0.03) and at 256 ch x 1e5 (225 024 tiles of 879 a
-// channel: 21.45 against 26.44 ms, spreads 0.11 and 0.10), and did not at 64 ch x 1e6 (8790 tiles a channel: 536.8 against 548.3 ms
-// with spreads of 26 and 6 -- the serial walk is the call).  So: from kArbRatesTiledMinTiles tiles, up to kArbRatesTiledMaxPerChannel
-// tiles a channel, and never with a cut span; every other call stays on the universal kernel unless MRHIP_ARB_RATES_TILED=1 forces the
-// tiled one.  Both limits are GUARDS ON UNMEASURED GROUND, not causes: nothing about 880 tiles a channel makes the tiled kernel worse
-// (at 8790 it still read 1.02x, inside the spread, because the walk hides the filter kernel), and 256 ch x 1.001e5 falls back to the
-// universal kernel only because no row was measured beyond 879.  A measurement of the filter kernels alone at long channels (kernel
-// trace, the walk set aside) is what would let the cap go.
-constexpr long long kArbRatesTiledMinTiles = 225024, kArbRatesTiledMaxPerChannel = 879;
+// reads global memory.  The default rule (mode -1) takes the calls the measured rows cover, from kArbRatesTiledRule[tk.bank].min_tiles
+// tiles, up to .max_per_channel tiles a channel, and never with a cut span; every other call stays on the universal kernel unless
+// MRHIP_ARB_RATES_TILED=1 (shared taps) or MRHIP_ARB_RATES_BANK_TILED=1 (per-channel taps) forces the tiled one.  The two entries came
+// out equal and rest on different measured rows:
+//
+// Shared taps (profiles/r09/arb_rates.txt; the figures of the run DESIGN.md quotes): the tiled kernel beat the
+// universal one by far more than the spread of the repeats at 4096 ch x 1e4 (360 448 tiles of 88 a channel: 3.125 against 3.449 ms,
+// spreads 0.04 and 0.03) and at 256 ch x 1e5 (225 024 tiles of 879 a channel: 21.45 against 26.44 ms, spreads 0.11 and 0.10), and did
+// not at 64 ch x 1e6 (8790 tiles a channel: 536.8 against 548.3 ms with spreads of 26 and 6 -- the serial walk is the call).  Both limits
+// are GUARDS ON UNMEASURED GROUND, not causes: nothing about 880 tiles a channel makes the tiled kernel worse (at 8790 it still read
+// 1.02x, inside the spread, because the walk hides the filter kernel), and 256 ch x 1.001e5 falls back to the universal kernel only
+// because no row was measured beyond 879.  A measurement of the filter kernels alone at long channels (kernel trace, the walk set aside)
+// is what would let the cap go.
+//
+// Per-channel taps (profiles/r12/arb_rates_bank.txt, both runs): the tiled kernel beat the universal one by far
+// more than the spread of the repeats at 4096 ch x 1e4 (360 448 tiles of 88 a channel: 2.804 against 3.105 ms and 2.797 against 3.122,
+// spreads <= 0.053) and at 256 ch x 1e5 (225 024 tiles of 879 a channel: 18.101 against 23.016 ms and 18.119 against 23.027, spreads
+// <= 0.035), and did not at 64 ch x 1e6 (8790 tiles a channel: 464.8 against 459.2 ms and 431.4 against 479.8 with spreads of 29 to 55
+// -- the serial walk is the call).  As for shared taps both limits are GUARDS ON UNMEASURED GROUND, not causes: nothing about 880 tiles
+// a channel makes the tiled kernel worse (at 8790 the rows cannot tell the kernels apart because the walk hides them), and a call of
+// fewer tiles falls back only because no smaller row was measured.
+struct RatesTiledRule { long long min_tiles, max_per_channel; };      // (a limit < 0 would mean: never)
+constexpr RatesTiledRule kArbRatesTiledRule[2] = {{225024, 879}, {225024, 879}};       // [tk.bank]: shared taps, per-channel taps
 bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int /*num_cus*/, int mode, ArbTileArgs *out, size_t *lds)
 {
-    if (mode == 0 || tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate_min > 0.0)) return false;
+    if (mode == 0 || tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate_min > 0.0)) return false;
     const int TP = a.T + 1;
     const size_t bank_elems = static_cast<size_t>(a.Nphi) * TP;
     const size_t banks_bytes = (2 * bank_elems * variant_tap_bytes(tk) + 15) / 16 * 16;
@@ -340,102 +353,57 @@ bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, 
     ArbTileArgs ta;
     size_t bytes;
     if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate_min, mode == 1, &ta, &bytes)) return false;
-    if (mode != 1 && (ta.total_tiles < kArbRatesTiledMinTiles || ta.tiles_per_channel > kArbRatesTiledMaxPerChannel)) return false;
+    const RatesTiledRule rule = kArbRatesTiledRule[tk.bank ? 1 : 0];
+    if (mode != 1 && (rule.min_tiles < 0 || ta.total_tiles < rule.min_tiles || ta.tiles_per_channel > rule.max_per_channel)) return false;
     *out = ta;
     *lds = bytes;
     return true;
 }
 
-// arb_rates_bank_tiled_kernel (per-channel RATES and per-channel TAPS, kernels_rates_bank_arb.hip): the LDS geometry of
-// plan_arb_bank_tiled -- ONE channel's pfb and dpfb (column pitch T + 1) plus the sample tile at two workgroups a CU (78 KiB a
-// workgroup); one channel a lane (cpl = 1) -- and the tiling and span of plan_arb_rates_tiled: n_out is the call's bound (the counts
-// are on the device), the kernel skips the tiles at or behind a channel's count, the span is planned for the SLOWEST channel (rate_min)
-// and cut to the room only when the kernel is forced.  The default rule takes the calls the measured rows cover (DESIGN.md 9 item 21,
-// profiles/r12/arb_rates_bank.txt, both runs): the tiled kernel beat the universal one by far more than the spread of the repeats at
-// 4096 ch x 1e4 (360 448 tiles of 88 a channel: 2.804 against 3.105 ms and 2.797 against 3.122, spreads <= 0.053) and at 256 ch x 1e5
-// (225 024 tiles of 879 a channel: 18.101 against 23.016 ms and 18.119 against 23.027, spreads <= 0.035), and did not at 64 ch x 1e6
-// (8790 tiles a channel: 464.8 against 459.2 ms and 431.4 against 479.8 with spreads of 29 to 55 -- the serial walk is the call).  So:
-// from kArbRatesBankTiledMinTiles tiles, up to kArbRatesBankTiledMaxPerChannel tiles a channel, and never with a cut span; every other
-// call stays on the universal kernel unless MRHIP_ARB_RATES_BANK_TILED=1 forces the tiled one.  As for plan_arb_rates_tiled both limits
-// are GUARDS ON UNMEASURED GROUND, not causes: nothing about 880 tiles a channel makes the tiled kernel worse (at 8790 the rows cannot
-// tell the kernels apart because the walk hides them), and a call of fewer tiles falls back only because no smaller row was measured.
-constexpr long long kArbRatesBankTiledMinTiles = 225024, kArbRatesBankTiledMaxPerChannel = 879;
-bool plan_arb_rates_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int /*num_cus*/, int mode, ArbTileArgs *out, size_t *lds)
-{
-    if (mode == 0 || !tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate_min > 0.0)) return false;
-    const int TP = a.T + 1;
-    const size_t bank_elems = static_cast<size_t>(a.Nphi) * TP;
-    const size_t banks_bytes = (2 * bank_elems * variant_tap_bytes(tk) + 15) / 16 * 16;
-    const ArbVariantShape v{banks_bytes, 78 * 1024, 78 * 1024, TP, static_cast<int>(bank_elems), 1, false};
-    ArbTileArgs ta;
-    size_t bytes;
-    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate_min, mode == 1, &ta, &bytes)) return false;
-    if (mode != 1 && (ta.total_tiles < kArbRatesBankTiledMinTiles || ta.tiles_per_channel > kArbRatesBankTiledMaxPerChannel)) return false;
-    *out = ta;
-    *lds = bytes;
-    return true;
-}
-
-// farrow_rates_multi_kernel (FIRFarrow with per-channel RATES, kernels_rates_farrow.hip): no LDS -- the one polynomial bank is read as
-// scalar operands, the windows from global memory -- so the plan is the tiling alone: a tile is kFarrowRatesOPL consecutive runs of
-// kVariantThreads outputs of one channel, one channel a lane (cpl = 1), and the tiling goes by n_out, the call's bound (the counts are
-// on the device; the kernel skips the tiles and the slots at or behind a channel's count).  The default rule takes the calls the
-// measured rows cover (profiles/r10/farrow_rates.txt): the multi kernel beat the universal one by more than the
-// spread of the repeats in both runs at 4096 ch x 1e4 (90 112 tiles of 22 a channel: 2.722 against 2.856 ms and 2.703 against 2.843,
-// spreads <= 0.05), and did not at 256 ch x 1e5 (56 320 tiles of 220 a channel: 21.86 against 21.83 ms and 21.85 against 21.81) nor at
-// 64 ch x 1e6 (140 672 tiles of 2198 a channel: 508.5 against 519.0 ms with spreads of 33 and 38) -- there the serial walk is the call.
-// So: from kFarrowRatesMultiMinTiles tiles, up to kFarrowRatesMultiMaxPerChannel tiles a channel; every other call stays on the
-// universal kernel unless MRHIP_FARROW_RATES_MULTI=1 selects the multi kernel.  As for plan_arb_rates_tiled both limits are GUARDS ON
-// UNMEASURED GROUND, not causes.  The kernel trace of the same file says where the gain is: alone, the multi kernel took 0.584 ms
-// against the universal one's 0.745 in the first row (8 taps per phase) and was level with it in the other two (32 taps per phase: 2.94
-// against 2.80 ms in the longest launches), where the walk is 95 % and more of the call anyway.
-constexpr long long kFarrowRatesMultiMinTiles = 90112, kFarrowRatesMultiMaxPerChannel = 22;
+// farrow_rates_multi_kernel (FIRFarrow with per-channel RATES, kernels_rates_farrow.hip; either bank key): no LDS -- the polynomial bank
+// (the one, or with tk.bank the tile's channel's) is read as scalar operands, the windows from global memory -- so the plan is the
+// tiling alone: a tile is kFarrowRatesOPL consecutive runs of kVariantThreads outputs of ONE channel, so one polynomial bank, one channel
+// a lane (cpl = 1), and the tiling goes by n_out, the call's bound (the counts are on the device; the kernel skips the tiles and the
+// slots at or behind a channel's count).  The default rule (mode -1) takes the calls the measured rows cover, from
+// kFarrowRatesMultiRule[tk.bank].min_tiles tiles, up to .max_per_channel tiles a channel; every other call stays on the universal kernel
+// unless MRHIP_FARROW_RATES_MULTI=1 (the one bank) or MRHIP_FARROW_RATES_BANK_MULTI=1 (a bank per channel) selects the multi kernel.
+// The two entries came out equal and rest on different measured rows:
+//
+// The one bank (profiles/r10/farrow_rates.txt): the multi kernel beat the universal one by more than the spread of
+// the repeats in both runs at 4096 ch x 1e4 (90 112 tiles of 22 a channel: 2.722 against 2.856 ms and 2.703 against 2.843, spreads
+// <= 0.05), and did not at 256 ch x 1e5 (56 320 tiles of 220 a channel: 21.86 against 21.83 ms and 21.85 against 21.81) nor at 64 ch x
+// 1e6 (140 672 tiles of 2198 a channel: 508.5 against 519.0 ms with spreads of 33 and 38) -- there the serial walk is the call.  As for
+// plan_arb_rates_tiled both limits are GUARDS ON UNMEASURED GROUND, not causes.  The kernel trace of the same file says where the gain
+// is: alone, the multi kernel took 0.584 ms against the universal one's 0.745 in the first row (8 taps per phase) and was level with it
+// in the other two (32 taps per phase: 2.94 against 2.80 ms in the longest launches), where the walk is 95 % and more of the call anyway.
+//
+// A bank per channel (profiles/r13/farrow_rates_bank.txt, both runs): the multi kernel beat the universal one by
+// far more than the spread of the repeats at 4096 ch x 1e4 (90 112 tiles of 22 a channel: 2.349 against 2.561 ms and 2.364 against
+// 2.563, spreads <= 0.019) and did not at 256 ch x 1e5 (56 320 tiles of 220 a channel: 18.460 against 18.473 ms and 18.422 against
+// 18.525, spreads 0.06 to 0.17) nor at 64 ch x 1e6 (140 672 tiles of 2198 a channel: 464.5 against 464.6 ms and 462.6 against 477.4 with
+// spreads of 5 to 45 -- the serial walk is the call).  As for the one bank, whose limits came out the same, both are GUARDS ON
+// UNMEASURED GROUND, not causes.  (A limit < 0 would mean: never.)
+constexpr RatesTiledRule kFarrowRatesMultiRule[2] = {{90112, 22}, {90112, 22}};        // [tk.bank]: the one bank, a bank per channel
 bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int /*num_cus*/, int mode, ArbTileArgs *out)
 {
-    if (mode == 0 || tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || a.nch < 1) return false;
+    if (mode == 0 || tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || a.nch < 1) return false;
     ArbTileArgs ta{};
     ta.cpl = 1;
     ta.tile_out = static_cast<long long>(kFarrowRatesOPL) * kVariantThreads;
     ta.tiles_per_channel = (a.n_out + ta.tile_out - 1) / ta.tile_out;
     ta.total_tiles = ta.tiles_per_channel * a.nch;
-    if (mode != 1 && (ta.total_tiles < kFarrowRatesMultiMinTiles || ta.tiles_per_channel > kFarrowRatesMultiMaxPerChannel)) return false;
+    const RatesTiledRule rule = kFarrowRatesMultiRule[tk.bank ? 1 : 0];
+    if (mode != 1 && (rule.min_tiles < 0 || ta.total_tiles < rule.min_tiles || ta.tiles_per_channel > rule.max_per_channel)) return false;
     *out = ta;
     return true;
 }
 
-// its persistent grid: what the chip holds, no more workgroups than tiles, at least one; a test's replacement (MRHIP_FARROW_RATES_GRID)
-// may also ask for more workgroups than tiles (their runs are empty)
+// its persistent grid: what the chip holds, no more workgroups than tiles, at least one; a test's replacement (MRHIP_FARROW_RATES_GRID,
+// MRHIP_FARROW_RATES_BANK_GRID) may also ask for more workgroups than tiles (their runs are empty)
 long long farrow_rates_multi_grid(long long total_tiles, long long chip_grid, int grid_fixed)
 {
     if (grid_fixed > 0) return std::min<long long>(grid_fixed, 65535);
     return std::max<long long>(std::min<long long>(chip_grid, total_tiles), 1);
-}
-
-// farrow_rates_bank_multi_kernel (FIRFarrow with per-channel RATES and per-channel TAPS, kernels_rates_bank_farrow.hip): the tiling of
-// plan_farrow_rates_multi -- a tile is kFarrowRatesOPL consecutive runs of kVariantThreads outputs of ONE channel, so one polynomial bank,
-// one channel a lane (cpl = 1), the tiling goes by n_out, the call's bound -- on a filter that HAS a bank per channel (tk.bank).  No LDS,
-// so nothing else to plan; the grid is farrow_rates_multi_grid's.  The default rule (mode -1) takes the calls the measured rows cover
-// (profiles/r13/farrow_rates_bank.txt, both runs): the multi kernel beat the universal one by far more than the
-// spread of the repeats at 4096 ch x 1e4 (90 112 tiles of 22 a channel: 2.349 against 2.561 ms and 2.364 against 2.563, spreads <= 0.019)
-// and did not at 256 ch x 1e5 (56 320 tiles of 220 a channel: 18.460 against 18.473 ms and 18.422 against 18.525, spreads 0.06 to 0.17)
-// nor at 64 ch x 1e6 (140 672 tiles of 2198 a channel: 464.5 against 464.6 ms and 462.6 against 477.4 with spreads of 5 to 45 -- the serial
-// walk is the call).  So: from kFarrowRatesBankMultiMinTiles tiles, up to kFarrowRatesBankMultiMaxPerChannel tiles a channel; every other
-// call stays on the universal kernel unless MRHIP_FARROW_RATES_BANK_MULTI=1 selects the multi kernel.  As for plan_farrow_rates_multi,
-// whose limits came out the same, both are GUARDS ON UNMEASURED GROUND, not causes.  (A limit < 0 would mean: never.)
-constexpr long long kFarrowRatesBankMultiMinTiles = 90112, kFarrowRatesBankMultiMaxPerChannel = 22;
-bool plan_farrow_rates_bank_multi(const TypeKey &tk, const FarrowArgs &a, int /*num_cus*/, int mode, ArbTileArgs *out)
-{
-    if (mode == 0 || !tk.bank || tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || a.nch < 1) return false;
-    ArbTileArgs ta{};
-    ta.cpl = 1;
-    ta.tile_out = static_cast<long long>(kFarrowRatesOPL) * kVariantThreads;
-    ta.tiles_per_channel = (a.n_out + ta.tile_out - 1) / ta.tile_out;
-    ta.total_tiles = ta.tiles_per_channel * a.nch;
-    if (mode != 1 && (kFarrowRatesBankMultiMinTiles < 0 || ta.total_tiles < kFarrowRatesBankMultiMinTiles ||
-                      ta.tiles_per_channel > kFarrowRatesBankMultiMaxPerChannel))
-        return false;
-    *out = ta;
-    return true;
 }
 
 // arb_bank_ctaps_tiled_kernel: both banks of ONE channel as (re, im) pairs of R (column pitch T + 1) plus the sample tile fit LDS at

@@ -1,4 +1,4 @@
-// kernels_rates_arb.hip -- FIRArbitrary (src/Filters.jl:91-117, 663-742) with PER-CHANNEL RATES.
+// kernels_rates_arb.hip -- FIRArbitrary (src/Filters.jl:91-117, 663-742) with PER-CHANNEL RATES, over shared or PER-CHANNEL TAPS.
 //
 // In the reference N signals are N FIRFilter(h, rate_c, N𝜙) objects, and every rate_c may differ (receivers each off its own clock trimmed
 // to a common rate, per-emitter Doppler time-scale correction, per-channel fractional delay).  The phase schedule (update(), :663-673)
@@ -22,7 +22,17 @@
 // oldest sample first, the first product initialises the accumulator, no start-from-zero seam; STRICT: every multiply and add rounded
 // separately in R, FUSED: one fma per tap; the combine in Float64, then rounded to R (RealTaps, variant_device.h) -- so channel c is bit
 // for bit mrhip_create_arbitrary(h, rates[c], N𝜙, nch = 1) fed x_c.  This file is compiled with -ffp-contract=off.
-// Both filter kernels end with the ShiftFold epilogue (the history does not depend on the rate).  No workgroup waits for another.
+// Both filter kernels end with the ShiftFold epilogue (the history depends on neither the rate nor the taps).  No workgroup waits for
+// another.
+//
+// PER-CHANNEL TAPS (BANK, the kernels' last template argument): the general case of the reference's model, N FIRFilter(h_c, rate_c, N𝜙)
+// objects with taps and rate both differing per channel (receivers each off its own clock AND each with its own front-end equaliser;
+// per-emitter Doppler correction with the emitter's own matched pulse).  A filter on which mrhip_set_channel_taps was called holds nch
+// pfb and nch dpfb banks, [nch][Nphi][T] in R, in the place of the one shared pair (include/multirate_hip.h, "Per-channel taps with
+// per-channel rates for FIRArbitrary"), and TypeKey::bank is set; everything else of a call is as above.  The kernels are ONE text for
+// both: BANK moves the column of the universal kernel to bank ch, and in the tiled kernel moves the copy of the banks into LDS from in
+// front of the tile loop to the first live tile of each channel.  Channel c is then bit for bit mrhip_create_arbitrary(h_c, rates[c], N𝜙,
+// nch = 1) fed x_c.  rates_key is the one place that reads TypeKey::bank on the launch side.
 #include "rates_arb.h"
 #include "sched_step.h"
 #include "variant_device.h"
@@ -98,19 +108,21 @@ __global__ __launch_bounds__(kRatesSchedThreads) void rates_set_kernel(RateChann
 }
 
 // One lane per (channel, output), any (Nphi, T, hLen, rates): blockIdx.x covers the outputs up to the call's bound, blockIdx.y strides
-// the channels; the channel's count is uniform over the workgroup.
-template <typename TX, typename R, int NCX, bool FUSED>
+// the channels; the channel's count is uniform over the workgroup.  BANK: tp / dp start at bank ch.
+template <typename TX, typename R, int NCX, bool FUSED, bool BANK>
 __global__ __launch_bounds__(kVariantThreads) void arb_rates_generic_kernel(ArbArgs a, RatesArgs r)
 {
     using A = RealTaps<TX, R, NCX, FUSED>;
     using Sample = typename A::Sample;
     const long long k = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    [[maybe_unused]] const long long bank_elems = static_cast<long long>(a.Nphi) * a.T;      // (read under BANK only)
     for (int ch = blockIdx.y; ch < a.nch; ch += gridDim.y) {
         if (k >= r.rec[ch].count) continue;
         const long long n = a.n_idx[static_cast<long long>(ch) * r.slice + k];
         double alpha;
         const int phi = arb_phase(a.acc[static_cast<long long>(ch) * r.slice + k], &alpha);
-        const long long col = static_cast<long long>(phi) * a.T;
+        long long col = static_cast<long long>(phi) * a.T;
+        if constexpr (BANK) col = ch * bank_elems + col;       // column phi of bank ch
         const long long base = n - a.T;             // 0-based index of the oldest sample (>= -H: n >= 1)
         const R *__restrict__ tp = static_cast<const R *>(a.taps) + col;
         const R *__restrict__ dp = static_cast<const R *>(a.dtaps) + col;
@@ -132,13 +144,30 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_generic_kernel(ArbA
     else dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }
 
+// The pfb and the dpfb bank that start at element `first` of taps / dtaps -> LDS with a column pitch of TP taps, both in ONE pass over the
+// elements (one index division for the pair; bank_to_lds of variant_device.h is this loop for one bank): element (phi, i) at phi*TP + i.
+template <typename R>
+__device__ __forceinline__ void rates_banks_to_lds(R *lpfb, R *ldpfb, const void *taps, const void *dtaps, long long first, int elems, int T, int TP, int tid)
+{
+    const R *__restrict__ g0 = static_cast<const R *>(taps) + first;
+    const R *__restrict__ g1 = static_cast<const R *>(dtaps) + first;
+    for (int e = tid; e < elems; e += kVariantThreads) {
+        const int phi = e / T, i = e - phi * T;
+        lpfb[phi * TP + i] = g0[e];
+        ldpfb[phi * TP + i] = g1[e];
+    }
+}
+
 // Persistent workgroups in the channel-major tile order (tile_run, variant_device.h).  A tile is (channel, run of tile_out = 256
-// outputs); the tiling goes by the call's bound, and the tiles behind a channel's count are skipped.  pfb and dpfb are shared by the
-// channels: they go into LDS ONCE per workgroup (column pitch T + 1: lanes of different phases read different LDS banks).  The tile's run
-// of samples is read from the channel's own slice of the schedule (tile_span) -- so it follows that channel's rate -- and staged through
-// LDS (stage_window); a tile whose run is longer than the planned span (a channel that decimates heavily) reads its windows from global
-// memory.
-template <typename TX, typename R, int NCX, bool FUSED>
+// outputs); the tiling goes by the call's bound.  A tile at or behind its channel's count is skipped BEFORE any barrier (the skip is
+// uniform over the workgroup).  The workgroup holds ONE pfb and dpfb in LDS (column pitch T + 1: lanes of different phases read different
+// LDS banks).  !BANK: the pair all channels share, copied ONCE per workgroup in front of the tile loop.  BANK: one channel's pair,
+// reloaded only when a live tile belongs to another channel than the one in LDS (ch_in_lds): the first live tile after any number of
+// skipped ones finds its own channel's banks or loads them, and a channel without outputs in this call never has its banks loaded.  The
+// tile's run of samples is read from the channel's own slice of the schedule (tile_span) -- so it follows that channel's rate -- and
+// staged through LDS up to the channel's own length (stage_window); a tile whose run is longer than the planned span (a channel that
+// decimates heavily) reads its windows from global memory (arb_dots_global), its taps still from LDS.
+template <typename TX, typename R, int NCX, bool FUSED, bool BANK>
 __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArgs a, RatesArgs r, ArbTileArgs ta)
 {
     using A = RealTaps<TX, R, NCX, FUSED>;
@@ -151,22 +180,17 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArg
     const int tid = threadIdx.x;
     const int T = a.T, TP = ta.tap_pitch;
     const TileRun run = tile_run(ta.total_tiles);
-    if (run.begin < run.end) {           // (uniform over the workgroup) the shared banks -> LDS: element (phi, i) at phi*TP + i
-        const R *__restrict__ g0 = static_cast<const R *>(a.taps);
-        const R *__restrict__ g1 = static_cast<const R *>(a.dtaps);
-        const int bank_elems = a.Nphi * T;
-        for (int e = tid; e < bank_elems; e += kVariantThreads) {
-            const int phi = e / T, i = e - phi * T;
-            lpfb[phi * TP + i] = g0[e];
-            ldpfb[phi * TP + i] = g1[e];
-        }
+    const int bank_elems = a.Nphi * T;
+    [[maybe_unused]] int ch_in_lds = -1;
+    if constexpr (!BANK) {
+        if (run.begin < run.end) rates_banks_to_lds(lpfb, ldpfb, a.taps, a.dtaps, 0, bank_elems, T, TP, tid);
     }
 
     for (long long tile = run.begin; tile < run.end; ++tile) {
         const BankTile t = bank_tile<true>(tile, ta, a.n_out);
         const int ch = t.ch;
         const long long count = r.rec[ch].count;
-        if (t.k0 >= count) continue;     // (uniform over the workgroup) a tile behind the channel's count
+        if (t.k0 >= count) continue;     // (uniform over the workgroup) a tile at or behind the channel's count: no barrier, no banks
         const long long len = rates_channel_len(r.x_lens, a.x_len, ch);      // (uniform too: the window is staged up to the channel's own end)
         const long long klast = (t.klast < count ? t.klast : count - 1);
         const int *__restrict__ nc = a.n_idx + static_cast<long long>(ch) * r.slice;
@@ -175,9 +199,15 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArg
         const Sample *__restrict__ xc = static_cast<const Sample *>(a.x) + static_cast<long long>(ch) * a.x_stride;
         const Sample *__restrict__ hc = static_cast<const Sample *>(a.hist) + static_cast<long long>(ch) * a.H;
 
-        __syncthreads();   // the previous tile's reads of the window are done
+        __syncthreads();   // the previous live tile's reads of the window (BANK: and of the banks) are done
+        if constexpr (BANK) {
+            if (ch != ch_in_lds) {   // (uniform over the workgroup) channel ch's banks
+                rates_banks_to_lds(lpfb, ldpfb, a.taps, a.dtaps, static_cast<long long>(ch) * bank_elems, bank_elems, T, TP, tid);
+                ch_in_lds = ch;
+            }
+        }
         if (w.staged) stage_window(lx, xc, hc, w.o, static_cast<int>(w.span), len, a.H, tid);
-        __syncthreads();   // (the first one of a workgroup: the banks are in LDS too)
+        __syncthreads();   // (!BANK, the first one of a workgroup: the banks are in LDS too)
 
         R *__restrict__ yc = A::channel_out(a.y, ch, a.y_stride);
         for (long long k = t.k0 + tid; k <= klast; k += kVariantThreads) {
@@ -208,6 +238,12 @@ __global__ __launch_bounds__(kVariantThreads) void arb_rates_tiled_kernel(ArbArg
     else dev::shiftin_by_last_workgroup<TX, NCX>(a.fold, a.x, a.hist, a.x_stride, a.x_len, a.H, a.nch);
 }
 
+template <typename TX, typename R, int NCX, bool BANK>
+auto arb_rates_tiled_fn(bool fused)
+{
+    return fused ? arb_rates_tiled_kernel<TX, R, NCX, true, BANK> : arb_rates_tiled_kernel<TX, R, NCX, false, BANK>;
+}
+
 }  // namespace
 
 hipError_t launch_rates_schedule(const RatesSchedArgs &s, bool pow2, hipStream_t st)
@@ -233,17 +269,27 @@ hipError_t launch_rates_set(RateChannel *rec, const double *rates, double lo, do
     return hipGetLastError();
 }
 
-// (the names mrhip_last_kernel_name reports carry no kernel suffix: include/multirate_hip.h at mrhip_last_kernel_name)
+// TypeKey::bank is read HERE and nowhere else in this unit: it chooses the kernels' BANK argument (dispatch_variant_flag), the names
+// mrhip_last_kernel_name reports (without a kernel suffix: include/multirate_hip.h at mrhip_last_kernel_name) and the environment switches
+// together.  (MRHIP_ENV_INT caches per call site behind a literal name: two sites a switch.)
+static RatesKey rates_key(const TypeKey &tk)
+{
+    return RatesKey{tk.bank, tk.bank ? "arb_rates_bank_generic" : "arb_rates_generic", tk.bank ? "arb_rates_bank_tiled" : "arb_rates_tiled",
+                    tk.bank ? MRHIP_ENV_INT("MRHIP_ARB_RATES_BANK_TILED", -1) : MRHIP_ENV_INT("MRHIP_ARB_RATES_TILED", -1),
+                    tk.bank ? MRHIP_ENV_INT("MRHIP_ARB_RATES_BANK_GRID", 0) : MRHIP_ENV_INT("MRHIP_ARB_RATES_GRID", 0)};
+}
+
 hipError_t launch_arb_rates_generic(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, hipStream_t s, const char **kname)
 {
-    if (tk.bank || tk.complex_h || a.dyn) return hipErrorInvalidValue;
+    if (tk.complex_h || a.dyn) return hipErrorInvalidValue;
     if (a.n_out <= 0) return hipSuccess;
     const long long bx = (a.n_out + kVariantThreads - 1) / kVariantThreads;
     if (bx > 0x7fffffffLL) return hipErrorInvalidValue;
-    *kname = "arb_rates_generic";
+    const RatesKey key = rates_key(tk);
+    *kname = key.generic;
     const dim3 grid(static_cast<unsigned>(bx), static_cast<unsigned>(a.nch < 65535 ? a.nch : 65535), 1);
-    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
-        launch_kernel(fused ? arb_rates_generic_kernel<TX, R, NCX, true> : arb_rates_generic_kernel<TX, R, NCX, false>, grid,
+    return dispatch_variant_flag(tk, key.bank, [&]<typename TX, typename R, int NCX, bool BANK>() -> hipError_t {
+        launch_kernel(fused ? arb_rates_generic_kernel<TX, R, NCX, true, BANK> : arb_rates_generic_kernel<TX, R, NCX, false, BANK>, grid,
                       dim3(kVariantThreads), 0, s, a, r);
         return hipGetLastError();
     });
@@ -251,19 +297,19 @@ hipError_t launch_arb_rates_generic(const TypeKey &tk, bool fused, const ArbArgs
 
 bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, ArbTileArgs *out, size_t *lds)
 {
-    return plan_arb_rates_tiled(tk, a, rate_min, num_cus, MRHIP_ENV_INT("MRHIP_ARB_RATES_TILED", -1), out, lds);
+    return plan_arb_rates_tiled(tk, a, rate_min, num_cus, rates_key(tk).tiled_mode, out, lds);
 }
 
 hipError_t prepare_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbTileArgs &ta, size_t lds, int num_cus, long long *grid)
 {
-    if (tk.bank || tk.complex_h) return hipErrorInvalidValue;
-    const int grid_fixed = MRHIP_ENV_INT("MRHIP_ARB_RATES_GRID", 0);
-    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
-        auto kfn = fused ? arb_rates_tiled_kernel<TX, R, NCX, true> : arb_rates_tiled_kernel<TX, R, NCX, false>;
-        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(kfn), kVariantThreads, lds, num_cus, ta.total_tiles);
+    if (tk.complex_h) return hipErrorInvalidValue;
+    const RatesKey key = rates_key(tk);
+    return dispatch_variant_flag(tk, key.bank, [&]<typename TX, typename R, int NCX, bool BANK>() -> hipError_t {
+        const PersistentGrid pg = persistent_grid(reinterpret_cast<const void *>(arb_rates_tiled_fn<TX, R, NCX, BANK>(fused)), kVariantThreads, lds,
+                                                  num_cus, ta.total_tiles);
         if (pg.err != hipSuccess) return pg.err;
         long long g = std::max<long long>(std::min<long long>(pg.grid, ta.total_tiles), 1);
-        if (grid_fixed > 0) g = std::min<long long>(grid_fixed, 65535);       // (tests: also more workgroups than tiles)
+        if (key.grid_fixed > 0) g = std::min<long long>(key.grid_fixed, 65535);       // (tests: also more workgroups than tiles)
         *grid = g;
         return hipSuccess;
     });
@@ -272,11 +318,11 @@ hipError_t prepare_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbTileA
 hipError_t launch_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, const ArbTileArgs &ta, size_t lds,
                                   long long grid, hipStream_t s, const char **kname)
 {
-    if (tk.bank || tk.complex_h || a.dyn || grid < 1) return hipErrorInvalidValue;
-    *kname = "arb_rates_tiled";
-    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
-        auto kfn = fused ? arb_rates_tiled_kernel<TX, R, NCX, true> : arb_rates_tiled_kernel<TX, R, NCX, false>;
-        launch_kernel(kfn, dim3(static_cast<unsigned>(grid)), dim3(kVariantThreads), lds, s, a, r, ta);
+    if (tk.complex_h || a.dyn || grid < 1) return hipErrorInvalidValue;
+    const RatesKey key = rates_key(tk);
+    *kname = key.tiled;
+    return dispatch_variant_flag(tk, key.bank, [&]<typename TX, typename R, int NCX, bool BANK>() -> hipError_t {
+        launch_kernel(arb_rates_tiled_fn<TX, R, NCX, BANK>(fused), dim3(static_cast<unsigned>(grid)), dim3(kVariantThreads), lds, s, a, r, ta);
         return hipGetLastError();
     });
 }

@@ -32,8 +32,8 @@ struct mrhip_filter {
     // per-channel RATES (mrhip_create_arbitrary_rates; rates_arb.h, kernels_rates_arb.hip only): one shared pfb / dpfb, and per channel a
     // record on the device (rate, Δ, 𝜙Accumulator, xIdx, inputDeficit, the latest call's count) and a slice of the schedule buffers.  The
     // host fields below that carry ONE state (phiIdx ... delta) mean nothing on such a filter; `rate` holds the largest rate (the bound).
-    // (after mrhip_set_channel_taps on a FIRArbitrary one: `bank` is set too, d_taps / d_dtaps / h_taps / h_dtaps hold nch banks; kernels_rates_bank_arb.hip only)
-    // (after mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb on a FIRFarrow one: `bank` is set too, d_pnfb / h_pnfb hold nch banks; kernels_rates_bank_farrow.hip only)
+    // (after mrhip_set_channel_taps on a FIRArbitrary one: `bank` is set too, d_taps / d_dtaps / h_taps / h_dtaps hold nch banks; the BANK kernels of kernels_rates_arb.hip only)
+    // (after mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb on a FIRFarrow one: `bank` is set too, d_pnfb / h_pnfb hold nch banks; the BANK kernels of kernels_rates_farrow.hip only)
     bool rates = false;
     std::vector<double> h_rates;                           // [nch]
     // device-resident updates (mrhip_set_channel_rates_device / _taps_device / _pnfb_device): the host no longer knows the values.

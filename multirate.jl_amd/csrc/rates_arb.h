@@ -1,7 +1,8 @@
 // rates_arb.h -- FIRArbitrary with PER-CHANNEL RATES (mrhip_create_arbitrary_rates; include/multirate_hip.h, "Per-channel rates for
-// FIRArbitrary"): what api.hip, host_logic.cpp (the tiled kernel's plan) and kernels_rates_arb.hip (the three kernels) share; and, below,
+// FIRArbitrary"): what api.hip, host_logic.cpp (the tiled kernel's plan) and kernels_rates_arb.hip (the kernels) share; and, below,
 // FIRFarrow with per-channel rates (mrhip_create_farrow_rates; kernels_rates_farrow.hip), which uses the same records and schedule
-// kernel.  Kept out of mrhip_internal.h so that only those units depend on it.
+// kernel.  Either filter may hold shared taps or a bank per channel (TypeKey::bank): one set of functions per family serves both.  Kept
+// out of mrhip_internal.h so that only those units depend on it.
 #pragma once
 
 #include "mrhip_internal.h"
@@ -62,37 +63,32 @@ struct RatesHistSource {           // the rule as the argument of dev::shiftin_r
     MRHIP_RATES_HD HistSource operator()(long long i, long long len, int H) const { return rates_hist_source(i, len, H); }
 };
 
-// kernels_rates_arb.hip
+// What TypeKey::bank chooses on the launch side of a family, read in ONE place per unit (rates_key there): the kernels' BANK argument,
+// the names mrhip_last_kernel_name reports and the values of the family's two environment switches.
+struct RatesKey { bool bank; const char *generic, *tiled; int tiled_mode, grid_fixed; };
+
+// kernels_rates_arb.hip.  Every function below takes either bank key: shared taps (ArbArgs::taps / dtaps hold the ONE pair of banks) or
+// per-channel taps (mrhip_set_channel_taps on a filter of mrhip_create_arbitrary_rates; include/multirate_hip.h, "Per-channel taps with
+// per-channel rates for FIRArbitrary": nch banks, [nch][Nphi][T] in R, and TypeKey::bank is set).  Records, slices, schedule kernel and
+// RatesArgs serve both unchanged.  The key selects the reported name (arb_rates_generic / arb_rates_tiled, arb_rates_bank_generic /
+// arb_rates_bank_tiled) and the switches (MRHIP_ARB_RATES_TILED / _GRID, MRHIP_ARB_RATES_BANK_TILED / _BANK_GRID).
 hipError_t launch_rates_schedule(const RatesSchedArgs &s, bool pow2, hipStream_t st);
 hipError_t launch_rates_reset(RateChannel *rec, int nch, hipStream_t st);                  // constructor state, in stream order
 hipError_t launch_arb_rates_generic(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
-bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, ArbTileArgs *out, size_t *lds);
-// the tiled kernel's persistent grid (occupancy query, LDS attribute): everything about its launch that can fail ahead of the launch
+bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, ArbTileArgs *out, size_t *lds);   // (reads the key's TILED switch)
+// the tiled kernel's persistent grid (occupancy query, LDS attribute; the key's GRID switch): everything about its launch that can fail
+// ahead of the launch
 hipError_t prepare_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbTileArgs &ta, size_t lds, int num_cus, long long *grid);
 hipError_t launch_arb_rates_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, const ArbTileArgs &ta, size_t lds,
                                   long long grid, hipStream_t s, const char **kname);
-// host_logic.cpp: the switch value passed in (MRHIP_ARB_RATES_TILED: 0 never, 1 wherever the plan fits, -1 the default rule)
+// host_logic.cpp: the switch value passed in (0 never, 1 wherever the plan fits, -1 the default rule of the bank key)
 bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, int mode, ArbTileArgs *out, size_t *lds);
-
-// ---- FIRArbitrary with per-channel rates AND per-channel taps (mrhip_set_channel_taps on a filter of mrhip_create_arbitrary_rates;
-// include/multirate_hip.h, "Per-channel taps with per-channel rates for FIRArbitrary") ---------------------------------------------------
-// Records, slices, schedule kernel and RatesArgs above serve it unchanged; ArbArgs::taps / dtaps hold nch banks, [nch][Nphi][T] in R,
-// and TypeKey::bank is set.
-// kernels_rates_bank_arb.hip
-hipError_t launch_arb_rates_bank_generic(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
-bool plan_arb_rates_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, ArbTileArgs *out, size_t *lds);   // (reads MRHIP_ARB_RATES_BANK_TILED)
-// the tiled kernel's persistent grid (occupancy query, LDS attribute; MRHIP_ARB_RATES_BANK_GRID): what can fail ahead of the launch
-hipError_t prepare_arb_rates_bank_tiled(const TypeKey &tk, bool fused, const ArbTileArgs &ta, size_t lds, int num_cus, long long *grid);
-hipError_t launch_arb_rates_bank_tiled(const TypeKey &tk, bool fused, const ArbArgs &a, const RatesArgs &r, const ArbTileArgs &ta, size_t lds,
-                                       long long grid, hipStream_t s, const char **kname);
-// host_logic.cpp: the switch value passed in (MRHIP_ARB_RATES_BANK_TILED: 0 never, 1 wherever the plan fits, -1 the default rule)
-bool plan_arb_rates_bank_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, int mode, ArbTileArgs *out, size_t *lds);
 
 // ---- FIRFarrow with per-channel rates (mrhip_create_farrow_rates;include/multirate_hip.h, "Per-channel rates for FIRFarrow") --------
 // The schedule kernel, the records, the reset kernel and RatesArgs above serve it unchanged: update() of FIRFarrow (Filters.jl:780-786)
 // is FIRArbitrary's recurrence on the same Float64 quantity, and the constructor state (:141-144) is the one rates_reset_kernel writes
 // (𝜙Idx = 1.0 is the accumulator, inputDeficit = xIdx = 1).  RatesArgs stands beside FarrowArgs (n_idx / acc: the bases of the slices,
-// n_out: the call's bound, dyn NULL, seam_below = T, pnfb: the ONE bank [T][polyorder+1]).
+// n_out: the call's bound, dyn NULL, seam_below = T, pnfb: the ONE bank [T][polyorder+1], or one per channel).
 //
 // farrow_rates_multi_kernel: a lane owns kFarrowRatesOPL outputs of one channel, output `tid` of as many consecutive runs of
 // kVariantThreads outputs; a tile is those runs (tile_out = kFarrowRatesOPL * kVariantThreads outputs of one channel).
@@ -107,32 +103,22 @@ MRHIP_RATES_HD inline int farrow_rates_live_slots(long long k0, int tid, long lo
     return slots < kFarrowRatesOPL ? static_cast<int>(slots) : kFarrowRatesOPL;
 }
 
-// kernels_rates_farrow.hip
+// kernels_rates_farrow.hip.  Every function below takes either bank key: the ONE bank, or a bank per channel
+// (mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb on a filter of mrhip_create_farrow_rates*; include/multirate_hip.h,
+// "Per-channel taps with per-channel rates for FIRFarrow": FarrowArgs::pnfb holds nch banks, [nch][T][polyorder+1], and TypeKey::bank is
+// set).  Records, slices, schedule kernel, RatesArgs and the tile of kFarrowRatesOPL runs serve both unchanged.  The key selects the
+// reported name (farrow_rates_generic / farrow_rates_multi, farrow_rates_bank_generic / farrow_rates_bank_multi) and the switches
+// (MRHIP_FARROW_RATES_MULTI / _GRID, MRHIP_FARROW_RATES_BANK_MULTI / _BANK_GRID).
 hipError_t launch_farrow_rates_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
-bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, ArbTileArgs *out);      // (reads MRHIP_FARROW_RATES_MULTI)
-// the multi kernel's persistent grid (occupancy query): everything about its launch that can fail ahead of the launch
+bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, ArbTileArgs *out);      // (reads the key's MULTI switch)
+// the multi kernel's persistent grid (occupancy query; the key's GRID switch): everything about its launch that can fail ahead of the launch
 hipError_t prepare_farrow_rates_multi(const TypeKey &tk, bool fused, const ArbTileArgs &ta, int num_cus, long long *grid);
 hipError_t launch_farrow_rates_multi(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, const ArbTileArgs &ta,
                                      long long grid, hipStream_t s, const char **kname);
-// host_logic.cpp: the switch value passed in (MRHIP_FARROW_RATES_MULTI: 0 never, 1 every call, -1 the default rule), and the grid from
-// what the chip holds (chip_grid), the tile count and a test's replacement (grid_fixed > 0: also more workgroups than tiles)
+// host_logic.cpp: the switch value passed in (0 never, 1 every call, -1 the default rule of the bank key), and the grid from what the
+// chip holds (chip_grid), the tile count and a test's replacement (grid_fixed > 0: also more workgroups than tiles)
 bool plan_farrow_rates_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
 long long farrow_rates_multi_grid(long long total_tiles, long long chip_grid, int grid_fixed);
-
-// ---- FIRFarrow with per-channel rates AND per-channel taps (mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb on a filter of
-// mrhip_create_farrow_rates*; include/multirate_hip.h, "Per-channel taps with per-channel rates for FIRFarrow") -------------------------
-// Records, slices, schedule kernel, RatesArgs and the tile of kFarrowRatesOPL runs above serve it unchanged; FarrowArgs::pnfb holds nch
-// banks, [nch][T][polyorder+1], and TypeKey::bank is set.  The Horner chains and the dots both units run: rates_farrow_device.h.
-// kernels_rates_bank_farrow.hip
-hipError_t launch_farrow_rates_bank_generic(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
-bool plan_farrow_rates_bank_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, ArbTileArgs *out);   // (reads MRHIP_FARROW_RATES_BANK_MULTI)
-// the multi kernel's persistent grid (occupancy query; MRHIP_FARROW_RATES_BANK_GRID): what can fail ahead of the launch
-hipError_t prepare_farrow_rates_bank_multi(const TypeKey &tk, bool fused, const ArbTileArgs &ta, int num_cus, long long *grid);
-hipError_t launch_farrow_rates_bank_multi(const TypeKey &tk, bool fused, const FarrowArgs &a, const RatesArgs &r, const ArbTileArgs &ta,
-                                          long long grid, hipStream_t s, const char **kname);
-// host_logic.cpp: the switch value passed in (MRHIP_FARROW_RATES_BANK_MULTI: 0 never, 1 wherever the plan fits, -1 the default rule);
-// the grid is farrow_rates_multi_grid's
-bool plan_farrow_rates_bank_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
 
 // ---- Device-resident updates (mrhip_set_channel_rates_device, mrhip_set_channel_taps_device, mrhip_set_channel_pnfb_device;
 // include/multirate_hip.h, "Device-resident updates for the filters with per-channel rates") ---------------------------------------------

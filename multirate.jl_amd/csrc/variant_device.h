@@ -4,7 +4,9 @@
 // real-tap and a complex-tap body differ -- the bodies that are one kernel under two algebras, and the two launch shapes.  The plans of
 // the tiled kernels: host_logic.cpp.  The statements inside the algebras are the contract of include/multirate_hip.h: oldest sample
 // first, the first product initialises the sum, every operation rounded separately in R, FUSED (real taps only) one explicit fma per
-// tap (mac, pipe_stage.h).  The including units are compiled with -ffp-contract=off.
+// tap (mac, pipe_stage.h).  The two per-channel-rate units (kernels_rates_arb.hip, kernels_rates_farrow.hip: shared and per-channel taps in
+// ONE text each, BANK the kernels' last template argument) use the dispatch, the staging, the tile hand-out, RealTaps and the FIRFarrow
+// coefficient reads from here and keep their kernels to themselves.  The including units are compiled with -ffp-contract=off.
 #pragma once
 
 #include <algorithm>
@@ -25,6 +27,14 @@ hipError_t dispatch_variant(const TypeKey &tk, F &&f)
     if (!tk.x_f64 && tk.r_f64) return tk.complex_x ? f.template operator()<float, double, 2>() : f.template operator()<float, double, 1>();
     if (tk.x_f64 && tk.r_f64) return tk.complex_x ? f.template operator()<double, double, 2>() : f.template operator()<double, double, 1>();
     return hipErrorInvalidValue;
+}
+// ... and one bool beside them: the last template argument of the per-channel-rate kernels (BANK, kernels_rates_*.hip)
+template <typename F>
+hipError_t dispatch_variant_flag(const TypeKey &tk, bool flag, F &&f)
+{
+    return dispatch_variant(tk, [&]<typename TX, typename R, int NCX>() -> hipError_t {
+        return flag ? f.template operator()<TX, R, NCX, true>() : f.template operator()<TX, R, NCX, false>();
+    });
 }
 
 // ---- FIRFarrow with per-channel taps: the coefficient reads and the Horner chains ------------------------------------------------

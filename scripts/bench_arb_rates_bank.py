@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-channel taps with per-channel rates for FIRArbitrary (FIRFilter.per_channel_taps_and_rates, mrhip_set_channel_taps,
-csrc/kernels_rates_bank_arb.hip) against what a user did before, on one MI355X.
+the BANK kernels of csrc/kernels_rates_arb.hip) against what a user did before, on one MI355X.
 
 The three workloads of DESIGN.md 9 items 17, 18 and 21 (w1 ... w3: Float32, Nphi 32, the rates spread evenly over [2.0, 2.25], every
 channel with taps of its own), each run five ways:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-channel taps with per-channel rates for FIRFarrow (FIRFilter.per_channel_taps_and_rates_farrow, mrhip_set_channel_taps_farrow,
-mrhip_set_channel_pnfb, csrc/kernels_rates_bank_farrow.hip) against what a user did before, on one MI355X.
+mrhip_set_channel_pnfb, the BANK kernels of csrc/kernels_rates_farrow.hip) against what a user did before, on one MI355X.
 
 The three workloads of DESIGN.md 9 items 17, 18, 21 and 22 (w1 ... w3: Float32, Nphi 32, polyorder 4, the rates spread evenly over
 [2.0, 2.25], every channel with taps of its own), each run these ways:

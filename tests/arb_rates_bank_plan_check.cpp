@@ -1,7 +1,7 @@
 // arb_rates_bank_plan_check.cpp -- stand-alone program of tests/test_rates_bank_arb_cpu.py: the two pure functions behind
 // mrhip_set_channel_taps (csrc/host_logic.cpp) on the rows of stdin.
 //   plan x_f64 r_f64 complex_x complex_h bank Nphi T n_out nch rate_min num_cus mode
-//        -> plan_arb_rates_bank_tiled (the switch value passed in), answered as
+//        -> plan_arb_rates_tiled (the switch value passed in; either bank key), answered as
 //           ok cpl tap_pitch bank_elems x_offset_bytes max_span tile_out tiles_per_channel total_tiles lds      (zeros after ok: refused)
 //   taps is_rates is_farrow h_is_null hLen tap_dtype filter_hLen filter_tap_dtype
 //        -> check_channel_taps, answered as
@@ -31,7 +31,7 @@ int main()
             a.Nphi = static_cast<int>(v[5]); a.T = static_cast<int>(v[6]); a.n_out = v[7]; a.nch = static_cast<int>(v[8]);
             ArbTileArgs ta{};
             size_t lds = 0;
-            const bool ok = plan_arb_rates_bank_tiled(tk, a, rate, static_cast<int>(v[10]), static_cast<int>(v[11]), &ta, &lds);
+            const bool ok = plan_arb_rates_tiled(tk, a, rate, static_cast<int>(v[10]), static_cast<int>(v[11]), &ta, &lds);
             if (!ok) { ta = ArbTileArgs{}; lds = 0; }
             std::printf("%d %d %d %d %d %d %lld %lld %lld %lld\n", ok ? 1 : 0, ta.cpl, ta.tap_pitch, ta.bank_elems, ta.x_offset_bytes, ta.max_span,
                         static_cast<long long>(ta.tile_out), static_cast<long long>(ta.tiles_per_channel), static_cast<long long>(ta.total_tiles),

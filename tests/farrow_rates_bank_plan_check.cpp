@@ -1,7 +1,7 @@
 // farrow_rates_bank_plan_check.cpp -- stand-alone program of tests/test_rates_bank_farrow_cpu.py: the pure functions behind
 // mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb (csrc/host_logic.cpp) on the rows of stdin.
 //   plan x_f64 r_f64 complex_x complex_h bank T polyorder n_out nch num_cus mode chip_grid grid_fixed count
-//        -> plan_farrow_rates_bank_multi (the switch value passed in), farrow_rates_multi_grid and, for the LAST tile of a channel that
+//        -> plan_farrow_rates_multi (the switch value passed in; either bank key), farrow_rates_multi_grid and, for the LAST tile of a channel that
 //           reaches `count`, farrow_rates_live_slots (csrc/rates_arb.h: what the kernel evaluates per lane), answered as
 //           ok cpl tile_out tiles_per_channel total_tiles grid k0  and the number of lanes with 0, 1, ... kFarrowRatesOPL live slots
 //           (zeros after ok: refused)
@@ -30,7 +30,7 @@ int main()
             FarrowArgs a{};
             a.T = static_cast<int>(v[5]); a.polyorder = static_cast<int>(v[6]); a.n_out = v[7]; a.nch = static_cast<int>(v[8]);
             ArbTileArgs ta{};
-            const bool ok = plan_farrow_rates_bank_multi(tk, a, static_cast<int>(v[9]), static_cast<int>(v[10]), &ta);
+            const bool ok = plan_farrow_rates_multi(tk, a, static_cast<int>(v[9]), static_cast<int>(v[10]), &ta);
             if (!ok) {
                 std::printf("0 0 0 0 0 0 0");
                 for (int j = 0; j <= kFarrowRatesOPL; ++j) std::printf(" 0");

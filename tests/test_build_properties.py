@@ -38,6 +38,20 @@ def _kernel_scratch(obj):
     return out
 
 
+def _assert_rates_filter_kernel(sizes, kernel, each=12):
+    """a filter kernel of the per-channel-rate units (kernels_rates_arb.hip, kernels_rates_farrow.hip) takes BANK -- shared taps or a bank
+    per channel -- as its LAST template argument: `each` instantiations with BANK false and `each` with BANK true, told apart by the end
+    of the mangled argument list (Lb0E / Lb1E, then the E of the list, the E of the nested name and the v of the return type), and none
+    with scratch memory or AccVGPRs.  `sizes`: _kernel_scratch of the unit's object."""
+    mine = {k: v for k, v in sizes.items() if kernel in k}
+    for bank in (0, 1):
+        n = len([k for k in mine if re.search(rf"Lb{bank}EEEv", k)])
+        assert n == each, f"expected {each} instantiations of {kernel} with BANK = {bank} in the object, found {n}"
+    assert len(mine) == 2 * each, f"expected {2 * each} instantiations of {kernel} in the object, found {len(mine)}"
+    spilling = {k: v for k, v in mine.items() if v != 0}
+    assert not spilling, f"{kernel}: instantiations with scratch or AccVGPRs: {list(spilling.items())[:6]}"
+
+
 @pytest.mark.parametrize("src,kernel", [("kernels_arb_pipe.hip", "arb_pipe_kernel"), ("kernels_farrow_pipe.hip", "farrow_pipe_kernel")])
 def test_pipe_kernels_use_no_scratch(pkg, src, kernel):
     obj = os.path.join(CSRC, "build", src + ".o")

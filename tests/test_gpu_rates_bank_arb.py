@@ -1,4 +1,4 @@
-"""GPU tests of per-channel taps with per-channel rates for FIRArbitrary (csrc/kernels_rates_bank_arb.hip): mrhip_set_channel_taps on a
+"""GPU tests of per-channel taps with per-channel rates for FIRArbitrary (the BANK kernels of csrc/kernels_rates_arb.hip): mrhip_set_channel_taps on a
 filter of mrhip_create_arbitrary_rates, FIRFilter.set_channel_taps(H) and FIRFilter.per_channel_taps_and_rates(H, rates, Nphi) -- one
 FIRFilter(H[c], rates[c], Nphi) per channel behind one filter object.
 

@@ -1,4 +1,4 @@
-"""GPU tests of per-channel taps with per-channel rates for FIRFarrow (csrc/kernels_rates_bank_farrow.hip): mrhip_set_channel_taps_farrow
+"""GPU tests of per-channel taps with per-channel rates for FIRFarrow (the BANK kernels of csrc/kernels_rates_farrow.hip): mrhip_set_channel_taps_farrow
 and mrhip_set_channel_pnfb on a filter of mrhip_create_farrow_rates*, FIRFilter.set_channel_taps_farrow(H), FIRFilter.set_channel_pnfb(PN)
 and FIRFilter.per_channel_taps_and_rates_farrow(H, rates, Nphi, polyorder) -- one FIRFilter(H[c], rates[c], Nphi, polyorder) per channel
 behind one filter object.

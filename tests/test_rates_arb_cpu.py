@@ -1,11 +1,12 @@
 """CPU-only checks of per-channel rates for FIRArbitrary (FIRFilter.per_channel_rates, mrhip_create_arbitrary_rates,
 csrc/kernels_rates_arb.hip): the four exported symbols and their declarations, the argument errors of the Python constructor, the
 answers the older constructors keep, the build conditions of the kernel unit, the instantiations in the object the build made (the
-two filter kernels for (Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED = 12 each, the
-schedule kernel for a power-of-two N𝜙 and for any other; none with scratch memory or AccVGPRs), the serial walk over the shared step
-header (csrc/sched_step.h) in a stand-alone program built by the host compiler with -ffp-contract=off, against the oracle's schedule,
-and the tiled kernel's plan (csrc/host_logic.cpp: plan_arb_rates_tiled) through a second stand-alone program, built with
--fsanitize=address,undefined, against values computed here from the plan's stated formulas."""
+two filter kernels for (Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED = 12 each for
+shared taps and 12 each for a bank per channel, the schedule kernel for a power-of-two N𝜙 and for any other; none with scratch memory
+or AccVGPRs), the serial walk over the shared step header (csrc/sched_step.h) in a stand-alone program built by the host compiler with
+-ffp-contract=off, against the oracle's schedule, and the tiled kernel's plan (csrc/host_logic.cpp: plan_arb_rates_tiled, which takes
+either bank key) through a second stand-alone program, built with -fsanitize=address,undefined, against values computed here from the
+plan's stated formulas."""
 import math
 import os
 import re
@@ -15,7 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_build_properties import CSRC, LLVM, _kernel_scratch
+from test_build_properties import CSRC, LLVM, _assert_rates_filter_kernel, _kernel_scratch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KB = 1024
@@ -133,7 +134,9 @@ def test_rates_kernels_use_no_scratch(pkg):
     if os.path.getmtime(obj) < newest:
         pytest.skip("object older than its source")
     sizes = _kernel_scratch(obj)
-    for kernel, count in (("arb_rates_generic_kernel", 12), ("arb_rates_tiled_kernel", 12), ("rates_schedule_kernel", 2), ("rates_reset_kernel", 1)):
+    for kernel in ("arb_rates_generic_kernel", "arb_rates_tiled_kernel"):       # 12 with BANK false and 12 with BANK true, none spilling
+        _assert_rates_filter_kernel(sizes, kernel)
+    for kernel, count in (("rates_schedule_kernel", 2), ("rates_reset_kernel", 1)):
         mine = {k: v for k, v in sizes.items() if kernel in k}
         assert len(mine) == count, f"expected {count} instantiations of {kernel} in the object, found {len(mine)}"
         spilling = {k: v for k, v in mine.items() if v != 0}
@@ -215,15 +218,20 @@ def test_the_shared_step_walks_the_oracles_schedule(O, tmp_path):
 # ---- the plan ------------------------------------------------------------------------------------------------------------------
 # a row: x_f64 r_f64 complex_x complex_h bank Nphi T n_out nch rate_min num_cus mode
 XF64, RF64, CX, CH, BANK, NPHI, T, NOUT, NCH, RATE, CUS, MODE = range(12)
+# the default rule (mode -1) by the row's bank key, (from tiles, up to tiles a channel): the measured rows the tiled kernel won with
+# shared taps and with a bank per channel (item 21)
+RULE = {0: (225_024, 879), 1: (225_024, 879)}
 
 
 def _expected(r):
-    """the plan from its stated formulas: the ONE shared pfb and dpfb, (2 Nphi (T+1) sizeof(R) + 15)/16*16 bytes, at most 78 KiB
-    together with the samples; the samples take 40 KiB or what is left, in whole 16-byte units; one channel a lane; the span
-    ceil(255/rate_min) + T + 2, cut to the room only when forced; a tile is 256 outputs of one channel, the tiling goes by n_out (the
-    call's bound); the default rule (mode -1) is the measured one: from 225 024 tiles, up to 879 tiles a channel"""
+    """the plan from its stated formulas, for either bank key: ONE pfb and dpfb in LDS (the shared pair, or one channel's),
+    (2 Nphi (T+1) sizeof(R) + 15)/16*16 bytes, at most 78 KiB together with the samples; the samples take 40 KiB or what is left, in
+    whole 16-byte units; one channel a lane; the span ceil(255/rate_min) + T + 2, cut to the room only when forced; a tile is 256
+    outputs of one channel, the tiling goes by n_out (the call's bound); the default rule (mode -1) is the measured one of the row's
+    bank key: from 225 024 tiles, up to 879 tiles a channel"""
     refused = [0] * 10
-    if r[MODE] == 0 or r[BANK] or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[NPHI] < 1 or not r[RATE] > 0.0:
+    min_tiles, max_per_channel = RULE[r[BANK]]
+    if r[MODE] == 0 or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[NPHI] < 1 or not r[RATE] > 0.0:
         return refused
     sample = (8 if r[XF64] else 4) * (2 if r[CX] else 1)
     tap = 8 if r[RF64] else 4
@@ -239,7 +247,7 @@ def _expected(r):
     if per_tile > span and r[MODE] != 1:                                    # a cut span: only when forced
         return refused
     tpc = -(-r[NOUT] // 256)
-    if r[MODE] != 1 and (tpc * r[NCH] < 225_024 or tpc > 879):
+    if r[MODE] != 1 and (tpc * r[NCH] < min_tiles or tpc > max_per_channel):
         return refused
     return [1, 1, pitch, r[NPHI] * pitch, fixed, span, 256, tpc, tpc * r[NCH], fixed + span * sample]
 
@@ -286,8 +294,10 @@ def test_the_plan_of_the_tiled_kernel(tmp_path):
     assert all(w[0] == (r[MODE] != 0) for r, w in named("the smallest measured win") + named("many short channels"))
     assert all(w[8] == 225_024 and w[7] == 879 for _, w in named("the smallest measured win") if w[0])
     assert all(w[0] == (r[MODE] == 1) for r, w in named("a channel fewer") + named("a tile a channel more"))
-    for name in ("mode 0", "mode -1", "n_out < 1", "T < 1", "Nphi < 1", "rate <= 0", "complex taps", "a bank", "over 78 KiB", "not even one window"):
+    for name in ("mode 0", "mode -1", "n_out < 1", "T < 1", "Nphi < 1", "rate <= 0", "complex taps", "over 78 KiB", "not even one window"):
         assert named(name) and all(not w[0] for _, w in named(name)), name
+    # a bank key is no refusal: the plan of the per-channel-taps kernel, whose LDS geometry is the shared pair's
+    assert named("a bank") and all(r[BANK] and w == _expected(r[:BANK] + [0] + r[BANK + 1:]) and w[0] for r, w in named("a bank"))
     assert all(w[0] == (r[MODE] == 1) for r, w in zip(rows, want) if (r, w) in named("cut span") + named("two tiles"))
     assert all(w[0] and w[5] == math.ceil(255 / 2.123) + 8 + 2 == 131 for _, w in named("the span the slowest rate asks for"))
     assert all(w[5] == 40 * KB // ((8 if r[XF64] else 4) * (2 if r[CX] else 1)) < 25_510 for r, w in named("cut span") if w[0])

@@ -1,10 +1,10 @@
 """CPU-only checks of per-channel taps with per-channel rates for FIRArbitrary (mrhip_set_channel_taps, FIRFilter.set_channel_taps,
-FIRFilter.per_channel_taps_and_rates, csrc/kernels_rates_bank_arb.hip): the exported symbol, its declaration and its place in host.ABI
+FIRFilter.per_channel_taps_and_rates, the BANK kernels of csrc/kernels_rates_arb.hip): the exported symbol, its declaration and its place in host.ABI
 and in the Julia shim; the constructor table that stays at sixteen; the argument errors of the two Python methods on unbound filters;
 the answers per_channel_rates and the older constructors keep; the build conditions of the kernel unit; the instantiations in the object
 the build made (both filter kernels for (Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED =
-12 each, none with scratch memory or AccVGPRs); and, through a stand-alone program built with -fsanitize=address,undefined, the tiled
-kernel's plan (csrc/host_logic.cpp: plan_arb_rates_bank_tiled) against values computed here from the plan's stated formulas and the pure
+12 each with BANK true beside the 12 each with BANK false, none with scratch memory or AccVGPRs); and, through a stand-alone program
+built with -fsanitize=address,undefined, the tiled kernel's plan (csrc/host_logic.cpp: plan_arb_rates_tiled on both bank keys) against values computed here from the plan's stated formulas and the pure
 argument checks of mrhip_set_channel_taps (check_channel_taps) against a table of (arguments -> status, message)."""
 import math
 import os
@@ -15,11 +15,11 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_build_properties import CSRC, LLVM, _kernel_scratch
+from test_build_properties import CSRC, LLVM, _assert_rates_filter_kernel, _kernel_scratch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KB = 1024
-UNIT = "kernels_rates_bank_arb.hip"
+UNIT = "kernels_rates_arb.hip"                                               # one unit for shared taps and for a bank per channel
 
 
 def test_the_library_exports_the_symbol_and_the_header_declares_it(pkg):
@@ -97,9 +97,10 @@ def test_per_channel_rates_and_the_older_constructors_keep_their_answers(pkg):
 
 def test_the_unit_is_in_the_makefile_with_separately_rounded_arithmetic():
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SRCS\s*=.*\bkernels_rates_bank_arb\.hip\b", mk, flags=re.M)
+    assert re.search(r"^SRCS\s*=.*\bkernels_rates_arb\.hip\b", mk, flags=re.M)
     assert re.search(r"^CXXFLAGS\s*=.*-ffp-contract=off", mk, flags=re.M)
-    assert re.search(r"^.*kernels_rates_bank_arb\.hip\.o.*:.*\bvariant_device\.h\b.*\brates_arb\.h\b", mk, flags=re.M)
+    assert re.search(r"^.*kernels_rates_arb\.hip\.o.*:.*\bvariant_device\.h\b.*\brates_arb\.h\b", mk, flags=re.M)
+    assert "kernels_rates_bank_arb" not in mk and not os.path.exists(os.path.join(CSRC, "kernels_rates_bank_arb.hip"))      # no second unit
     src = open(os.path.join(CSRC, UNIT)).read()
     assert "#pragma clang fp contract(off)" in src
     assert '#include "variant_device.h"' in src and '#include "rates_arb.h"' in src and "RealTaps<TX, R, NCX, FUSED>" in src
@@ -108,14 +109,50 @@ def test_the_unit_is_in_the_makefile_with_separately_rounded_arithmetic():
     assert "asm" not in src                                                  # plain HIP
     assert "atomic" not in src.lower()                                       # no atomics: no workgroup waits for another, no spin loop
     assert '"arb_rates_bank_generic"' in src and '"arb_rates_bank_tiled"' in src and not re.search(r'"[a-z_]+_kernel"', src)
+    # both kernels end with the epilogue, ragged and plain, and no return stands in front of it
+    assert src.count("shiftin_by_last_workgroup") == 2 and src.count("shiftin_ragged_by_last_workgroup") == 2
+    for kernel in ("arb_rates_generic_kernel(ArbArgs a, RatesArgs r)", "arb_rates_tiled_kernel(ArbArgs a, RatesArgs r, ArbTileArgs ta)"):
+        body = src.split(kernel)[1].split("dev::shiftin_by_last_workgroup")[0]
+        assert "dev::shiftin_ragged_by_last_workgroup" in body and not re.search(r"\breturn;", body), kernel
+    # BANK is the kernels' last template argument and stands at the statements that differ: the column's bank base (stated ONCE), and in
+    # the tiled kernel where the banks go into LDS -- in front of the tile loop, or behind the first barrier of a live tile of another
+    # channel; the copy loop itself is stated once
+    assert src.count("template <typename TX, typename R, int NCX, bool FUSED, bool BANK>\n__global__") == 2
+    assert src.count("ch * bank_elems") == 1 and "if constexpr (BANK) col = ch * bank_elems + col;" in src
+    tiled = src.split("arb_rates_tiled_kernel(ArbArgs a, RatesArgs r, ArbTileArgs ta)")[1].split("dev::shiftin_by_last_workgroup")[0]
+    loop = tiled.index("for (long long tile = run.begin")
+    assert tiled.index("if constexpr (!BANK)") < tiled.index("if (run.begin < run.end) rates_banks_to_lds(") < loop
+    assert loop < tiled.index("__syncthreads();") < tiled.index("if constexpr (BANK)") < tiled.index("if (ch != ch_in_lds)") < tiled.index("stage_window(")
+    assert tiled.count("rates_banks_to_lds(") == 2 and src.count("void rates_banks_to_lds(") == 1
+    assert src.count("lpfb[phi * TP + i] = g0[e];") == 1 and src.count("ldpfb[phi * TP + i] = g1[e];") == 1
 
 
-def test_the_sibling_unit_still_passes_its_own_pins():
-    src = open(os.path.join(CSRC, "kernels_rates_arb.hip")).read()
+def test_the_bank_key_is_read_in_one_place_and_selects_argument_name_and_switch_together():
+    """(was: the sibling unit's launches refuse a bank key.)  With one unit the key is the selector: TypeKey::bank is read in ONE function
+    of the unit, which gives the kernels' BANK argument, the reported names and the switches of that key; nothing else of the unit reads
+    it, and the launches keep their other refusals"""
+    src = open(os.path.join(CSRC, UNIT)).read()
+    code = "\n".join(line.split("//")[0] for line in src.splitlines())
+    key = code.split("static RatesKey rates_key(const TypeKey &tk)")[1].split("\n}\n")[0]
+    assert code.count("tk.bank") == key.count("tk.bank") == 5
+    assert 'RatesKey{tk.bank, tk.bank ? "arb_rates_bank_generic" : "arb_rates_generic", tk.bank ? "arb_rates_bank_tiled" : "arb_rates_tiled",' in key
+    assert 'tk.bank ? MRHIP_ENV_INT("MRHIP_ARB_RATES_BANK_TILED", -1) : MRHIP_ENV_INT("MRHIP_ARB_RATES_TILED", -1)' in key
+    assert 'tk.bank ? MRHIP_ENV_INT("MRHIP_ARB_RATES_BANK_GRID", 0) : MRHIP_ENV_INT("MRHIP_ARB_RATES_GRID", 0)' in key
+    assert code.count("MRHIP_ENV_INT(") == 4                                  # the four switches, each a literal name at a site of its own
+    assert code.count("dispatch_variant_flag(tk, key.bank, [&]<typename TX, typename R, int NCX, bool BANK>()") == 3 and "dispatch_variant(" not in code
+    assert code.count("*kname = key.generic;") == 1 and code.count("*kname = key.tiled;") == 1 and code.count("*kname = ") == 2
+    assert "rates_key(tk).tiled_mode" in code and code.count("key.grid_fixed") == 2
+    assert "if (tk.complex_h || a.dyn) return hipErrorInvalidValue;" in code and "if (tk.complex_h) return hipErrorInvalidValue;" in code
+    assert "if (tk.complex_h || a.dyn || grid < 1) return hipErrorInvalidValue;" in code
     assert '"arb_rates_generic"' in src and '"arb_rates_tiled"' in src and not re.search(r'"[a-z_]+_kernel"', src)
-    assert "if (tk.bank || tk.complex_h || a.dyn) return hipErrorInvalidValue;" in src       # its launches keep refusing a bank key
-    assert "arb_rates_bank" not in src
-    assert src.count("arb_rates_generic_kernel<TX, R, NCX, true>") == 1 and src.count("arb_rates_tiled_kernel<TX, R, NCX, true>") == 2
+    assert "arb_rates_bank_generic_kernel" not in src and "arb_rates_bank_tiled_kernel" not in src       # no second kernel, no wrapper
+    assert src.count("arb_rates_generic_kernel<TX, R, NCX, true, BANK>") == 1 and src.count("arb_rates_tiled_kernel<TX, R, NCX, true, BANK>") == 1
+    hdr = open(os.path.join(CSRC, "rates_arb.h")).read()
+    assert not re.search(r"\b\w+_rates_bank_(generic|tiled|multi)\(", hdr)   # one set of declarations per family
+    api = open(os.path.join(CSRC, "api.hip")).read()
+    calls = api.split("static int rates_call(")[1].split("\nint mrhip_filt_device_rates(")[0]
+    assert not re.search(r"_rates_bank_(generic|tiled|multi)\(", calls)
+    assert calls.index("prepare_arb_rates_tiled(") < calls.index("launch_rates_schedule(") < calls.index("launch_arb_rates_tiled(")   # what can fail: before the state moves
 
 
 def test_rates_bank_kernels_use_no_scratch(pkg):
@@ -126,26 +163,25 @@ def test_rates_bank_kernels_use_no_scratch(pkg):
     if os.path.getmtime(obj) < newest:
         pytest.skip("object older than its source")
     sizes = _kernel_scratch(obj)
-    for kernel, count in (("arb_rates_bank_generic_kernel", 12), ("arb_rates_bank_tiled_kernel", 12)):
-        mine = {k: v for k, v in sizes.items() if kernel in k}
-        assert len(mine) == count, f"expected {count} instantiations of {kernel} in the object, found {len(mine)}"
-        spilling = {k: v for k, v in mine.items() if v != 0}
-        assert not spilling, f"{kernel}: instantiations with scratch or AccVGPRs: {list(spilling.items())[:6]}"
+    for kernel in ("arb_rates_generic_kernel", "arb_rates_tiled_kernel"):       # 12 with BANK true beside the 12 with BANK false, none spilling
+        _assert_rates_filter_kernel(sizes, kernel)
 
 
 # ---- the plan and the argument checks, through one stand-alone program ------------------------------------------------------------
 # a plan row: x_f64 r_f64 complex_x complex_h bank Nphi T n_out nch rate_min num_cus mode
 XF64, RF64, CX, CH, BANK, NPHI, T, NOUT, NCH, RATE, CUS, MODE = range(12)
 RULE_MIN_TILES, RULE_MAX_PER_CHANNEL = 225_024, 879    # the default rule (mode -1): the measured rows the tiled kernel won
+SHARED_RULE = (225_024, 879)                           # ... and with shared taps: the rule of a row without a bank key
 
 
 def _expected(r):
-    """the plan from its stated formulas: ONE channel's pfb and dpfb, (2 Nphi (T+1) sizeof(R) + 15)/16*16 bytes, at most 78 KiB together
-    with the samples; the samples take 40 KiB or what is left, in whole 16-byte units; one channel a lane; the span
+    """the plan from its stated formulas, the limits of the default rule by the row's bank key: ONE channel's pfb and dpfb (without a
+    bank key: the shared pair, the same geometry), (2 Nphi (T+1) sizeof(R) + 15)/16*16 bytes, at most 78 KiB together with the samples; the samples take 40 KiB or what is left, in whole 16-byte units; one channel a lane; the span
     ceil(255/rate_min) + T + 2 (the slowest channel), cut to the room only when forced; a tile is 256 outputs of one channel, the tiling
     goes by n_out (the call's bound); the default rule (mode -1) as DESIGN.md 9 item 21 derives it"""
     refused = [0] * 10
-    if r[MODE] == 0 or not r[BANK] or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[NPHI] < 1 or not r[RATE] > 0.0:
+    min_tiles, max_per_channel = (RULE_MIN_TILES, RULE_MAX_PER_CHANNEL) if r[BANK] else SHARED_RULE
+    if r[MODE] == 0 or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[NPHI] < 1 or not r[RATE] > 0.0:
         return refused
     sample = (8 if r[XF64] else 4) * (2 if r[CX] else 1)
     tap = 8 if r[RF64] else 4
@@ -161,7 +197,7 @@ def _expected(r):
     if per_tile > span and r[MODE] != 1:                                    # a cut span: only when forced
         return refused
     tpc = -(-r[NOUT] // 256)
-    if r[MODE] != 1 and (RULE_MIN_TILES is None or tpc * r[NCH] < RULE_MIN_TILES or tpc > RULE_MAX_PER_CHANNEL):
+    if r[MODE] != 1 and (min_tiles is None or tpc * r[NCH] < min_tiles or tpc > max_per_channel):
         return refused
     return [1, 1, pitch, r[NPHI] * pitch, fixed, span, 256, tpc, tpc * r[NCH], fixed + span * sample]
 
@@ -236,8 +272,10 @@ def test_the_plan_of_the_tiled_kernel_and_the_argument_checks(tmp_path):
     want = [_expected(r) for r in rows]
     named = lambda name: [(r, w) for r, w, n in zip(rows, want, why) if n == name]
     # the rows reach every return, the default rule from both sides of each of its limits
-    for name in ("mode 0", "n_out < 1", "T < 1", "Nphi < 1", "rate <= 0", "complex taps", "shared taps", "over 78 KiB", "not even one window"):
+    for name in ("mode 0", "n_out < 1", "T < 1", "Nphi < 1", "rate <= 0", "complex taps", "over 78 KiB", "not even one window"):
         assert named(name) and all(not w[0] for _, w in named(name)), name
+    # shared taps are no refusal: the plan of the shared-taps kernel, whose LDS geometry is one channel's
+    assert named("shared taps") and all(not r[BANK] and w == _expected(r[:BANK] + [1] + r[BANK + 1:]) and w[0] for r, w in named("shared taps"))
     assert all(w[0] == (r[MODE] == 1) for r, w in named("cut span") + named("two tiles"))
     if RULE_MIN_TILES is None:
         assert all(not w[0] for _, w in named("mode -1") + [(r, w) for r, w in zip(rows, want) if r[MODE] == -1])

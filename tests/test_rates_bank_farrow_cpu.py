@@ -1,12 +1,12 @@
 """CPU-only checks of per-channel taps with per-channel rates for FIRFarrow (mrhip_set_channel_taps_farrow, mrhip_set_channel_pnfb,
-FIRFilter.set_channel_taps_farrow, FIRFilter.set_channel_pnfb, FIRFilter.per_channel_taps_and_rates_farrow,
-csrc/kernels_rates_bank_farrow.hip): the exported symbols, their declarations and their place in host.ABI and in the Julia shim; the
+FIRFilter.set_channel_taps_farrow, FIRFilter.set_channel_pnfb, FIRFilter.per_channel_taps_and_rates_farrow, the BANK kernels of
+csrc/kernels_rates_farrow.hip): the exported symbols, their declarations and their place in host.ABI and in the Julia shim; the
 constructor table that stays at sixteen; the argument errors of the Python methods on unbound filters and the remembered matrix; the
 answers the older constructors and set_channel_taps keep; the build conditions of the kernel unit and the ONE text of the Horner chains
-and the dots both FIRFarrow units with per-channel rates use; the instantiations in the object the build made (both filter kernels for
-(Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED = 12 each, none with scratch memory or
-AccVGPRs); and, through a stand-alone program built with -fsanitize=address,undefined, the multi kernel's plan (csrc/host_logic.cpp:
-plan_farrow_rates_bank_multi) against values computed here from the plan's stated formulas and the pure argument checks of the two calls
+and the dots all FIRFarrow kernels with per-channel rates use; the instantiations in the object the build made (both filter kernels for
+(Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED = 12 each with BANK true beside the 12 each
+with BANK false, none with scratch memory or AccVGPRs); and, through a stand-alone program built with -fsanitize=address,undefined, the
+multi kernel's plan (csrc/host_logic.cpp: plan_farrow_rates_multi on both bank keys) against values computed here from the plan's stated formulas and the pure argument checks of the two calls
 (check_channel_taps_farrow) against a table of (arguments -> status, message)."""
 import os
 import re
@@ -16,11 +16,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_build_properties import CSRC, LLVM, _kernel_scratch
+from test_build_properties import CSRC, LLVM, _assert_rates_filter_kernel, _kernel_scratch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNIT = "kernels_rates_bank_farrow.hip"
-SHARED = "rates_farrow_device.h"
+UNIT = "kernels_rates_farrow.hip"                                            # one unit for the one bank and for a bank per channel
 SYMBOLS = ("mrhip_set_channel_taps_farrow", "mrhip_set_channel_pnfb")
 OPL, LANES = 4, 256
 
@@ -131,19 +130,20 @@ def test_the_older_constructors_and_set_channel_taps_keep_their_answers(pkg):
 
 def test_the_unit_is_in_the_makefile_with_separately_rounded_arithmetic():
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SRCS\s*=.*\bkernels_rates_bank_farrow\.hip\b", mk, flags=re.M)
+    assert re.search(r"^SRCS\s*=.*\bkernels_rates_farrow\.hip\b", mk, flags=re.M)
     assert re.search(r"^CXXFLAGS\s*=.*-ffp-contract=off", mk, flags=re.M)
-    assert re.search(r"^.*kernels_rates_bank_farrow\.hip\.o.*:.*\bvariant_device\.h\b.*\brates_arb\.h\b.*\brates_farrow_device\.h\b", mk, flags=re.M)
-    assert re.search(r"^.*kernels_rates_farrow\.hip\.o.*:.*\brates_farrow_device\.h\b", mk, flags=re.M)
+    assert re.search(r"^.*kernels_rates_farrow\.hip\.o.*:.*\bvariant_device\.h\b.*\brates_arb\.h\b", mk, flags=re.M)
+    assert "kernels_rates_bank_farrow" not in mk and "rates_farrow_device" not in mk      # no second unit, no header for two
+    assert not os.path.exists(os.path.join(CSRC, "kernels_rates_bank_farrow.hip")) and not os.path.exists(os.path.join(CSRC, "rates_farrow_device.h"))
     src = open(os.path.join(CSRC, UNIT)).read()
     assert "#pragma clang fp contract(off)" in src
-    assert '#include "variant_device.h"' in src and '#include "rates_arb.h"' in src and '#include "rates_farrow_device.h"' in src
+    assert '#include "variant_device.h"' in src and '#include "rates_arb.h"' in src and "#include \"rates_farrow_device.h\"" not in src
     assert "RealTaps<TX, R, NCX, FUSED>" in src
     assert "farrow_bank_horner<PP, 1>" in src and "typedef" not in src and "kFarrowBankUnrolledP =" not in src
     assert "tile_run(" in src and "bank_tile<true>(" in src and "farrow_rates_live_slots(" in src
     # both kernels end with the epilogue, ragged and plain, and no return stands in front of it
     assert src.count("shiftin_by_last_workgroup") == 2 and src.count("shiftin_ragged_by_last_workgroup") == 2
-    for kernel in ("farrow_rates_bank_generic_kernel(FarrowArgs a, RatesArgs r)", "farrow_rates_bank_multi_kernel(FarrowArgs a, RatesArgs r, ArbTileArgs ta)"):
+    for kernel in ("farrow_rates_generic_kernel(FarrowArgs a, RatesArgs r)", "farrow_rates_multi_kernel(FarrowArgs a, RatesArgs r, ArbTileArgs ta)"):
         body = src.split(kernel)[1].split("dev::shiftin_by_last_workgroup")[0]
         assert "dev::shiftin_ragged_by_last_workgroup" in body and not re.search(r"\breturn;", body), kernel
     assert "fma(" not in src                                                 # Horner is never fused; the dot's fma is RealTaps' (mac)
@@ -151,43 +151,55 @@ def test_the_unit_is_in_the_makefile_with_separately_rounded_arithmetic():
     assert not re.search(r"\bwhile\s*\(", src) and "atomic" not in src.lower()      # no waits between workgroups, no spin loops, no atomics
     assert "__syncthreads" not in src and "__shared__" not in src            # no LDS staging (not measured ahead of plain reads)
     assert '"farrow_rates_bank_generic"' in src and '"farrow_rates_bank_multi"' in src and not re.search(r'"[a-z_]+_kernel"', src)
-    assert "ch * bank_elems" in src and src.count("ch * bank_elems") == 2    # the bank base of the channel, once a kernel
+    # BANK is the kernels' last template argument and stands at the ONE statement a kernel that differs: the bank base of the channel
+    assert src.count("template <typename TX, typename R, int NCX, bool FUSED, bool BANK>\n__global__") == 1
+    assert src.count("template <typename TX, typename R, int NCX, bool FUSED, int OPL, bool BANK>\n__global__") == 1
+    assert src.count("ch * bank_elems") == 2 and src.count("if constexpr (BANK) pc = reinterpret_cast<farrow_coef_t>(reinterpret_cast<uintptr_t>(a.pnfb)) + ch * bank_elems;") == 2
+    assert src.count("if constexpr (") - src.count("if constexpr (PP >= 0)") == 2
 
 
 def test_the_horner_chains_and_the_dots_are_stated_once():
-    shared = open(os.path.join(CSRC, SHARED)).read()
-    new, old = open(os.path.join(CSRC, UNIT)).read(), open(os.path.join(CSRC, "kernels_rates_farrow.hip")).read()
+    src = open(os.path.join(CSRC, UNIT)).read()
     for text in ("void farrow_rates_horner(", "void farrow_rates_dots(", "R farrow_rates_round("):
-        assert shared.count(text) == 1 and text not in new and text not in old, text
-    assert "#pragma clang fp contract(off)" in shared and "fma(" not in shared and "asm" not in shared
-    for unit in (new, old):
-        assert '#include "rates_farrow_device.h"' in unit
-        assert unit.count("farrow_rates_dots<A, kFarrowBankUnrolledP, OPL>(") == 1 and unit.count("farrow_rates_dots<A, -1, OPL>(") == 1
-        assert "farrow_rates_round<R>(" in unit
-    # the sibling's launches keep refusing a bank key, the new ones refuse a filter without banks
-    assert old.count("if (tk.bank || tk.complex_h || a.dyn") == 2 and "if (tk.bank || tk.complex_h) return hipErrorInvalidValue;" in old
-    assert new.count("if (!tk.bank || tk.complex_h || a.dyn") == 2 and "if (!tk.bank || tk.complex_h) return hipErrorInvalidValue;" in new
-    assert "farrow_rates_bank" not in old
+        assert src.count(text) == 1, text
+        others = [f for f in os.listdir(CSRC) if f != UNIT and os.path.isfile(os.path.join(CSRC, f)) and f.endswith((".hip", ".h", ".inc", ".cpp"))]
+        assert others and not [f for f in others if text in open(os.path.join(CSRC, f)).read()], text
+    # one kernel text for both bank keys: the dots are called once per polyorder path
+    assert src.count("farrow_rates_dots<A, kFarrowBankUnrolledP, OPL>(") == 1 and src.count("farrow_rates_dots<A, -1, OPL>(") == 1
+    assert "farrow_rates_round<R>(" in src
+    # (was: the sibling's launches refuse a bank key, the new ones a filter without banks.)  The key is the selector: TypeKey::bank is read
+    # in ONE function of the unit, which gives the kernels' BANK argument, the reported names and the switches of that key together
+    code = "\n".join(line.split("//")[0] for line in src.splitlines())
+    key = code.split("static RatesKey rates_key(const TypeKey &tk)")[1].split("\n}\n")[0]
+    assert code.count("tk.bank") == key.count("tk.bank") == 5
+    assert 'RatesKey{tk.bank, tk.bank ? "farrow_rates_bank_generic" : "farrow_rates_generic", tk.bank ? "farrow_rates_bank_multi" : "farrow_rates_multi",' in key
+    assert 'tk.bank ? MRHIP_ENV_INT("MRHIP_FARROW_RATES_BANK_MULTI", -1) : MRHIP_ENV_INT("MRHIP_FARROW_RATES_MULTI", -1)' in key
+    assert 'tk.bank ? MRHIP_ENV_INT("MRHIP_FARROW_RATES_BANK_GRID", 0) : MRHIP_ENV_INT("MRHIP_FARROW_RATES_GRID", 0)' in key
+    assert code.count("MRHIP_ENV_INT(") == 4                                  # the four switches, each a literal name at a site of its own
+    assert code.count("dispatch_variant_flag(tk, key.bank, [&]<typename TX, typename R, int NCX, bool BANK>()") == 3 and "dispatch_variant(" not in code
+    assert code.count("*kname = key.generic;") == 1 and code.count("*kname = key.tiled;") == 1 and code.count("*kname = ") == 2
+    assert "rates_key(tk).tiled_mode" in code and code.count("key.grid_fixed") == 1
+    assert "if (tk.complex_h || a.dyn) return hipErrorInvalidValue;" in code and "if (tk.complex_h) return hipErrorInvalidValue;" in code
+    assert "if (tk.complex_h || a.dyn || grid < 1 || ta.tile_out != static_cast<long long>(kFarrowRatesOPL) * kVariantThreads)" in code
+    assert "farrow_rates_bank_generic_kernel" not in src and "farrow_rates_bank_multi_kernel" not in src      # no second kernel, no wrapper
     api = open(os.path.join(CSRC, "api.hip")).read()
     calls = api.split("static int rates_call(")[1].split("\nint mrhip_filt_device_rates(")[0]
-    assert calls.index("farrow && tk.bank") < calls.index("} else if (bound > 0 && !f->force_generic && farrow)")    # the bank first
-    assert calls.index("launch_farrow_rates_bank_multi(") < calls.index("launch_farrow_rates_multi(")
-    assert calls.index("prepare_farrow_rates_bank_multi(") < calls.index("launch_rates_schedule(")      # what can fail: before the state moves
+    assert not re.search(r"_rates_bank_(generic|tiled|multi)\(", calls)      # the launches take either key
+    assert calls.index("if (bound > 0 && !f->force_generic && farrow)") < calls.index("} else if (bound > 0 && !f->force_generic)")    # two plan branches
+    assert calls.count("force_generic") == 2 and calls.count("MRHIP_CHECK_HIP(launch_") == 5            # ... the schedule and four filter launches
+    assert calls.index("prepare_farrow_rates_multi(") < calls.index("launch_rates_schedule(") < calls.index("launch_farrow_rates_multi(")   # what can fail: before the state moves
 
 
 def test_rates_bank_farrow_kernels_use_no_scratch(pkg):
     obj = os.path.join(CSRC, "build", UNIT + ".o")
     if not os.path.exists(obj) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
         pytest.skip("no built object (the library came prebuilt) or no llvm tools")
-    newest = max(os.path.getmtime(os.path.join(CSRC, s)) for s in (UNIT, SHARED, "variant_device.h", "ctaps_device.h", "rates_arb.h"))
+    newest = max(os.path.getmtime(os.path.join(CSRC, s)) for s in (UNIT, "variant_device.h", "ctaps_device.h", "rates_arb.h"))
     if os.path.getmtime(obj) < newest:
         pytest.skip("object older than its source")
     sizes = _kernel_scratch(obj)
-    for kernel, count in (("farrow_rates_bank_generic_kernel", 12), ("farrow_rates_bank_multi_kernel", 12)):
-        mine = {k: v for k, v in sizes.items() if kernel in k}
-        assert len(mine) == count, f"expected {count} instantiations of {kernel} in the object, found {len(mine)}"
-        spilling = {k: v for k, v in mine.items() if v != 0}
-        assert not spilling, f"{kernel}: instantiations with scratch or AccVGPRs: {list(spilling.items())[:6]}"
+    for kernel in ("farrow_rates_generic_kernel", "farrow_rates_multi_kernel"):  # 12 with BANK true beside the 12 with BANK false, none spilling
+        _assert_rates_filter_kernel(sizes, kernel)
 
 
 # ---- the plan and the argument checks, through one stand-alone program ------------------------------------------------------------
@@ -196,20 +208,22 @@ XF64, RF64, CX, CH, BANK, T, P, NOUT, NCH, CUS, MODE, CHIP, FIXED, COUNT = range
 # the default rule (mode -1), from the measured rows (profiles/r13/farrow_rates_bank.txt): the multi kernel beat the
 # universal one by more than the spread of the repeats at 4096 ch x 1e4 only (22 tiles a channel, 90 112 tiles)
 RULE_MIN_TILES, RULE_MAX_PER_CHANNEL = 90_112, 22
+SHARED_RULE = (90_112, 22)             # ... and over the one bank: the rule of a row without a bank key
 
 
 def _expected(r):
-    """from the stated formulas: a filter with a bank per channel only; a tile is OPL runs of 256 outputs of one channel, the tiling goes by
+    """from the stated formulas, the limits of the default rule by the row's bank key (with or without a bank per channel); a tile is OPL runs of 256 outputs of one channel, the tiling goes by
     n_out (the call's bound); the default rule (mode -1) as DESIGN.md 9 item 22 derives it (None: never); the grid is what the chip holds,
     at most a workgroup a tile, at least one, or a test's replacement (at most 65535).  Lane tid of the tile at k0 owns outputs
     k0 + tid + 256 j: those below the count are live."""
     refused = [0] * (7 + OPL + 1)
-    if r[MODE] == 0 or not r[BANK] or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[P] < 0 or r[NCH] < 1:
+    min_tiles, max_per_channel = (RULE_MIN_TILES, RULE_MAX_PER_CHANNEL) if r[BANK] else SHARED_RULE
+    if r[MODE] == 0 or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[P] < 0 or r[NCH] < 1:
         return refused
     tile = OPL * LANES
     tpc = -(-r[NOUT] // tile)
     total = tpc * r[NCH]
-    if r[MODE] != 1 and (RULE_MIN_TILES is None or total < RULE_MIN_TILES or tpc > RULE_MAX_PER_CHANNEL):
+    if r[MODE] != 1 and (min_tiles is None or total < min_tiles or tpc > max_per_channel):
         return refused
     grid = min(r[FIXED], 65535) if r[FIXED] > 0 else max(min(r[CHIP], total), 1)
     k0 = max([tau * tile for tau in range(tpc) if tau * tile < r[COUNT]], default=0)
@@ -338,8 +352,10 @@ def test_the_plan_of_the_multi_kernel_and_the_argument_checks(tmp_path):
         assert [w[3:5] for m, w in rule("many short channels") if m == -1] == [[22, 90_112]]          # the measured row the multi kernel won
         assert not any(w[0] for m, w in rule("long channels") + rule("few long channels") if m == -1)  # ... and the two it did not
     assert named("mode 1")[0][0] == 1
-    for name in ("mode 0", "n_out < 1", "T < 1", "polyorder < 0", "no channel", "complex taps", "shared taps"):
+    for name in ("mode 0", "n_out < 1", "T < 1", "polyorder < 0", "no channel", "complex taps"):
         assert named(name) and all(not w[0] for w in named(name)), name
+    # shared taps are no refusal: the plan of the one-bank kernel, the same tiling (the base row, whose mode is 1)
+    assert named("shared taps") == named("mode 1") and named("shared taps")[0][0] == 1 and [r[BANK] for r, n in zip(rows, why) if n == "shared taps"] == [0]
     assert all(w[0] for w in named("every type") + named("polyorder 0"))
     text = "".join("plan " + " ".join(str(v) for v in r) + "\n" for r in rows)
     text += "".join("args " + " ".join(map(str, args)) + "\n" for args, _ in ARGS_TABLE)

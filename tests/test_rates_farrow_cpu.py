@@ -2,9 +2,9 @@
 mrhip_create_farrow_rates_pnfb, csrc/kernels_rates_farrow.hip) and of mrhip_set_channel_rates: the three exported symbols and their
 declarations, the argument errors of the Python constructor and of set_channel_rates, the description of the unbound filter, the
 answers the older constructors keep, the build conditions of the kernel unit, the instantiations in the object the build made (both
-filter kernels for (Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED = 12 each; none with
-scratch memory or AccVGPRs), and the host side of the multi kernel (csrc/host_logic.cpp: plan_farrow_rates_multi,
-farrow_rates_multi_grid; csrc/rates_arb.h: farrow_rates_live_slots, which the kernel evaluates per lane) through a stand-alone program
+filter kernels for (Tx scalar, R) in {(f32,f32), (f32,f64), (f64,f64)} x real / complex samples x STRICT / FUSED = 12 each for the one
+bank and 12 each for a bank per channel; none with scratch memory or AccVGPRs), and the host side of the multi kernel
+(csrc/host_logic.cpp: plan_farrow_rates_multi, which takes either bank key, farrow_rates_multi_grid; csrc/rates_arb.h: farrow_rates_live_slots, which the kernel evaluates per lane) through a stand-alone program
 built with -fsanitize=address,undefined, against values computed here from the stated formulas."""
 import os
 import re
@@ -14,7 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_build_properties import CSRC, LLVM, _kernel_scratch
+from test_build_properties import CSRC, LLVM, _assert_rates_filter_kernel, _kernel_scratch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("mrhip_create_farrow_rates", "mrhip_create_farrow_rates_pnfb", "mrhip_set_channel_rates")
@@ -165,29 +165,30 @@ def test_rates_farrow_kernels_use_no_scratch(pkg):
     if os.path.getmtime(obj) < newest:
         pytest.skip("object older than its source")
     sizes = _kernel_scratch(obj)
-    for kernel, count in (("farrow_rates_generic_kernel", 12), ("farrow_rates_multi_kernel", 12)):
-        mine = {k: v for k, v in sizes.items() if kernel in k}
-        assert len(mine) == count, f"expected {count} instantiations of {kernel} in the object, found {len(mine)}"
-        spilling = {k: v for k, v in mine.items() if v != 0}
-        assert not spilling, f"{kernel}: instantiations with scratch or AccVGPRs: {list(spilling.items())[:6]}"
+    for kernel in ("farrow_rates_generic_kernel", "farrow_rates_multi_kernel"):  # 12 with BANK false and 12 with BANK true, none spilling
+        _assert_rates_filter_kernel(sizes, kernel)
 
 
 # ---- the host side of the multi kernel -----------------------------------------------------------------------------------------
 # a row: x_f64 r_f64 complex_x complex_h bank T polyorder n_out nch num_cus mode chip_grid grid_fixed count
 XF64, RF64, CX, CH, BANK, T, P, NOUT, NCH, CUS, MODE, CHIP, FIXED, COUNT = range(14)
+# the default rule (mode -1) by the row's bank key, (from tiles, up to tiles a channel): the measured rows the multi kernel won over the
+# one bank and over a bank per channel (item 22)
+RULE = {0: (90_112, 22), 1: (90_112, 22)}
 
 
 def _expected(r):
-    """from the stated formulas: a tile is OPL runs of 256 outputs of one channel, the tiling goes by n_out (the call's bound); the
-    default rule (mode -1) is the measured one: from 90 112 tiles, up to 22 tiles a channel; the grid is what the chip holds, at most a workgroup a tile, at least one, or a
+    """from the stated formulas, for either bank key: a tile is OPL runs of 256 outputs of one channel, the tiling goes by n_out (the
+    call's bound); the default rule (mode -1) is the measured one of the row's bank key: from 90 112 tiles, up to 22 tiles a channel; the grid is what the chip holds, at most a workgroup a tile, at least one, or a
     test's replacement (at most 65535).  Lane tid of the tile at k0 owns outputs k0 + tid + 256 j: those below the count are live."""
     refused = [0] * (7 + OPL + 1)
-    if r[MODE] == 0 or r[BANK] or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[P] < 0 or r[NCH] < 1:
+    min_tiles, max_per_channel = RULE[r[BANK]]
+    if r[MODE] == 0 or r[CH] or r[NOUT] < 1 or r[T] < 1 or r[P] < 0 or r[NCH] < 1:
         return refused
     tile = OPL * LANES
     tpc = -(-r[NOUT] // tile)
     total = tpc * r[NCH]
-    if r[MODE] != 1 and (total < 90_112 or tpc > 22):
+    if r[MODE] != 1 and (total < min_tiles or tpc > max_per_channel):
         return refused
     grid = min(r[FIXED], 65535) if r[FIXED] > 0 else max(min(r[CHIP], total), 1)
     k0 = max([tau * tile for tau in range(tpc) if tau * tile < r[COUNT]], default=0)
@@ -265,8 +266,10 @@ def test_the_plan_of_the_multi_kernel(tmp_path):
     for name in ("a channel fewer", "a tile a channel more", "few long channels"):      # the default rule from both sides of both limits
         assert all(w[0] == (m == 1) for m, w in rule(name)) and len(rule(name)) == 3, name
     assert named("mode 1")[0][0] == 1
-    for name in ("mode -1", "mode 0", "n_out < 1", "T < 1", "polyorder < 0", "no channel", "complex taps", "a bank"):
+    for name in ("mode -1", "mode 0", "n_out < 1", "T < 1", "polyorder < 0", "no channel", "complex taps"):
         assert named(name) and all(not w[0] for w in named(name)), name
+    # a bank key is no refusal: the plan of the bank-per-channel kernel, the same tiling (the base row in mode 1)
+    assert named("a bank") == named("mode 1") and named("a bank")[0][0] == 1 and [r[BANK] for r, n in zip(rows, why) if n == "a bank"] == [1]
     assert all(w[0] for w in named("every type") + named("polyorder 0"))
     text = "".join(" ".join(str(v) for v in r) + "\n" for r in rows)
     p = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)

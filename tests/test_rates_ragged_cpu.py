@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_build_properties import CSRC, LLVM, _kernel_scratch
+from test_build_properties import CSRC, LLVM, _assert_rates_filter_kernel, _kernel_scratch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "mrhip_filt_device_rates_ragged"
@@ -178,16 +178,21 @@ def test_the_touched_device_code_is_plain_hip():
     assert "stage_window(lx, xc, hc, w.o, static_cast<int>(w.span), len, a.H, tid)" in arb  # the tiled kernel stages up to the channel's end
 
 
+# (a filter kernel's count: (instantiations over shared taps, over a bank per channel) -- BANK is its last template argument)
 @pytest.mark.parametrize("unit,kernels", [
-    ("kernels_rates_arb.hip", (("arb_rates_generic_kernel", 12), ("arb_rates_tiled_kernel", 12), ("rates_schedule_kernel", 2), ("rates_ragged_schedule_kernel", 2),
-                               ("rates_reset_kernel", 1))),
-    ("kernels_rates_farrow.hip", (("farrow_rates_generic_kernel", 12), ("farrow_rates_multi_kernel", 12)))])
+    ("kernels_rates_arb.hip", (("arb_rates_generic_kernel", (12, 12)), ("arb_rates_tiled_kernel", (12, 12)), ("rates_schedule_kernel", 2),
+                               ("rates_ragged_schedule_kernel", 2), ("rates_reset_kernel", 1))),
+    ("kernels_rates_farrow.hip", (("farrow_rates_generic_kernel", (12, 12)), ("farrow_rates_multi_kernel", (12, 12))))])
 def test_the_touched_units_use_no_scratch_and_no_accvgprs(pkg, unit, kernels):
     obj = os.path.join(CSRC, "build", unit + ".o")
     assert os.path.exists(obj), "the build leaves its objects in csrc/build"
     assert os.path.exists(os.path.join(LLVM, "llvm-objdump")), "no llvm tools"
     sizes = _kernel_scratch(obj)
     for kernel, count in kernels:
+        if isinstance(count, tuple):
+            assert count[0] == count[1]
+            _assert_rates_filter_kernel(sizes, kernel, each=count[0])
+            continue
         mine = {k: v for k, v in sizes.items() if kernel in k}
         assert len(mine) == count, f"expected {count} instantiations of {kernel} in the object, found {len(mine)}"
         spilling = {k: v for k, v in mine.items() if v != 0}
