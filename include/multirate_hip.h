@@ -824,6 +824,63 @@ int mrhip_set_channel_rates_device(mrhip_filter *f, const double *rates /* DEVIC
 int mrhip_set_channel_taps_device(mrhip_filter *f, const void *h /* DEVICE, [nchannels][hLen] */, int64_t hLen, int tap_dtype, void *stream);
 int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb /* DEVICE, [nchannels][tapsPerPhi][polyorder+1] */, int64_t tapsPerPhi,
                                   int64_t polyorder, void *stream);
+/* Complex per-channel taps with per-channel rates for FIRArbitrary (mrhip_set_channel_ctaps and mrhip_set_channel_ctaps_device on a
+ * filter of mrhip_create_arbitrary_rates): one FIRFilter(h_c::Vector{Complex}, rates[c], Nphi) per channel behind one handle.  Doppler
+ * is both at once: a time scale, which is a rate per channel, and a carrier offset, which is a prototype rotated to the channel's own
+ * frequency; a tracker moves both every chunk.  Both are CALLS on an existing filter, the twins of mrhip_set_channel_taps and
+ * mrhip_set_channel_taps_device, not constructors: there are still sixteen constructors and the ABI version stays 1.
+ *   - h holds nchannels rows of hLen (re, im) pairs, row-major, row c = h_c: the layout of mrhip_create_arbitrary_bank_ctaps;
+ *   - filter kinds: f must come from mrhip_create_arbitrary_rates, with or without earlier mrhip_set_channel_taps* calls.  A filter of
+ *     mrhip_create_farrow_rates* answers MRHIP_ERR_UNSUPPORTED, "complex taps with per-channel rates for FIRFarrow are left out"; any
+ *     other filter answers MRHIP_ERR_INVALID_ARG;
+ *   - checks, in this order, each before anything changes, each message naming the function: f == NULL (MRHIP_ERR_INVALID_ARG); the
+ *     filter kind (above); h == NULL (MRHIP_ERR_INVALID_ARG); hLen other than the filter's (MRHIP_ERR_INVALID_ARG: tapsPerPhi, the
+ *     history length and the history do not change); the tap dtype, which must be the complex type of the filter's real tap precision
+ *     -- Complex64 on a filter with Float32 taps, Complex128 on one with Float64 taps: out of range is MRHIP_ERR_INVALID_ARG, a real
+ *     type MRHIP_ERR_INVALID_ARG with a message that points to mrhip_set_channel_taps, the other complex precision
+ *     MRHIP_ERR_INVALID_ARG; last, a filter in FUSED numerics is MRHIP_ERR_UNSUPPORTED: complex taps have no FUSED form, as everywhere
+ *     in the library ("Complex taps");
+ *   - effect (mrhip_set_channel_ctaps): every row goes through dh_c = [diff(h_c), 0], per component in the tap's scalar type, and the
+ *     two taps2pfb calls, exactly as mrhip_create_arbitrary_bank_ctaps builds its banks, widened exactly to R.  The filter then holds
+ *     nchannels pfb and nchannels dpfb banks of (re, im) pairs: nchannels * 2 * Nphi * tapsPerPhi * 2 * sizeof(R) bytes, allocated by
+ *     the first call of either function and reused by every later one.  The order of steps is mrhip_set_channel_taps': the checks, the
+ *     host banks and the allocation come first; then ONE wait for the filter's stream; then the upload and the swap; the shared pair or
+ *     the real banks are freed after the wait.  A refused or failed call leaves the filter bit for bit as it was;
+ *   - from the next call on the filter's tap type is the complex one and the output element type is mrhip_output_dtype(tap_dtype,
+ *     sample_dtype): a filter over REAL samples now writes COMPLEX outputs, and the caller's y must be of that type (y_capacity and
+ *     y_stride count such elements).  mrhip_set_numerics(FUSED) answers MRHIP_ERR_UNSUPPORTED as on
+ *     every complex-tap filter.  phiAccumulator, inputDeficit, the rates (installed from the host or from the device, with their
+ *     declared range), the history, the schedule buffers and mrhip_outputlength_bound are untouched.  mrhip_reset keeps the taps.  Either
+ *     function may be called again: the taps may change between calls.  mrhip_set_channel_states, mrhip_set_channel_rates and
+ *     mrhip_set_channel_rates_device work as before;
+ *   - parity: channel c continues bit for bit as mrhip_create_arbitrary_ctaps(h_c, rates[c], Nphi, nchannels = 1) fed x_c, that filter
+ *     given channel c's (inputDeficit, phiAccumulator) and its history: the outputs, the count of every call, the end state and the
+ *     history, through mrhip_filt_device_rates and mrhip_filt_device_rates_ragged, including the short-input path of filt!
+ *     (src/Filters.jl:705-709) and a channel of ragged length 0.  STRICT only.  Arithmetic: that of "Complex taps" -- both dots over one
+ *     window, oldest sample first, every multiply, add and subtract rounded separately in R, the combine per component in Float64;
+ *   - tap queries: mrhip_get_taps and mrhip_arbitrary_tapsforphase answer in the layout of "Per-channel complex taps for FIRArbitrary"
+ *     -- nchannels banks or rows of (re, im) pairs one after the other;
+ *   - going back: mrhip_set_channel_taps and mrhip_set_channel_taps_device on a filter that holds complex taps answer
+ *     MRHIP_ERR_UNSUPPORTED, "going back to real taps is left out" (no filter could be in that state before);
+ *   - mrhip_set_channel_ctaps_device: h is a DEVICE pointer of the same layout.  The same checks, then the stream rules of
+ *     mrhip_set_channel_taps_device: the call adopts `stream`, a capturing stream is MRHIP_ERR_UNSUPPORTED.  One kernel
+ *     (rates_cbank_build_kernel) builds both complex banks in stream order, bit for bit what mrhip_set_channel_ctaps uploads: bank c
+ *     holds at c*Nphi*T + phi*T + i the pair h_c[j], j = (T-1-i)*Nphi + phi, (0, 0) for j >= hLen; the dpfb bank h_c[j+1] - h_c[j], one
+ *     subtraction per component rounded in the tap's scalar type, (0, 0) for j >= hLen-1.  The first call on a filter that does not hold
+ *     complex banks yet allocates them, waits once for the filter's stream and flips the type; every later call enqueues one kernel and
+ *     returns.  Afterwards the host copy is stale and the tap queries wait for the stream and read the banks back;
+ *   - kernels: arb_rates_ctaps_generic (any shape) and arb_rates_ctaps_tiled (ONE channel's two banks of pairs in LDS, reloaded when a
+ *     workgroup's run crosses into another channel; MRHIP_ARB_RATES_CTAPS_TILED = 1 selects it wherever its plan fits, 0 never, the
+ *     default rule follows the measured rows: from 225 024 tiles, up to 879 tiles a channel);
+ *     MRHIP_FORCE_GENERIC = 1 keeps the universal one;
+ *   - a filter on which neither function was called runs the launches, kernels and messages it always ran: mrhip_set_channel_taps,
+ *     mrhip_set_channel_taps_farrow, mrhip_set_channel_taps_device and the constructors keep answering a complex tap dtype with
+ *     MRHIP_ERR_UNSUPPORTED;
+ *   - left out on purpose: FIRFarrow with complex taps and per-channel rates; one shared complex tap vector without a bank per channel
+ *     (install the same row nchannels times); going back to real taps; a FUSED form; graph capture, rings, cascades and sharding;
+ *     lengths on the device; the parallel schedule for long channels. */
+int mrhip_set_channel_ctaps(mrhip_filter *f, const void *h /* [nchannels][hLen] (re, im) */, int64_t hLen, int tap_dtype);
+int mrhip_set_channel_ctaps_device(mrhip_filter *f, const void *h /* DEVICE, same layout */, int64_t hLen, int tap_dtype, void *stream);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call
@@ -991,7 +1048,9 @@ int mrhip_timing_read(mrhip_filter *f, int64_t *n_launches, double *total_ms);
  * cases live in tests/test_gpu_rates_arb.py until they move into that table.  The same holds for farrow_rates_generic and
  * farrow_rates_multi (FIRFarrow with per-channel rates; their cases: tests/test_gpu_rates_farrow.py), and for arb_rates_bank_generic
  * and arb_rates_bank_tiled (per-channel taps with per-channel rates; their cases: tests/test_gpu_rates_bank_arb.py), and for
- * farrow_rates_bank_generic and farrow_rates_bank_multi (the same for FIRFarrow; their cases: tests/test_gpu_rates_bank_farrow.py). */
+ * farrow_rates_bank_generic and farrow_rates_bank_multi (the same for FIRFarrow; their cases: tests/test_gpu_rates_bank_farrow.py), and
+ * for arb_rates_ctaps_generic and arb_rates_ctaps_tiled (complex per-channel taps with per-channel rates; their cases:
+ * tests/test_gpu_rates_arb_ctaps.py). */
 const char *mrhip_last_kernel_name(const mrhip_filter *f);
 /* How the phase schedule of a FIRArbitrary / FIRFarrow filter -- update(), src/Filters.jl:663-673 and :780-792 -- has
  * been evaluated so far.  info[0..n) receives, as far as n reaches:

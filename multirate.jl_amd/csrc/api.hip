@@ -302,7 +302,9 @@ int refresh_host_taps(mrhip_filter *f)
         MRHIP_CHECK_HIP(hipMemcpy(pn.data(), f->d_pnfb, pn.size() * sizeof(double), hipMemcpyDeviceToHost));
         f->h_pnfb.swap(pn);
     } else {
-        const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->Nphi) * static_cast<size_t>(f->T), es = dtype_scalar_size(f->th);
+        // (complex per-channel taps, mrhip_set_channel_ctaps_device: every element is an (re, im) pair, two scalars)
+        const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->Nphi) * static_cast<size_t>(f->T) * (dtype_is_complex(f->th) ? 2 : 1),
+                     es = dtype_scalar_size(f->th);
         const bool narrow = f->r_f64 && !dtype_is_f64(f->th);
         std::vector<unsigned char> host[2];
         std::vector<double> wide(narrow ? n : 0);
@@ -1873,8 +1875,13 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
         tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
         if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
     } else if (bound > 0 && !f->force_generic) {      // (no other plan_* sees such a call)
-        tiled = plan_arb_rates_tiled(tk, a, rates_min(f), f->num_cus, &ta, &lds);
-        if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
+        if (tk.complex_h) {        // complex per-channel taps (mrhip_set_channel_ctaps): the plan and the kernels of kernels_rates_arb_ctaps.hip
+            tiled = plan_arb_rates_ctaps_tiled(tk, a, rates_min(f), f->num_cus, &ta, &lds);
+            if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_ctaps_tiled(tk, ta, lds, f->num_cus, &tiled_grid));
+        } else {
+            tiled = plan_arb_rates_tiled(tk, a, rates_min(f), f->num_cus, &ta, &lds);
+            if (tiled) MRHIP_CHECK_HIP(prepare_arb_rates_tiled(tk, fused, ta, lds, f->num_cus, &tiled_grid));
+        }
     }
     if (h_lens) {
         if (int rc = ragged_upload(f, h_lens, stream)) return rc;
@@ -1884,7 +1891,12 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
     if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
         // (tk.bank -- shared taps or a bank per channel -- picks the kernel's instantiation and its reported name inside the launch)
-        if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
+        if (tk.complex_h) {        // (FIRArbitrary only: no FIRFarrow filter holds complex taps here; no FUSED form)
+            const hipError_t e = tiled ? launch_arb_rates_ctaps_tiled(tk, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel)
+                                       : launch_arb_rates_ctaps_generic(tk, a, ra, stream, &f->last_kernel);
+            MRHIP_CHECK_HIP(e);
+        }
+        else if (farrow && tiled) MRHIP_CHECK_HIP(launch_farrow_rates_multi(tk, fused, fa, ra, ta, tiled_grid, stream, &f->last_kernel));
         else if (farrow) MRHIP_CHECK_HIP(launch_farrow_rates_generic(tk, fused, fa, ra, stream, &f->last_kernel));
         else if (tiled) MRHIP_CHECK_HIP(launch_arb_rates_tiled(tk, fused, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel));
         else MRHIP_CHECK_HIP(launch_arb_rates_generic(tk, fused, a, ra, stream, &f->last_kernel));
@@ -2031,6 +2043,8 @@ int mrhip_set_channel_rates(mrhip_filter *f, const double *rates)
 int mrhip_set_channel_taps(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
+    if (f->rates && dtype_is_complex(f->th))          // (after mrhip_set_channel_ctaps*: the filter's outputs are complex from then on)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps: the filter holds complex per-channel taps (mrhip_set_channel_ctaps); going back to real taps is left out");
     if (Refusal r = check_channel_taps(f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th)) return fail(r.status, r.message);
     std::vector<unsigned char> pfb, dpfb;
     (void)create_pfb_banks(h, hLen, tap_dtype, f->Nphi, static_cast<size_t>(f->nch), &pfb, &dpfb);
@@ -2168,6 +2182,8 @@ int mrhip_set_channel_rates_device(mrhip_filter *f, const double *rates, double 
 int mrhip_set_channel_taps_device(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype, void *stream_)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps_device: NULL filter");
+    if (f->rates && dtype_is_complex(f->th))          // (after mrhip_set_channel_ctaps*: the filter's outputs are complex from then on)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps_device: the filter holds complex per-channel taps (mrhip_set_channel_ctaps); going back to real taps is left out");
     if (Refusal r = check_channel_taps_device(f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th)) return fail(r.status, r.message);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     DeviceGuard guard(f->device);
@@ -2239,6 +2255,118 @@ int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb, int64_t t
         f->d_pnfb = d_new;
         f->d_pnfb_t = nullptr;
         f->bank = true;
+    }
+    f->taps_stale = true;
+    return MRHIP_OK;
+}
+
+// ---- Complex per-channel taps on a filter of mrhip_create_arbitrary_rates (include/multirate_hip.h, "Complex per-channel taps with
+// per-channel rates for FIRArbitrary") ------------------------------------------------------------------------------------------------
+// The filter's tap type becomes the complex one: TypeKey::complex_h and ::bank are set from here on (rates_call: the kernels of
+// kernels_rates_arb_ctaps.hip), the outputs are mrhip_output_dtype(tap_dtype, sample_dtype).  Called with the new banks installed.
+static void ctaps_flip_type(mrhip_filter *f, int tap_dtype)
+{
+    f->bank = true;
+    f->th = tap_dtype;
+    f->ty = mrhip_output_dtype(tap_dtype, f->tx);
+}
+
+// nch pfb and nch dpfb banks of (re, im) pairs in the place of the shared pair or of the real banks -- create_pfb_banks with rows = nch,
+// widened to R as upload_taps widens mrhip_create_arbitrary_bank_ctaps'.  The order of steps is mrhip_set_channel_taps': checks, host
+// banks and the first call's two allocations come before anything of the filter changes; then ONE wait for the filter's stream (the
+// kernels enqueued so far read the banks), the upload and the swap; the shared or real banks are freed after the wait.  Records, rates,
+// history and the schedule buffers stay.
+int mrhip_set_channel_ctaps(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_ctaps: NULL filter");
+    if (Refusal r = check_channel_ctaps("mrhip_set_channel_ctaps", f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th,
+                                        f->numerics == MRHIP_NUMERICS_FUSED))
+        return fail(r.status, r.message);
+    std::vector<unsigned char> pfb, dpfb;
+    (void)create_pfb_banks(h, hLen, tap_dtype, f->Nphi, static_cast<size_t>(f->nch), &pfb, &dpfb);
+    const size_t n = pfb.size() / dtype_scalar_size(tap_dtype), rsize = f->r_f64 ? 8 : 4;      // n scalars: two a tap
+    std::vector<double> wide[2];                                    // Complex64 taps under Float64 arithmetic: widened exactly
+    const void *src[2] = {pfb.data(), dpfb.data()};
+    if (f->r_f64 && !dtype_is_f64(tap_dtype))
+        for (int b = 0; b < 2; ++b) {
+            const float *s = static_cast<const float *>(src[b]);
+            wide[b].assign(s, s + n);
+            src[b] = wide[b].data();
+        }
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "mrhip_set_channel_ctaps: hipSetDevice failed");
+    const bool first = !dtype_is_complex(f->th);                    // the filter holds the shared pair or real banks: new allocations
+    void *d_new[2] = {f->d_taps, f->d_dtaps};                       // (a later call: the complex banks of the first one, reused)
+    if (first) {
+        d_new[0] = d_new[1] = nullptr;
+        if (hipMalloc(&d_new[0], n * rsize) != hipSuccess || hipMalloc(&d_new[1], n * rsize) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d_new[0]) (void)hipFree(d_new[0]);
+            return fail(MRHIP_ERR_HIP, "mrhip_set_channel_ctaps: no device memory for the channels' filter banks");
+        }
+    }
+    int rc = drain_filter(f);
+    for (int b = 0; b < 2 && !rc; ++b)                                  // (complete on return)
+        if (hipMemcpy(d_new[b], src[b], n * rsize, hipMemcpyHostToDevice) != hipSuccess) rc = fail(MRHIP_ERR_HIP, "mrhip_set_channel_ctaps: uploading the filter banks failed");
+    if (rc) {
+        if (first) { (void)hipFree(d_new[0]); (void)hipFree(d_new[1]); }
+        return rc;
+    }
+    if (first) {
+        (void)hipFree(f->d_taps_alloc);
+        (void)hipFree(f->d_dtaps_alloc);
+        f->d_taps = f->d_taps_alloc = d_new[0];
+        f->d_dtaps = f->d_dtaps_alloc = d_new[1];
+        ctaps_flip_type(f, tap_dtype);
+    }
+    f->h_taps.swap(pfb);
+    f->h_dtaps.swap(dpfb);
+    f->taps_stale = false;                                            // (the host copies are current again)
+    return MRHIP_OK;
+}
+
+// The same banks from h in DEVICE memory (rates_cbank_build_kernel), the twin of mrhip_set_channel_taps_device: the checks, then the
+// stream rules (a capturing stream is refused, the stream is adopted).  A filter that does not hold complex banks yet: the two
+// allocations first (a failure leaves the filter as it was), then ONE wait for the filter's stream -- the kernels enqueued so far read
+// the banks that are freed here --, the kernel, and the type flips; every later call enqueues its kernel and returns.
+int mrhip_set_channel_ctaps_device(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_ctaps_device: NULL filter");
+    if (Refusal r = check_channel_ctaps("mrhip_set_channel_ctaps_device", f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th,
+                                        f->numerics == MRHIP_NUMERICS_FUSED))
+        return fail(r.status, r.message);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "mrhip_set_channel_ctaps_device: hipSetDevice failed");
+    if (int rc = device_update_stream(f, "mrhip_set_channel_ctaps_device", stream)) return rc;
+    const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->Nphi) * static_cast<size_t>(f->T) * 2, rsize = f->r_f64 ? 8 : 4;
+    const bool first = !dtype_is_complex(f->th);
+    void *d_new[2] = {f->d_taps, f->d_dtaps};                       // (a later call: the complex banks of the first one, reused)
+    if (first) {
+        d_new[0] = d_new[1] = nullptr;
+        if (hipMalloc(&d_new[0], n * rsize) != hipSuccess || hipMalloc(&d_new[1], n * rsize) != hipSuccess) {
+            (void)hipGetLastError();
+            if (d_new[0]) (void)hipFree(d_new[0]);
+            return fail(MRHIP_ERR_HIP, "mrhip_set_channel_ctaps_device: no device memory for the channels' filter banks");
+        }
+    }
+    auto bail = [&](int rc) { if (first) { (void)hipFree(d_new[0]); (void)hipFree(d_new[1]); } return rc; };
+    if (first)
+        if (int rc = drain_filter(f)) return bail(rc);
+    if (int rc = adopt_stream(f, stream)) return bail(rc);
+    BankBuildArgs b{};
+    b.h = h; b.pfb = d_new[0]; b.dpfb = d_new[1];
+    b.hLen = f->hLen; b.T = f->T; b.Nphi = f->Nphi; b.nch = static_cast<int>(f->nch);
+    if (launch_rates_cbank_build(dtype_is_f64(tap_dtype), f->r_f64, b, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail(MRHIP_ERR_HIP, "mrhip_set_channel_ctaps_device: the bank build kernel could not be launched"));
+    }
+    if (first) {
+        (void)hipFree(f->d_taps_alloc);
+        (void)hipFree(f->d_dtaps_alloc);
+        f->d_taps = f->d_taps_alloc = d_new[0];
+        f->d_dtaps = f->d_dtaps_alloc = d_new[1];
+        ctaps_flip_type(f, tap_dtype);
     }
     f->taps_stale = true;
     return MRHIP_OK;

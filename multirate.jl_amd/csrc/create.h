@@ -78,6 +78,10 @@ Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, Cre
 Refusal check_channel_rates(const double *rates, int64_t nch, double *rate_max);
 // the checks of mrhip_set_channel_taps that need no device: the filter's kind, h, hLen and the tap type against the filter's own
 Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th);
+// the checks of mrhip_set_channel_ctaps and mrhip_set_channel_ctaps_device (`who`: the function's name) that need no device, in their
+// order: the filter's kind, h, hLen, the tap type against the complex type of the filter's tap precision (f_th: real, or complex after
+// an earlier call), and the filter's numerics (fused: complex taps have no FUSED form)
+Refusal check_channel_ctaps(const char *who, bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th, bool fused);
 // the same for mrhip_set_channel_taps_farrow (pnfb_call false: src = h, len = hLen against the filter's hLen, th against its tap type)
 // and mrhip_set_channel_pnfb (pnfb_call true: src = pnfb, len = tapsPerPhi and polyorder against the filter's; th is not looked at)
 Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder, int th,

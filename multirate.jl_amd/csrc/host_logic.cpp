@@ -360,6 +360,41 @@ bool plan_arb_rates_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, 
     return true;
 }
 
+// arb_rates_ctaps_tiled_kernel (per-channel RATES with COMPLEX per-channel taps, kernels_rates_arb_ctaps.hip): both banks of ONE channel
+// as (re, im) pairs of R (column pitch T + 1 pairs) plus the sample tile fit LDS at two workgroups a CU (78 KiB a workgroup, as for
+// plan_arb_rates_tiled and plan_arb_bank_ctaps_tiled); one channel a lane (cpl = 1).  n_out is the call's bound, the tiling goes by it;
+// the span is planned for the SLOWEST channel (rate_min) and cut to the room only when the kernel is forced -- everything as
+// plan_arb_rates_tiled states it, with a pair where that has a tap.
+//
+// The default rule (mode -1), written the way kArbRatesTiledRule is, takes the calls the measured rows cover, from .min_tiles tiles, up
+// to .max_per_channel tiles a channel, and never with a cut span; every other call stays on the universal kernel unless
+// MRHIP_ARB_RATES_CTAPS_TILED=1 forces the tiled one.  The rows (profiles/r15/arb_rates_ctaps.txt, Complex64 taps,
+// both runs): the tiled kernel beat the universal one by more than the spread of the repeats at 4096 ch x 1e4 Float32 (360 448 tiles
+// of 88 a channel: 2.866 against 3.424 ms and 2.918 against 3.443, spreads <= 0.304), at the same shape with ComplexF32 samples (2.712
+// against 3.689 ms and 2.731 against 3.671, spreads <= 0.026) and at 256 ch x 1e5 (225 024 tiles of 879 a channel: 18.353 against
+// 23.052 ms and 18.336 against 23.001, spreads <= 0.110 but for one repeat of the universal kernel at 24.128), and did not at 64 ch x
+// 1e6 (8790 tiles a channel: 498.5 against 515.3 ms and 481.5 against 484.3 with spreads of 23 to 45 -- the serial walk is the call).
+// As for the real-tap kernels, whose limits came out the same, both are GUARDS ON UNMEASURED GROUND, not causes: the kernel trace of
+// the same file has the tiled kernel ALONE at 2.76 ms against the universal one's 14.07 in the longest row (and 1.06 against 5.75 at
+// 256 ch x 1e5), beside a walk of 519 ms (17.3 ms) -- nothing about 880 tiles a channel makes it worse, the rows only cannot show it.
+constexpr RatesTiledRule kArbRatesCtapsTiledRule = {225024, 879};
+bool plan_arb_rates_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int /*num_cus*/, int mode, ArbTileArgs *out, size_t *lds)
+{
+    if (mode == 0 || !tk.bank || !tk.complex_h || a.n_out < 1 || a.T < 1 || a.Nphi < 1 || !(rate_min > 0.0)) return false;
+    const int TP = a.T + 1;
+    const size_t bank_pairs = static_cast<size_t>(a.Nphi) * TP;
+    const size_t banks_bytes = (2 * bank_pairs * variant_tap_bytes(tk) + 15) / 16 * 16;
+    const ArbVariantShape v{banks_bytes, 78 * 1024, 78 * 1024, TP, static_cast<int>(bank_pairs), 1, false};
+    ArbTileArgs ta;
+    size_t bytes;
+    if (!plan_variant_arb_tiled(v, a.T, a.n_out, a.nch, variant_sample_bytes(tk), rate_min, mode == 1, &ta, &bytes)) return false;
+    const RatesTiledRule rule = kArbRatesCtapsTiledRule;
+    if (mode != 1 && (rule.min_tiles < 0 || ta.total_tiles < rule.min_tiles || ta.tiles_per_channel > rule.max_per_channel)) return false;
+    *out = ta;
+    *lds = bytes;
+    return true;
+}
+
 // farrow_rates_multi_kernel (FIRFarrow with per-channel RATES, kernels_rates_farrow.hip; either bank key): no LDS -- the polynomial bank
 // (the one, or with tk.bank the tile's channel's) is read as scalar operands, the windows from global memory -- so the plan is the
 // tiling alone: a tile is kFarrowRatesOPL consecutive runs of kVariantThreads outputs of ONE channel, so one polynomial bank, one channel
@@ -744,6 +779,30 @@ Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t
     if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: bad tap dtype"};
     if (dtype_is_complex(th)) return {MRHIP_ERR_UNSUPPORTED, std::string("mrhip_set_channel_taps: ") + kRatesHint + " (the taps are Float32 / Float64)"};
     if (th != f_th) return {MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps: the taps must have the filter's tap dtype"};
+    return {};
+}
+
+// mrhip_set_channel_ctaps and mrhip_set_channel_ctaps_device (`who`; the public header, "Complex per-channel taps with per-channel rates
+// for FIRArbitrary"): what the two calls refuse before they touch the device, in their order and each naming the function -- the filter
+// (a FIRFarrow one with per-channel rates is status 5: left out), then h, hLen against the filter's, the tap type (out of range, real,
+// the other complex precision: f_th is the filter's tap type, real or already complex -- its precision counts), and last the filter's
+// numerics: complex taps have no FUSED form
+Refusal check_channel_ctaps(const char *who_, bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th, bool fused)
+{
+    const std::string who = who_;
+    if (is_rates && is_farrow) return {MRHIP_ERR_UNSUPPORTED, who + ": complex taps with per-channel rates for FIRFarrow are left out"};
+    if (!is_rates) return {MRHIP_ERR_INVALID_ARG, who + " takes a filter of mrhip_create_arbitrary_rates"};
+    if (!h) return {MRHIP_ERR_INVALID_ARG, who + ": h is NULL"};
+    if (hLen != f_hLen)
+        return {MRHIP_ERR_INVALID_ARG, who + ": hLen must be the filter's (" + std::to_string(f_hLen) + " taps a channel; got " + std::to_string(hLen) +
+                                       "): tapsPerPhi, the history length and the history do not change"};
+    if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, who + ": bad tap dtype"};
+    if (!dtype_is_complex(th))
+        return {MRHIP_ERR_INVALID_ARG, who + ": the taps must be Complex64 or Complex128 (real taps go through mrhip_set_channel_taps" +
+                                       (who.ends_with("_device") ? "_device)" : ")")};
+    if (dtype_is_f64(th) != dtype_is_f64(f_th))
+        return {MRHIP_ERR_INVALID_ARG, who + ": the taps must be the complex type of the filter's tap precision (Complex64 on Float32 taps, Complex128 on Float64 taps)"};
+    if (fused) return {MRHIP_ERR_UNSUPPORTED, who + ": the filter is in FUSED numerics and no FUSED form is defined for complex taps (the public header: complex taps)"};
     return {};
 }
 

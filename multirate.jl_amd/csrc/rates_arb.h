@@ -154,4 +154,41 @@ hipError_t launch_rates_bank_build(bool tap_f64, bool r_f64, const BankBuildArgs
 // ... and n Float64 coefficients into the filter's polynomial banks, rounded to Float32 and widened back for Float32 taps
 hipError_t launch_rates_pnfb_install(bool tap_f32, const double *src, double *dst, long long n, hipStream_t st);
 
+// ---- COMPLEX per-channel taps on the FIRArbitrary filter with per-channel rates (mrhip_set_channel_ctaps, mrhip_set_channel_ctaps_device;
+// include/multirate_hip.h, "Complex per-channel taps with per-channel rates for FIRArbitrary") -------------------------------------------
+// The filter holds nch pfb and nch dpfb banks of (re, im) pairs of R, [nch][Nphi][T], and TypeKey::complex_h and ::bank are both set.
+// Records, slices, schedule kernel and RatesArgs serve it unchanged; the two filter kernels and the bank build kernel live in
+// kernels_rates_arb_ctaps.hip (kernels_rates_arb.hip refuses a complex_h key), their plan in host_logic.cpp.  Reported names:
+// arb_rates_ctaps_generic / arb_rates_ctaps_tiled; switches: MRHIP_ARB_RATES_CTAPS_TILED (-1 rule, 0, 1), MRHIP_ARB_RATES_CTAPS_GRID.
+//
+// The banks of one channel from its row of hLen (re, im) pairs, h[2j] and h[2j + 1]: the index map is rates_bank_tap_index, the values
+// are those of the real banks component by component -- create_pfb_banks moves a pair as one element, arbitrary_dh subtracts the
+// components each on their own, ONE subtraction rounded in the tap's scalar type.  The build kernel and tests/arb_rates_ctaps_check.cpp
+// run this text.
+template <typename TAP> struct RatesTapPair { TAP re, im; };
+template <typename TAP>
+MRHIP_RATES_HD inline RatesTapPair<TAP> rates_cbank_pfb_value(const TAP *h, long long hLen, long long j)
+{
+    return j < hLen ? RatesTapPair<TAP>{h[2 * j], h[2 * j + 1]} : RatesTapPair<TAP>{TAP(0), TAP(0)};
+}
+template <typename TAP>
+MRHIP_RATES_HD inline RatesTapPair<TAP> rates_cbank_dpfb_value(const TAP *h, long long hLen, long long j)
+{
+    return j + 1 < hLen ? RatesTapPair<TAP>{TAP(h[2 * j + 2] - h[2 * j]), TAP(h[2 * j + 3] - h[2 * j + 1])} : RatesTapPair<TAP>{TAP(0), TAP(0)};
+}
+
+// kernels_rates_arb_ctaps.hip.  The key must have complex_h and bank set; fused is not an argument: complex taps have no FUSED form.
+hipError_t launch_arb_rates_ctaps_generic(const TypeKey &tk, const ArbArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
+bool plan_arb_rates_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, ArbTileArgs *out, size_t *lds);   // (reads MRHIP_ARB_RATES_CTAPS_TILED)
+// the tiled kernel's persistent grid (occupancy query, LDS attribute; MRHIP_ARB_RATES_CTAPS_GRID): everything about its launch that can
+// fail ahead of the launch
+hipError_t prepare_arb_rates_ctaps_tiled(const TypeKey &tk, const ArbTileArgs &ta, size_t lds, int num_cus, long long *grid);
+hipError_t launch_arb_rates_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, const RatesArgs &r, const ArbTileArgs &ta, size_t lds, long long grid,
+                                        hipStream_t s, const char **kname);
+// BankBuildArgs over pairs: h is [nch][hLen] (re, im) pairs in the tap's scalar type, pfb / dpfb [nch][Nphi*T] pairs of R; the row is
+// staged in LDS when its hLen pairs fit kBankBuildLdsBytes
+hipError_t launch_rates_cbank_build(bool tap_f64, bool r_f64, const BankBuildArgs &b, hipStream_t st);
+// host_logic.cpp: the switch value passed in (0 never, 1 wherever the plan fits, -1 the default rule)
+bool plan_arb_rates_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, int mode, ArbTileArgs *out, size_t *lds);
+
 }  // namespace mrhip

@@ -120,6 +120,8 @@ ABI = [
     ("mrhip_set_channel_rates_device", _i, [_vp, _vp, _d, _d, _vp]),
     ("mrhip_set_channel_taps_device", _i, [_vp, _vp, _i64, _i, _vp]),
     ("mrhip_set_channel_pnfb_device", _i, [_vp, _vp, _i64, _i64, _vp]),
+    ("mrhip_set_channel_ctaps", _i, [_vp, _vp, _i64, _i]),
+    ("mrhip_set_channel_ctaps_device", _i, [_vp, _vp, _i64, _i, _vp]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -346,6 +348,7 @@ class FIRFilter:
         self._pnfb_in = None
         self._rates = None                # per-channel rates (FIRFilter.per_channel_rates, .per_channel_rates_farrow): Float64, one per channel; self.rate is the largest
         self._chan_taps = None            # per-channel taps ON TOP of per-channel rates (FIRFilter.set_channel_taps, .per_channel_taps_and_rates): the (nchannels, hLen) matrix, installed by mrhip_set_channel_taps
+        self._chan_ctaps = None           # COMPLEX per-channel taps on top of per-channel rates (FIRFilter.set_channel_ctaps, .set_channel_ctaps_device, .per_channel_complex_taps_and_rates): the (nchannels, hLen) complex matrix, installed by mrhip_set_channel_ctaps; self.h stays the real placeholder the filter is created over
         self._chan_farrow = None          # the same for FIRFarrow (FIRFilter.set_channel_taps_farrow, .set_channel_pnfb, .per_channel_taps_and_rates_farrow): ("taps", the (nchannels, hLen) matrix) or ("pnfb", the (nchannels, tapsPer𝜙, polyorder+1) banks), whichever call came last
         self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow, .per_channel_complex_taps_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
@@ -484,6 +487,23 @@ class FIRFilter:
         f.set_channel_taps(H)
         return f
 
+    @classmethod
+    def per_channel_complex_taps_and_rates(cls, H, rates, Nphi: int = 32, *, device: int = 0):
+        """One FIRFilter(H[c]::Vector{Complex}, rates[c]::Float, N𝜙) per channel behind one filter object: FIRArbitrary with COMPLEX
+        per-channel taps and per-channel rates (per-emitter Doppler correction: a time scale and a carrier offset per channel).
+        ``H``: shape (nchannels, hLen), complex64 or complex128; ``rates``: one rate > 0 per channel.  It is the two steps in one:
+        the filter of ``per_channel_rates`` over placeholder taps ``real(H[0])`` of the same length and precision, followed by
+        ``set_channel_ctaps(H)``.  Channel c is bit for bit ``FIRFilter.complex_taps_arbitrary(H[c], rates[c], Nphi)`` fed ``x[c]``
+        (include/multirate_hip.h: complex per-channel taps with per-channel rates for FIRArbitrary).  STRICT only."""
+        who = "per_channel_complex_taps_and_rates"
+        H = np.asarray(H)
+        if H.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+            raise MultirateHIPError(1, f"{who} takes complex64 or complex128 taps; real taps: FIRFilter.per_channel_taps_and_rates")
+        H = _tap_matrix(H, who)
+        f = cls.per_channel_rates(np.ascontiguousarray(H[0].real), rates, Nphi, device=device)
+        f.set_channel_ctaps(H)
+        return f
+
     @staticmethod
     def _checked_rates(rates, who):
         """one finite rate > 0 per channel, at least one, as a Float64 vector (the checks the library repeats)"""
@@ -606,7 +626,8 @@ class FIRFilter:
             return
         if tx not in _NP2DT:
             raise MultirateHIPError(1, f"unsupported sample dtype {tx}")
-        for mirror, call in ((self._rates, "set_channel_rates_device"), (self._chan_taps, "set_channel_taps_device"), (self._chan_farrow, "set_channel_pnfb_device")):
+        for mirror, call in ((self._rates, "set_channel_rates_device"), (self._chan_taps, "set_channel_taps_device"), (self._chan_farrow, "set_channel_pnfb_device"),
+                             (self._chan_ctaps, "set_channel_ctaps_device")):
             if isinstance(mirror, _DeviceResident):
                 raise MultirateHIPError(1, f"the filter was closed after {call}: its values lived on the device and are gone; install new ones "
                                            f"through the host call before binding again")
@@ -638,6 +659,8 @@ class FIRFilter:
             _check(self._lib.mrhip_set_channel_taps(self._handle, _ptr(self._chan_taps), self._chan_taps.shape[1], _NP2DT[self._chan_taps.dtype]))
         if self._chan_farrow is not None:                            # (set_channel_taps_farrow / set_channel_pnfb on the unbound filter)
             self._install_chan_farrow(*self._chan_farrow)
+        if self._chan_ctaps is not None:                             # (set_channel_ctaps on the unbound filter; after the real taps, if both were set)
+            _check(self._lib.mrhip_set_channel_ctaps(self._handle, _ptr(self._chan_ctaps), self._chan_ctaps.shape[1], _NP2DT[self._chan_ctaps.dtype]))
 
     def _install_chan_farrow(self, what, M):
         if what == "taps":
@@ -665,7 +688,15 @@ class FIRFilter:
     def output_dtype(self):
         if self._tx is None:
             return None
-        return _DT2NP[self._lib.mrhip_output_dtype(_NP2DT[self.h.dtype], _NP2DT[self._tx])]
+        return _DT2NP[self._lib.mrhip_output_dtype(_NP2DT[self._tap_dtype], _NP2DT[self._tx])]
+
+    @property
+    def _tap_dtype(self):
+        """the filter's tap type: that of ``h``, or the complex type of its precision once complex per-channel taps are installed
+        (``set_channel_ctaps`` and its siblings on a filter of ``per_channel_rates``)"""
+        if self._chan_ctaps is None:
+            return self.h.dtype
+        return np.dtype(np.complex128 if self.h.dtype == np.float64 else np.complex64)
 
     @property
     def state(self) -> _State:
@@ -712,8 +743,8 @@ class FIRFilter:
         shape (nchannels, tapsPer𝜙, N𝜙)."""
         if self._handle is None:
             raise MultirateHIPError(1, "taps() needs a bound filter")
-        if self._bank is not None or self._chan_taps is not None:
-            out = np.zeros((self._nch, self.Nphi, self.tapsPerPhi), dtype=self.h.dtype)
+        if self._bank is not None or self._chan_taps is not None or self._chan_ctaps is not None:
+            out = np.zeros((self._nch, self.Nphi, self.tapsPerPhi), dtype=self._tap_dtype)
             _check(self._lib.mrhip_get_taps(self._handle, which, _ptr(out)))
             return out.transpose(0, 2, 1).copy()
         out = np.zeros(self.tapsPerPhi * self.Nphi, dtype=self.h.dtype)
@@ -735,9 +766,9 @@ class FIRFilter:
         tapsforphase(kernel::FIRFarrow, phase), src/Filters.jl:764-775."""
         if self._handle is None or self.kind not in (ARBITRARY, FARROW):
             raise MultirateHIPError(1, "tapsforphase() needs a bound FIRArbitrary or FIRFarrow filter")
-        banks = self._bank is not None or (self._chan_taps is not None and self.kind == ARBITRARY) or (self._chan_farrow is not None and self.kind == FARROW)
+        banks = self._bank is not None or ((self._chan_taps is not None or self._chan_ctaps is not None) and self.kind == ARBITRARY) or (self._chan_farrow is not None and self.kind == FARROW)
         rows = (self._nch, self.tapsPerPhi) if banks else self.tapsPerPhi   # (a per-channel filter: one row per channel)
-        out = np.zeros(rows, dtype=self.h.dtype)
+        out = np.zeros(rows, dtype=self._tap_dtype)
         fn = self._lib.mrhip_farrow_tapsforphase if self.kind == FARROW else self._lib.mrhip_arbitrary_tapsforphase
         _check(fn(self._handle, float(phase), _ptr(out)))
         return out
@@ -986,6 +1017,8 @@ class FIRFilter:
         if self.kind != ARBITRARY:
             raise MultirateHIPError(5, "set_channel_taps: FIRFarrow with per-channel taps and per-channel rates is not this call's (set_channel_taps_farrow or set_channel_pnfb; FIRFilter.per_channel_rates takes this call)")
         H = _tap_matrix(_real_taps(H, "set_channel_taps", "complex taps with per-channel rates are left out"), "set_channel_taps")
+        if self._chan_ctaps is not None:
+            raise MultirateHIPError(5, "set_channel_taps: the filter holds complex per-channel taps (set_channel_ctaps); going back to real taps is left out")
         if H.shape != (len(self._rates), len(self.h)):
             raise MultirateHIPError(1, f"set_channel_taps takes a {(len(self._rates), len(self.h))} matrix, one row of the filter's hLen taps per channel; got {H.shape}")
         if H.dtype != self.h.dtype:
@@ -1079,9 +1112,60 @@ class FIRFilter:
             raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates")
         if self.kind != ARBITRARY:
             raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates_farrow takes set_channel_pnfb_device (the fit on the device is left out)")
+        if self._chan_ctaps is not None:
+            raise MultirateHIPError(5, f"{who}: the filter holds complex per-channel taps (set_channel_ctaps); going back to real taps is left out")
         stream = self._device_update_args(who, H, self.h.dtype, (len(self._rates), len(self.h)))
         _check(self._lib.mrhip_set_channel_taps_device(self._handle, C.c_void_p(H.data_ptr()), len(self.h), _NP2DT[self.h.dtype], C.c_void_p(stream)))
         self._chan_taps = _DeviceResident((self._nch, len(self.h)))
+
+    def _takes_ctaps(self, who):
+        """the filter checks of the complex per-channel tap calls, in the library's order: the filter kind, then (by the callers) the
+        matrix, then the numerics"""
+        if self._rates is not None and self.kind == FARROW:
+            raise MultirateHIPError(5, f"{who}: complex taps with per-channel rates for FIRFarrow are left out")
+        if self._rates is None or self.kind != ARBITRARY:
+            raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates")
+        return np.dtype(np.complex128 if self.h.dtype == np.float64 else np.complex64)
+
+    def set_channel_ctaps(self, H):
+        """COMPLEX per-channel taps on a filter of ``per_channel_rates``, with or without earlier ``set_channel_taps``
+        (``mrhip_set_channel_ctaps``; waits for the filter's stream): ``H`` has shape (nchannels, hLen) in the complex type of the
+        filter's tap precision (complex64 on float32 taps, complex128 on float64 taps), row c replaces the taps of channel c -- a
+        prototype rotated to the channel's own centre frequency beside the channel's own rate (Doppler: a time scale and a carrier
+        offset).  phiAccumulator, inputDeficit, rates and history stay; channel c continues bit for bit as
+        ``FIRFilter.complex_taps_arbitrary(H[c], rates[c], Nphi)`` given its state and history would (STRICT only: a FUSED filter is
+        status 5).  From then on ``output_dtype`` is complex also over real samples, ``taps(which)`` has shape (nchannels, tapsPer𝜙, N𝜙)
+        and ``tapsforphase`` (nchannels, tapsPer𝜙), both complex; the taps may change between calls; ``reset()`` keeps them; going back
+        to real taps is status 5.  Unbound: the taps are installed at ``bind``."""
+        who = "set_channel_ctaps"
+        ct = self._takes_ctaps(who)
+        H = _tap_matrix(np.asarray(H), who)
+        if H.shape != (len(self._rates), len(self.h)):
+            raise MultirateHIPError(1, f"{who} takes a {(len(self._rates), len(self.h))} matrix, one row of the filter's hLen taps per channel; got {H.shape}")
+        if H.dtype.kind != "c":
+            raise MultirateHIPError(1, f"{who} takes complex taps; real taps: set_channel_taps")
+        if H.dtype != ct:
+            raise MultirateHIPError(1, f"{who} takes taps of the complex type of the filter's tap precision, {ct}; got {H.dtype}")
+        if self.numerics != NUMERICS_STRICT:
+            raise MultirateHIPError(5, f"{who}: the filter is in FUSED numerics and no FUSED form is defined for complex taps")
+        H = np.ascontiguousarray(H).copy()
+        if self._handle is not None:
+            _check(self._lib.mrhip_set_channel_ctaps(self._handle, _ptr(H), H.shape[1], _NP2DT[H.dtype]))
+        self._chan_ctaps = H
+
+    def set_channel_ctaps_device(self, H):
+        """Complex per-channel taps from DEVICE memory on a filter of ``per_channel_rates`` (``mrhip_set_channel_ctaps_device``),
+        enqueued on torch's current stream: ``H`` is a contiguous (nchannels, hLen) CUDA tensor in the complex type of the filter's tap
+        precision.  Both banks are built on the device, bit for bit those of ``set_channel_ctaps``.  The first call on a filter that
+        holds no complex banks yet allocates them and waits once; every later call only enqueues a kernel.  ``taps()`` and
+        ``tapsforphase`` read the banks back."""
+        who = "set_channel_ctaps_device"
+        ct = self._takes_ctaps(who)
+        stream = self._device_update_args(who, H, ct, (len(self._rates), len(self.h)))
+        if self.numerics != NUMERICS_STRICT:
+            raise MultirateHIPError(5, f"{who}: the filter is in FUSED numerics and no FUSED form is defined for complex taps")
+        _check(self._lib.mrhip_set_channel_ctaps_device(self._handle, C.c_void_p(H.data_ptr()), len(self.h), _NP2DT[ct], C.c_void_p(stream)))
+        self._chan_ctaps = _DeviceResident((self._nch, len(self.h)))
 
     def set_channel_pnfb_device(self, PN):
         """Per-channel polynomial banks from DEVICE memory on a filter of ``per_channel_rates_farrow``

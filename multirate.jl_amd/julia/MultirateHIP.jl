@@ -16,7 +16,7 @@ export FIRFilter, FIRKernel, FIRStandard, FIRDecimator, FIRInterpolator, FIRRati
        filt, filt!, taps2pfb, outputlength, inputlength, reset, nextphase, setphase, tapsforphase, tapsforphase!, polyfit,
        firdes, firprototype, kaiserlength, kaiser, FIRResponse, LOWPASS, BANDPASS, HIGHPASS, BANDSTOP,
        FilterCascade, filt_device!, filt_device_chunked!, scheduleinfo, advancestate!, ChunkRing, pushchunks!, drain, ringinfo, ShardedFIRFilter,
-       RatesFIRFilter, channelstates, setchannelstates!, setrates!
+       RatesFIRFilter, channelstates, setchannelstates!, setrates!, set_channel_ctaps!, set_channel_ctaps_device!
 
 const libmr = get(ENV, "MRHIP_LIB_PATH", joinpath(@__DIR__, "..", "libmultirate_hip.so"))
 
@@ -545,11 +545,13 @@ mutable struct RatesFIRFilter{Th}
     device::Int
     handle::Ptr{Cvoid}
     Tx::Union{DataType,Nothing}
+    CH::Union{Nothing,Matrix{Complex{Th}}}  # COMPLEX per-channel taps (set_channel_ctaps!, FIRArbitrary): one column of hLen taps per channel, installed at bind! behind H
+    ctaps::Bool                     # the filter holds complex taps (set_channel_ctaps!, set_channel_ctaps_device!): the outputs are complex also over real samples
 end
 function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
-    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing)
+    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing, nothing, false)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 # FIRFilter(h, rates::Vector, N𝜙, polyorder): one FIRFilter(h, rates[c], N𝜙, polyorder) -- FIRFarrow -- per channel behind one object
@@ -558,7 +560,7 @@ function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer,
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
     0 <= polyorder <= min(32, Nphi - 1) || error("polyorder must be in 0..min(32, Nphi-1)")
-    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing)
+    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing, nothing, false)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
@@ -579,8 +581,11 @@ function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
     f.handle, f.Tx = out[], Tx
     f.H === nothing || (f.polyorder >= 0 ? set_channel_taps_farrow!(f, f.H) : set_channel_taps!(f, f.H))
     f.PN === nothing || set_channel_pnfb!(f, f.PN)
+    f.CH === nothing || set_channel_ctaps!(f, f.CH)
     f
 end
+# the element type of the outputs: promote_out(Th, Tx), or its complex type once the filter holds complex taps
+outtype(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx} = f.ctaps ? promote_out(Complex{Th}, Tx) : promote_out(Th, Tx)
 # per-channel taps on top of the per-channel rates (mrhip_set_channel_taps; include/multirate_hip.h, "Per-channel taps with per-channel
 # rates for FIRArbitrary"): column c of H is channel c's h_c, size(H) == (length(f.h), nchannels).  Every channel keeps its phase, deficit,
 # rate and history; the taps may change between calls (the call waits for the filter's stream); reset keeps the current taps.  An unbound
@@ -630,6 +635,24 @@ end
 function set_channel_taps_device!(f::RatesFIRFilter{Th}, h::Ptr{Th}, stream::Ptr{Cvoid} = C_NULL) where {Th}
     f.handle == C_NULL && error("set_channel_taps_device! needs a bound filter")
     check(ccall((:mrhip_set_channel_taps_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}), f.handle, h, length(f.h), dtypecode(Th), stream))
+    f
+end
+# COMPLEX per-channel taps on top of the per-channel rates (mrhip_set_channel_ctaps, mrhip_set_channel_ctaps_device; include/multirate_hip.h,
+# "Complex per-channel taps with per-channel rates for FIRArbitrary"): column c of H is channel c's h_c::Vector{Complex{Th}},
+# size(H) == (length(f.h), nchannels).  Every channel keeps its phase, deficit, rate and history; from the next call on the outputs are
+# complex, also over real samples; the taps may change between calls; reset keeps them; going back to real taps is refused.  An unbound
+# filter installs them at bind!.  The device call takes a device pointer of the same layout and needs a bound filter.  FIRArbitrary only.
+function set_channel_ctaps!(f::RatesFIRFilter{Th}, H::Matrix{Complex{Th}}) where {Th}
+    f.polyorder < 0 || error("complex taps with per-channel rates for FIRFarrow are left out")
+    size(H) == (length(f.h), length(f.rates)) || error("H takes one column of $(length(f.h)) taps per channel")
+    f.handle == C_NULL || check(ccall((:mrhip_set_channel_ctaps, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint), f.handle, H, size(H, 1), dtypecode(Complex{Th})))
+    f.CH, f.ctaps = copy(H), true
+    f
+end
+function set_channel_ctaps_device!(f::RatesFIRFilter{Th}, h::Ptr{Complex{Th}}, stream::Ptr{Cvoid} = C_NULL) where {Th}
+    f.handle == C_NULL && error("set_channel_ctaps_device! needs a bound filter")
+    check(ccall((:mrhip_set_channel_ctaps_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}), f.handle, h, length(f.h), dtypecode(Complex{Th}), stream))
+    f.ctaps = true
     f
 end
 function set_channel_pnfb_device!(f::RatesFIRFilter, pnfb::Ptr{Float64}, stream::Ptr{Cvoid} = C_NULL)
@@ -693,7 +716,7 @@ const libhip = "libamdhip64"
 function rates_filt_host!(y::Matrix{Tb}, f::RatesFIRFilter{Th}, x::Matrix{Tx}, lengths::Union{Nothing,Vector{Int64}}) where {Tb,Th,Tx}
     size(x, 2) == length(f.rates) || error("a filter of $(length(f.rates)) rates takes that many channels")
     bind!(f, Tx)
-    Tb === promote_out(Th, Tx) || error("the outputs are $(promote_out(Th, Tx))")
+    Tb === outtype(f, Tx) || error("the outputs are $(outtype(f, Tx))")
     n, nch = size(x)
     cap = size(y, 1)
     size(y, 2) == nch || error("one column of y per channel")
@@ -722,7 +745,7 @@ function rates_filt_host!(y::Matrix{Tb}, f::RatesFIRFilter{Th}, x::Matrix{Tx}, l
 end
 function filt(f::RatesFIRFilter{Th}, x::Matrix{Tx}) where {Th,Tx}
     bind!(f, Tx)
-    y = Matrix{promote_out(Th, Tx)}(undef, outputlengthbound(f, size(x, 1)), size(x, 2))
+    y = Matrix{outtype(f, Tx)}(undef, outputlengthbound(f, size(x, 1)), size(x, 2))
     counts = rates_filt_host!(y, f, x, nothing)
     [y[1:counts[c], c] for c in 1:size(x, 2)]
 end
@@ -735,7 +758,7 @@ function filt!(Y::Matrix, f::RatesFIRFilter, X::Matrix, lengths::Vector{<:Intege
 end
 function filt(f::RatesFIRFilter{Th}, X::Matrix{Tx}, lengths::Vector{<:Integer}) where {Th,Tx}
     bind!(f, Tx)
-    Y = Matrix{promote_out(Th, Tx)}(undef, outputlengthbound(f, maximum(lengths; init = 0)), size(X, 2))
+    Y = Matrix{outtype(f, Tx)}(undef, outputlengthbound(f, maximum(lengths; init = 0)), size(X, 2))
     counts = filt!(Y, f, X, lengths)
     [Y[1:counts[c], c] for c in 1:size(X, 2)]
 end
