@@ -294,7 +294,9 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     samples (both filters with per-channel rates; the contract stands at its declaration);
  *   - per-channel taps on top of the per-channel rates: mrhip_set_channel_taps ("Per-channel taps with per-channel rates for
  *     FIRArbitrary", below);
- *   - left out on purpose: complex taps combined with per-channel rates; evaluating
+ *   - complex taps on top of the per-channel rates: mrhip_set_channel_ctaps and mrhip_set_channel_ctaps_device ("Complex per-channel
+ *     taps with per-channel rates for FIRArbitrary", below);
+ *   - left out on purpose: evaluating
  *     a long channel's schedule with the parallel tables / chain / emit machinery instead of the serial walk (the next speed step
  *     for few long channels); graph capture, rings, cascades and sharding of such a filter; a mrhip_filt_device_multi that serves
  *     FIRArbitrary streams in one launch. */
@@ -328,7 +330,9 @@ typedef enum { MRHIP_NUMERICS_STRICT = 0, MRHIP_NUMERICS_FUSED = 1 } mrhip_numer
  *     MRHIP_FARROW_RATES_MULTI = 1 selects it, the default rule selects it nowhere until measurements say where);
  *   - per-channel taps on top of the per-channel rates: mrhip_set_channel_taps_farrow and mrhip_set_channel_pnfb ("Per-channel taps
  *     with per-channel rates for FIRFarrow", below);
- *   - left out on purpose: complex taps combined with per-channel rates; graph capture, rings,
+ *   - complex taps on top of the per-channel rates: mrhip_set_channel_ctaps_farrow and mrhip_set_channel_pnfb_ctaps* ("Complex
+ *     per-channel taps with per-channel rates for FIRFarrow", below);
+ *   - left out on purpose: graph capture, rings,
  *     cascades and sharding of such a filter; the parallel schedule for long channels, which stays the named next speed step and is shared by both filters. */
 
 typedef struct mrhip_filter mrhip_filter; /* opaque; replaces FIRFilter{Tk}, src/Filters.jl:151-155 */
@@ -762,7 +766,8 @@ int mrhip_set_channel_taps(mrhip_filter *f, const void *h /* [nchannels][hLen] *
  *     never, the default rule follows the measured rows); MRHIP_FORCE_GENERIC = 1 keeps the universal one;
  *   - mrhip_set_channel_taps keeps answering MRHIP_ERR_UNSUPPORTED for a FIRFarrow filter; a filter on which neither function was
  *     called runs the launches and kernels it always ran; the ABI version stays 1; there are still sixteen constructors;
- *   - left out on purpose: complex taps with per-channel rates; going back to shared taps; a stream-ordered update without the host
+ *   - complex banks: mrhip_set_channel_ctaps_farrow and mrhip_set_channel_pnfb_ctaps* (below);
+ *   - left out on purpose: going back to shared taps; a stream-ordered update without the host
  *     wait (it needs double-buffered banks); the fit on the device; graph capture, rings, cascades and sharding; the parallel schedule
  *     for long channels. */
 int mrhip_set_channel_taps_farrow(mrhip_filter *f, const void *h /* [nchannels][hLen] */, int64_t hLen, int tap_dtype);
@@ -876,11 +881,76 @@ int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb /* DEVICE,
  *   - a filter on which neither function was called runs the launches, kernels and messages it always ran: mrhip_set_channel_taps,
  *     mrhip_set_channel_taps_farrow, mrhip_set_channel_taps_device and the constructors keep answering a complex tap dtype with
  *     MRHIP_ERR_UNSUPPORTED;
- *   - left out on purpose: FIRFarrow with complex taps and per-channel rates; one shared complex tap vector without a bank per channel
+ *   - FIRFarrow with complex taps and per-channel rates: the three calls of the next section;
+ *   - left out on purpose: one shared complex tap vector without a bank per channel
  *     (install the same row nchannels times); going back to real taps; a FUSED form; graph capture, rings, cascades and sharding;
  *     lengths on the device; the parallel schedule for long channels. */
 int mrhip_set_channel_ctaps(mrhip_filter *f, const void *h /* [nchannels][hLen] (re, im) */, int64_t hLen, int tap_dtype);
 int mrhip_set_channel_ctaps_device(mrhip_filter *f, const void *h /* DEVICE, same layout */, int64_t hLen, int tap_dtype, void *stream);
+/* Complex per-channel taps with per-channel rates for FIRFarrow (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps and
+ * mrhip_set_channel_pnfb_ctaps_device on a filter of mrhip_create_farrow_rates*): one FIRFilter(h_c::Vector{Complex}, rates[c], Nphi,
+ * polyorder) per channel behind one handle.  FIRFarrow is the kernel the reference offers for a continuously variable rate, and Doppler
+ * is a time scale AND a carrier offset: the matched pulse or equaliser of channel c is a complex prototype rotated to that channel's
+ * frequency, and a tracker moves the rate every chunk.  The three are CALLS on an existing filter, the twins of
+ * mrhip_set_channel_taps_farrow, mrhip_set_channel_pnfb and mrhip_set_channel_pnfb_device, not constructors: there are still sixteen
+ * constructors and the ABI version stays 1.  This completes the table of the per-channel-rate filters.
+ *   - layouts: h holds nchannels rows of hLen (re, im) pairs, row-major, row c = h_c (mrhip_create_farrow_bank_ctaps); pnfb holds
+ *     [nchannels][tapsPerPhi][polyorder+1] (re, im) pairs of Float64, ascending powers ("Per-channel complex taps for FIRFarrow");
+ *   - filter kinds: f must come from mrhip_create_farrow_rates or mrhip_create_farrow_rates_pnfb, with or without earlier
+ *     mrhip_set_channel_taps_farrow / mrhip_set_channel_pnfb* calls.  A filter of mrhip_create_arbitrary_rates answers
+ *     MRHIP_ERR_INVALID_ARG with a message that points to mrhip_set_channel_ctaps; any other filter answers MRHIP_ERR_INVALID_ARG;
+ *   - checks, in this order, each before anything changes, each message naming the function: f == NULL (MRHIP_ERR_INVALID_ARG); the
+ *     filter kind (above); h or pnfb == NULL (MRHIP_ERR_INVALID_ARG); hLen, or tapsPerPhi and polyorder, other than the filter's
+ *     (MRHIP_ERR_INVALID_ARG: the history length and the history do not change); mrhip_set_channel_ctaps_farrow only, the tap dtype,
+ *     which must be the complex type of the filter's tap precision -- out of range is MRHIP_ERR_INVALID_ARG, a real type
+ *     MRHIP_ERR_INVALID_ARG with a message that points to mrhip_set_channel_taps_farrow, the other complex precision
+ *     MRHIP_ERR_INVALID_ARG; last, a filter in FUSED numerics is MRHIP_ERR_UNSUPPORTED: complex taps have no FUSED form ("Complex
+ *     taps").  The two pnfb calls take no dtype: the filter becomes Complex64 over Float32 taps and Complex128 over Float64 taps;
+ *   - effect (mrhip_set_channel_ctaps_farrow): every row goes through taps2pfb and the fit per component, then the rounding to the
+ *     tap's scalar, exactly as mrhip_create_farrow_bank_ctaps builds its banks: bank c is bit for bit the bank of
+ *     mrhip_create_farrow_ctaps(h_c, ...).  A rank-deficient fit is MRHIP_ERR_INVALID_ARG.  mrhip_set_channel_pnfb_ctaps: every
+ *     coefficient component is rounded as mrhip_create_farrow_pnfb_ctaps rounds.  The filter then holds nchannels * tapsPerPhi *
+ *     (polyorder+1) pairs of Float64, allocated by the first of the three calls and reused by every later one.  The order of steps is
+ *     mrhip_set_channel_pnfb's: the checks, the host banks and the allocation come first; then ONE wait for the filter's stream; then
+ *     the upload and the swap; the one shared bank or the real banks are freed after the wait.  A refused or failed call leaves the
+ *     filter bit for bit as it was;
+ *   - mrhip_set_channel_pnfb_ctaps_device: pnfb is a DEVICE pointer of the same layout.  The same checks, then the stream rules of
+ *     mrhip_set_channel_pnfb_device: the call adopts `stream`, a capturing stream is MRHIP_ERR_UNSUPPORTED.  The kernel is that of
+ *     mrhip_set_channel_pnfb_device (rates_pnfb_install_kernel) over twice as many doubles -- the rounding is per component.  The first
+ *     install on a filter that does not hold complex banks yet allocates them, waits once for the filter's stream and flips the type;
+ *     every later call enqueues one kernel and returns.  Afterwards the host copy is stale and the tap queries wait for the stream and
+ *     read the banks back.  Parity is with mrhip_set_channel_pnfb_ctaps given the same array;
+ *   - from the next call on the filter's tap type is the complex one and the output element type is mrhip_output_dtype(tap, sample):
+ *     a filter over REAL samples now writes COMPLEX outputs, and the caller's y must be of that type (y_capacity and y_stride count
+ *     such elements).  mrhip_set_numerics(FUSED) answers MRHIP_ERR_UNSUPPORTED as on every complex-tap filter.  phiAccumulator,
+ *     inputDeficit, the rates (installed from the host or from the device, with their declared range), the history, the schedule
+ *     buffers and mrhip_outputlength_bound are untouched.  mrhip_reset keeps the taps.  Any of the three may be called again: the
+ *     taps may change between calls;
+ *   - parity: channel c continues bit for bit as mrhip_create_farrow_pnfb_ctaps(bank_c, rates[c], Nphi, polyorder, nchannels = 1) fed
+ *     x_c, that filter given channel c's (inputDeficit, phiAccumulator) and its history: the outputs, the count of every call, the end
+ *     state and the history, through mrhip_filt_device_rates and mrhip_filt_device_rates_ragged, including the short-input path, the
+ *     zero-start seam on every call and a channel of ragged length 0.  STRICT only.  Arithmetic: that of "FIRFarrow with complex taps"
+ *     on bank c -- Horner in Float64 per component, never fused; one rounding to the tap's scalar, widened exactly to R; the dot oldest
+ *     sample first, every multiply, add and subtract rounded separately;
+ *   - tap queries: mrhip_get_pnfb and mrhip_farrow_tapsforphase answer in the layout of "Per-channel complex taps for FIRFarrow" --
+ *     nchannels banks or rows one after the other;
+ *   - going back: mrhip_set_channel_taps_farrow, mrhip_set_channel_pnfb and mrhip_set_channel_pnfb_device on a filter that holds
+ *     complex banks answer MRHIP_ERR_UNSUPPORTED, "going back to real taps is left out" (no filter could be in that state before);
+ *   - kernels: farrow_rates_ctaps_generic (any shape) and farrow_rates_ctaps_multi (four outputs a lane share each tap's scalar
+ *     coefficient loads, a tile is one channel and so one bank; MRHIP_FARROW_RATES_CTAPS_MULTI = 1 selects it for every call, 0 never,
+ *     the default rule follows the measured rows: from 90 112 tiles, up to 22 tiles a channel); MRHIP_FARROW_RATES_CTAPS_GRID replaces
+ *     its grid; MRHIP_FORCE_GENERIC = 1 keeps the universal one;
+ *   - a filter on which none of the three was called runs the launches, kernels and messages it always ran: mrhip_set_channel_ctaps
+ *     keeps answering a FIRFarrow filter as quoted above, mrhip_set_channel_taps_farrow and the constructors keep answering a complex
+ *     tap dtype with MRHIP_ERR_UNSUPPORTED;
+ *   - left out on purpose: the FIRFarrow fit on the device; one shared complex bank without a bank per channel (install the same bank
+ *     nchannels times); going back to real taps; a FUSED form; lengths on the device; graph capture, rings, cascades and sharding;
+ *     the parallel schedule for long channels. */
+int mrhip_set_channel_ctaps_farrow(mrhip_filter *f, const void *h /* [nchannels][hLen] (re, im) */, int64_t hLen, int tap_dtype);
+int mrhip_set_channel_pnfb_ctaps(mrhip_filter *f, const double *pnfb /* [nchannels][tapsPerPhi][polyorder+1] (re, im) Float64 */, int64_t tapsPerPhi,
+                                 int64_t polyorder);
+int mrhip_set_channel_pnfb_ctaps_device(mrhip_filter *f, const double *pnfb /* DEVICE, same layout */, int64_t tapsPerPhi, int64_t polyorder,
+                                        void *stream);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call
@@ -1050,7 +1120,8 @@ int mrhip_timing_read(mrhip_filter *f, int64_t *n_launches, double *total_ms);
  * and arb_rates_bank_tiled (per-channel taps with per-channel rates; their cases: tests/test_gpu_rates_bank_arb.py), and for
  * farrow_rates_bank_generic and farrow_rates_bank_multi (the same for FIRFarrow; their cases: tests/test_gpu_rates_bank_farrow.py), and
  * for arb_rates_ctaps_generic and arb_rates_ctaps_tiled (complex per-channel taps with per-channel rates; their cases:
- * tests/test_gpu_rates_arb_ctaps.py). */
+ * tests/test_gpu_rates_arb_ctaps.py), and for farrow_rates_ctaps_generic and farrow_rates_ctaps_multi (the same for FIRFarrow; their
+ * cases: tests/test_gpu_rates_farrow_ctaps.py). */
 const char *mrhip_last_kernel_name(const mrhip_filter *f);
 /* How the phase schedule of a FIRArbitrary / FIRFarrow filter -- update(), src/Filters.jl:663-673 and :780-792 -- has
  * been evaluated so far.  info[0..n) receives, as far as n reaches:

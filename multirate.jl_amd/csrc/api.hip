@@ -298,7 +298,8 @@ int refresh_host_taps(mrhip_filter *f)
     if (!guard.ok) return fail(MRHIP_ERR_HIP, "hipSetDevice failed");
     if (int rc = drain_filter(f)) return rc;
     if (f->kind == MRHIP_FIR_FARROW) {
-        std::vector<double> pn(static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1));
+        // (complex per-channel taps, mrhip_set_channel_pnfb_ctaps_device: every coefficient is an (re, im) pair, two Float64)
+        std::vector<double> pn(static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1) * (dtype_is_complex(f->th) ? 2 : 1));
         MRHIP_CHECK_HIP(hipMemcpy(pn.data(), f->d_pnfb, pn.size() * sizeof(double), hipMemcpyDeviceToHost));
         f->h_pnfb.swap(pn);
     } else {
@@ -1871,9 +1872,14 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     size_t lds = 0;
     long long tiled_grid = 0;
     bool tiled = false;
-    if (bound > 0 && !f->force_generic && farrow) {      // (tiled: farrow_rates_multi_kernel, which stages nothing: no rate in its plan)
-        tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
-        if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
+    if (bound > 0 && !f->force_generic && farrow) {      // (tiled: the multi kernels, which stage nothing: no rate in their plans)
+        if (tk.complex_h) {        // complex per-channel taps (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps*): kernels_rates_farrow_ctaps.hip
+            tiled = plan_farrow_rates_ctaps_multi(tk, fa, f->num_cus, &ta);
+            if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_ctaps_multi(tk, ta, f->num_cus, &tiled_grid));
+        } else {
+            tiled = plan_farrow_rates_multi(tk, fa, f->num_cus, &ta);
+            if (tiled) MRHIP_CHECK_HIP(prepare_farrow_rates_multi(tk, fused, ta, f->num_cus, &tiled_grid));
+        }
     } else if (bound > 0 && !f->force_generic) {      // (no other plan_* sees such a call)
         if (tk.complex_h) {        // complex per-channel taps (mrhip_set_channel_ctaps): the plan and the kernels of kernels_rates_arb_ctaps.hip
             tiled = plan_arb_rates_ctaps_tiled(tk, a, rates_min(f), f->num_cus, &ta, &lds);
@@ -1891,7 +1897,12 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
     if (bound > 0) {               // (an empty call: zero counts, history and state unchanged)
         // (tk.bank -- shared taps or a bank per channel -- picks the kernel's instantiation and its reported name inside the launch)
-        if (tk.complex_h) {        // (FIRArbitrary only: no FIRFarrow filter holds complex taps here; no FUSED form)
+        if (farrow && tk.complex_h) {      // (complex per-channel taps: no FUSED form)
+            const hipError_t e = tiled ? launch_farrow_rates_ctaps_multi(tk, fa, ra, ta, tiled_grid, stream, &f->last_kernel)
+                                       : launch_farrow_rates_ctaps_generic(tk, fa, ra, stream, &f->last_kernel);
+            MRHIP_CHECK_HIP(e);
+        }
+        else if (tk.complex_h) {   // (FIRArbitrary)
             const hipError_t e = tiled ? launch_arb_rates_ctaps_tiled(tk, a, ra, ta, lds, tiled_grid, stream, &f->last_kernel)
                                        : launch_arb_rates_ctaps_generic(tk, a, ra, stream, &f->last_kernel);
             MRHIP_CHECK_HIP(e);
@@ -2130,6 +2141,8 @@ static int install_channel_pnfb(mrhip_filter *f, const std::string &who, std::ve
 int mrhip_set_channel_taps_farrow(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps_farrow: NULL filter");
+    if (f->rates && f->kind == MRHIP_FIR_FARROW && dtype_is_complex(f->th))      // (after mrhip_set_channel_ctaps_farrow / _pnfb_ctaps*: the filter's outputs are complex from then on)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps_farrow: the filter holds complex per-channel taps (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps); going back to real taps is left out");
     if (Refusal r = check_channel_taps_farrow(false, f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, f->polyorder, tap_dtype, f->hLen, f->polyorder, f->th))
         return fail(r.status, r.message);
     std::vector<double> pn;                                             // one fit per row, as mrhip_create_farrow_bank builds its banks
@@ -2141,6 +2154,8 @@ int mrhip_set_channel_taps_farrow(mrhip_filter *f, const void *h, int64_t hLen, 
 int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb, int64_t tapsPerPhi, int64_t polyorder)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_pnfb: NULL filter");
+    if (f->rates && f->kind == MRHIP_FIR_FARROW && dtype_is_complex(f->th))      // (after mrhip_set_channel_ctaps_farrow / _pnfb_ctaps*: the filter's outputs are complex from then on)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_pnfb: the filter holds complex per-channel taps (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps); going back to real taps is left out");
     if (Refusal r = check_channel_taps_farrow(true, f->rates, f->kind == MRHIP_FIR_FARROW, pnfb, tapsPerPhi, polyorder, f->th, f->T, f->polyorder, f->th))
         return fail(r.status, r.message);
     std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1));
@@ -2226,6 +2241,8 @@ int mrhip_set_channel_taps_device(mrhip_filter *f, const void *h, int64_t hLen, 
 int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb, int64_t tapsPerPhi, int64_t polyorder, void *stream_)
 {
     if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_pnfb_device: NULL filter");
+    if (f->rates && f->kind == MRHIP_FIR_FARROW && dtype_is_complex(f->th))      // (after mrhip_set_channel_ctaps_farrow / _pnfb_ctaps*: the filter's outputs are complex from then on)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_pnfb_device: the filter holds complex per-channel taps (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps); going back to real taps is left out");
     if (Refusal r = check_channel_pnfb_device(f->rates, f->kind == MRHIP_FIR_FARROW, pnfb, tapsPerPhi, polyorder, f->T, f->polyorder, f->th))
         return fail(r.status, r.message);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -2367,6 +2384,114 @@ int mrhip_set_channel_ctaps_device(mrhip_filter *f, const void *h, int64_t hLen,
         f->d_taps = f->d_taps_alloc = d_new[0];
         f->d_dtaps = f->d_dtaps_alloc = d_new[1];
         ctaps_flip_type(f, tap_dtype);
+    }
+    f->taps_stale = true;
+    return MRHIP_OK;
+}
+
+// ---- Complex per-channel taps on a filter of mrhip_create_farrow_rates* (include/multirate_hip.h, "Complex per-channel taps with
+// per-channel rates for FIRFarrow") ---------------------------------------------------------------------------------------------------
+// nch polynomial banks of (re, im) pairs, [nch][T][polyorder+1][2] Float64, in the place of the one shared bank or of the real banks.
+// `pn` holds them as the caller or the fit gave them; every component is rounded to the tap's scalar here, as create_filter rounds
+// (Poly{T} storage).  The order of steps is install_channel_pnfb's: the checks and the host banks are the caller's, the first call's
+// allocation comes before anything of the filter changes; then ONE wait for the filter's stream (the kernels enqueued so far read the
+// banks), the upload and the swap; the shared bank or the real banks are freed after the wait.  Records, rates, history and the
+// schedule buffers stay; the tap type flips (ctaps_flip_type: rates_call takes the kernels of kernels_rates_farrow_ctaps.hip).
+static int install_channel_pnfb_ctaps(mrhip_filter *f, const std::string &who, std::vector<double> &pn)
+{
+    if (!dtype_is_f64(f->th)) for (double &c : pn) c = static_cast<double>(static_cast<float>(c));
+    const size_t bytes = pn.size() * sizeof(double);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, who + ": hipSetDevice failed");
+    const bool first = !dtype_is_complex(f->th);                        // the filter holds the shared bank or real banks: a new allocation
+    double *d_new = f->d_pnfb;                                          // (a later call: the complex banks of the first one, reused)
+    if (first) {
+        d_new = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&d_new), bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MRHIP_ERR_HIP, who + ": no device memory for the channels' polynomial banks");
+        }
+    }
+    int rc = drain_filter(f);
+    if (!rc && hipMemcpy(d_new, pn.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)     // (complete on return)
+        rc = fail(MRHIP_ERR_HIP, who + ": uploading the polynomial banks failed");
+    if (rc) {
+        if (first) (void)hipFree(d_new);
+        return rc;
+    }
+    if (first) {
+        (void)hipFree(f->d_pnfb);
+        if (f->d_pnfb_t) (void)hipFree(f->d_pnfb_t);
+        f->d_pnfb = d_new;
+        f->d_pnfb_t = nullptr;
+        ctaps_flip_type(f, dtype_is_f64(f->th) ? MRHIP_C128 : MRHIP_C64);
+    }
+    f->h_pnfb.swap(pn);
+    f->taps_stale = false;                                            // (the host copy is current again)
+    return MRHIP_OK;
+}
+
+int mrhip_set_channel_ctaps_farrow(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_ctaps_farrow: NULL filter");
+    if (Refusal r = check_channel_ctaps_farrow("mrhip_set_channel_ctaps_farrow", false, f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, f->polyorder,
+                                               tap_dtype, f->hLen, f->polyorder, f->th, f->numerics == MRHIP_NUMERICS_FUSED))
+        return fail(r.status, r.message);
+    std::vector<double> pn;                                             // one fit per row and component, as mrhip_create_farrow_bank_ctaps builds its banks
+    if (!create_farrow_banks(h, hLen, tap_dtype, f->Nphi, f->polyorder, static_cast<size_t>(f->nch), &pn))
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_ctaps_farrow: polynomial fit is rank deficient");
+    return install_channel_pnfb_ctaps(f, "mrhip_set_channel_ctaps_farrow", pn);
+}
+
+int mrhip_set_channel_pnfb_ctaps(mrhip_filter *f, const double *pnfb, int64_t tapsPerPhi, int64_t polyorder)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_pnfb_ctaps: NULL filter");
+    if (Refusal r = check_channel_ctaps_farrow("mrhip_set_channel_pnfb_ctaps", true, f->rates, f->kind == MRHIP_FIR_FARROW, pnfb, tapsPerPhi, polyorder,
+                                               f->th, f->T, f->polyorder, f->th, f->numerics == MRHIP_NUMERICS_FUSED))
+        return fail(r.status, r.message);
+    std::vector<double> pn(pnfb, pnfb + static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1) * 2);
+    return install_channel_pnfb_ctaps(f, "mrhip_set_channel_pnfb_ctaps", pn);
+}
+
+// The same banks from pnfb in DEVICE memory, the twin of mrhip_set_channel_pnfb_device: the checks, then the stream rules (a capturing
+// stream is refused, the stream is adopted).  The kernel is rates_pnfb_install_kernel over twice as many doubles: the rounding is per
+// component.  A filter that does not hold complex banks yet: the allocation first (a failure leaves the filter as it was), then ONE
+// wait for the filter's stream -- the kernels enqueued so far read the bank that is freed here --, the kernel, and the type flips; every
+// later call enqueues its kernel and returns.
+int mrhip_set_channel_pnfb_ctaps_device(mrhip_filter *f, const double *pnfb, int64_t tapsPerPhi, int64_t polyorder, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_pnfb_ctaps_device: NULL filter");
+    if (Refusal r = check_channel_ctaps_farrow("mrhip_set_channel_pnfb_ctaps_device", true, f->rates, f->kind == MRHIP_FIR_FARROW, pnfb, tapsPerPhi,
+                                               polyorder, f->th, f->T, f->polyorder, f->th, f->numerics == MRHIP_NUMERICS_FUSED))
+        return fail(r.status, r.message);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, "mrhip_set_channel_pnfb_ctaps_device: hipSetDevice failed");
+    if (int rc = device_update_stream(f, "mrhip_set_channel_pnfb_ctaps_device", stream)) return rc;
+    const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(f->polyorder + 1) * 2;
+    const bool first = !dtype_is_complex(f->th);
+    double *d_new = f->d_pnfb;                                          // (a later call: the complex banks of the first one, reused)
+    if (first) {
+        d_new = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&d_new), n * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MRHIP_ERR_HIP, "mrhip_set_channel_pnfb_ctaps_device: no device memory for the channels' polynomial banks");
+        }
+    }
+    auto bail = [&](int rc) { if (first) (void)hipFree(d_new); return rc; };
+    if (first)
+        if (int rc = drain_filter(f)) return bail(rc);
+    if (int rc = adopt_stream(f, stream)) return bail(rc);
+    if (launch_rates_pnfb_install(!dtype_is_f64(f->th), pnfb, d_new, static_cast<long long>(n), stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail(MRHIP_ERR_HIP, "mrhip_set_channel_pnfb_ctaps_device: the install kernel could not be launched"));
+    }
+    if (first) {
+        (void)hipFree(f->d_pnfb);
+        if (f->d_pnfb_t) (void)hipFree(f->d_pnfb_t);
+        f->d_pnfb = d_new;
+        f->d_pnfb_t = nullptr;
+        ctaps_flip_type(f, dtype_is_f64(f->th) ? MRHIP_C128 : MRHIP_C64);
     }
     f->taps_stale = true;
     return MRHIP_OK;

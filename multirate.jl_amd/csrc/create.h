@@ -82,6 +82,12 @@ Refusal check_channel_taps(bool is_rates, bool is_farrow, const void *h, int64_t
 // order: the filter's kind, h, hLen, the tap type against the complex type of the filter's tap precision (f_th: real, or complex after
 // an earlier call), and the filter's numerics (fused: complex taps have no FUSED form)
 Refusal check_channel_ctaps(const char *who, bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th, bool fused);
+// the checks of mrhip_set_channel_ctaps_farrow (pnfb_call false: src = h, len = hLen, th the tap type), mrhip_set_channel_pnfb_ctaps and
+// mrhip_set_channel_pnfb_ctaps_device (pnfb_call true: src = pnfb, len = tapsPerPhi; th is not looked at) that need no device, in their
+// order (`who`: the function's name): the filter's kind, src, the lengths against the filter's, the tap type against the complex type of
+// the filter's tap precision (f_th: real, or complex after an earlier call), and the filter's numerics (fused: no FUSED form)
+Refusal check_channel_ctaps_farrow(const char *who, bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder,
+                                   int th, int64_t f_len, int64_t f_polyorder, int f_th, bool fused);
 // the same for mrhip_set_channel_taps_farrow (pnfb_call false: src = h, len = hLen against the filter's hLen, th against its tap type)
 // and mrhip_set_channel_pnfb (pnfb_call true: src = pnfb, len = tapsPerPhi and polyorder against the filter's; th is not looked at)
 Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder, int th,

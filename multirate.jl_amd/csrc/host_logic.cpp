@@ -441,6 +441,35 @@ long long farrow_rates_multi_grid(long long total_tiles, long long chip_grid, in
     return std::max<long long>(std::min<long long>(chip_grid, total_tiles), 1);
 }
 
+// farrow_rates_ctaps_multi_kernel (FIRFarrow with per-channel RATES and COMPLEX per-channel taps, kernels_rates_farrow_ctaps.hip): as for
+// plan_farrow_rates_multi there is no LDS, so the plan is the tiling alone: a tile is kFarrowRatesCtapsOPL consecutive runs of
+// kVariantThreads outputs of ONE channel (one polynomial bank of pairs, one channel a lane: cpl = 1), and the tiling goes by n_out, the
+// call's bound (the kernel skips the tiles and the slots at or behind a channel's count).  mode 0: never; 1: every call; -1: the default
+// rule, written the way kFarrowRatesMultiRule is -- from .min_tiles tiles, up to .max_per_channel tiles a channel; a limit < 0 would
+// mean NEVER.  The rule admits the multi kernel only in rows where it was measured ahead of the universal one on the MI355X (DESIGN.md
+// 9 item 26, profiles/r16/farrow_rates_ctaps.txt, Complex64 taps, both runs, four outputs a lane): ahead by more than the spread of the
+// repeats at 4096 ch x 1e4 Float32 (90 112 tiles of 22 a channel: 2.549 against 2.713 ms and 2.525 against 2.704, spreads <= 0.057) and
+// at the same shape with ComplexF32 samples (2.665 against 2.781 ms and 2.667 against 2.769, spreads <= 0.058); NOT ahead at 256 ch x
+// 1e5 (56 320 tiles of 220 a channel: 19.022 against 18.990 ms and 19.055 against 18.992; ComplexF32: 19.352 against 19.164 and 19.361
+// against 19.132 -- behind by more than the spread) nor at 64 ch x 1e6 (140 672 tiles of 2198 a channel: 463 to 536 ms either way with
+// spreads of 13 to 52 -- the serial walk is the call).  The limits came out as kFarrowRatesMultiRule's and, as there, both are GUARDS
+// ON UNMEASURED GROUND, not causes.  (With two outputs a lane the kernel was ahead nowhere: 2.710 against 2.728 ms and 2.692 against
+// 2.701 in the first row, inside the spread, and behind in the second and third.)
+constexpr RatesTiledRule kFarrowRatesCtapsMultiRule = {90112, 22};
+bool plan_farrow_rates_ctaps_multi(const TypeKey &tk, const FarrowArgs &a, int /*num_cus*/, int mode, ArbTileArgs *out)
+{
+    if (mode == 0 || !tk.bank || !tk.complex_h || a.n_out < 1 || a.T < 1 || a.polyorder < 0 || a.nch < 1) return false;
+    ArbTileArgs ta{};
+    ta.cpl = 1;
+    ta.tile_out = static_cast<long long>(kFarrowRatesCtapsOPL) * kVariantThreads;
+    ta.tiles_per_channel = (a.n_out + ta.tile_out - 1) / ta.tile_out;
+    ta.total_tiles = ta.tiles_per_channel * a.nch;
+    const RatesTiledRule rule = kFarrowRatesCtapsMultiRule;
+    if (mode != 1 && (rule.min_tiles < 0 || ta.total_tiles < rule.min_tiles || ta.tiles_per_channel > rule.max_per_channel)) return false;
+    *out = ta;
+    return true;
+}
+
 // arb_bank_ctaps_tiled_kernel: both banks of ONE channel as (re, im) pairs of R (column pitch T + 1) plus the sample tile fit LDS at
 // two workgroups a CU (78 KiB a workgroup, as for plan_arb_bank_tiled); one channel a lane (cpl = 1); the span follows from the rate
 // and is cut only when the kernel is forced.  The default rule: the tiled kernel was faster than the universal one by far more than
@@ -830,6 +859,40 @@ Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow,
     if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, who + ": bad tap dtype"};
     if (dtype_is_complex(th)) return {MRHIP_ERR_UNSUPPORTED, who + ": " + kRatesHint + " (the taps are Float32 / Float64)"};
     if (th != f_th) return {MRHIP_ERR_INVALID_ARG, who + ": the taps must have the filter's tap dtype"};
+    return {};
+}
+
+// mrhip_set_channel_ctaps_farrow (pnfb_call false: src = h, len = hLen against the filter's hLen, th against the complex type of the
+// filter's tap precision), mrhip_set_channel_pnfb_ctaps and mrhip_set_channel_pnfb_ctaps_device (pnfb_call true: src = pnfb, len =
+// tapsPerPhi and polyorder against the filter's; th is not looked at) -- `who`; the public header, "Complex per-channel taps with
+// per-channel rates for FIRFarrow": what the three calls refuse before they touch the device, in their order and each naming the
+// function -- the filter (a FIRArbitrary one with per-channel rates is pointed to its own call), then h / pnfb, then hLen or
+// (tapsPerPhi, polyorder) against the filter's own, then (taps only) the tap type (out of range, real, the other complex precision:
+// f_th is the filter's tap type, real or already complex -- its precision counts), and last the filter's numerics: complex taps have no
+// FUSED form
+Refusal check_channel_ctaps_farrow(const char *who_, bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder,
+                                   int th, int64_t f_len, int64_t f_polyorder, int f_th, bool fused)
+{
+    const std::string who = who_;
+    if (is_rates && !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + ": a filter of mrhip_create_arbitrary_rates takes mrhip_set_channel_ctaps"};
+    if (!is_rates || !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + " takes a filter of mrhip_create_farrow_rates or mrhip_create_farrow_rates_pnfb"};
+    if (!src) return {MRHIP_ERR_INVALID_ARG, who + (pnfb_call ? ": pnfb is NULL" : ": h is NULL")};
+    if (pnfb_call) {
+        if (len != f_len || polyorder != f_polyorder)
+            return {MRHIP_ERR_INVALID_ARG, who + ": tapsPerPhi and polyorder must be the filter's (" + std::to_string(f_len) + " polynomials of order " +
+                                           std::to_string(f_polyorder) + " a channel; got " + std::to_string(len) + " of order " + std::to_string(polyorder) +
+                                           "): the history length and the history do not change"};
+    } else {
+        if (len != f_len)
+            return {MRHIP_ERR_INVALID_ARG, who + ": hLen must be the filter's (" + std::to_string(f_len) + " taps a channel; got " + std::to_string(len) +
+                                           "): tapsPerPhi, the history length and the history do not change"};
+        if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, who + ": bad tap dtype"};
+        if (!dtype_is_complex(th))
+            return {MRHIP_ERR_INVALID_ARG, who + ": the taps must be Complex64 or Complex128 (real taps go through mrhip_set_channel_taps_farrow)"};
+        if (dtype_is_f64(th) != dtype_is_f64(f_th))
+            return {MRHIP_ERR_INVALID_ARG, who + ": the taps must be the complex type of the filter's tap precision (Complex64 on Float32 taps, Complex128 on Float64 taps)"};
+    }
+    if (fused) return {MRHIP_ERR_UNSUPPORTED, who + ": the filter is in FUSED numerics and no FUSED form is defined for complex taps (the public header: complex taps)"};
     return {};
 }
 

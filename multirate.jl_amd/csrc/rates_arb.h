@@ -191,4 +191,37 @@ hipError_t launch_rates_cbank_build(bool tap_f64, bool r_f64, const BankBuildArg
 // host_logic.cpp: the switch value passed in (0 never, 1 wherever the plan fits, -1 the default rule)
 bool plan_arb_rates_ctaps_tiled(const TypeKey &tk, const ArbArgs &a, double rate_min, int num_cus, int mode, ArbTileArgs *out, size_t *lds);
 
+// ---- COMPLEX per-channel taps on the FIRFarrow filter with per-channel rates (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps,
+// mrhip_set_channel_pnfb_ctaps_device; include/multirate_hip.h, "Complex per-channel taps with per-channel rates for FIRFarrow") ---------
+// The filter holds nch polynomial banks of (re, im) pairs of Float64, [nch][T][polyorder+1][2], and TypeKey::complex_h and ::bank are both
+// set.  Records, slices, schedule kernel, RatesArgs and rates_pnfb_install_kernel (over twice as many doubles: the rounding is per
+// component) serve it unchanged; the two filter kernels live in kernels_rates_farrow_ctaps.hip (kernels_rates_farrow.hip refuses a
+// complex_h key), the multi kernel's plan in host_logic.cpp.  Reported names: farrow_rates_ctaps_generic / farrow_rates_ctaps_multi;
+// switches: MRHIP_FARROW_RATES_CTAPS_MULTI (-1 rule, 0, 1), MRHIP_FARROW_RATES_CTAPS_GRID.
+//
+// farrow_rates_ctaps_multi_kernel: a lane owns kFarrowRatesCtapsOPL outputs of one channel, output `tid` of as many consecutive runs of
+// kVariantThreads outputs; a tile is those runs (tile_out = kFarrowRatesCtapsOPL * kVariantThreads outputs of one channel).  4, not 2:
+// a slot carries two Float64 Horner chains and a complex sum, and both counts compile without scratch for every instantiation (at 4: 77
+// to 105 VGPRs); measured, 4 is ahead of the universal kernel at 4096 ch x 1e4 and 2 is not.
+constexpr int kFarrowRatesCtapsOPL = 4;
+// the live slots of lane `tid` in the tile that starts at output k0: farrow_rates_live_slots with this kernel's slot count
+MRHIP_RATES_HD inline int farrow_rates_ctaps_live_slots(long long k0, int tid, long long count)
+{
+    const long long left = count - k0 - tid;                     // outputs from the lane's first slot to the count
+    if (left <= 0) return 0;
+    const long long slots = (left + kVariantThreads - 1) / kVariantThreads;
+    return slots < kFarrowRatesCtapsOPL ? static_cast<int>(slots) : kFarrowRatesCtapsOPL;
+}
+
+// kernels_rates_farrow_ctaps.hip.  The key must have complex_h and bank set; fused is not an argument: complex taps have no FUSED form.
+hipError_t launch_farrow_rates_ctaps_generic(const TypeKey &tk, const FarrowArgs &a, const RatesArgs &r, hipStream_t s, const char **kname);
+bool plan_farrow_rates_ctaps_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, ArbTileArgs *out);      // (reads MRHIP_FARROW_RATES_CTAPS_MULTI)
+// the multi kernel's persistent grid (occupancy query; MRHIP_FARROW_RATES_CTAPS_GRID): everything about its launch that can fail ahead of
+// the launch
+hipError_t prepare_farrow_rates_ctaps_multi(const TypeKey &tk, const ArbTileArgs &ta, int num_cus, long long *grid);
+hipError_t launch_farrow_rates_ctaps_multi(const TypeKey &tk, const FarrowArgs &a, const RatesArgs &r, const ArbTileArgs &ta, long long grid,
+                                           hipStream_t s, const char **kname);
+// host_logic.cpp: the switch value passed in (0 never, 1 every call, -1 the default rule); the grid is farrow_rates_multi_grid's
+bool plan_farrow_rates_ctaps_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
+
 }  // namespace mrhip

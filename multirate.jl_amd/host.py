@@ -122,6 +122,9 @@ ABI = [
     ("mrhip_set_channel_pnfb_device", _i, [_vp, _vp, _i64, _i64, _vp]),
     ("mrhip_set_channel_ctaps", _i, [_vp, _vp, _i64, _i]),
     ("mrhip_set_channel_ctaps_device", _i, [_vp, _vp, _i64, _i, _vp]),
+    ("mrhip_set_channel_ctaps_farrow", _i, [_vp, _vp, _i64, _i]),
+    ("mrhip_set_channel_pnfb_ctaps", _i, [_vp, _vp, _i64, _i64]),
+    ("mrhip_set_channel_pnfb_ctaps_device", _i, [_vp, _vp, _i64, _i64, _vp]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -349,6 +352,7 @@ class FIRFilter:
         self._rates = None                # per-channel rates (FIRFilter.per_channel_rates, .per_channel_rates_farrow): Float64, one per channel; self.rate is the largest
         self._chan_taps = None            # per-channel taps ON TOP of per-channel rates (FIRFilter.set_channel_taps, .per_channel_taps_and_rates): the (nchannels, hLen) matrix, installed by mrhip_set_channel_taps
         self._chan_ctaps = None           # COMPLEX per-channel taps on top of per-channel rates (FIRFilter.set_channel_ctaps, .set_channel_ctaps_device, .per_channel_complex_taps_and_rates): the (nchannels, hLen) complex matrix, installed by mrhip_set_channel_ctaps; self.h stays the real placeholder the filter is created over
+        self._farrow_ctaps = False        # the FIRFarrow mirror below holds COMPLEX banks (FIRFilter.set_channel_ctaps_farrow, .set_channel_pnfb_ctaps, .set_channel_pnfb_ctaps_device, .per_channel_complex_taps_and_rates_farrow): _chan_farrow is then ("ctaps", the complex (nchannels, hLen) matrix) or ("cpnfb", the complex banks); self.h stays the real vector the filter is created over
         self._chan_farrow = None          # the same for FIRFarrow (FIRFilter.set_channel_taps_farrow, .set_channel_pnfb, .per_channel_taps_and_rates_farrow): ("taps", the (nchannels, hLen) matrix) or ("pnfb", the (nchannels, tapsPer𝜙, polyorder+1) banks), whichever call came last
         self._bank = None                 # per-channel taps (FIRFilter.per_channel, .per_channel_complex_taps, .per_channel_arbitrary, .per_channel_complex_taps_arbitrary, .per_channel_farrow, .per_channel_complex_taps_farrow): the (nchannels, hLen) matrix; self.h is its row 0
         if isinstance(ratio, (float, np.floating)):
@@ -559,6 +563,33 @@ class FIRFilter:
         return f
 
     @classmethod
+    def per_channel_complex_taps_and_rates_farrow(cls, H, rates, Nphi: int = 32, polyorder=4, *, pnfb=None, device: int = 0):
+        """One FIRFilter(H[c]::Vector{Complex}, rates[c]::Float, N𝜙, polyorder) per channel behind one filter object: FIRFarrow with
+        COMPLEX per-channel taps and per-channel rates (per-emitter Doppler correction with a tracker that calls ``set_channel_rates``
+        every chunk: a time scale and a carrier offset per channel).  ``H``: shape (nchannels, hLen), complex64 or complex128;
+        ``rates``: one rate > 0 per channel.  It is the two steps in one: the filter of ``per_channel_rates_farrow`` over placeholder
+        taps ``real(H[0])`` of the same length and precision, followed by ``set_channel_ctaps_farrow(H)`` -- every row fitted on its
+        own -- or, with a complex ``pnfb`` of shape (nchannels, tapsPer𝜙, polyorder+1), by ``set_channel_pnfb_ctaps(pnfb)``: ``H`` then
+        only gives hLen and the precision.  Channel c is bit for bit ``FIRFilter.complex_taps_farrow(H[c], rates[c], Nphi, polyorder)``
+        (on bank c) fed ``x[c]`` (include/multirate_hip.h: complex per-channel taps with per-channel rates for FIRFarrow).  STRICT
+        only."""
+        who = "per_channel_complex_taps_and_rates_farrow"
+        H = np.asarray(H)
+        if H.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+            raise MultirateHIPError(1, f"{who} takes complex64 or complex128 taps; real taps: FIRFilter.per_channel_taps_and_rates_farrow")
+        H = _tap_matrix(H, who)
+        if pnfb is None:
+            f = cls.per_channel_rates_farrow(np.ascontiguousarray(H[0].real), rates, Nphi, polyorder, device=device)
+            f.set_channel_ctaps_farrow(H)
+        else:
+            PN = np.asarray(pnfb)
+            if PN.ndim != 3 or PN.shape[0] < 1 or PN.dtype.kind != "c":
+                raise MultirateHIPError(1, f"{who} takes a complex pnfb of shape (nchannels, tapsPerPhi, polyorder+1); got {PN.dtype} {PN.shape}")
+            f = cls.per_channel_rates_farrow(np.ascontiguousarray(H[0].real), rates, Nphi, polyorder, pnfb=np.ascontiguousarray(PN[0].real), device=device)
+            f.set_channel_pnfb_ctaps(PN)
+        return f
+
+    @classmethod
     def per_channel_complex_taps_arbitrary(cls, H, rate, Nphi: int = 32, *, device: int = 0):
         """One FIRFilter(H[c]::Vector{Complex64 / Complex128}, rate::Float, N𝜙) per channel behind one filter object: FIRArbitrary
         with per-channel complex taps (a prototype rotated to every channel's own centre frequency in front of a common clock-trim or
@@ -626,7 +657,7 @@ class FIRFilter:
             return
         if tx not in _NP2DT:
             raise MultirateHIPError(1, f"unsupported sample dtype {tx}")
-        for mirror, call in ((self._rates, "set_channel_rates_device"), (self._chan_taps, "set_channel_taps_device"), (self._chan_farrow, "set_channel_pnfb_device"),
+        for mirror, call in ((self._rates, "set_channel_rates_device"), (self._chan_taps, "set_channel_taps_device"), (self._chan_farrow, "set_channel_pnfb_ctaps_device" if self._farrow_ctaps else "set_channel_pnfb_device"),
                              (self._chan_ctaps, "set_channel_ctaps_device")):
             if isinstance(mirror, _DeviceResident):
                 raise MultirateHIPError(1, f"the filter was closed after {call}: its values lived on the device and are gone; install new ones "
@@ -665,6 +696,10 @@ class FIRFilter:
     def _install_chan_farrow(self, what, M):
         if what == "taps":
             _check(self._lib.mrhip_set_channel_taps_farrow(self._handle, _ptr(M), M.shape[1], _NP2DT[M.dtype]))
+        elif what == "ctaps":
+            _check(self._lib.mrhip_set_channel_ctaps_farrow(self._handle, _ptr(M), M.shape[1], _NP2DT[M.dtype]))
+        elif what == "cpnfb":                 # (complex128: (re, im) pairs of Float64, the C layout)
+            _check(self._lib.mrhip_set_channel_pnfb_ctaps(self._handle, _ptr(M), M.shape[1], M.shape[2] - 1))
         else:
             _check(self._lib.mrhip_set_channel_pnfb(self._handle, _ptr(M), M.shape[1], M.shape[2] - 1))
 
@@ -693,8 +728,9 @@ class FIRFilter:
     @property
     def _tap_dtype(self):
         """the filter's tap type: that of ``h``, or the complex type of its precision once complex per-channel taps are installed
-        (``set_channel_ctaps`` and its siblings on a filter of ``per_channel_rates``)"""
-        if self._chan_ctaps is None:
+        (``set_channel_ctaps`` and its siblings on a filter of ``per_channel_rates``; ``set_channel_ctaps_farrow`` and its siblings on
+        one of ``per_channel_rates_farrow``)"""
+        if self._chan_ctaps is None and not self._farrow_ctaps:
             return self.h.dtype
         return np.dtype(np.complex128 if self.h.dtype == np.float64 else np.complex64)
 
@@ -757,7 +793,7 @@ class FIRFilter:
         if self._handle is None or self.kind != FARROW:
             raise MultirateHIPError(1, "pnfb() needs a bound FIRFarrow filter")
         shape = (self.tapsPerPhi, self.polyorder + 1)
-        out = np.zeros((self._nch,) + shape if self._bank is not None or self._chan_farrow is not None else shape, dtype=np.complex128 if self.h.dtype.kind == "c" else np.float64)
+        out = np.zeros((self._nch,) + shape if self._bank is not None or self._chan_farrow is not None else shape, dtype=np.complex128 if self._tap_dtype.kind == "c" else np.float64)
         _check(self._lib.mrhip_get_pnfb(self._handle, _ptr(out)))
         return out
 
@@ -1044,6 +1080,8 @@ class FIRFilter:
         who = "set_channel_taps_farrow"
         self._takes_farrow_rates(who)
         H = _tap_matrix(_real_taps(H, who, "complex taps with per-channel rates are left out"), who)
+        if self._farrow_ctaps:
+            raise MultirateHIPError(5, f"{who}: the filter holds complex per-channel taps (set_channel_ctaps_farrow, set_channel_pnfb_ctaps); going back to real taps is left out")
         if H.shape != (len(self._rates), len(self.h)):
             raise MultirateHIPError(1, f"{who} takes a {(len(self._rates), len(self.h))} matrix, one row of the filter's hLen taps per channel; got {H.shape}")
         if H.dtype != self.h.dtype:
@@ -1062,6 +1100,8 @@ class FIRFilter:
         who = "set_channel_pnfb"
         self._takes_farrow_rates(who)
         PN = _real_taps(PN, who, "complex taps with per-channel rates are left out")
+        if self._farrow_ctaps:
+            raise MultirateHIPError(5, f"{who}: the filter holds complex per-channel taps (set_channel_ctaps_farrow, set_channel_pnfb_ctaps); going back to real taps is left out")
         want = (len(self._rates), self.tapsPerPhi, self.polyorder + 1)
         if PN.shape != want:
             raise MultirateHIPError(1, f"{who} takes banks of shape (nchannels, tapsPerPhi, polyorder+1) = {want}; got {PN.shape}")
@@ -1177,10 +1217,86 @@ class FIRFilter:
             raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates takes set_channel_taps_device")
         if self._rates is None or self.kind != FARROW:
             raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates_farrow")
+        if self._farrow_ctaps:
+            raise MultirateHIPError(5, f"{who}: the filter holds complex per-channel taps (set_channel_ctaps_farrow, set_channel_pnfb_ctaps); going back to real taps is left out")
         shape = (len(self._rates), self.tapsPerPhi, self.polyorder + 1)
         stream = self._device_update_args(who, PN, np.float64, shape)
         _check(self._lib.mrhip_set_channel_pnfb_device(self._handle, C.c_void_p(PN.data_ptr()), self.tapsPerPhi, self.polyorder, C.c_void_p(stream)))
         self._chan_farrow = _DeviceResident(shape)
+
+    # -- complex per-channel taps on a filter of per_channel_rates_farrow (include/multirate_hip.h, "Complex per-channel taps with
+    # per-channel rates for FIRFarrow")
+    def _takes_ctaps_farrow(self, who):
+        """the filter checks of the three calls, in the library's order: the filter kind, then (by the callers) the array, then the
+        numerics"""
+        if self._rates is not None and self.kind == ARBITRARY:
+            raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates takes set_channel_ctaps")
+        if self._rates is None or self.kind != FARROW:
+            raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates_farrow")
+        return np.dtype(np.complex128 if self.h.dtype == np.float64 else np.complex64)
+
+    def _strict_for_ctaps(self, who):
+        if self.numerics != NUMERICS_STRICT:
+            raise MultirateHIPError(5, f"{who}: the filter is in FUSED numerics and no FUSED form is defined for complex taps")
+
+    def set_channel_ctaps_farrow(self, H):
+        """COMPLEX per-channel taps on a filter of ``per_channel_rates_farrow``, with or without earlier ``set_channel_taps_farrow`` /
+        ``set_channel_pnfb`` (``mrhip_set_channel_ctaps_farrow``; waits for the filter's stream): ``H`` has shape (nchannels, hLen) in
+        the complex type of the filter's tap precision, row c replaces the taps of channel c and is fitted on its own, per component,
+        as ``per_channel_complex_taps_farrow`` fits its rows -- a matched pulse rotated to the channel's own frequency beside the
+        channel's own, continuously variable rate (Doppler).  phiAccumulator, inputDeficit, rates and history stay; channel c
+        continues bit for bit as ``FIRFilter.complex_taps_farrow(H[c], rates[c], Nphi, polyorder)`` given its state and history would
+        (STRICT only: a FUSED filter is status 5).  From then on ``output_dtype`` is complex also over real samples, ``pnfb()`` has
+        shape (nchannels, tapsPer𝜙, polyorder+1) and ``tapsforphase`` (nchannels, tapsPer𝜙), both complex; the taps may change
+        between calls; ``reset()`` keeps them; going back to real taps is status 5.  Unbound: the taps are installed at ``bind``."""
+        who = "set_channel_ctaps_farrow"
+        ct = self._takes_ctaps_farrow(who)
+        H = _tap_matrix(np.asarray(H), who)
+        if H.shape != (len(self._rates), len(self.h)):
+            raise MultirateHIPError(1, f"{who} takes a {(len(self._rates), len(self.h))} matrix, one row of the filter's hLen taps per channel; got {H.shape}")
+        if H.dtype.kind != "c":
+            raise MultirateHIPError(1, f"{who} takes complex taps; real taps: set_channel_taps_farrow")
+        if H.dtype != ct:
+            raise MultirateHIPError(1, f"{who} takes taps of the complex type of the filter's tap precision, {ct}; got {H.dtype}")
+        self._strict_for_ctaps(who)
+        H = np.ascontiguousarray(H).copy()
+        if self._handle is not None:
+            self._install_chan_farrow("ctaps", H)
+        self._chan_farrow, self._farrow_ctaps = ("ctaps", H), True
+
+    def set_channel_pnfb_ctaps(self, PN):
+        """Caller-fitted COMPLEX per-channel polynomial banks on a filter of ``per_channel_rates_farrow``
+        (``mrhip_set_channel_pnfb_ctaps``; waits for the filter's stream): ``PN`` is complex of shape (nchannels, tapsPer𝜙,
+        polyorder+1), ascending powers; every component is rounded to the filter's tap precision as a handed-over complex ``pnfb``
+        is.  The filter becomes complex64 over float32 taps and complex128 over float64 taps.  Everything else as
+        ``set_channel_ctaps_farrow``."""
+        who = "set_channel_pnfb_ctaps"
+        self._takes_ctaps_farrow(who)
+        PN = np.asarray(PN)
+        want = (len(self._rates), self.tapsPerPhi, self.polyorder + 1)
+        if PN.shape != want:
+            raise MultirateHIPError(1, f"{who} takes banks of shape (nchannels, tapsPerPhi, polyorder+1) = {want}; got {PN.shape}")
+        if PN.dtype.kind != "c":
+            raise MultirateHIPError(1, f"{who} takes complex banks; real banks: set_channel_pnfb")
+        self._strict_for_ctaps(who)
+        PN = np.ascontiguousarray(PN, dtype=np.complex128).copy()
+        if self._handle is not None:
+            self._install_chan_farrow("cpnfb", PN)
+        self._chan_farrow, self._farrow_ctaps = ("cpnfb", PN), True
+
+    def set_channel_pnfb_ctaps_device(self, PN):
+        """Complex per-channel polynomial banks from DEVICE memory on a filter of ``per_channel_rates_farrow``
+        (``mrhip_set_channel_pnfb_ctaps_device``), enqueued on torch's current stream: ``PN`` is a contiguous complex128 CUDA tensor of
+        shape (nchannels, tapsPer𝜙, polyorder+1), rounded per component to the filter's tap precision on the device as
+        ``set_channel_pnfb_ctaps`` rounds on the host.  The first call on a filter that holds no complex banks yet allocates them and
+        waits once; every later call only enqueues a kernel.  ``pnfb()`` and ``tapsforphase`` read the banks back."""
+        who = "set_channel_pnfb_ctaps_device"
+        self._takes_ctaps_farrow(who)
+        shape = (len(self._rates), self.tapsPerPhi, self.polyorder + 1)
+        stream = self._device_update_args(who, PN, np.complex128, shape)
+        self._strict_for_ctaps(who)
+        _check(self._lib.mrhip_set_channel_pnfb_ctaps_device(self._handle, C.c_void_p(PN.data_ptr()), self.tapsPerPhi, self.polyorder, C.c_void_p(stream)))
+        self._chan_farrow, self._farrow_ctaps = _DeviceResident(shape), True
 
     def outputlength_bound(self, inputlength: int) -> int:
         """The largest per-channel output count a call of ``inputlength`` samples can have whatever the stream state

@@ -16,7 +16,8 @@ export FIRFilter, FIRKernel, FIRStandard, FIRDecimator, FIRInterpolator, FIRRati
        filt, filt!, taps2pfb, outputlength, inputlength, reset, nextphase, setphase, tapsforphase, tapsforphase!, polyfit,
        firdes, firprototype, kaiserlength, kaiser, FIRResponse, LOWPASS, BANDPASS, HIGHPASS, BANDSTOP,
        FilterCascade, filt_device!, filt_device_chunked!, scheduleinfo, advancestate!, ChunkRing, pushchunks!, drain, ringinfo, ShardedFIRFilter,
-       RatesFIRFilter, channelstates, setchannelstates!, setrates!, set_channel_ctaps!, set_channel_ctaps_device!
+       RatesFIRFilter, channelstates, setchannelstates!, setrates!, set_channel_ctaps!, set_channel_ctaps_device!,
+       set_channel_ctaps_farrow!, set_channel_pnfb_ctaps!, set_channel_pnfb_ctaps_device!
 
 const libmr = get(ENV, "MRHIP_LIB_PATH", joinpath(@__DIR__, "..", "libmultirate_hip.so"))
 
@@ -546,12 +547,13 @@ mutable struct RatesFIRFilter{Th}
     handle::Ptr{Cvoid}
     Tx::Union{DataType,Nothing}
     CH::Union{Nothing,Matrix{Complex{Th}}}  # COMPLEX per-channel taps (set_channel_ctaps!, FIRArbitrary): one column of hLen taps per channel, installed at bind! behind H
-    ctaps::Bool                     # the filter holds complex taps (set_channel_ctaps!, set_channel_ctaps_device!): the outputs are complex also over real samples
+    ctaps::Bool                     # the filter holds complex taps (set_channel_ctaps!, set_channel_ctaps_device!; FIRFarrow: set_channel_ctaps_farrow!, set_channel_pnfb_ctaps!, set_channel_pnfb_ctaps_device!): the outputs are complex also over real samples
+    CPN::Union{Nothing,Array{ComplexF64,3}}  # COMPLEX per-channel caller-fitted banks (set_channel_pnfb_ctaps!, FIRFarrow): (polyorder+1) x tapsPer𝜙 x nchannels, installed at bind!
 end
 function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer = 32; device::Integer = 0) where {Th<:Union{Float32,Float64}}
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
-    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing, nothing, false)
+    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, -1, device, C_NULL, nothing, nothing, false, nothing)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 # FIRFilter(h, rates::Vector, N𝜙, polyorder): one FIRFilter(h, rates[c], N𝜙, polyorder) -- FIRFarrow -- per channel behind one object
@@ -560,7 +562,7 @@ function FIRFilter(h::Vector{Th}, rates::Vector{<:AbstractFloat}, Nphi::Integer,
     isempty(rates) && error("one rate per channel, at least one")
     all(r -> r > 0.0, rates) || error("rate must be greater than 0")
     0 <= polyorder <= min(32, Nphi - 1) || error("polyorder must be in 0..min(32, Nphi-1)")
-    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing, nothing, false)
+    f = RatesFIRFilter{Th}(copy(h), nothing, nothing, Vector{Float64}(rates), Nphi, polyorder, device, C_NULL, nothing, nothing, false, nothing)
     finalizer(f -> (f.handle == C_NULL || ccall((:mrhip_destroy, libmr), Cvoid, (Ptr{Cvoid},), f.handle); f.handle = C_NULL; nothing), f)
 end
 function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
@@ -581,7 +583,8 @@ function bind!(f::RatesFIRFilter{Th}, ::Type{Tx}) where {Th,Tx}
     f.handle, f.Tx = out[], Tx
     f.H === nothing || (f.polyorder >= 0 ? set_channel_taps_farrow!(f, f.H) : set_channel_taps!(f, f.H))
     f.PN === nothing || set_channel_pnfb!(f, f.PN)
-    f.CH === nothing || set_channel_ctaps!(f, f.CH)
+    f.CH === nothing || (f.polyorder >= 0 ? set_channel_ctaps_farrow!(f, f.CH) : set_channel_ctaps!(f, f.CH))
+    f.CPN === nothing || set_channel_pnfb_ctaps!(f, f.CPN)
     f
 end
 # the element type of the outputs: promote_out(Th, Tx), or its complex type once the filter holds complex taps
@@ -652,6 +655,34 @@ end
 function set_channel_ctaps_device!(f::RatesFIRFilter{Th}, h::Ptr{Complex{Th}}, stream::Ptr{Cvoid} = C_NULL) where {Th}
     f.handle == C_NULL && error("set_channel_ctaps_device! needs a bound filter")
     check(ccall((:mrhip_set_channel_ctaps_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}), f.handle, h, length(f.h), dtypecode(Complex{Th}), stream))
+    f.ctaps = true
+    f
+end
+# the same for FIRFarrow (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps, mrhip_set_channel_pnfb_ctaps_device;
+# include/multirate_hip.h, "Complex per-channel taps with per-channel rates for FIRFarrow"): column c of H is channel c's
+# h_c::Vector{Complex{Th}}, fitted on its own per component; PN[:, i, c] holds the polyorder+1 complex coefficients of channel c's
+# polynomial i, ascending powers (in memory (re, im) pairs of Float64, the C layout), rounded per component to Th.  Every channel keeps
+# its phase, deficit, rate and history; from the next call on the outputs are complex, also over real samples; the banks may change
+# between calls; reset keeps them; going back to real taps is refused.  An unbound filter installs them at bind! (whichever call came
+# last).  The device call takes a device pointer of PN's layout and needs a bound filter.
+function set_channel_ctaps_farrow!(f::RatesFIRFilter{Th}, H::Matrix{Complex{Th}}) where {Th}
+    f.polyorder >= 0 || error("set_channel_ctaps_farrow!: FIRFarrow only (FIRArbitrary: set_channel_ctaps!)")
+    size(H) == (length(f.h), length(f.rates)) || error("H takes one column of $(length(f.h)) taps per channel")
+    f.handle == C_NULL || check(ccall((:mrhip_set_channel_ctaps_farrow, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint), f.handle, H, size(H, 1), dtypecode(Complex{Th})))
+    f.CH, f.CPN, f.ctaps = copy(H), nothing, true
+    f
+end
+function set_channel_pnfb_ctaps!(f::RatesFIRFilter{Th}, PN::Array{ComplexF64,3}) where {Th}
+    f.polyorder >= 0 || error("set_channel_pnfb_ctaps!: FIRFarrow only")
+    T = cld(length(f.h), f.Nphi)
+    size(PN) == (f.polyorder + 1, T, length(f.rates)) || error("PN takes (polyorder+1) x tapsPerPhi x nchannels = $((f.polyorder + 1, T, length(f.rates)))")
+    f.handle == C_NULL || check(ccall((:mrhip_set_channel_pnfb_ctaps, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64), f.handle, PN, T, f.polyorder))
+    f.CPN, f.CH, f.ctaps = copy(PN), nothing, true
+    f
+end
+function set_channel_pnfb_ctaps_device!(f::RatesFIRFilter, pnfb::Ptr{ComplexF64}, stream::Ptr{Cvoid} = C_NULL)
+    f.handle == C_NULL && error("set_channel_pnfb_ctaps_device! needs a bound filter")
+    check(ccall((:mrhip_set_channel_pnfb_ctaps_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}), f.handle, pnfb, cld(length(f.h), f.Nphi), f.polyorder, stream))
     f.ctaps = true
     f
 end
