@@ -669,7 +669,9 @@ int mrhip_filt_device_rates(mrhip_filter *f, const void *x, int64_t x_len, int64
  *     mrhip_set_channel_states, mrhip_set_channel_rates and mrhip_reset are those of mrhip_filt_device_rates, and the two calls mix
  *     freely on one filter.  A ragged call sizes its grid by the longest channel and skips the tiles behind a channel's count;
  *   - left out on purpose: lengths that live on the device; compacting the tiles of channels that end early; graph capture,
- *     cascades, rings and sharding. */
+ *     cascades, rings and sharding.  (Since added: lengths that live on the device, and such a filter behind another filter --
+ *     mrhip_filt_device_rates_lens_device and mrhip_filt_device_rates_chained, "Input lengths from device memory, and chaining, for
+ *     the filters with per-channel rates" below.) */
 int mrhip_filt_device_rates_ragged(mrhip_filter *f, const void *x, const int64_t *x_lens /* HOST, [nchannels] */, int64_t x_stride,
                                    void *y, int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream);
 /* the nchannels states of such a filter, after waiting for the filter's stream; MRHIP_ERR_BUFFER_TOO_SMALL if a channel's walk ever
@@ -824,7 +826,8 @@ int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb /* [nchannels][ta
  *     still sixteen constructors;
  *   - left out on purpose: input lengths that live on the device; the FIRFarrow fit on the device (a mrhip_set_channel_taps_farrow
  *     twin); updates from a stream other than the one the filter's calls run on without ordering by the caller (the device arrays are
- *     read on `stream`); graph capture; complex taps; the parallel schedule for long channels. */
+ *     read on `stream`); graph capture; complex taps; the parallel schedule for long channels.  (Since added: input lengths that
+ *     live on the device, mrhip_filt_device_rates_lens_device below; complex taps, the two sections that follow.) */
 int mrhip_set_channel_rates_device(mrhip_filter *f, const double *rates /* DEVICE, [nchannels] */, double rate_lo, double rate_hi, void *stream);
 int mrhip_set_channel_taps_device(mrhip_filter *f, const void *h /* DEVICE, [nchannels][hLen] */, int64_t hLen, int tap_dtype, void *stream);
 int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb /* DEVICE, [nchannels][tapsPerPhi][polyorder+1] */, int64_t tapsPerPhi,
@@ -951,6 +954,55 @@ int mrhip_set_channel_pnfb_ctaps(mrhip_filter *f, const double *pnfb /* [nchanne
                                  int64_t polyorder);
 int mrhip_set_channel_pnfb_ctaps_device(mrhip_filter *f, const double *pnfb /* DEVICE, same layout */, int64_t tapsPerPhi, int64_t polyorder,
                                         void *stream);
+/* Input lengths from device memory, and chaining, for the filters with per-channel rates (mrhip_create_arbitrary_rates,
+ * mrhip_create_farrow_rates*, with shared, per-channel or complex per-channel taps).  Rates, taps and polynomial banks arrive from device
+ * memory in stream order (above); the input LENGTHS of mrhip_filt_device_rates_ragged are a HOST array, so a length computed on the GPU
+ * -- a burst detector's count, a jitter buffer's fill level, the output counts of an earlier filter -- had to travel to the host and be
+ * waited for.  The two calls below fill the filter's device array of lengths by a kernel (rates_lens_set_kernel, one lane per channel)
+ * in the place of the copy from the host; everything behind it is the ragged call.  They remove the last host round trip from the loop
+ * of filter call, tracker, update, filter call.  No new constructor; the ABI version stays 1.
+ *   - mrhip_filt_device_rates_lens_device is mrhip_filt_device_rates_ragged with x_lens in DEVICE memory, read in stream order: the
+ *     array must hold its values by the time `stream` reaches the call and may be overwritten by work enqueued on `stream` afterwards.
+ *     The host cannot see the values, so the caller declares their maximum, x_len_max, which takes the place of "the largest of
+ *     x_lens" in every check of the ragged call -- fewer than 2^31-1 samples, x_stride >= x_len_max for nchannels > 1, the bound
+ *     mrhip_outputlength_bound(f, x_len_max) <= 2^24, y_capacity and y_stride at least that bound -- and in the sizing of the launch
+ *     and of the tiled kernels' plans;
+ *   - on the device channel c reads l = x_lens[c]; 0 <= l <= x_len_max: the channel is fed x_c[0 : l).  Any other value -- negative,
+ *     above the declared maximum -- feeds the channel NOTHING in this call, which is the ragged call's length 0: state and history are
+ *     kept, the count is 0, and the channel's record receives a sticky "length refused" mark.  A refused value never reaches the walk,
+ *     the history fold or a filter kernel;
+ *   - after the import the call is the ragged call: the same launches, the same kernel names from mrhip_last_kernel_name, the same
+ *     timing bracket (the import kernel runs in front of it).  Parity: channel c is bit for bit the one-channel filter fed
+ *     x_c[0 : l_c) -- outputs, count, end state, history -- under STRICT and FUSED, for both families, for shared, per-channel and
+ *     complex per-channel taps.  The call mixes freely with mrhip_filt_device_rates and mrhip_filt_device_rates_ragged on one filter;
+ *   - host waits: only where mrhip_filt_device_rates waits (growth of the schedule buffers).  No pinned staging slot is used;
+ *   - reporting: mrhip_get_channel_states returns MRHIP_ERR_INVALID_ARG while a record holds the mark ("a device-resident LENGTH was
+ *     refused ... the channel was fed nothing"; the states are filled in all the same).  An overrun and a refused rate keep their
+ *     answers and go first, in that order.  mrhip_set_channel_states and mrhip_reset clear the mark as they clear the others;
+ *   - refused before anything is enqueued or any state moves, each with a message that names the function: a NULL f or x_lens, a filter
+ *     without per-channel rates, a negative x_len_max or y_capacity, x NULL with x_len_max above 0, x_stride below x_len_max for
+ *     nchannels > 1 (all MRHIP_ERR_INVALID_ARG); x_len_max of 2^31-1 or more, a capturing stream, a bound above 2^24
+ *     (MRHIP_ERR_UNSUPPORTED); capacity or stride below the bound (MRHIP_ERR_BUFFER_TOO_SMALL);
+ *   - mrhip_filt_device_rates_chained: f has per-channel rates; its input x is what prev's latest call wrote, earlier on the same
+ *     stream, and its lengths are that call's counts, taken on the device.
+ *       prev with per-channel rates: the same nchannels and device; the length of channel c is the `count` of prev's record c.  The
+ *       records hold the counts of prev's LATEST call: the chained call must be enqueued between that call of prev and prev's next one
+ *       on the stream.  A prev that has not been called since its creation or mrhip_reset is refused.
+ *       prev a one-state filter: the same nchannels, and its latest call was planned on the device (mrhip_filt_device_async, a call
+ *       under capture: the condition of mrhip_filt_device_chained); every channel is fed that call's one count.
+ *     x_len_bound = mrhip_outputlength_bound(prev, prev's (largest) input length) plays x_len_max's part in every check above,
+ *     including the refusal on the device of a count above it.  Refused on the host, ahead of any launch and in this function's name
+ *     (MRHIP_ERR_INVALID_ARG): prev == f, different channel counts or devices, f's sample dtype other than prev's output dtype, the two
+ *     cases of prev above; then the refusals of mrhip_filt_device_rates_lens_device.  Parity: channel c of f is bit for bit the
+ *     one-channel filter fed the outputs of prev's channel c, call after call; prev is not touched.  mrhip_filt_device_chained and
+ *     mrhip_cascade_create keep refusing filters with per-channel rates;
+ *   - left out on purpose: graph capture of these filters; compacting the tiles of channels that end early; a one-state filter
+ *     BEHIND a filter with per-channel rates (one length against many counts); mrhip_cascade_*, rings and sharding; the parallel
+ *     schedule for long channels. */
+int mrhip_filt_device_rates_lens_device(mrhip_filter *f, const void *x, const int64_t *x_lens /* DEVICE, [nchannels] */, int64_t x_len_max,
+                                        int64_t x_stride, void *y, int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream);
+int mrhip_filt_device_rates_chained(mrhip_filter *f, const mrhip_filter *prev, const void *x, int64_t x_len_bound, int64_t x_stride,
+                                    void *y, int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream);
 /* wait for everything the filter has enqueued (after a HIP-graph capture of one of its calls: for the device -- replays run
  * on streams the library never saw) and take the device-resident stream state over into the host object;
  * *last_n_written (optional) receives the per-channel count of the last call.  Returns the status of a device-planned call

@@ -774,6 +774,7 @@ int mrhip_reset(mrhip_filter *f)
     auto rates_too = [&](int rc) -> int {
         if (rc != MRHIP_OK || !f->rates) return rc;
         MRHIP_CHECK_HIP(launch_rates_reset(f->d_rrec, static_cast<int>(f->nch), f->last_stream));
+        f->rates_called = false;                       // (the records hold no call's counts: mrhip_filt_device_rates_chained)
         return MRHIP_OK;
     };
     if (fast) {
@@ -1780,14 +1781,21 @@ int64_t mrhip_outputlength_bound(const mrhip_filter *f, int64_t inputlength)
 // The channels' lengths of a ragged call: kRatesRaggedSlots pinned host slots of nch lengths each, used in turn, and the filter's ONE
 // device array the kernels read.  A slot is guarded by an event recorded behind its upload: the only host wait of a ragged call beyond
 // mrhip_filt_device_rates' own is for a slot whose upload, kRatesRaggedSlots calls back, has not run yet.
-static int ragged_staging(mrhip_filter *f)
+static int ragged_lengths_array(mrhip_filter *f)      // the device array alone: all a call needs whose lengths a kernel writes
 {
     if (f->d_xlens) return MRHIP_OK;
+    MRHIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&f->d_xlens), static_cast<size_t>(f->nch) * sizeof(long long)));
+    return MRHIP_OK;
+}
+
+static int ragged_staging(mrhip_filter *f)
+{
+    if (f->rag_pin) return MRHIP_OK;
     const size_t row = static_cast<size_t>(f->nch) * sizeof(long long);
-    if (!f->rag_pin) MRHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&f->rag_pin), row * kRatesRaggedSlots, hipHostMallocDefault));
     for (hipEvent_t &e : f->rag_ev)
         if (!e) MRHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    MRHIP_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&f->d_xlens), row));
+    if (int rc = ragged_lengths_array(f)) return rc;
+    MRHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&f->rag_pin), row * kRatesRaggedSlots, hipHostMallocDefault));
     return MRHIP_OK;
 }
 
@@ -1805,6 +1813,16 @@ static int ragged_upload(mrhip_filter *f, const int64_t *h_lens, hipStream_t str
     return MRHIP_OK;
 }
 
+// ... or, where the lengths live on the device (mrhip_filt_device_rates_lens_device / _chained): the import kernel moves them from their
+// source into the device array in stream order -- the accepted length, or 0 and the record's mark (rates_lens_set_kernel)
+static int ragged_import(mrhip_filter *f, const RatesLensArgs &import, int64_t len_max, hipStream_t stream)
+{
+    RatesLensArgs la = import;
+    la.rec = f->d_rrec; la.x_lens = f->d_xlens; la.len_max = len_max; la.nch = static_cast<int>(f->nch);
+    MRHIP_CHECK_HIP(launch_rates_lens_set(la, stream));
+    return MRHIP_OK;
+}
+
 // the smallest rate the tiled kernels' plans size their spans for: the smallest of the rates the host installed, or the lower end of the
 // range the caller declared for rates that came from device memory (mrhip_set_channel_rates_device)
 static double rates_min(const mrhip_filter *f)
@@ -1814,14 +1832,18 @@ static double rates_min(const mrhip_filter *f)
 
 // What both entry points enqueue once their checks are through.  x_len: the call's one length, or the largest of h_lens (HOST, [nch]: a
 // ragged call); bound: mrhip_outputlength_bound of it.
+// import: NULL, or the import of a call whose lengths come from device memory (mrhip_filt_device_rates_lens_device / _chained): a kernel
+// writes them into d_xlens where the upload of h_lens would stand -- the third case beside "one length" and "a host array".
 static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64_t *h_lens, int64_t x_stride, void *y, int64_t y_stride,
-                      int64_t bound, int64_t *counts_out, hipStream_t stream)
+                      int64_t bound, int64_t *counts_out, hipStream_t stream, const RatesLensArgs *import = nullptr)
 {
     if (int rc = adopt_stream(f, stream)) return rc;
     if (h_lens) {
         if (int rc = ragged_staging(f)) return rc;
+    } else if (import) {
+        if (int rc = ragged_lengths_array(f)) return rc;
     }
-    const long long *const d_lens = h_lens ? f->d_xlens : nullptr;
+    const long long *const d_lens = h_lens || import ? f->d_xlens : nullptr;
     const size_t entries = static_cast<size_t>(f->nch) * static_cast<size_t>(bound);
     if (entries > f->rs_cap) {
         const size_t cap = std::max<size_t>(entries + entries / 4, 4096);
@@ -1891,7 +1913,10 @@ static int rates_call(mrhip_filter *f, const void *x, int64_t x_len, const int64
     }
     if (h_lens) {
         if (int rc = ragged_upload(f, h_lens, stream)) return rc;
+    } else if (import) {
+        if (int rc = ragged_import(f, *import, x_len, stream)) return rc;
     }
+    f->rates_called = true;
     // (the timing bracket holds BOTH launches of the call: the walk is most of a long call)
     if (int rc = timing_mark(f, stream)) return rc;
     MRHIP_CHECK_HIP(launch_rates_schedule(sa, (f->Nphi & (f->Nphi - 1)) == 0, stream));
@@ -1976,6 +2001,69 @@ int mrhip_filt_device_rates_ragged(mrhip_filter *f, const void *x, const int64_t
     return rates_call(f, x, len_max, x_lens, x_stride, y, y_stride, bound, counts_out, stream);
 }
 
+// ---- Input lengths from device memory, and chaining (include/multirate_hip.h, "Input lengths from device memory, and chaining, for the
+// filters with per-channel rates") -----------------------------------------------------------------------------------------------------
+// What both calls do once their own checks are through: the device, stream and buffer checks of mrhip_filt_device_rates_ragged with the
+// declared maximum in the place of the largest length, every refusal in the name of `who`; then rates_call with the import in front of
+// the schedule kernel.  No pinned slot, and no host wait beyond mrhip_filt_device_rates' own (growth of the schedule buffers).
+static int rates_device_lengths_call(const char *who_, mrhip_filter *f, const void *x, int64_t len_max, int64_t x_stride, void *y, int64_t y_capacity,
+                                     int64_t y_stride, int64_t *counts_out, hipStream_t stream, const RatesLensArgs &import)
+{
+    const std::string who(who_);
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, who + ": hipSetDevice failed");
+    if (stream_is_capturing(stream))
+        return fail(MRHIP_ERR_UNSUPPORTED, who + ": a filter with per-channel rates is not captured into a HIP graph (its schedule buffers grow "
+                                                 "with the call)");
+    const int64_t bound = output_bound(f, len_max);
+    if (bound > (1LL << 24))
+        return fail(MRHIP_ERR_UNSUPPORTED, who + ": a call of a filter with per-channel rates holds at most 2^24 schedule entries per channel: "
+                                                 "feed shorter pieces");
+    if (y_capacity < bound)
+        return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small: " + who + " needs room for mrhip_outputlength_bound(the declared maximum "
+                                                "of the lengths) outputs per channel");
+    if (f->nch > 1 && y_stride < bound)
+        return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "buffer is too small: " + who + " needs y_stride >= mrhip_outputlength_bound(the declared "
+                                                "maximum of the lengths)");
+    if (bound > 0 && !y) return fail(MRHIP_ERR_INVALID_ARG, who + ": y is NULL");
+    return rates_call(f, x, len_max, nullptr, x_stride, y, y_stride, bound, counts_out, stream, &import);
+}
+
+// mrhip_filt_device_rates_ragged with the lengths read from DEVICE memory in stream order: rates_lens_set_kernel moves x_lens[c] into the
+// filter's array where it lies in [0, x_len_max], else feeds the channel nothing and marks its record.
+int mrhip_filt_device_rates_lens_device(mrhip_filter *f, const void *x, const int64_t *x_lens, int64_t x_len_max, int64_t x_stride, void *y,
+                                        int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream_)
+{
+    static const char *const who = "mrhip_filt_device_rates_lens_device";
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_lens_device: NULL filter");
+    if (!f->rates)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_lens_device takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates");
+    if (y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_lens_device: negative y_capacity");
+    if (Refusal r = check_device_lengths(who, x_lens == nullptr, x_len_max, x == nullptr, f->nch, x_stride)) return fail(r.status, r.message);
+    RatesLensArgs import{};
+    import.src = reinterpret_cast<const long long *>(x_lens);
+    import.source = kRatesLensCaller;
+    return rates_device_lengths_call(who, f, x, x_len_max, x_stride, y, y_capacity, y_stride, counts_out, static_cast<hipStream_t>(stream_), import);
+}
+
+// f behind prev on one stream: x is what prev's latest call wrote, the lengths are that call's counts -- record c of a prev with per-channel
+// rates, the ONE count in the call record of a one-state prev whose latest call was planned on the device -- taken by the import kernel.
+int mrhip_filt_device_rates_chained(mrhip_filter *f, const mrhip_filter *prev, const void *x, int64_t x_len_bound, int64_t x_stride, void *y,
+                                    int64_t y_capacity, int64_t y_stride, int64_t *counts_out, void *stream_)
+{
+    static const char *const who = "mrhip_filt_device_rates_chained";
+    if (!f || !prev) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_chained: NULL filter");
+    if (Refusal r = check_rates_chain(f->rates, prev == f, prev->rates, f->nch, prev->nch, f->device, prev->device, f->tx, prev->ty, prev->rates_called,
+                                      prev->last_call_dev_planned && prev->last_call_rec))
+        return fail(r.status, r.message);
+    if (y_capacity < 0) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_chained: negative y_capacity");
+    if (Refusal r = check_device_lengths(who, false, x_len_bound, x == nullptr, f->nch, x_stride)) return fail(r.status, r.message);
+    RatesLensArgs import{};
+    if (prev->rates) { import.prev_rec = prev->d_rrec; import.source = kRatesLensRecords; }
+    else { import.prev_call = prev->last_call_rec; import.source = kRatesLensCall; }
+    return rates_device_lengths_call(who, f, x, x_len_bound, x_stride, y, y_capacity, y_stride, counts_out, static_cast<hipStream_t>(stream_), import);
+}
+
 int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
 {
     if (!f || !out) return fail(MRHIP_ERR_INVALID_ARG, "NULL argument");
@@ -1984,7 +2072,7 @@ int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
     if (int rc = drain_filter(f)) return rc;          // the records are written by the filter's own last call
     std::vector<RateChannel> v(static_cast<size_t>(f->nch));
     MRHIP_CHECK_HIP(hipMemcpy(v.data(), f->d_rrec, v.size() * sizeof(RateChannel), hipMemcpyDeviceToHost));
-    bool overrun = false, rate_refused = false;
+    bool overrun = false, rate_refused = false, length_refused = false;
     for (size_t c = 0; c < v.size(); ++c) {
         const RateChannel &r = v[c];
         mrhip_channel_state &o = out[c];
@@ -1994,11 +2082,16 @@ int mrhip_get_channel_states(mrhip_filter *f, mrhip_channel_state *out)
         o.inputDeficit = r.inputDeficit; o.xIdx = r.xIdx; o.last_count = r.count;
         overrun = overrun || (r.error != 0 && r.error != MRHIP_ERR_INVALID_ARG);
         rate_refused = rate_refused || r.error == MRHIP_ERR_INVALID_ARG;
+        length_refused = length_refused || r.len_refused != 0;
     }
     if (overrun) return fail(MRHIP_ERR_BUFFER_TOO_SMALL, "a channel's schedule overran the bound of its call (outputs were clipped): mrhip_reset the filter");
     if (rate_refused)
         return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_rates_device: a device-resident rate was refused (not finite, or outside the declared "
                                            "[rate_lo, rate_hi]); the channel kept its rate: mrhip_set_channel_states or mrhip_reset clears this");
+    if (length_refused)
+        return fail(MRHIP_ERR_INVALID_ARG, "mrhip_filt_device_rates_lens_device / _chained: a device-resident LENGTH was refused (negative, or above the "
+                                           "declared maximum); the channel was fed nothing in that call: mrhip_set_channel_states or mrhip_reset "
+                                           "clears this");
     return MRHIP_OK;
 }
 
@@ -2018,7 +2111,7 @@ int mrhip_set_channel_states(mrhip_filter *f, const int64_t *inputDeficit, const
     if (int rc = drain_filter(f)) return rc;
     std::vector<RateChannel> v(static_cast<size_t>(f->nch));
     MRHIP_CHECK_HIP(hipMemcpy(v.data(), f->d_rrec, v.size() * sizeof(RateChannel), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < v.size(); ++c) { v[c].inputDeficit = inputDeficit[c]; v[c].acc = phiAccumulator[c]; v[c].error = 0; }
+    for (size_t c = 0; c < v.size(); ++c) { v[c].inputDeficit = inputDeficit[c]; v[c].acc = phiAccumulator[c]; v[c].error = 0; v[c].len_refused = 0; }
     MRHIP_CHECK_HIP(hipMemcpy(f->d_rrec, v.data(), v.size() * sizeof(RateChannel), hipMemcpyHostToDevice));
     return MRHIP_OK;
 }

@@ -95,6 +95,16 @@ Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow,
 // the length checks of mrhip_filt_device_rates_ragged, in its order: x_lens itself, every length (negative, then 2^31-1 and above), x
 // against the largest length, x_stride against it for nch > 1; *len_max: the largest length (what the call's bound is taken from)
 Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null, int64_t x_stride, int64_t *len_max);
+// Lengths the host never sees (the public header, "Input lengths from device memory, and chaining, for the filters with per-channel rates"):
+// the checks of check_ragged_lengths with the declared maximum in the place of the largest length, in the same order and in the name of
+// `who` (mrhip_filt_device_rates_lens_device: x_len_max; mrhip_filt_device_rates_chained: x_len_bound, and lens_is_null false): the
+// lengths' pointer, the maximum (negative, then 2^31-1 and above), x against it, x_stride against it for nch > 1
+Refusal check_device_lengths(const char *who, bool lens_is_null, int64_t len_max, bool x_is_null, int64_t nch, int64_t x_stride);
+// what mrhip_filt_device_rates_chained refuses about the pair (f, prev) ahead of the length checks, in its order: f without per-channel
+// rates, prev == f, the channel counts, the devices, f's sample dtype against prev's output dtype; then a prev with per-channel rates that
+// no call has moved since creation or reset, or a one-state prev whose latest call was not planned on the device
+Refusal check_rates_chain(bool f_is_rates, bool same_filter, bool prev_is_rates, int64_t f_nch, int64_t prev_nch, int f_device, int prev_device,
+                          int f_tx, int prev_ty, bool prev_called, bool prev_dev_planned);
 // The device-resident updates (the public header, "Device-resident updates for the filters with per-channel rates"): what the three calls
 // refuse before they look at the stream, each in its own name.
 // mrhip_set_channel_rates_device: f is a filter with per-channel rates, rates is there, and the declared range [rate_lo, rate_hi]

@@ -941,6 +941,36 @@ Refusal check_ragged_lengths(const int64_t *x_lens, int64_t nch, bool x_is_null,
     return {};
 }
 
+Refusal check_device_lengths(const char *who, bool lens_is_null, int64_t len_max, bool x_is_null, int64_t nch, int64_t x_stride)
+{
+    const std::string w(who);
+    const bool chained = w == "mrhip_filt_device_rates_chained";
+    const char *name = chained ? "x_len_bound" : "x_len_max";
+    if (lens_is_null) return {MRHIP_ERR_INVALID_ARG, w + ": x_lens is NULL"};
+    if (len_max < 0) return {MRHIP_ERR_INVALID_ARG, w + ": negative " + name + " (the declared maximum of the lengths must be >= 0)"};
+    if (len_max >= 0x7fffffffLL) return {MRHIP_ERR_UNSUPPORTED, w + ": a call takes fewer than 2^31-1 samples per channel"};
+    if (len_max > 0 && x_is_null) return {MRHIP_ERR_INVALID_ARG, w + ": x is NULL"};
+    if (nch > 1 && x_stride < len_max) return {MRHIP_ERR_INVALID_ARG, w + ": x_stride < " + name};
+    return {};
+}
+
+Refusal check_rates_chain(bool f_is_rates, bool same_filter, bool prev_is_rates, int64_t f_nch, int64_t prev_nch, int f_device, int prev_device,
+                          int f_tx, int prev_ty, bool prev_called, bool prev_dev_planned)
+{
+    const std::string w("mrhip_filt_device_rates_chained");
+    if (!f_is_rates) return {MRHIP_ERR_INVALID_ARG, w + " takes a filter of mrhip_create_arbitrary_rates or mrhip_create_farrow_rates"};
+    if (same_filter) return {MRHIP_ERR_INVALID_ARG, w + ": prev is the filter itself"};
+    if (f_nch != prev_nch) return {MRHIP_ERR_INVALID_ARG, w + ": the two filters have different numbers of channels"};
+    if (f_device != prev_device) return {MRHIP_ERR_INVALID_ARG, w + ": the two filters live on different devices"};
+    if (f_tx != prev_ty) return {MRHIP_ERR_INVALID_ARG, w + ": the filter's sample dtype is not the previous filter's output dtype"};
+    if (prev_is_rates && !prev_called)
+        return {MRHIP_ERR_INVALID_ARG, w + ": the previous filter has not been called since its creation or mrhip_reset: its records hold no call's counts"};
+    if (!prev_is_rates && !prev_dev_planned)
+        return {MRHIP_ERR_INVALID_ARG, w + ": the previous filter's latest call was not planned on the device (mrhip_filt_device_async, or a call "
+                                           "under capture): its count is not in its call record"};
+    return {};
+}
+
 Refusal create_check_params(const CreateEntry &e, int64_t hLen, int64_t nch, CreateParams *p)
 {
     if (e.family == kCreateRational) {

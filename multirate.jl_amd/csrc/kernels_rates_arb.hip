@@ -91,6 +91,7 @@ __global__ __launch_bounds__(kRatesSchedThreads) void rates_reset_kernel(RateCha
     const int c = static_cast<int>(blockIdx.x) * kRatesSchedThreads + static_cast<int>(threadIdx.x);
     if (c >= nch) return;
     rec[c].acc = 1.0; rec[c].inputDeficit = 1; rec[c].xIdx = 1; rec[c].count = 0; rec[c].error = 0;    // Filters.jl:110-115
+    rec[c].len_refused = 0;
 }
 
 // mrhip_set_channel_rates_device: the rate of channel c from DEVICE memory, in stream order.  A value that is finite and inside the range
@@ -105,6 +106,22 @@ __global__ __launch_bounds__(kRatesSchedThreads) void rates_set_kernel(RateChann
     const double r = rates[c];
     if (r >= lo && r <= hi) { rec[c].rate = r; rec[c].delta = N / r; }      // Filters.jl:113
     else if (rec[c].error == 0) rec[c].error = MRHIP_ERR_INVALID_ARG;
+}
+
+// mrhip_filt_device_rates_lens_device, mrhip_filt_device_rates_chained: the length of channel c from DEVICE memory, in stream order, into
+// the filter's array of lengths that the ragged schedule kernel and the filter kernels behind it read.  The value comes from the caller's
+// array, from record c of the previous filter (its latest call's count) or from the previous one-state filter's call record (one count
+// for every channel).  rates_length_accepted (rates_arb.h) decides: an accepted value is stored; any other stores 0 -- the channel is fed
+// nothing, as by a ragged call's length 0 -- and marks the record.  Nothing else of the record is touched; every lane stores to its own
+// channel's words only.
+__global__ __launch_bounds__(kRatesSchedThreads) void rates_lens_set_kernel(RatesLensArgs a)
+{
+    const int c = static_cast<int>(blockIdx.x) * kRatesSchedThreads + static_cast<int>(threadIdx.x);
+    if (c >= a.nch) return;
+    const long long l = a.source == kRatesLensCaller ? a.src[c] : a.source == kRatesLensRecords ? a.prev_rec[c].count : a.prev_call->n_out;
+    const bool ok = rates_length_accepted(l, a.len_max);
+    a.x_lens[c] = ok ? l : 0;
+    if (!ok) a.rec[c].len_refused = 1;
 }
 
 // One lane per (channel, output), any (Nphi, T, hLen, rates): blockIdx.x covers the outputs up to the call's bound, blockIdx.y strides
@@ -266,6 +283,13 @@ hipError_t launch_rates_set(RateChannel *rec, const double *rates, double lo, do
 {
     const dim3 grid(static_cast<unsigned>((nch + kRatesSchedThreads - 1) / kRatesSchedThreads));
     hipLaunchKernelGGL(rates_set_kernel, grid, dim3(kRatesSchedThreads), 0, st, rec, rates, lo, hi, N, nch);
+    return hipGetLastError();
+}
+
+hipError_t launch_rates_lens_set(const RatesLensArgs &l, hipStream_t st)
+{
+    const dim3 grid(static_cast<unsigned>((l.nch + kRatesSchedThreads - 1) / kRatesSchedThreads));
+    hipLaunchKernelGGL(rates_lens_set_kernel, grid, dim3(kRatesSchedThreads), 0, st, l);
     return hipGetLastError();
 }
 

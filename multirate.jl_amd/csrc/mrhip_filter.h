@@ -49,6 +49,9 @@ struct mrhip_filter {
     hipEvent_t rag_ev[mrhip::kRatesRaggedSlots] = {};
     bool rag_busy[mrhip::kRatesRaggedSlots] = {};
     int rag_next = 0;
+    // (mrhip_filt_device_rates_lens_device / _chained fill d_xlens by a kernel: the array alone, no slot.)  rates_called: a call has moved the
+    // records since creation or mrhip_reset, so their `count` is a call's (what a filter chained behind this one takes its lengths from)
+    bool rates_called = false;
 
     // device memory
     void *d_taps = nullptr, *d_dtaps = nullptr;            // (inside d_taps_alloc / d_dtaps_alloc: kTapPad zero elements either side)

@@ -18,7 +18,7 @@ struct RateChannel {
     long long inputDeficit, xIdx;  // 1-based, reference field names
     long long count;               // outputs of the latest call
     long long error;               // sticky: a call whose walk ran past the slice its bound gave it (mrhip_get_channel_states reports it)
-    long long pad;
+    long long len_refused;         // sticky, apart from `error`: a device-resident LENGTH of this channel was refused (rates_lens_set_kernel)
 };
 static_assert(sizeof(RateChannel) == 64, "one record a cache line half");
 
@@ -62,6 +62,27 @@ MRHIP_RATES_HD inline HistSource rates_hist_source(long long i, long long len, i
 struct RatesHistSource {           // the rule as the argument of dev::shiftin_ragged_by_last_workgroup (pair_device.h)
     MRHIP_RATES_HD HistSource operator()(long long i, long long len, int H) const { return rates_hist_source(i, len, H); }
 };
+
+// ---- Input lengths from device memory, and chaining (mrhip_filt_device_rates_lens_device, mrhip_filt_device_rates_chained;
+// include/multirate_hip.h, "Input lengths from device memory, and chaining, for the filters with per-channel rates") ---------------------
+// The acceptance rule of a length the host never saw: channel c is fed l samples where 0 <= l <= len_max (the maximum the caller
+// declared, for which the launch is sized and the buffers were checked); any other value feeds the channel NOTHING in this call.  The
+// import kernel (rates_lens_set_kernel, kernels_rates_arb.hip) and tests/rates_device_lengths_check.cpp run this text.
+MRHIP_RATES_HD inline bool rates_length_accepted(long long l, long long len_max) { return l >= 0 && l <= len_max; }
+
+enum RatesLensSource { kRatesLensCaller = 0, kRatesLensRecords = 1, kRatesLensCall = 2 };
+struct RatesLensArgs {             // the import kernel: one lane per channel
+    RateChannel *rec;              // [nch]: the filter's records (the mark of a refused length)
+    long long *x_lens;             // [nch]: the filter's device array of lengths, which the schedule and filter kernels of the call read
+    const long long *src;          // kRatesLensCaller: the caller's lengths, DEVICE, [nch]
+    const RateChannel *prev_rec;   // kRatesLensRecords: the records of the previous filter (per-channel rates), [nch]: `count`
+    const DevCall *prev_call;      // kRatesLensCall: the call record of the previous one-state filter: `n_out`, for every channel
+    long long len_max;
+    int nch;
+    int source;                    // RatesLensSource
+};
+// kernels_rates_arb.hip: the accepted length, or 0 and the mark, into x_lens[c], in stream order
+hipError_t launch_rates_lens_set(const RatesLensArgs &l, hipStream_t st);
 
 // What TypeKey::bank chooses on the launch side of a family, read in ONE place per unit (rates_key there): the kernels' BANK argument,
 // the names mrhip_last_kernel_name reports and the values of the family's two environment switches.

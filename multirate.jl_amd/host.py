@@ -111,6 +111,8 @@ ABI = [
     *_create_rows(),
     ("mrhip_filt_device_rates", _i, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     ("mrhip_filt_device_rates_ragged", _i, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    ("mrhip_filt_device_rates_lens_device", _i, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    ("mrhip_filt_device_rates_chained", _i, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     ("mrhip_get_channel_states", _i, [_vp, _vp]),
     ("mrhip_set_channel_states", _i, [_vp, _vp, _vp]),
     ("mrhip_set_channel_rates", _i, [_vp, _vp]),
@@ -964,9 +966,9 @@ class FIRFilter:
         _check(self._lib.mrhip_filt_host(self._handle, _ptr(x), n, n, _ptr(buffer), cap, cap, C.byref(nw)))
         return nw.value
 
-    def _filt_into_rates(self, buffer, x, counts=None, lengths=None):
-        """``mrhip_filt_device_rates`` (with ``lengths``: ``mrhip_filt_device_rates_ragged``) on torch's current stream; returns the
-        int64 device tensor of the counts without waiting.  ``lengths`` may be reused as soon as the call returns."""
+    def _rates_call_args(self, buffer, x, counts):
+        """what the calls of a filter with per-channel rates share: the checks of x, buffer and counts, and (nchannels, samples per row,
+        x stride, capacity, y stride, counts, stream)"""
         if not _is_torch(x) or not x.is_cuda or not _is_torch(buffer) or not buffer.is_cuda:
             raise MultirateHIPError(1, "a filter with per-channel rates takes torch device tensors")
         if (x.shape[-1] > 0 and x.stride(-1) != 1) or (buffer.shape[-1] > 0 and buffer.stride(-1) != 1):      # (an empty row has no stride to speak of)
@@ -986,7 +988,12 @@ class FIRFilter:
             counts = torch.empty(nch, dtype=torch.int64, device=x.device)
         elif not (_is_torch(counts) and counts.is_cuda and counts.dtype == torch.int64 and counts.numel() >= nch and counts.is_contiguous()):
             raise MultirateHIPError(1, "counts must be a contiguous int64 CUDA tensor of nchannels elements")
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        return nch, n, xs, cap, ys, counts, torch.cuda.current_stream(x.device).cuda_stream
+
+    def _filt_into_rates(self, buffer, x, counts=None, lengths=None):
+        """``mrhip_filt_device_rates`` (with ``lengths``: ``mrhip_filt_device_rates_ragged``) on torch's current stream; returns the
+        int64 device tensor of the counts without waiting.  ``lengths`` may be reused as soon as the call returns."""
+        nch, n, xs, cap, ys, counts, stream = self._rates_call_args(buffer, x, counts)
         if lengths is not None:
             lens = np.ascontiguousarray(lengths, dtype=np.int64)
             if lens.shape != (nch,):
@@ -998,6 +1005,54 @@ class FIRFilter:
             return counts
         _check(self._lib.mrhip_filt_device_rates(self._handle, C.c_void_p(x.data_ptr()), n, xs, C.c_void_p(buffer.data_ptr()), cap, ys,
                                                  C.c_void_p(counts.data_ptr()), C.c_void_p(stream)))
+        return counts
+
+    def filt_rates_async(self, buffer, x, *, lengths=None, max_length=None, after=None, counts=None):
+        """A call of a filter with per-channel rates whose input lengths the host never sees, enqueued on torch's current stream; returns
+        the int64 device tensor of the counts WITHOUT waiting.  Exactly one of the two sources is given:
+
+        ``lengths``: a CUDA int64 tensor of ``nchannels`` lengths, read in stream order (it may be produced by work enqueued just before
+        the call and overwritten by work enqueued after it), with ``max_length``, the declared maximum of its values: ``buffer`` needs
+        ``outputlength_bound(max_length)`` per row.  Channel c is fed ``x[c, :lengths[c]]``; a value outside ``[0, max_length]`` feeds
+        the channel nothing in this call and makes ``channel_states`` raise until ``set_channel_states`` or ``reset()``
+        (``mrhip_filt_device_rates_lens_device``).
+
+        ``after=prev``: ``x`` is the buffer ``prev``'s latest call on this stream wrote, and the lengths are that call's counts, taken
+        on the device -- per channel from a ``prev`` with per-channel rates, the one count of a one-state ``prev`` whose latest call was
+        ``filt_into_async``.  ``max_length`` (default: the row length of ``x``) is ``prev.outputlength_bound`` of ``prev``'s (largest)
+        input length (``mrhip_filt_device_rates_chained``)."""
+        if self._rates is None:
+            raise MultirateHIPError(1, "filt_rates_async needs a filter of FIRFilter.per_channel_rates or FIRFilter.per_channel_rates_farrow")
+        if (lengths is None) == (after is None):
+            raise MultirateHIPError(1, "filt_rates_async takes exactly one of lengths (with max_length) and after")
+        nrates = len(self._rates)
+        if lengths is not None:
+            if not _is_torch(lengths) or not lengths.is_cuda:
+                raise MultirateHIPError(1, "filt_rates_async: lengths must be a CUDA tensor (host lengths go through filt_into(buffer, x, lengths))")
+            if lengths.dtype != torch.int64:
+                raise MultirateHIPError(1, f"filt_rates_async: lengths must be int64, got {lengths.dtype}")
+            if tuple(lengths.shape) != (nrates,) or not lengths.is_contiguous():
+                raise MultirateHIPError(1, f"filt_rates_async: lengths takes {nrates} contiguous values, one per channel; got shape {tuple(lengths.shape)}")
+            if max_length is None or int(max_length) != max_length or max_length < 0:
+                raise MultirateHIPError(1, "filt_rates_async: lengths comes with max_length, the declared maximum of its values (an integer >= 0)")
+        else:
+            if not isinstance(after, FIRFilter) or after._handle is None:
+                raise MultirateHIPError(1, "filt_rates_async: after must be a bound FIRFilter whose latest call wrote x")
+            if max_length is not None and (int(max_length) != max_length or max_length < 0):
+                raise MultirateHIPError(1, "filt_rates_async: max_length must be an integer >= 0")
+        nch, n, xs, cap, ys, counts, stream = self._rates_call_args(buffer, x, counts)
+        bound = n if max_length is None else int(max_length)
+        if bound > n:
+            raise MultirateHIPError(1, f"filt_rates_async: max_length {bound} exceeds the {n} samples a row of x holds")
+        if lengths is not None:
+            if lengths.device != x.device:
+                raise MultirateHIPError(1, "filt_rates_async: lengths is not on the filter's device")
+            _check(self._lib.mrhip_filt_device_rates_lens_device(self._handle, C.c_void_p(x.data_ptr()), C.c_void_p(lengths.data_ptr()), bound, xs,
+                                                                 C.c_void_p(buffer.data_ptr()), cap, ys, C.c_void_p(counts.data_ptr()),
+                                                                 C.c_void_p(stream)))
+        else:
+            _check(self._lib.mrhip_filt_device_rates_chained(self._handle, after._handle, C.c_void_p(x.data_ptr()), bound, xs,
+                                                             C.c_void_p(buffer.data_ptr()), cap, ys, C.c_void_p(counts.data_ptr()), C.c_void_p(stream)))
         return counts
 
     @property

@@ -18,6 +18,7 @@ export FIRFilter, FIRKernel, FIRStandard, FIRDecimator, FIRInterpolator, FIRRati
        FilterCascade, filt_device!, filt_device_chunked!, scheduleinfo, advancestate!, ChunkRing, pushchunks!, drain, ringinfo, ShardedFIRFilter,
        RatesFIRFilter, channelstates, setchannelstates!, setrates!, set_channel_ctaps!, set_channel_ctaps_device!,
        set_channel_ctaps_farrow!, set_channel_pnfb_ctaps!, set_channel_pnfb_ctaps_device!
+export filt_rates_lens_device!, filt_rates_chained!
 
 const libmr = get(ENV, "MRHIP_LIB_PATH", joinpath(@__DIR__, "..", "libmultirate_hip.so"))
 
@@ -716,6 +717,32 @@ function filt_device!(f::RatesFIRFilter, yptr::Ptr{Cvoid}, ycap::Integer, ystrid
     check(ccall((:mrhip_filt_device_rates_ragged, libmr), Cint,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}),
                 f.handle, xptr, xlens, xstride, yptr, ycap, ystride, countsptr, stream))
+    nothing
+end
+# Input lengths from DEVICE memory, and chaining (include/multirate_hip.h, "Input lengths from device memory, and chaining, for the filters
+# with per-channel rates"): nothing of a call's lengths passes through the host.  xlens is a device pointer to nchannels Int64, read in
+# stream order; xlenmax is the declared maximum of its values, for which the launch is sized and y must have room
+# (outputlengthbound(f, xlenmax)).  A value outside 0:xlenmax feeds its channel nothing in this call and makes channelstates throw until
+# setchannelstates! or reset!.
+function filt_rates_lens_device!(f::RatesFIRFilter, yptr::Ptr{Cvoid}, ycap::Integer, ystride::Integer, xptr::Ptr{Cvoid}, xlens::Ptr{Int64},
+                                 xlenmax::Integer, xstride::Integer, ::Type{Tx}; countsptr::Ptr{Int64} = Ptr{Int64}(C_NULL),
+                                 stream::Ptr{Cvoid} = C_NULL) where {Tx}
+    bind!(f, Tx)
+    check(ccall((:mrhip_filt_device_rates_lens_device, libmr), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}),
+                f.handle, xptr, xlens, xlenmax, xstride, yptr, ycap, ystride, countsptr, stream))
+    nothing
+end
+# f behind prev on one stream: x is what prev's latest call wrote, the lengths are that call's counts, taken on the device -- per channel
+# from a RatesFIRFilter, the one count of a FIRFilter whose latest call was filt_device_async!.  xlenbound = outputlengthbound(prev, the
+# (largest) input length of that call).  Valid between that call of prev and prev's next one on the stream.
+function filt_rates_chained!(f::RatesFIRFilter, prev::Union{RatesFIRFilter,FIRFilter}, yptr::Ptr{Cvoid}, ycap::Integer, ystride::Integer,
+                             xptr::Ptr{Cvoid}, xlenbound::Integer, xstride::Integer, ::Type{Tx}; countsptr::Ptr{Int64} = Ptr{Int64}(C_NULL),
+                             stream::Ptr{Cvoid} = C_NULL) where {Tx}
+    bind!(f, Tx)
+    check(ccall((:mrhip_filt_device_rates_chained, libmr), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}),
+                f.handle, prev.handle, xptr, xlenbound, xstride, yptr, ycap, ystride, countsptr, stream))
     nothing
 end
 # the channels' states, after waiting for the filter's stream
