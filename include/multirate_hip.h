@@ -771,7 +771,7 @@ int mrhip_set_channel_taps(mrhip_filter *f, const void *h /* [nchannels][hLen] *
  *   - complex banks: mrhip_set_channel_ctaps_farrow and mrhip_set_channel_pnfb_ctaps* (below);
  *   - left out on purpose: going back to shared taps; a stream-ordered update without the host
  *     wait (it needs double-buffered banks); the fit on the device; graph capture, rings, cascades and sharding; the parallel schedule
- *     for long channels. */
+ *     for long channels.  (Since added: the fit on the device, mrhip_set_channel_taps_farrow_device below.) */
 int mrhip_set_channel_taps_farrow(mrhip_filter *f, const void *h /* [nchannels][hLen] */, int64_t hLen, int tap_dtype);
 int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb /* [nchannels][tapsPerPhi][polyorder+1] */, int64_t tapsPerPhi, int64_t polyorder);
 /* Device-resident updates for the filters with per-channel rates (mrhip_create_arbitrary_rates, mrhip_create_farrow_rates*, with or
@@ -827,7 +827,8 @@ int mrhip_set_channel_pnfb(mrhip_filter *f, const double *pnfb /* [nchannels][ta
  *   - left out on purpose: input lengths that live on the device; the FIRFarrow fit on the device (a mrhip_set_channel_taps_farrow
  *     twin); updates from a stream other than the one the filter's calls run on without ordering by the caller (the device arrays are
  *     read on `stream`); graph capture; complex taps; the parallel schedule for long channels.  (Since added: input lengths that
- *     live on the device, mrhip_filt_device_rates_lens_device below; complex taps, the two sections that follow.) */
+ *     live on the device, mrhip_filt_device_rates_lens_device below; complex taps, the two sections that follow; the FIRFarrow fit on
+ *     the device, mrhip_set_channel_taps_farrow_device below.) */
 int mrhip_set_channel_rates_device(mrhip_filter *f, const double *rates /* DEVICE, [nchannels] */, double rate_lo, double rate_hi, void *stream);
 int mrhip_set_channel_taps_device(mrhip_filter *f, const void *h /* DEVICE, [nchannels][hLen] */, int64_t hLen, int tap_dtype, void *stream);
 int mrhip_set_channel_pnfb_device(mrhip_filter *f, const double *pnfb /* DEVICE, [nchannels][tapsPerPhi][polyorder+1] */, int64_t tapsPerPhi,
@@ -948,12 +949,61 @@ int mrhip_set_channel_ctaps_device(mrhip_filter *f, const void *h /* DEVICE, sam
  *     tap dtype with MRHIP_ERR_UNSUPPORTED;
  *   - left out on purpose: the FIRFarrow fit on the device; one shared complex bank without a bank per channel (install the same bank
  *     nchannels times); going back to real taps; a FUSED form; lengths on the device; graph capture, rings, cascades and sharding;
- *     the parallel schedule for long channels. */
+ *     the parallel schedule for long channels.  (Since added: the FIRFarrow fit on the device, mrhip_set_channel_ctaps_farrow_device
+ *     below.) */
 int mrhip_set_channel_ctaps_farrow(mrhip_filter *f, const void *h /* [nchannels][hLen] (re, im) */, int64_t hLen, int tap_dtype);
 int mrhip_set_channel_pnfb_ctaps(mrhip_filter *f, const double *pnfb /* [nchannels][tapsPerPhi][polyorder+1] (re, im) Float64 */, int64_t tapsPerPhi,
                                  int64_t polyorder);
 int mrhip_set_channel_pnfb_ctaps_device(mrhip_filter *f, const double *pnfb /* DEVICE, same layout */, int64_t tapsPerPhi, int64_t polyorder,
                                         void *stream);
+/* The FIRFarrow fit on the device for the filters with per-channel rates (mrhip_set_channel_taps_farrow_device and
+ * mrhip_set_channel_ctaps_farrow_device on a filter of mrhip_create_farrow_rates*).  A block-LMS equaliser or a matched-pulse tracker
+ * produces TAPS, not fitted polynomial banks; mrhip_set_channel_taps_farrow and mrhip_set_channel_ctaps_farrow take them from HOST memory,
+ * wait for the filter's stream and fit every row on the host, which costs many chunks' worth of time.  The two calls below take the taps
+ * from DEVICE memory and fit them there, in stream order: the cell the sections above list as left out ("the FIRFarrow fit on the
+ * device").  They are CALLS on an existing filter, the twins of mrhip_set_channel_taps_farrow and mrhip_set_channel_ctaps_farrow, not
+ * constructors: there are still sixteen constructors and the ABI version stays 1.
+ *   - layouts and checks: mrhip_set_channel_taps_farrow_device takes the layout and the argument checks of mrhip_set_channel_taps_farrow
+ *     (h: nchannels rows of hLen taps in the filter's tap dtype), mrhip_set_channel_ctaps_farrow_device those of
+ *     mrhip_set_channel_ctaps_farrow (rows of (re, im) pairs in the complex type of the filter's tap precision; a FUSED filter is
+ *     MRHIP_ERR_UNSUPPORTED), in the same order, each message naming the new function.  A filter of mrhip_create_arbitrary_rates is
+ *     MRHIP_ERR_INVALID_ARG with a message that points to mrhip_set_channel_taps_device (mrhip_set_channel_ctaps_device); any other
+ *     filter is MRHIP_ERR_INVALID_ARG.  The real call on a filter that holds complex banks is MRHIP_ERR_UNSUPPORTED, "going back to real
+ *     taps is left out";
+ *   - Nphi: a lane keeps its row of Nphi taps in LDS, so the calls serve Nphi up to 1024; a larger Nphi is MRHIP_ERR_UNSUPPORTED with a
+ *     message that states the bound and points to the host call;
+ *   - rank: whether the fit is rank deficient depends on (Nphi, polyorder) alone -- polyorder + 1 > Nphi, possible on a filter of
+ *     mrhip_create_farrow_rates_pnfb -- and is decided on the host: MRHIP_ERR_INVALID_ARG, "polynomial fit is rank deficient";
+ *   - stream: the rules of mrhip_set_channel_pnfb_device (mrhip_set_channel_pnfb_ctaps_device).  The call adopts `stream` and takes
+ *     effect behind the calls already enqueued and ahead of every later one; h is read in stream order.  A capturing stream is
+ *     MRHIP_ERR_UNSUPPORTED.  Every refusal comes before anything is enqueued or changed;
+ *   - the fit: mrhip_polyfit's, a Householder QR of the Vandermonde matrix A[r][p] = (r+1)^p.  A is the same for every row of every
+ *     channel, so its side of the factorisation -- the reflectors, their squared norms and the triangle R, (polyorder+1) * (Nphi +
+ *     polyorder + 2) Float64 -- is computed once per filter on the host by the same statements, at the first of these calls, uploaded
+ *     then and freed by mrhip_destroy.  One kernel (rates_farrow_fit_kernel, a lane per channel, row and component) applies the
+ *     reflections to the row h_c[(tapsPerPhi-1-i)*Nphi + phi], phi = 0 ... Nphi-1 (0 past hLen), widened exactly to Float64, back-
+ *     substitutes, and writes the polyorder+1 coefficients into the filter's bank, rounded to Float32 and widened back per component on a
+ *     filter with Float32 taps.  Same order of operations, every multiply, add and subtract rounded on its own, IEEE Float64 division:
+ *     the banks are BIT FOR BIT those of mrhip_set_channel_taps_farrow (mrhip_set_channel_ctaps_farrow) given the same matrix;
+ *   - effect: from the next call on the filter is bit for bit the filter after the host call with the same matrix -- banks, outputs,
+ *     counts, states and history, under STRICT and (real taps) FUSED, through mrhip_filt_device_rates, the ragged call, the
+ *     device-lengths call and the chained call, on the universal and the multi kernels.  mrhip_set_channel_ctaps_farrow_device on a
+ *     filter over real samples makes it write complex outputs from then on, as mrhip_set_channel_pnfb_ctaps_device does;
+ *   - allocation and waits: a filter whose bank is still shared (for the complex call: that holds no complex banks yet) allocates the
+ *     nchannels banks first, then waits ONCE for the filter's stream, and the bank it held is freed right after that wait; the first of
+ *     these calls on a filter uploads the QR table during the same wait (a filter that already holds its banks waits for the table
+ *     alone).  Every later call enqueues one kernel and returns without waiting.  A failed allocation leaves the filter bit for bit as
+ *     it was;
+ *   - host copies: afterwards the host copy is stale; mrhip_get_pnfb and mrhip_farrow_tapsforphase wait for the filter's stream and read
+ *     the banks back.  mrhip_reset keeps the banks.  Host and device installs mix freely;
+ *   - existing calls answer as before: mrhip_set_channel_taps_device on a FIRFarrow filter keeps its MRHIP_ERR_UNSUPPORTED and its
+ *     message; a filter on which neither function was called runs the launches and kernels it always ran;
+ *   - left out on purpose: the fit in the constructors and on the one-rate FIRFarrow filters; a faster host fit (mrhip_polyfit factors
+ *     per row and stays the yardstick); graph capture; one shared complex bank; a FUSED form for complex taps; the parallel schedule
+ *     for long channels. */
+int mrhip_set_channel_taps_farrow_device(mrhip_filter *f, const void *h /* DEVICE, [nchannels][hLen] */, int64_t hLen, int tap_dtype, void *stream);
+int mrhip_set_channel_ctaps_farrow_device(mrhip_filter *f, const void *h /* DEVICE, [nchannels][hLen] (re, im) */, int64_t hLen, int tap_dtype,
+                                          void *stream);
 /* Input lengths from device memory, and chaining, for the filters with per-channel rates (mrhip_create_arbitrary_rates,
  * mrhip_create_farrow_rates*, with shared, per-channel or complex per-channel taps).  Rates, taps and polynomial banks arrive from device
  * memory in stream order (above); the input LENGTHS of mrhip_filt_device_rates_ragged are a HOST array, so a length computed on the GPU

@@ -415,7 +415,7 @@ void mrhip_destroy(mrhip_filter *f)
     for (void *p : {f->d_taps_alloc, f->d_dtaps_alloc, static_cast<void *>(f->d_pnfb), static_cast<void *>(f->d_pnfb_t), f->d_hist[0], f->d_hist[1], f->d_hist[2], static_cast<void *>(f->d_counters), f->d_sched_n, f->d_sched_acc,
                     f->d_xbuf[0], f->d_xbuf[1], f->d_ybuf[0], f->d_ybuf[1]})
         if (p) (void)hipFree(p);
-    for (void *p : {static_cast<void *>(f->d_rrec), f->d_rs_n, f->d_rs_acc, static_cast<void *>(f->d_xlens)})
+    for (void *p : {static_cast<void *>(f->d_rrec), f->d_rs_n, f->d_rs_acc, static_cast<void *>(f->d_xlens), static_cast<void *>(f->d_fit_table)})
         if (p) (void)hipFree(p);
     if (f->rag_pin) (void)hipHostFree(f->rag_pin);
     for (hipEvent_t e : f->rag_ev)
@@ -2588,6 +2588,93 @@ int mrhip_set_channel_pnfb_ctaps_device(mrhip_filter *f, const double *pnfb, int
     }
     f->taps_stale = true;
     return MRHIP_OK;
+}
+
+// ---- The FIRFarrow fit on the device (include/multirate_hip.h, "The FIRFarrow fit on the device for the filters with per-channel
+// rates") -----------------------------------------------------------------------------------------------------------------------------
+// What the two calls share behind their argument checks, in this order, everything up to the launch before anything of the filter
+// changes: the plan (N𝜙 above the bound is refused), the QR table of (N𝜙, polyorder) -- a rank-deficient fit is decided HERE, on the
+// host, as polyfit_rows would decide it for every row --, the stream rules, the allocations (the banks as mrhip_set_channel_pnfb_device /
+// _pnfb_ctaps_device allocate them, the table on the first of these calls), ONE wait where a bank is freed or the table is uploaded, and
+// the fit kernel (launch_rates_fit), which writes the coefficients straight into the banks.
+static int fit_taps_device(mrhip_filter *f, const std::string &who, const char *host_call, bool complex_h, const void *h, hipStream_t stream)
+{
+    FarrowFitPlan plan{};
+    if (!plan_rates_fit(f->Nphi, &plan))
+        return fail(MRHIP_ERR_UNSUPPORTED, who + ": the fit on the device serves Nphi up to " + std::to_string(kFarrowFitNphiMax) + " (a lane's row is kept in LDS; the filter has Nphi = " +
+                                           std::to_string(f->Nphi) + "): " + host_call + " fits on the host");
+    std::vector<double> table;                                              // (a filter that holds its table was factored by an earlier call)
+    const int m = static_cast<int>(f->polyorder) + 1;
+    if (!f->d_fit_table && !polyfit_factor(f->Nphi, static_cast<int>(f->polyorder), &table))
+        return fail(MRHIP_ERR_INVALID_ARG, who + ": polynomial fit is rank deficient");
+    DeviceGuard guard(f->device);
+    if (!guard.ok) return fail(MRHIP_ERR_HIP, who + ": hipSetDevice failed");
+    if (int rc = device_update_stream(f, who.c_str(), stream)) return rc;
+    const int nc = complex_h ? 2 : 1;
+    const size_t n = static_cast<size_t>(f->nch) * static_cast<size_t>(f->T) * static_cast<size_t>(m) * nc;
+    const bool first = complex_h ? !dtype_is_complex(f->th) : !f->bank;     // the filter holds the shared bank (or real banks): a new allocation
+    double *d_new = f->d_pnfb, *d_table = f->d_fit_table;                   // (a later call: the banks and the table of the first one, reused)
+    if (first) {
+        d_new = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&d_new), n * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MRHIP_ERR_HIP, who + ": no device memory for the channels' polynomial banks");
+        }
+    }
+    auto bail = [&](int rc) {
+        if (first) (void)hipFree(d_new);
+        if (!f->d_fit_table && d_table) (void)hipFree(d_table);
+        return rc;
+    };
+    if (!f->d_fit_table) {
+        d_table = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&d_table), table.size() * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return bail(fail(MRHIP_ERR_HIP, who + ": no device memory for the fit's QR table"));
+        }
+    }
+    if (first || !f->d_fit_table) {                                         // the one wait: the kernels enqueued so far read the bank freed below
+        if (int rc = drain_filter(f)) return bail(rc);
+        if (!f->d_fit_table && hipMemcpy(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)   // (complete on return)
+            return bail(fail(MRHIP_ERR_HIP, who + ": uploading the fit's QR table failed"));
+    }
+    if (int rc = adopt_stream(f, stream)) return bail(rc);
+    FarrowFitArgs a{};
+    a.h = h; a.pnfb = d_new;
+    a.hLen = f->hLen; a.T = f->T; a.Nphi = f->Nphi; a.m = m;
+    a.items = static_cast<long long>(f->nch) * f->T * nc;
+    if (launch_rates_fit(dtype_is_f64(f->th), complex_h, a, d_table, plan, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return bail(fail(MRHIP_ERR_HIP, who + ": the fit kernel could not be launched"));
+    }
+    f->d_fit_table = d_table;
+    if (first) {
+        (void)hipFree(f->d_pnfb);
+        if (f->d_pnfb_t) (void)hipFree(f->d_pnfb_t);
+        f->d_pnfb = d_new;
+        f->d_pnfb_t = nullptr;
+        if (complex_h) ctaps_flip_type(f, dtype_is_f64(f->th) ? MRHIP_C128 : MRHIP_C64);
+        else f->bank = true;
+    }
+    f->taps_stale = true;
+    return MRHIP_OK;
+}
+
+int mrhip_set_channel_taps_farrow_device(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_taps_farrow_device: NULL filter");
+    if (f->rates && f->kind == MRHIP_FIR_FARROW && dtype_is_complex(f->th))      // (after mrhip_set_channel_ctaps_farrow* / _pnfb_ctaps*: the filter's outputs are complex from then on)
+        return fail(MRHIP_ERR_UNSUPPORTED, "mrhip_set_channel_taps_farrow_device: the filter holds complex per-channel taps (mrhip_set_channel_ctaps_farrow, mrhip_set_channel_pnfb_ctaps); going back to real taps is left out");
+    if (Refusal r = check_channel_taps_farrow_device(f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th)) return fail(r.status, r.message);
+    return fit_taps_device(f, "mrhip_set_channel_taps_farrow_device", "mrhip_set_channel_taps_farrow", false, h, static_cast<hipStream_t>(stream_));
+}
+
+int mrhip_set_channel_ctaps_farrow_device(mrhip_filter *f, const void *h, int64_t hLen, int tap_dtype, void *stream_)
+{
+    if (!f) return fail(MRHIP_ERR_INVALID_ARG, "mrhip_set_channel_ctaps_farrow_device: NULL filter");
+    if (Refusal r = check_channel_ctaps_farrow_device(f->rates, f->kind == MRHIP_FIR_FARROW, h, hLen, tap_dtype, f->hLen, f->th, f->numerics == MRHIP_NUMERICS_FUSED))
+        return fail(r.status, r.message);
+    return fit_taps_device(f, "mrhip_set_channel_ctaps_farrow_device", "mrhip_set_channel_ctaps_farrow", true, h, static_cast<hipStream_t>(stream_));
 }
 
 int mrhip_sync_state(mrhip_filter *f, int64_t *last_n_written)

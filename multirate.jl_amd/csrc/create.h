@@ -114,6 +114,13 @@ Refusal check_channel_taps_device(bool is_rates, bool is_farrow, const void *h, 
 // mrhip_set_channel_pnfb_device: a FIRArbitrary filter is pointed to mrhip_set_channel_taps_device, then check_channel_taps_farrow(true, ...)
 Refusal check_channel_pnfb_device(bool is_rates, bool is_farrow, const void *pnfb, int64_t tapsPerPhi, int64_t polyorder, int64_t f_T,
                                   int64_t f_polyorder, int f_th);
+// The FIRFarrow fit on the device (the public header, "The FIRFarrow fit on the device for the filters with per-channel rates"): what the
+// two calls refuse before they look at the plan, the fit's rank or the stream, each in its own name.
+// mrhip_set_channel_taps_farrow_device: check_channel_taps_farrow(false, ...) with a FIRArbitrary filter pointed to mrhip_set_channel_taps_device
+Refusal check_channel_taps_farrow_device(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th);
+// mrhip_set_channel_ctaps_farrow_device: check_channel_ctaps_farrow(who, false, ...) with a FIRArbitrary filter pointed to
+// mrhip_set_channel_ctaps_device and real taps to mrhip_set_channel_taps_farrow_device
+Refusal check_channel_ctaps_farrow_device(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th, bool fused);
 // (c) the banks, `rows` tap vectors of hLen taps each, one bank per row, one after the other.  taps2pfb of every row into pfb and
 // (dpfb != NULL: FIRArbitrary) of its dh = [diff(h), 0] into dpfb; returns tapsPerPhi
 int64_t create_pfb_banks(const void *h, int64_t hLen, int th, int64_t Nphi, size_t rows, std::vector<unsigned char> *pfb, std::vector<unsigned char> *dpfb);

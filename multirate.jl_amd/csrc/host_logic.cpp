@@ -756,6 +756,61 @@ bool polyfit_rows(const double *y, int64_t n, int polyorder, double *coef)
     return true;
 }
 
+// The A side of polyfit_rows above, statement for statement, without a right-hand side (rates_arb.h, "The FIRFarrow fit on the
+// device"): the reflector of every column, its vnorm2 and, at the end, the triangle go into the table polyfit_apply reads.  A zero
+// column norm and a zero pivot answer false here as they do there -- neither depends on b.
+bool polyfit_factor(int64_t n, int polyorder, std::vector<double> *table)
+{
+    const int m = polyorder + 1;
+    if (n < m || m < 1) return false;
+    const size_t pitch = static_cast<size_t>(polyfit_table_pitch(n, m));
+    table->assign(polyfit_table_size(n, m), 0.0);
+    std::vector<double> A(static_cast<size_t>(n) * m);
+    for (int64_t r = 0; r < n; ++r) {
+        double v = 1.0;
+        for (int c = 0; c < m; ++c) { A[static_cast<size_t>(r) * m + c] = v; v *= static_cast<double>(r + 1); }
+    }
+    for (int c = 0; c < m; ++c) {                     // Householder reflections, column by column
+        double norm = 0.0;
+        for (int64_t r = c; r < n; ++r) norm += A[static_cast<size_t>(r) * m + c] * A[static_cast<size_t>(r) * m + c];
+        norm = std::sqrt(norm);
+        if (norm == 0.0) return false;
+        const double akk = A[static_cast<size_t>(c) * m + c];
+        const double alpha = akk > 0 ? -norm : norm;
+        std::vector<double> v(static_cast<size_t>(n - c));
+        v[0] = akk - alpha;
+        for (int64_t r = c + 1; r < n; ++r) v[static_cast<size_t>(r - c)] = A[static_cast<size_t>(r) * m + c];
+        double vnorm2 = 0.0;
+        for (double t : v) vnorm2 += t * t;
+        if (vnorm2 == 0.0) continue;                  // (the table's vnorm2 stays 0: polyfit_apply skips the column as well)
+        for (int cc = c; cc < m; ++cc) {
+            double dot = 0.0;
+            for (int64_t r = c; r < n; ++r) dot += v[static_cast<size_t>(r - c)] * A[static_cast<size_t>(r) * m + cc];
+            const double f = 2.0 * dot / vnorm2;
+            for (int64_t r = c; r < n; ++r) A[static_cast<size_t>(r) * m + cc] -= f * v[static_cast<size_t>(r - c)];
+        }
+        double *col = table->data() + static_cast<size_t>(c) * pitch;
+        for (int64_t r = c; r < n; ++r) col[r] = v[static_cast<size_t>(r - c)];
+        col[n] = vnorm2;
+    }
+    for (int c = m - 1; c >= 0; --c) {                // the upper-triangular R of the back substitution
+        if (A[static_cast<size_t>(c) * m + c] == 0.0) return false;
+        for (int cc = 0; cc < m; ++cc) (*table)[static_cast<size_t>(c) * pitch + static_cast<size_t>(n) + 1 + cc] = A[static_cast<size_t>(c) * m + cc];
+    }
+    return true;
+}
+
+// the fit kernel's launch (rates_arb.h, plan_rates_fit): the lanes of a workgroup whose b columns, N𝜙 Float64 each, fit kFarrowFitLdsBytes
+bool plan_rates_fit(int64_t Nphi, FarrowFitPlan *out)
+{
+    if (Nphi < 1 || Nphi > kFarrowFitNphiMax) return false;
+    int lanes = kFarrowFitMaxLanes;
+    while (static_cast<long long>(lanes) * Nphi * 8 > kFarrowFitLdsBytes) lanes /= 2;
+    out->lanes = lanes;
+    out->lds_bytes = static_cast<size_t>(lanes) * static_cast<size_t>(Nphi) * 8;
+    return true;
+}
+
 // ---- the constructors' host side (create.h; the device work is create.hip's) --------------------------------------------------------
 
 Refusal create_check_args(const CreateEntry &e, const void *h, int64_t hLen, int th, int tx, int64_t nch, mrhip_filter **out)
@@ -839,11 +894,12 @@ Refusal check_channel_ctaps(const char *who_, bool is_rates, bool is_farrow, con
 // what the two calls refuse before they touch the device, in their order and each naming the function -- the filter (a FIRArbitrary one
 // with per-channel rates is pointed to its own call), then h / pnfb, then hLen or (tapsPerPhi, polyorder) against the filter's own, then
 // (taps only) the tap type: out of range, complex, the other real one
-Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder, int th,
-                                  int64_t f_len, int64_t f_polyorder, int f_th)
+namespace {
+// (`who`: the function's name; arb_call: the call a filter of mrhip_create_arbitrary_rates is pointed to)
+Refusal farrow_taps_checks(const std::string &who, const char *arb_call, bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len,
+                           int64_t polyorder, int th, int64_t f_len, int64_t f_polyorder, int f_th)
 {
-    const std::string who = pnfb_call ? "mrhip_set_channel_pnfb" : "mrhip_set_channel_taps_farrow";
-    if (is_rates && !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + ": a filter of mrhip_create_arbitrary_rates takes mrhip_set_channel_taps"};
+    if (is_rates && !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + ": a filter of mrhip_create_arbitrary_rates takes " + arb_call};
     if (!is_rates || !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + " takes a filter of mrhip_create_farrow_rates or mrhip_create_farrow_rates_pnfb"};
     if (!src) return {MRHIP_ERR_INVALID_ARG, who + (pnfb_call ? ": pnfb is NULL" : ": h is NULL")};
     if (pnfb_call) {
@@ -861,6 +917,22 @@ Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow,
     if (th != f_th) return {MRHIP_ERR_INVALID_ARG, who + ": the taps must have the filter's tap dtype"};
     return {};
 }
+}  // namespace
+
+Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder, int th,
+                                  int64_t f_len, int64_t f_polyorder, int f_th)
+{
+    return farrow_taps_checks(pnfb_call ? "mrhip_set_channel_pnfb" : "mrhip_set_channel_taps_farrow", "mrhip_set_channel_taps", pnfb_call, is_rates,
+                              is_farrow, src, len, polyorder, th, f_len, f_polyorder, f_th);
+}
+
+// mrhip_set_channel_taps_farrow_device (the public header, "The FIRFarrow fit on the device for the filters with per-channel rates"): the
+// checks of mrhip_set_channel_taps_farrow in their order, in the new function's name; a FIRArbitrary filter is pointed to
+// mrhip_set_channel_taps_device
+Refusal check_channel_taps_farrow_device(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th)
+{
+    return farrow_taps_checks("mrhip_set_channel_taps_farrow_device", "mrhip_set_channel_taps_device", false, is_rates, is_farrow, h, hLen, 0, th, f_hLen, 0, f_th);
+}
 
 // mrhip_set_channel_ctaps_farrow (pnfb_call false: src = h, len = hLen against the filter's hLen, th against the complex type of the
 // filter's tap precision), mrhip_set_channel_pnfb_ctaps and mrhip_set_channel_pnfb_ctaps_device (pnfb_call true: src = pnfb, len =
@@ -870,11 +942,12 @@ Refusal check_channel_taps_farrow(bool pnfb_call, bool is_rates, bool is_farrow,
 // (tapsPerPhi, polyorder) against the filter's own, then (taps only) the tap type (out of range, real, the other complex precision:
 // f_th is the filter's tap type, real or already complex -- its precision counts), and last the filter's numerics: complex taps have no
 // FUSED form
-Refusal check_channel_ctaps_farrow(const char *who_, bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder,
-                                   int th, int64_t f_len, int64_t f_polyorder, int f_th, bool fused)
+namespace {
+// (arb_call: the call a filter of mrhip_create_arbitrary_rates is pointed to; real_call: the call real taps are pointed to)
+Refusal farrow_ctaps_checks(const std::string &who, const char *arb_call, const char *real_call, bool pnfb_call, bool is_rates, bool is_farrow,
+                            const void *src, int64_t len, int64_t polyorder, int th, int64_t f_len, int64_t f_polyorder, int f_th, bool fused)
 {
-    const std::string who = who_;
-    if (is_rates && !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + ": a filter of mrhip_create_arbitrary_rates takes mrhip_set_channel_ctaps"};
+    if (is_rates && !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + ": a filter of mrhip_create_arbitrary_rates takes " + arb_call};
     if (!is_rates || !is_farrow) return {MRHIP_ERR_INVALID_ARG, who + " takes a filter of mrhip_create_farrow_rates or mrhip_create_farrow_rates_pnfb"};
     if (!src) return {MRHIP_ERR_INVALID_ARG, who + (pnfb_call ? ": pnfb is NULL" : ": h is NULL")};
     if (pnfb_call) {
@@ -888,12 +961,28 @@ Refusal check_channel_ctaps_farrow(const char *who_, bool pnfb_call, bool is_rat
                                            "): tapsPerPhi, the history length and the history do not change"};
         if (th < MRHIP_F32 || th > MRHIP_C128) return {MRHIP_ERR_INVALID_ARG, who + ": bad tap dtype"};
         if (!dtype_is_complex(th))
-            return {MRHIP_ERR_INVALID_ARG, who + ": the taps must be Complex64 or Complex128 (real taps go through mrhip_set_channel_taps_farrow)"};
+            return {MRHIP_ERR_INVALID_ARG, who + ": the taps must be Complex64 or Complex128 (real taps go through " + real_call + ")"};
         if (dtype_is_f64(th) != dtype_is_f64(f_th))
             return {MRHIP_ERR_INVALID_ARG, who + ": the taps must be the complex type of the filter's tap precision (Complex64 on Float32 taps, Complex128 on Float64 taps)"};
     }
     if (fused) return {MRHIP_ERR_UNSUPPORTED, who + ": the filter is in FUSED numerics and no FUSED form is defined for complex taps (the public header: complex taps)"};
     return {};
+}
+}  // namespace
+
+Refusal check_channel_ctaps_farrow(const char *who, bool pnfb_call, bool is_rates, bool is_farrow, const void *src, int64_t len, int64_t polyorder,
+                                   int th, int64_t f_len, int64_t f_polyorder, int f_th, bool fused)
+{
+    return farrow_ctaps_checks(who, "mrhip_set_channel_ctaps", "mrhip_set_channel_taps_farrow", pnfb_call, is_rates, is_farrow, src, len, polyorder, th,
+                               f_len, f_polyorder, f_th, fused);
+}
+
+// mrhip_set_channel_ctaps_farrow_device: the checks of mrhip_set_channel_ctaps_farrow in their order, in the new function's name; a
+// FIRArbitrary filter is pointed to mrhip_set_channel_ctaps_device, real taps to mrhip_set_channel_taps_farrow_device
+Refusal check_channel_ctaps_farrow_device(bool is_rates, bool is_farrow, const void *h, int64_t hLen, int th, int64_t f_hLen, int f_th, bool fused)
+{
+    return farrow_ctaps_checks("mrhip_set_channel_ctaps_farrow_device", "mrhip_set_channel_ctaps_device", "mrhip_set_channel_taps_farrow_device", false,
+                               is_rates, is_farrow, h, hLen, 0, th, f_hLen, 0, f_th, fused);
 }
 
 // mrhip_set_channel_rates_device: the host cannot see the rates, so the caller declares the range they lie in; the range is held to what

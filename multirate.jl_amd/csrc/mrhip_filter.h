@@ -52,6 +52,9 @@ struct mrhip_filter {
     // (mrhip_filt_device_rates_lens_device / _chained fill d_xlens by a kernel: the array alone, no slot.)  rates_called: a call has moved the
     // records since creation or mrhip_reset, so their `count` is a call's (what a filter chained behind this one takes its lengths from)
     bool rates_called = false;
+    // (mrhip_set_channel_taps_farrow_device / _ctaps_farrow_device: the QR table of the fit, polyfit_factor's, (polyorder+1) * (N𝜙 + polyorder
+    // + 2) Float64 -- computed and uploaded by the first of these calls, freed by mrhip_destroy)
+    double *d_fit_table = nullptr;
 
     // device memory
     void *d_taps = nullptr, *d_dtaps = nullptr;            // (inside d_taps_alloc / d_dtaps_alloc: kTapPad zero elements either side)

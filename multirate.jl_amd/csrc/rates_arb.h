@@ -245,4 +245,83 @@ hipError_t launch_farrow_rates_ctaps_multi(const TypeKey &tk, const FarrowArgs &
 // host_logic.cpp: the switch value passed in (0 never, 1 every call, -1 the default rule); the grid is farrow_rates_multi_grid's
 bool plan_farrow_rates_ctaps_multi(const TypeKey &tk, const FarrowArgs &a, int num_cus, int mode, ArbTileArgs *out);
 
+// ---- The FIRFarrow fit on the device (mrhip_set_channel_taps_farrow_device, mrhip_set_channel_ctaps_farrow_device; include/multirate_hip.h,
+// "The FIRFarrow fit on the device for the filters with per-channel rates") ---------------------------------------------------------------
+// polyfit_rows (host_logic.cpp) is a Householder QR of the Vandermonde matrix A[r][p] = (r+1)^p, n = N𝜙 rows and m = polyorder+1 columns.
+// A depends on (N𝜙, polyorder) alone, and neither the reflectors v_c, their vnorm2_c nor the triangle R depend on the right-hand side b:
+// polyfit_factor runs that side ONCE, on the host, polyfit_apply the b side and the back substitution per row -- together the statements
+// of polyfit_rows in their order, so the coefficients are polyfit_rows' bit for bit (every multiply, add and subtract rounded on its
+// own: -ffp-contract=off; the two divisions IEEE Float64).  The table, Float64, column c at c * polyfit_table_pitch(n, m):
+//     [0, n)      v_c[r] by the ROW r of A it belongs to (rows r < c: 0, never read)
+//     [n]         vnorm2_c (0: polyfit_rows skips the column's reflection, and so does polyfit_apply)
+//     [n+1+cc]    R[c][cc], cc = 0 ... m-1: row c of A after every reflection (the back substitution reads cc >= c)
+// m * (n + m + 1) = (polyorder+1) * (N𝜙 + polyorder + 2) values.
+MRHIP_RATES_HD inline long long polyfit_table_pitch(long long n, int m) { return n + m + 1; }
+inline size_t polyfit_table_size(long long n, int m) { return static_cast<size_t>(m) * static_cast<size_t>(polyfit_table_pitch(n, m)); }
+// host_logic.cpp: the A side of polyfit_rows, statement for statement; `table` receives polyfit_table_size(Nphi, polyorder+1) values.
+// false exactly where polyfit_rows answers false (it does so for every b or for none): n < m, a zero column norm, a zero pivot.
+bool polyfit_factor(int64_t Nphi, int polyorder, std::vector<double> *table);
+// The b side of polyfit_rows and its back substitution.  b: the n values of the row, element r at b[r * b_stride], OVERWRITTEN; coef:
+// the m coefficients, element c at coef[c * coef_stride].  coef may be b itself (coef[c] is written after the last read of b[c]): the
+// kernel keeps both in the lane's LDS column, the host program passes two arrays.  The table entries are indexed by loop counters only.
+MRHIP_RATES_HD inline void polyfit_apply(const double *table, long long n, int m, double *b, long long b_stride, double *coef, long long coef_stride)
+{
+    const long long pitch = polyfit_table_pitch(n, m);
+    for (int c = 0; c < m; ++c) {
+        const double *v = table + c * pitch;
+        const double vnorm2 = v[n];
+        if (vnorm2 == 0.0) continue;
+        double dot = 0.0;
+        for (long long r = c; r < n; ++r) dot += v[r] * b[r * b_stride];
+        const double f = 2.0 * dot / vnorm2;
+        for (long long r = c; r < n; ++r) b[r * b_stride] -= f * v[r];
+    }
+    for (int c = m - 1; c >= 0; --c) {
+        const double *R = table + c * pitch + n + 1;
+        double sacc = b[c * b_stride];
+        for (int cc = c + 1; cc < m; ++cc) sacc -= R[cc] * coef[cc * coef_stride];
+        coef[c * coef_stride] = sacc / R[c];
+    }
+}
+
+// Row i of channel c's polyphase bank, the n = N𝜙 values one fit takes: element 𝜙 is the tap h_c[j], j = (T-1-i)*N𝜙 + 𝜙, 0 for j >= hLen
+// -- rates_bank_tap_index at e = 𝜙*T + i (taps2pfb) --, so the row is CONTIGUOUS in the channel's taps from j0 on:
+MRHIP_RATES_HD inline long long farrow_fit_row_start(long long i, long long T, long long Nphi) { return (T - 1 - i) * Nphi; }
+// A lane's item, 0 <= item < nch * T * nc (nc = 1, or 2: the components of a complex tap), is (channel, row, component) with the component
+// fastest; its coefficient k goes to the filter's banks, [nch][T][m] scalars or (re, im) pairs, at farrow_fit_dst_index -- the place
+// create_farrow_banks gives it on the host.  The kernel and tests/rates_farrow_fit_check.cpp (over a guard-padded buffer) run this text.
+struct FarrowFitItem { long long c, i; int comp; };
+MRHIP_RATES_HD inline FarrowFitItem farrow_fit_item(long long item, long long T, int nc)
+{
+    const long long rows = T * nc, c = item / rows, rem = item - c * rows, i = rem / nc;
+    return FarrowFitItem{c, i, static_cast<int>(rem - i * nc)};
+}
+MRHIP_RATES_HD inline long long farrow_fit_dst_index(const FarrowFitItem &it, int k, long long T, int m, int nc)
+{
+    return ((it.c * T + it.i) * m + k) * nc + it.comp;
+}
+
+// The launch: one lane per (channel, row i, component), the lane's b in LDS as b[r][lane] (consecutive lanes on consecutive 8-byte
+// words), one wave a workgroup.  LDS per workgroup is lanes * N𝜙 * 8 bytes and stays within kFarrowFitLdsBytes (two workgroups a CU):
+// 64 lanes up to N𝜙 = 128, then the largest power of two that fits, down to kFarrowFitMinLanes at N𝜙 = kFarrowFitNphiMax; a larger N𝜙
+// is refused (an eighth of a wave at work and less is not worth a launch: the host call takes those).
+constexpr int kFarrowFitMaxLanes = 64;
+constexpr int kFarrowFitMinLanes = 8;
+constexpr long long kFarrowFitLdsBytes = 64 * 1024;
+constexpr long long kFarrowFitNphiMax = kFarrowFitLdsBytes / (8 * kFarrowFitMinLanes);      // 1024
+struct FarrowFitPlan { int lanes; size_t lds_bytes; };
+// host_logic.cpp: false: N𝜙 is refused (< 1, or above kFarrowFitNphiMax)
+bool plan_rates_fit(int64_t Nphi, FarrowFitPlan *out);
+
+struct FarrowFitArgs {             // rates_farrow_fit_kernel
+    const void *h;                 // DEVICE, [nch][hLen] taps (TAP), or (re, im) pairs of TAP
+    double *pnfb;                  // DEVICE, the filter's banks: [nch][T][m], or [nch][T][m] pairs
+    long long hLen, T, Nphi;
+    long long items;               // nch * T * components: one lane each
+    int m;                         // polyorder + 1
+};
+// kernels_rates_farrow_fit.hip (tap_f64: the scalar type of h; complex_h: pairs; table: DEVICE, polyfit_factor's -- a kernel parameter of
+// its own, so that it carries __restrict__ and its loads stay scalar)
+hipError_t launch_rates_fit(bool tap_f64, bool complex_h, const FarrowFitArgs &a, const double *table, const FarrowFitPlan &p, hipStream_t st);
+
 }  // namespace mrhip

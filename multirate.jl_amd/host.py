@@ -127,6 +127,8 @@ ABI = [
     ("mrhip_set_channel_ctaps_farrow", _i, [_vp, _vp, _i64, _i]),
     ("mrhip_set_channel_pnfb_ctaps", _i, [_vp, _vp, _i64, _i64]),
     ("mrhip_set_channel_pnfb_ctaps_device", _i, [_vp, _vp, _i64, _i64, _vp]),
+    ("mrhip_set_channel_taps_farrow_device", _i, [_vp, _vp, _i64, _i, _vp]),
+    ("mrhip_set_channel_ctaps_farrow_device", _i, [_vp, _vp, _i64, _i, _vp]),
     ("mrhip_get_pnfb", _i, [_vp, _vp]),
     ("mrhip_farrow_tapsforphase", _i, [_vp, _d, _vp]),
     ("mrhip_arbitrary_tapsforphase", _i, [_vp, _d, _vp]),
@@ -1281,11 +1283,11 @@ class FIRFilter:
 
     # -- complex per-channel taps on a filter of per_channel_rates_farrow (include/multirate_hip.h, "Complex per-channel taps with
     # per-channel rates for FIRFarrow")
-    def _takes_ctaps_farrow(self, who):
-        """the filter checks of the three calls, in the library's order: the filter kind, then (by the callers) the array, then the
-        numerics"""
+    def _takes_ctaps_farrow(self, who, arb_call="set_channel_ctaps"):
+        """the filter checks of the complex FIRFarrow calls, in the library's order: the filter kind (``arb_call``: where a FIRArbitrary
+        filter is pointed to), then (by the callers) the array, then the numerics"""
         if self._rates is not None and self.kind == ARBITRARY:
-            raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates takes set_channel_ctaps")
+            raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates takes {arb_call}")
         if self._rates is None or self.kind != FARROW:
             raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates_farrow")
         return np.dtype(np.complex128 if self.h.dtype == np.float64 else np.complex64)
@@ -1352,6 +1354,38 @@ class FIRFilter:
         self._strict_for_ctaps(who)
         _check(self._lib.mrhip_set_channel_pnfb_ctaps_device(self._handle, C.c_void_p(PN.data_ptr()), self.tapsPerPhi, self.polyorder, C.c_void_p(stream)))
         self._chan_farrow, self._farrow_ctaps = _DeviceResident(shape), True
+
+    # -- the FIRFarrow fit on the device (include/multirate_hip.h, "The FIRFarrow fit on the device for the filters with per-channel rates")
+    def set_channel_taps_farrow_device(self, H):
+        """Per-channel taps from DEVICE memory on a filter of ``per_channel_rates_farrow``, FITTED on the device
+        (``mrhip_set_channel_taps_farrow_device``), enqueued on torch's current stream: ``H`` is a contiguous (nchannels, hLen) CUDA
+        tensor in the filter's tap dtype -- what a block-LMS equaliser or a matched-pulse tracker leaves on the GPU.  The banks are bit
+        for bit those of ``set_channel_taps_farrow`` with the same matrix.  The first call on a filter whose bank is still shared
+        allocates the banks and waits once (the first of these calls also uploads the fit's table); every later call only enqueues a
+        kernel.  ``pnfb()`` and ``tapsforphase`` read the banks back.  Nphi above 1024: status 5 (the host call takes those)."""
+        who = "set_channel_taps_farrow_device"
+        if self._rates is not None and self.kind == ARBITRARY:
+            raise MultirateHIPError(1, f"{who}: a filter of FIRFilter.per_channel_rates takes set_channel_taps_device")
+        if self._rates is None or self.kind != FARROW:
+            raise MultirateHIPError(1, f"{who} needs a filter of FIRFilter.per_channel_rates_farrow")
+        if self._farrow_ctaps:
+            raise MultirateHIPError(5, f"{who}: the filter holds complex per-channel taps (set_channel_ctaps_farrow, set_channel_pnfb_ctaps); going back to real taps is left out")
+        stream = self._device_update_args(who, H, self.h.dtype, (len(self._rates), len(self.h)))
+        _check(self._lib.mrhip_set_channel_taps_farrow_device(self._handle, C.c_void_p(H.data_ptr()), len(self.h), _NP2DT[self.h.dtype], C.c_void_p(stream)))
+        self._chan_farrow = _DeviceResident((len(self._rates), self.tapsPerPhi, self.polyorder + 1))
+
+    def set_channel_ctaps_farrow_device(self, H):
+        """COMPLEX per-channel taps from DEVICE memory on a filter of ``per_channel_rates_farrow``, fitted per component on the device
+        (``mrhip_set_channel_ctaps_farrow_device``), enqueued on torch's current stream: ``H`` is a contiguous (nchannels, hLen) CUDA
+        tensor in the complex type of the filter's tap precision.  The banks are bit for bit those of ``set_channel_ctaps_farrow``
+        with the same matrix; the outputs are complex from then on, also over real samples (STRICT only: a FUSED filter is status 5).
+        Allocation and waiting as ``set_channel_pnfb_ctaps_device``; ``pnfb()`` and ``tapsforphase`` read the banks back."""
+        who = "set_channel_ctaps_farrow_device"
+        ct = self._takes_ctaps_farrow(who, "set_channel_ctaps_device")
+        stream = self._device_update_args(who, H, ct, (len(self._rates), len(self.h)))
+        self._strict_for_ctaps(who)
+        _check(self._lib.mrhip_set_channel_ctaps_farrow_device(self._handle, C.c_void_p(H.data_ptr()), len(self.h), _NP2DT[ct], C.c_void_p(stream)))
+        self._chan_farrow, self._farrow_ctaps = _DeviceResident((len(self._rates), self.tapsPerPhi, self.polyorder + 1)), True
 
     def outputlength_bound(self, inputlength: int) -> int:
         """The largest per-channel output count a call of ``inputlength`` samples can have whatever the stream state

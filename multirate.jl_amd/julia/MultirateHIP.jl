@@ -18,7 +18,7 @@ export FIRFilter, FIRKernel, FIRStandard, FIRDecimator, FIRInterpolator, FIRRati
        FilterCascade, filt_device!, filt_device_chunked!, scheduleinfo, advancestate!, ChunkRing, pushchunks!, drain, ringinfo, ShardedFIRFilter,
        RatesFIRFilter, channelstates, setchannelstates!, setrates!, set_channel_ctaps!, set_channel_ctaps_device!,
        set_channel_ctaps_farrow!, set_channel_pnfb_ctaps!, set_channel_pnfb_ctaps_device!
-export filt_rates_lens_device!, filt_rates_chained!
+export filt_rates_lens_device!, filt_rates_chained!, set_channel_taps_farrow_device!, set_channel_ctaps_farrow_device!
 
 const libmr = get(ENV, "MRHIP_LIB_PATH", joinpath(@__DIR__, "..", "libmultirate_hip.so"))
 
@@ -690,6 +690,21 @@ end
 function set_channel_pnfb_device!(f::RatesFIRFilter, pnfb::Ptr{Float64}, stream::Ptr{Cvoid} = C_NULL)
     f.handle == C_NULL && error("set_channel_pnfb_device! needs a bound filter")
     check(ccall((:mrhip_set_channel_pnfb_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Int64, Int64, Ptr{Cvoid}), f.handle, pnfb, cld(length(f.h), f.Nphi), f.polyorder, stream))
+    f
+end
+# The FIRFarrow fit on the device (mrhip_set_channel_taps_farrow_device, mrhip_set_channel_ctaps_farrow_device; include/multirate_hip.h,
+# "The FIRFarrow fit on the device for the filters with per-channel rates"): h is a DEVICE pointer to nchannels rows of length(f.h) taps
+# (the complex call: (re, im) pairs), fitted there in stream order, bit for bit the banks of set_channel_taps_farrow! /
+# set_channel_ctaps_farrow!.  A bound filter only; f.H / f.PN (f.CH / f.CPN) no longer describe the filter afterwards.
+function set_channel_taps_farrow_device!(f::RatesFIRFilter{Th}, h::Ptr{Th}, stream::Ptr{Cvoid} = C_NULL) where {Th}
+    f.handle == C_NULL && error("set_channel_taps_farrow_device! needs a bound filter")
+    check(ccall((:mrhip_set_channel_taps_farrow_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}), f.handle, h, length(f.h), dtypecode(Th), stream))
+    f
+end
+function set_channel_ctaps_farrow_device!(f::RatesFIRFilter{Th}, h::Ptr{Complex{Th}}, stream::Ptr{Cvoid} = C_NULL) where {Th}
+    f.handle == C_NULL && error("set_channel_ctaps_farrow_device! needs a bound filter")
+    check(ccall((:mrhip_set_channel_ctaps_farrow_device, libmr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}), f.handle, h, length(f.h), dtypecode(Complex{Th}), stream))
+    f.ctaps = true
     f
 end
 # FIRFilter(H::Matrix, rates::Vector, N𝜙, polyorder): one FIRFilter(H[:, c], rates[c], N𝜙, polyorder) per channel behind one object -- the
